@@ -2,7 +2,7 @@
 """Benchmark of the hot path: train iterations/sec (forward + backward of one view) of the differentiable
 Gaussian-splat rasterizer + fused multi-scale bilateral-grid colour transform.
 
-    python bench.py --gpus N --steps K --warmup W [--workload headline|c2|c3|c5]
+    python bench.py --gpus N --steps K --warmup W [--workload headline|c2|c3|c5] [--dump-outputs DIR] [--full]
 
 One STEP = one FRAME: every rank renders the views of its rig once (BASELINE.json: "2M Gaussians x 6 views x 1920x1080 fwd+bwd",
 "6 cams x 8 timesteps sharded across 8 GPUs"): per view SH -> projection -> tile intersection + ordering -> alpha compositing
@@ -12,9 +12,18 @@ gradient; the views' gradients are summed into ONE flat gradient buffer (the vis
 along the road (its own timestep), so the ranks see different -- overlapping -- parts of the scene.
 `value` = views (iterations) processed by all ranks per second ("weak" scaling: one frame per GPU per step).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel, HIP-event timed on the launch
-stream inside the timed region) and `cpu_baseline` (the oracle/ port of the same pipeline on the host cores, bounded sample,
-rank 0 at N=1 only).
+Prints ONE JSON line on rank 0: the headline (`value`, `ms_per_step` = milliseconds of one timed step, the workload in `config`).
+A plain run sets up, warms up, times exactly --steps steps once, and prints that line.  --full adds what takes runs of its own:
+the median of --repeats (default 5) timed regions, `roofline` (dominant kernel, HIP-event timed on the launch stream inside the
+timed region), the per-operator table, `selfcheck` (the timed frame against the eager frame; exit status 3 when they differ),
+the replayable-frame / other-row-order / drop-in-path / training-cadence figures, the exchange probe and `cpu_baseline` (the
+oracle/ port of the same pipeline on the host cores, bounded sample, rank 0 at N=1 only).
+
+--dump-outputs DIR writes what the last timed step computed, rank 0's view of it, as DIR/<name>.npy (float32; the losses
+float64): per view the loss, a fixed seeded sample of the pixels of the image / expected depth / opacity and of the sky
+colour's gradient, the camera-pose gradients, a fixed seeded sample of the rows of every per-Gaussian gradient and the grids'
+gradients in full -- at most 64 MB.  The inputs are seeded: equal arguments give equal inputs, so two builds can be compared
+output for output.
 """
 from __future__ import annotations
 
@@ -105,9 +114,14 @@ def parse():
     ap.add_argument("--no-train-cadence", action="store_true",
                     help="N = 1: skip config.train_cadence (one view per step; + optimizer step and densification statistics: the reference's loop)")
     ap.add_argument("--verbose", action="store_true")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region of --steps steps is run this many times (barrier + synchronize around each); the MEDIAN "
-                         "repeat is reported (a 0.2 s window on a shared host can swing 10-20 %), min / max beside it")
+                         "repeat is reported (a 0.2 s window on a shared host can swing 10-20 %), min / max beside it.  Default: 1, "
+                         "with --full 5")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline (module docstring); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (module docstring)")
     ap.add_argument("--no-graph", action="store_true",
                     help="N = 1: drive the frame through the eager host-count loop (one host wait per view, ~40 launches from Python) "
                          "instead of replaying the captured hipGraphs of graph_view.FrameGraph (default: same kernels, same order, "
@@ -504,9 +518,47 @@ def exchange_probe(args):
         return {"error": f"{type(e).__name__} (limit {args.probe_timeout}s)"}
 
 
+# --dump-outputs: fixed seeded samples of the per-Gaussian rows and of the pixels (2 M Gaussians, six views: ~42 MB in all)
+DUMP_ROWS, DUMP_PIXELS, DUMP_LIMIT = 131072, 65536, 64 << 20
+
+
+def _sample(n, k, seed):
+    """``k`` of ``range(n)`` (all of them when n <= k), sorted, drawn by a seeded host generator: the same on every run."""
+    if n <= k:
+        return torch.arange(n)
+    return torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+
+
+def dump_outputs(path, views, params, grids, skies, cams):
+    """What a caller of the timed step receives, after its last replay: ``views`` = per view (rgb, depth, opacity, loss)."""
+    import numpy as np
+    N, (H, W) = params["means"].shape[0], views[0][0].shape[:2]
+    rows, pix = _sample(N, DUMP_ROWS, 0).to(params["means"].device), _sample(H * W, DUMP_PIXELS, 1).to(views[0][0].device)
+
+    def pixels(t):
+        return t.detach().reshape(H * W, -1)[pix]
+    out = {"loss": torch.tensor([float(v[3]) for v in views], dtype=torch.float64)}
+    for i, name in enumerate(("rgb", "depth", "opacity")):
+        out[name] = torch.stack([pixels(v[i]) for v in views])
+    out["grad_sky"] = torch.stack([pixels(s.grad) for s in skies])
+    out["grad_viewmat"] = torch.stack([c.viewmat.grad.detach() for c in cams])
+    for k, p in params.items():
+        out[f"grad_{k}"] = p.grad.detach()[rows]
+    for i, g in enumerate(grids):
+        out[f"grad_grid{i}"] = g.grad.detach()
+    arrays = {k: v.cpu().numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32) for k, v in out.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), a)
+
+
 def main():
 
     args = parse()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.cpu_baseline_only:
         cpu_baseline_worker(args)
         return
@@ -568,12 +620,13 @@ def main():
     # (16-px tile, Gaussian) pairs per view = the intersections of the reference's algorithm (SURVEY.md 8d counts bytes per such pair);
     # the fused view builds its lists for larger tiles (fused_view.LIST_TILE) and never materialises them, so they are counted once here
     from bilateral_driving_amd import fused_view as FV
-    with torch.no_grad():
-        infos16 = [Hn.render_view(params, cams[v], grids, v, skies[v], factors=factors, list_tile=16)["info"] for v in range(V)]
-        M16 = [i["n_isects"] for i in infos16]
-        vis_masks = [(i["radii"].reshape(-1) > 0) for i in infos16] if coll else None
-        del infos16
-    torch.cuda.synchronize()
+    if args.full or coll:     # (--full: the roofline's pair counts; collectives: the ranks' visibility unions that price the exchange)
+        with torch.no_grad():
+            infos16 = [Hn.render_view(params, cams[v], grids, v, skies[v], factors=factors, list_tile=16)["info"] for v in range(V)]
+            M16 = [i["n_isects"] for i in infos16]
+            vis_masks = [(i["radii"].reshape(-1) > 0) for i in infos16] if coll else None
+            del infos16
+        torch.cuda.synchronize()
 
     stats = {}
     plan = None
@@ -670,6 +723,8 @@ def main():
                 flat._dirty, flat._clean = None, False
         L.enable_timers(False)
 
+    last_views = [None] * V     # (eager driver, --dump-outputs: the outputs of the last step's views)
+
     def step(s):
         if frame is not None:
             frame.step(wait=False)     # (pipelined: validity is checked once, after the timed region)
@@ -687,7 +742,10 @@ def main():
             out = Hn.render_view(params, cams[v], grids, v, skies[v], factors=factors, **kw)
             if not dense:
                 fx.begin_view(out["info"])
-            Hn.training_loss(out, targets[v], grids, grid_grads=None if dense else fx.tail_grads()).backward()
+            loss = Hn.training_loss(out, targets[v], grids, grid_grads=None if dense else fx.tail_grads())
+            loss.backward()
+            if args.dump_outputs:
+                last_views[v] = (out["rgb"], out["depth"], out["opacity"], loss)
             if not dense:
                 fx.end_view()
             stats.setdefault("M", []).append(out["info"]["n_isects"])
@@ -726,9 +784,49 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         reps = [float(x) for x in t.tolist()]
     elapsed = sorted(reps)[len(reps) // 2] if len(reps) % 2 else sorted(reps)[len(reps) // 2 - 1]   # (lower median for even counts)
-    dom_in_situ = None
     if frame is not None:
         assert frame.valid(), "a list outgrew its calibrated capacity during the timed region"
+    if args.dump_outputs and rank == 0:
+        views = [(vg.rgb, vg.depth, vg.opacity, vg.loss) for vg in frame.views] if frame is not None else last_views
+        dump_outputs(args.dump_outputs, views, params, grids, skies[:V], cams[:V])
+    last_views[:] = [None] * V
+    ms_per_step = elapsed / args.steps * 1e3
+    value = world * V * args.steps / elapsed
+    result = {
+        "metric": "train iters/sec (fwd+bwd) at 2M Gaussians, 6x1920x1080; HBM roofline %",
+        "value": value, "unit": "iters/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "repeats": len(reps), "ms_per_step_min": min(reps) / args.steps * 1e3,
+        "ms_per_step_max": max(reps) / args.steps * 1e3, "timing": "median of `repeats` timed regions of `steps` steps each",
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": f"{args.workload}{'' if args.scene == 'ring' else ' on the LIDAR-initialised street scene (harness.lidar_scene, opacity ' + args.lidar_opacity + '), NOT the scene the metric is quoted on'}: "
+                               f"{wl['text']}; {N} Gaussians, {len(cams)}-cam ring {W}x{H}, RGB+ED, grids "
+                               f"{[list(l) for l in wl['levels']]} factors {list(factors)}, L1+TV loss, camera-pose gradient live; one step = one "
+                               f"frame of {V} views per GPU (1 iter = 1 view)",
+                   "workload_name": args.workload, "scene": args.scene,
+                   "row_order": args.row_order + (" (Morton order of the centres, densify.spatial_order: applied once at load, outside the timed "
+                                                  "region; the set of Gaussians is the generator's)" if args.row_order == "spatial" else " (the generator's own order)"),
+                   "gaussians": N, "width": W, "height": H, "views": len(cams), "views_per_step": V,
+                   "frames_per_sec": value / V, "ms_per_view": ms_per_step / V, "parallelism": f"view-dp{world}",
+                   "step_driver": ("hipGraph replay (graph_view.FrameGraph): per view " +
+                                   ("two captured graphs (forward + L1/TV loss value | backward), the forwards on a second stream next to "
+                                    "the previous view's backward" if not args.no_overlap else "ONE captured graph = forward + L1/TV loss + backward") +
+                                   ", device-side list counts, no host wait") if frame is not None else
+                                  "autograd (forward, loss, loss.backward())",
+                   "gradient_buffer": "dense tensors (autograd accumulation)" if dense else "flat, visible rows only",
+                   "allreduce_bytes_per_step": fx.payload_bytes if coll else 0, "allreduce_dense_bytes": flat.nbytes if coll else 0,
+                   "exchanges_per_step": fx.n_exchanges if coll else 0,
+                   "collectives_forced_at_world1": bool(coll and world == 1),
+                   "exchange": None if not coll else dict(mode="view" if fx.per_view else "frame", chosen_by=args.exchange, plan=plan)},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result))
+        if coll:
+            dist.destroy_process_group()
+        return
+    dom_in_situ = None
+    if frame is not None:
         cnts = frame.counts()
         Ms, nvs = [c[0] for c in cnts], [c[1] for c in cnts]
         dom_in_situ = (len(dom_ms), sum(dom_ms) / max(len(dom_ms), 1)) if dom_ms else None
@@ -909,8 +1007,6 @@ def main():
             cadence = train_cadence(args, params, cams, grids, skies, targets, factors, V, dev)
         except Exception as e:   # measurement tooling must never take the bench line down
             cadence = {"error": f"{type(e).__name__}: {e}"}
-    ms_per_step = elapsed / args.steps * 1e3
-    value = world * V * args.steps / elapsed
 
     # ---- roofline of the dominant kernel: composite backward (K8).  Algorithmic bytes per launch: 44 B/isect read +
     # 28 B/pixel read + 48 B/isect gradient write.
@@ -1033,39 +1129,15 @@ def main():
                             "SURVEY.md 8(d) algorithmic bytes / that time; traffic = HBM bytes of all its kernels from the committed counter "
                             "passes of this workload.  The composite backward's block: `roofline_composite`"}
 
-    result = {
-        "metric": "train iters/sec (fwd+bwd) at 2M Gaussians, 6x1920x1080; HBM roofline %",
-        "value": value, "unit": "iters/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "repeats": len(reps), "ms_per_step_min": min(reps) / args.steps * 1e3,
-        "ms_per_step_max": max(reps) / args.steps * 1e3, "timing": "median of `repeats` timed regions of `steps` steps each",
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": f"{args.workload}{'' if args.scene == 'ring' else ' on the LIDAR-initialised street scene (harness.lidar_scene, opacity ' + args.lidar_opacity + '), NOT the scene the metric is quoted on'}: "
-                               f"{wl['text']}; {N} Gaussians, {len(cams)}-cam ring {W}x{H}, RGB+ED, grids "
-                               f"{[list(l) for l in wl['levels']]} factors {list(factors)}, L1+TV loss, camera-pose gradient live; one step = one "
-                               f"frame of {V} views per GPU (1 iter = 1 view)",
-                   "workload_name": args.workload, "scene": args.scene,
-                   "row_order": args.row_order + (" (Morton order of the centres, densify.spatial_order: applied once at load, outside the timed "
-                                                  "region; the set of Gaussians is the generator's)" if args.row_order == "spatial" else " (the generator's own order)"),
-                   f"{other_order}_row_order_iters_per_sec": other_order_its, "gaussians": N, "width": W, "height": H, "views": len(cams), "views_per_step": V,
-                   "frames_per_sec": value / V, "ms_per_view": ms_per_step / V, "api_path_iters_per_sec": api_its, "api_path_eager_iters_per_sec": api_eager_its,
-                   "n_visible_mean": nv_mean, "isects_mean": M_mean, "list_tile": FV.LIST_TILE,
-                   "list_pairs_mean": list_pairs_mean, "parallelism": f"view-dp{world}",
-                   "random_views_iters_per_sec": random_its,
-                   "train_cadence": cadence,
-                   "one_view_step_iters_per_sec": None if not cadence or "error" in cadence.get("one_view_step", {"error": 1}) else cadence["one_view_step"]["iters_per_sec"],
-                   "train_step_iters_per_sec": None if not cadence or "error" in cadence.get("train_step_deferred_adam", {"error": 1}) else cadence["train_step_deferred_adam"]["iters_per_sec"],
-                   "train_step_dense_adam_iters_per_sec": None if not cadence or "error" in cadence.get("train_step_dense_adam", {"error": 1}) else cadence["train_step_dense_adam"]["iters_per_sec"],
-                   "step_driver": ("hipGraph replay (graph_view.FrameGraph): per view " +
-                                   ("two captured graphs (forward + L1/TV loss value | backward), the forwards on a second stream next to "
-                                    "the previous view's backward" if not args.no_overlap else "ONE captured graph = forward + L1/TV loss + backward") +
-                                   ", device-side list counts, no host wait") if frame is not None else
-                                  "autograd (forward, loss, loss.backward())",
-                   "gradient_buffer": "dense tensors (autograd accumulation)" if dense else "flat, visible rows only",
-                   "allreduce_bytes_per_step": fx.payload_bytes if coll else 0, "allreduce_dense_bytes": flat.nbytes if coll else 0,
-                   "exchanges_per_step": fx.n_exchanges if coll else 0,
-                   "collectives_forced_at_world1": bool(coll and world == 1),
-                   "exchange": None if not coll else dict(mode="view" if fx.per_view else "frame", chosen_by=args.exchange, plan=plan)},
+    result["config"].update({
+        f"{other_order}_row_order_iters_per_sec": other_order_its, "api_path_iters_per_sec": api_its, "api_path_eager_iters_per_sec": api_eager_its,
+        "n_visible_mean": nv_mean, "isects_mean": M_mean, "list_tile": FV.LIST_TILE, "list_pairs_mean": list_pairs_mean,
+        "random_views_iters_per_sec": random_its,
+        "train_cadence": cadence,
+        "one_view_step_iters_per_sec": None if not cadence or "error" in cadence.get("one_view_step", {"error": 1}) else cadence["one_view_step"]["iters_per_sec"],
+        "train_step_iters_per_sec": None if not cadence or "error" in cadence.get("train_step_deferred_adam", {"error": 1}) else cadence["train_step_deferred_adam"]["iters_per_sec"],
+        "train_step_dense_adam_iters_per_sec": None if not cadence or "error" in cadence.get("train_step_dense_adam", {"error": 1}) else cadence["train_step_dense_adam"]["iters_per_sec"]})
+    result.update({
         "frame_valu_issue_frac": _frame_valu_issue(ms_per_step / V, args.workload) if (counters_apply and args.workload == "headline" and N == wl["gaussians"]) else None,
         "roofline": roofline,
         "roofline_composite": roofline_composite,
@@ -1073,7 +1145,7 @@ def main():
         "per_kernel": per_kernel,
         "per_kernel_source": per_kernel_source,
         "selfcheck": selfcheck,
-    }
+    })
     if rank == 0 and not coll and not args.no_exchange_probe:
         torch.cuda.empty_cache()
         probe = exchange_probe(args)

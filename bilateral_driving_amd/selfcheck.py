@@ -3,7 +3,7 @@
 ``graph_view.FrameGraph.step()`` (device-side list counts, SH colours in the record pack, loss on the transform's launch, two
 streams, in-place gradient rows) and the eager host-count loop (``harness.render_view`` -> ``training_loss`` -> autograd) are the
 same kernels in two drivers; the small-size tests tie both to the oracle.  This puts the two side by side at FULL size -- where
-capacities, 32-bit offsets and the binned schedule are actually stressed: ``bench.py`` runs it after every timed region
+capacities, 32-bit offsets and the binned schedule are actually stressed: ``bench.py --full`` runs it after its timed regions
 (``selfcheck`` block of its line), ``tests/test_gpu_04`` at BASELINE.json's c3 / c5 sizes.  Reference path being mirrored:
 /root/reference/project/tools/train.py:252-283 (one view: forward, losses, backward).
 """

@@ -3,7 +3,7 @@
 set -u
 TAG=$1; VAR=$2; shift 2
 OUT=gpurun_out/$TAG; mkdir -p $OUT
-Q="--no-cpu-baseline --no-pair-stats --no-api-path --no-random-views $*"
+Q="--full --no-cpu-baseline --no-pair-stats --no-api-path --no-random-views $*"
 for i in 1 2 3; do for val in 0 1; do
   (env $VAR=$val python bench.py $Q 2>$OUT/${VAR}${val}_$i.err | tail -1) > $OUT/${VAR}${val}_$i.json
 done; done

@@ -13,7 +13,7 @@ for round in 1 2; do
   for which in A B; do
     if [ $which = A ]; then E=$A; else E=$B; fi
     [ "$E" = "-" ] && E=""
-    (env $E timeout 600 python bench.py --no-cpu-baseline --no-api-path --repeats 3 "$@" 2>>$OUT/bench.stderr | tail -1) > $OUT/bench_$which$round.json
+    (env $E timeout 600 python bench.py --full --no-cpu-baseline --no-api-path --repeats 3 "$@" 2>>$OUT/bench.stderr | tail -1) > $OUT/bench_$which$round.json
     python - <<PY
 import json
 try:

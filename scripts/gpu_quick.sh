@@ -13,7 +13,7 @@ if [ -n "$TESTS" ]; then
   (timeout 900 python -m pytest $TESTS -q -m gpu -p no:cacheprovider -x 2>&1 | tail -60) > $OUT/tests.log
   tail -25 $OUT/tests.log
 fi
-(timeout 600 python bench.py --no-cpu-baseline "$@" 2>$OUT/bench.stderr | tail -1) > $OUT/bench.json
+(timeout 600 python bench.py --full --no-cpu-baseline "$@" 2>$OUT/bench.stderr | tail -1) > $OUT/bench.json
 tail -5 $OUT/bench.stderr
 python - <<PY
 import json
