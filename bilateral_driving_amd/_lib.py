@@ -67,6 +67,9 @@ _SIGS = {
     "bds_rasterize_kernel_name": (_i, [_i, _i, _i, _i, C.c_char_p, _i]),
     "bds_rasterize_bwd_schedule": (_i, [_i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f]),
     "bds_project_view_fwd": (_i, [_i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f]),
+    "bds_project_fwd_aa": (_i, [_i, _i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f]),
+    "bds_project_view_fwd_aa": (_i, [_i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _f, _f]),
+    "bds_project_view_bwd_list_aa": (_i, [_i, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_project_view_prepare_fwd": (_i, [_i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _f]),
     "bds_project_view_prepare_fwd_blocks": (_i, [_i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _f, _f]),
     "bds_project_view_fwd_blocks": (_i, [_i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f, _f]),
@@ -195,6 +198,7 @@ def lib():
 
 
 SPLAT_RECORD_FLOATS, GRAD_RECORD_FLOATS, POSE_GRAD_SLOTS = 12, 16, 64
+PROJ_AA_ACCUMULATE, PROJ_AA_ACTIVATED = 1, 2      # include/bds.h bds_project_view_bwd_list_aa flags
 OPT_DEBUG = 3          # profiling only: ablation mask
 OPT_SCHED_BINS = 8     # device-count compositor: 1 [default] = the forward's waves bin the backward's schedule, 0 = a sort launch (include/bds.h)
 OPT_CELLS = 7          # bilateral transform, bit mask [default 3]: 1 = cell-aligned kernels, 2 = one-pass pyramid forward, 0 = general kernels (include/bds.h)

@@ -187,8 +187,60 @@ BDS_HD M3 covar_world(const float *q, const float *s, M3 *Rq_out = nullptr) {
   return mul33_nt(Ms, Ms);
 }
 
+// det(J covc J^T) of the UN-blurred 2-D covariance without cancellation (rasterize_mode "antialiased": comp = sqrt(det S2 / det S)).
+// J covc J^T = A A^T with A = J R Rq diag(s) [2x3], so det = |a0 x a1|^2 (Cauchy-Binet) with a0 x a1 = cof(diag s) Rq^T (p x q),
+// p = R^T j0, q = R^T j1 (rows j0, j1 of J; Rq a rotation): a sum of three squares.  (R, the viewmat's block, is differentiated as the
+// free matrix it is for the pose gradient -- hence p x q and not R^T (j0 x j1).)  The difference s00 s11 - s01 s10 of the entries keeps
+// the rounding of products ~lambda_max^2 -- for a needle (lambda_min ~1e-6 lambda_max) all of det S2: comp off by O(1).
+BDS_HD void det2d_rows(const M3 &R, float j00, float j02, float j11, float j12, float *p, float *q) {
+  for (int i = 0; i < 3; i++) { p[i] = R.m[i] * j00 + R.m[6 + i] * j02; q[i] = R.m[3 + i] * j11 + R.m[6 + i] * j12; }
+}
+BDS_HD float det2d_unblurred(const M3 &R, const M3 &Rq, const float *s, float j00, float j02, float j11, float j12) {
+  float p[3], q[3], m[3];
+  det2d_rows(R, j00, j02, j11, j12, p, q);
+  const float w[3] = {p[1] * q[2] - p[2] * q[1], p[2] * q[0] - p[0] * q[2], p[0] * q[1] - p[1] * q[0]};
+  for (int i = 0; i < 3; i++) m[i] = Rq.m[i] * w[0] + Rq.m[3 + i] * w[1] + Rq.m[6 + i] * w[2];   // Rq^T w
+  const float a = s[1] * s[2] * m[0], b = s[0] * s[2] * m[1], d = s[0] * s[1] * m[2];
+  return a * a + b * b + d * d;
+}
+
+// Gradient of det2d_unblurred for the upstream value vD: into R (vR, row-major), the quaternion's rotation matrix (vRq), the scales
+// (vs) and the four non-zero entries of J (vj = {dJ00, dJ02, dJ11, dJ12}); all ADDED.  Sums of products: no cancelling differences.
+BDS_HD void det2d_unblurred_vjp(const M3 &R, const M3 &Rq, const float *s, float j00, float j02, float j11, float j12, float vD, float *vR,
+                                float *vRq, float *vs, float *vj) {
+  float p[3], q[3], m[3];
+  det2d_rows(R, j00, j02, j11, j12, p, q);
+  const float w[3] = {p[1] * q[2] - p[2] * q[1], p[2] * q[0] - p[0] * q[2], p[0] * q[1] - p[1] * q[0]};
+  for (int i = 0; i < 3; i++) m[i] = Rq.m[i] * w[0] + Rq.m[3 + i] * w[1] + Rq.m[6 + i] * w[2];
+  const float ga = 2.f * vD * s[1] * s[2] * m[0], gb = 2.f * vD * s[0] * s[2] * m[1], gd = 2.f * vD * s[0] * s[1] * m[2];
+  const float vm[3] = {ga * s[1] * s[2], gb * s[0] * s[2], gd * s[0] * s[1]};
+  vs[0] += gb * s[2] * m[1] + gd * s[1] * m[2];
+  vs[1] += ga * s[2] * m[0] + gd * s[0] * m[2];
+  vs[2] += ga * s[1] * m[0] + gb * s[0] * m[1];
+  float vw[3];
+  for (int k = 0; k < 3; k++) {
+    vw[k] = Rq.m[k * 3] * vm[0] + Rq.m[k * 3 + 1] * vm[1] + Rq.m[k * 3 + 2] * vm[2];
+    for (int i = 0; i < 3; i++) vRq[k * 3 + i] += w[k] * vm[i];
+  }
+  // w = p x q:  v_p = q x v_w,  v_q = v_w x p
+  const float vp[3] = {q[1] * vw[2] - q[2] * vw[1], q[2] * vw[0] - q[0] * vw[2], q[0] * vw[1] - q[1] * vw[0]};
+  const float vq[3] = {vw[1] * p[2] - vw[2] * p[1], vw[2] * p[0] - vw[0] * p[2], vw[0] * p[1] - vw[1] * p[0]};
+  // p = R^T j0, q = R^T j1 (j0 = (j00, 0, j02), j1 = (0, j11, j12))
+  for (int i = 0; i < 3; i++) {
+    vR[i] += j00 * vp[i];
+    vR[3 + i] += j11 * vq[i];
+    vR[6 + i] += j02 * vp[i] + j12 * vq[i];
+  }
+  vj[0] += R.m[0] * vp[0] + R.m[1] * vp[1] + R.m[2] * vp[2];
+  vj[1] += R.m[6] * vp[0] + R.m[7] * vp[1] + R.m[8] * vp[2];
+  vj[2] += R.m[3] * vq[0] + R.m[4] * vq[1] + R.m[5] * vq[2];
+  vj[3] += R.m[6] * vq[0] + R.m[7] * vq[1] + R.m[8] * vq[2];
+}
+
+// kExactComp (the "antialiased" kernels): comp from det2d_unblurred; false: the entries' difference (what the classic kernels compiled
+// to before -- they do not use comp).
 BDS_HD Proj project_one(const float *mean, const float *quat, const float *scale, const Camera &cam, int W, int H,
-                        float eps2d, float near_plane, float far_plane, float radius_clip) {
+                        float eps2d, float near_plane, float far_plane, float radius_clip, bool kExactComp = false) {
   Proj o;
   o.radius = 0; o.mx = o.my = o.depth = o.ca = o.cb = o.cc = o.comp = 0.f;
   const float *R = cam.R.m;
@@ -196,7 +248,8 @@ BDS_HD Proj project_one(const float *mean, const float *quat, const float *scale
   float y = R[3] * mean[0] + R[4] * mean[1] + R[5] * mean[2] + cam.t[1];
   float z = R[6] * mean[0] + R[7] * mean[1] + R[8] * mean[2] + cam.t[2];
   if (!(z > near_plane) || !(z < far_plane)) return o;
-  M3 cov = covar_world(quat, scale);
+  M3 Rq;
+  M3 cov = covar_world(quat, scale, kExactComp ? &Rq : nullptr);
   M3 covc = mul33_nt(mul33(cam.R, cov), cam.R);
   float lim_x = 1.3f * (0.5f * W / cam.fx), lim_y = 1.3f * (0.5f * H / cam.fy);
   float rz = 1.f / z, rz2 = rz * rz;
@@ -212,7 +265,7 @@ BDS_HD Proj project_one(const float *mean, const float *quat, const float *scale
   float s01 = t01 * j11 + t02 * j12;
   float s10 = t10 * j00 + t12 * j02;
   float s11 = t11 * j11 + t12 * j12;
-  float det_orig = s00 * s11 - s01 * s10;
+  float det_orig = kExactComp ? det2d_unblurred(cam.R, Rq, scale, j00, j02, j11, j12) : s00 * s11 - s01 * s10;
   s00 += eps2d; s11 += eps2d;
   float det = s00 * s11 - s01 * s10;
   if (!(det > 0.f)) return o;
@@ -277,9 +330,17 @@ struct ProjGrad {
 };
 
 // Backward of project_one for a Gaussian that was NOT culled.
+// v_comp (rasterize_mode "antialiased"): gradient of the compensation comp = sqrt(max(0, r)), r = D / det S, with S the blurred 2-D
+// covariance and D = det(S - eps I) = det2d_unblurred.  With v_r = v_comp 0.5 / (comp + 1e-6) (gsplat 1.3.0's guard; zero where the
+// clamp is active, r <= 0):  v_S += -v_r r conic (through det S: d(1 / det S) / dS = -conic / det S), and D's own gradient goes straight
+// into scales, quaternion, camera rotation and J (det2d_unblurred_vjp).  Mathematically that is gsplat's
+// v_S += v_r ((1 - r) conic - eps det(conic) I); in float32 that difference cancels to the short axis of a needle and leaves the
+// rounding of the long one (gradients off by O(1) where comp -> 0).
+// comp_out (optional) receives comp, recomputed from the same S.  With the defaults (v_comp = 0, comp_out = nullptr) the compensation
+// branch folds away: the classic callers compile to what they were.
 BDS_HD void project_one_vjp(const float *mean, const float *quat, const float *scale, const Camera &cam, int W, int H,
                             float eps2d, float v_mx, float v_my, float v_depth, float v_ca, float v_cb, float v_cc,
-                            ProjGrad &g) {
+                            ProjGrad &g, float v_comp = 0.f, float *comp_out = nullptr, float *vD_out = nullptr) {
   const float *R = cam.R.m;
   float x = R[0] * mean[0] + R[1] * mean[1] + R[2] * mean[2] + cam.t[0];
   float y = R[3] * mean[0] + R[4] * mean[1] + R[5] * mean[2] + cam.t[1];
@@ -311,8 +372,24 @@ BDS_HD void project_one_vjp(const float *mean, const float *quat, const float *s
   // cancelling scalar tau multiplies the conic itself -- an error in it has no mixed component -- and adj(V) is exact.
   const float ca = s11 * idet, cb = -0.5f * (s01 + s10) * idet, cc = s00 * idet;
   const float tau = v_ca * ca + v_cb * cb + v_cc * cc;
-  const float vs00 = v_cc * idet - tau * ca, vs11 = v_ca * idet - tau * cc;
-  const float vs01 = -0.5f * v_cb * idet - tau * cb, vs10 = vs01;   // (each off-diagonal entry: half of d / d s01)
+  float vs00 = v_cc * idet - tau * ca, vs11 = v_ca * idet - tau * cc;
+  float vs01 = -0.5f * v_cb * idet - tau * cb;   // (each off-diagonal entry: half of d / d s01)
+  if (v_comp != 0.f || comp_out != nullptr || vD_out != nullptr) {
+    // r = D / det S, D as project_one(..., kExactComp = true) forms it: comp_out is the forward's comp
+    const float r = det2d_unblurred(cam.R, Rq, scale, j00, j02, j11, j12) * idet;
+    const float comp = sqrtf(fmaxf(0.f, r));
+    if (comp_out) *comp_out = comp;
+    float vD = 0.f;
+    if (v_comp != 0.f && r > 0.f) {
+      const float v_r = v_comp * 0.5f / (comp + 1e-6f), kr = v_r * r;
+      vs00 -= kr * ca;
+      vs11 -= kr * cc;
+      vs01 -= kr * cb;
+      vD = v_r * idet;       // D's own gradient: project_one_vjp_aa
+    }
+    if (vD_out) *vD_out = vD;
+  }
+  const float vs10 = vs01;
   // v_covc = J^T v_S J  (3x3)
   float J[6] = {j00, 0.f, j02, 0.f, j11, j12};
   float VS[4] = {vs00, vs01, vs10, vs11};
@@ -375,6 +452,47 @@ BDS_HD void project_one_vjp(const float *mean, const float *quat, const float *s
     g.v_scale[j] = acc;
   }
   quat_to_rotmat_vjp(quat[0], quat[1], quat[2], quat[3], vRq, g.v_quat);
+}
+
+// The projection VJP of rasterize_mode "antialiased": project_one_vjp with v_comp, plus the gradient of D = det S2 (the numerator of
+// comp^2) taken on D's sum-of-squares form (det2d_unblurred_vjp) into scales, quaternion, camera rotation and -- through J -- the
+// camera-space mean.  comp_out: comp as project_one(..., kExactComp = true) returns it.
+BDS_HD void project_one_vjp_aa(const float *mean, const float *quat, const float *scale, const Camera &cam, int W, int H, float eps2d,
+                               float v_mx, float v_my, float v_depth, float v_ca, float v_cb, float v_cc, float v_comp, ProjGrad &g,
+                               float *comp_out) {
+  float vD = 0.f;
+  project_one_vjp(mean, quat, scale, cam, W, H, eps2d, v_mx, v_my, v_depth, v_ca, v_cb, v_cc, g, v_comp, comp_out, &vD);
+  if (vD == 0.f) return;
+  const float *R = cam.R.m;
+  const float x = R[0] * mean[0] + R[1] * mean[1] + R[2] * mean[2] + cam.t[0];
+  const float y = R[3] * mean[0] + R[4] * mean[1] + R[5] * mean[2] + cam.t[1];
+  const float z = R[6] * mean[0] + R[7] * mean[1] + R[8] * mean[2] + cam.t[2];
+  const float fx = cam.fx, fy = cam.fy;
+  const float lim_x = 1.3f * (0.5f * W / fx), lim_y = 1.3f * (0.5f * H / fy);
+  const float rz = 1.f / z, rz2 = rz * rz, rz3 = rz2 * rz;
+  const float tx = z * fminf(lim_x, fmaxf(-lim_x, x * rz));
+  const float ty = z * fminf(lim_y, fmaxf(-lim_y, y * rz));
+  const float j00 = fx * rz, j02 = -fx * tx * rz2, j11 = fy * rz, j12 = -fy * ty * rz2;
+  const M3 Rq = quat_to_rotmat(quat[0], quat[1], quat[2], quat[3]);
+  M3 dRq;
+  for (int i = 0; i < 9; i++) dRq.m[i] = 0.f;
+  float vj[4] = {0.f, 0.f, 0.f, 0.f};
+  det2d_unblurred_vjp(cam.R, Rq, scale, j00, j02, j11, j12, vD, g.v_R, dRq.m, g.v_scale, vj);
+  // J entries -> camera-space mean (as in project_one_vjp; vj = {dJ00, dJ02, dJ11, dJ12})
+  float vmc[3] = {0.f, 0.f, 0.f};
+  if (x * rz <= lim_x && x * rz >= -lim_x) vmc[0] += -fx * rz2 * vj[1];
+  else vmc[2] += -fx * rz3 * vj[1] * tx;
+  if (y * rz <= lim_y && y * rz >= -lim_y) vmc[1] += -fy * rz2 * vj[3];
+  else vmc[2] += -fy * rz3 * vj[3] * ty;
+  vmc[2] += -fx * rz2 * vj[0] - fy * rz2 * vj[2] + 2.f * fx * tx * rz3 * vj[1] + 2.f * fy * ty * rz3 * vj[3];
+  for (int i = 0; i < 3; i++) {
+    g.v_mean[i] += R[i] * vmc[0] + R[3 + i] * vmc[1] + R[6 + i] * vmc[2];
+    g.v_t[i] += vmc[i];
+    for (int j = 0; j < 3; j++) g.v_R[i * 3 + j] += vmc[i] * mean[j];
+  }
+  float vq[4];
+  quat_to_rotmat_vjp(quat[0], quat[1], quat[2], quat[3], dRq, vq);
+  for (int i = 0; i < 4; i++) g.v_quat[i] += vq[i];
 }
 
 // ------------------------------------------------------------------------------------------

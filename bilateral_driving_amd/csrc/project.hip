@@ -11,25 +11,32 @@ namespace bds {
 
 constexpr int kProjBlock = 256;
 
+// kAA (rasterize_mode "antialiased": bds_project_fwd with compensations, bds_project_fwd_aa): comp from det S2 as a sum of squares
+// (gs_math.h det2d_unblurred, what the backward differentiates), and -- with opacities / opac_eff given -- opac_eff[c,g] =
+// opacities[g] * comp, what the tile stage and the compositor read in that mode.
+template <bool kAA = false>
 __global__ __launch_bounds__(kProjBlock) void project_fwd_kernel(
     int C, int64_t N, const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ scales,
     const float *__restrict__ viewmats, const float *__restrict__ Ks, int W, int H, float eps2d, float near_plane,
     float far_plane, float radius_clip, int32_t *__restrict__ radii, float *__restrict__ means2d,
-    float *__restrict__ depths, float *__restrict__ conics, float *__restrict__ comps) {
+    float *__restrict__ depths, float *__restrict__ conics, float *__restrict__ comps,
+    const float *__restrict__ opacities = nullptr, float *__restrict__ opac_eff = nullptr) {
   const int64_t g = (int64_t)blockIdx.x * kProjBlock + threadIdx.x;
   if (g >= N) return;
   float m[3] = {means[g * 3], means[g * 3 + 1], means[g * 3 + 2]};
   float q[4] = {quats[g * 4], quats[g * 4 + 1], quats[g * 4 + 2], quats[g * 4 + 3]};
   float s[3] = {scales[g * 3], scales[g * 3 + 1], scales[g * 3 + 2]};
+  const float op = (kAA && opacities) ? opacities[g] : 0.f;
   for (int c = 0; c < C; c++) {
     Camera cam = load_camera(viewmats + c * 16, Ks + c * 9);  // wave-uniform -> scalar loads
-    Proj p = project_one(m, q, s, cam, W, H, eps2d, near_plane, far_plane, radius_clip);
+    Proj p = project_one(m, q, s, cam, W, H, eps2d, near_plane, far_plane, radius_clip, kAA);
     const int64_t o = (int64_t)c * N + g;
     radii[o] = p.radius;
     means2d[o * 2] = p.mx; means2d[o * 2 + 1] = p.my;
     depths[o] = p.depth;
     conics[o * 3] = p.ca; conics[o * 3 + 1] = p.cb; conics[o * 3 + 2] = p.cc;
     if (comps) comps[o] = p.comp;
+    if (kAA && opac_eff) opac_eff[o] = op * p.comp;
   }
 }
 
@@ -39,12 +46,14 @@ __device__ __forceinline__ float wave_sum_shfl(float v) {
   return v;
 }
 
+// kComp: v_comps [C,N] (rasterize_mode "antialiased") adds the compensation's gradient (gs_math.h project_one_vjp_aa)
+template <bool kComp = false>
 __global__ __launch_bounds__(kProjBlock) void project_bwd_kernel(
     int C, int64_t N, const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ scales,
     const float *__restrict__ viewmats, const float *__restrict__ Ks, int W, int H, float eps2d,
     const int32_t *__restrict__ radii, const float *__restrict__ v_means2d, const float *__restrict__ v_depths,
     const float *__restrict__ v_conics, float *__restrict__ v_means, float *__restrict__ v_quats,
-    float *__restrict__ v_scales, float *__restrict__ v_viewmats) {
+    float *__restrict__ v_scales, float *__restrict__ v_viewmats, const float *__restrict__ v_comps = nullptr) {
   __shared__ float red[kProjBlock / kWave][12];
   const int64_t g = (int64_t)blockIdx.x * kProjBlock + threadIdx.x;
   const bool live = g < N;
@@ -62,8 +71,12 @@ __global__ __launch_bounds__(kProjBlock) void project_bwd_kernel(
     for (int i = 0; i < 3; i++) pg.v_t[i] = 0.f;
     const int64_t o = (int64_t)c * N + g;
     if (live && radii[o] > 0) {
-      project_one_vjp(m, q, s, cam, W, H, eps2d, v_means2d[o * 2], v_means2d[o * 2 + 1], v_depths[o], v_conics[o * 3],
-                      v_conics[o * 3 + 1], v_conics[o * 3 + 2], pg);
+      if (kComp)
+        project_one_vjp_aa(m, q, s, cam, W, H, eps2d, v_means2d[o * 2], v_means2d[o * 2 + 1], v_depths[o], v_conics[o * 3],
+                           v_conics[o * 3 + 1], v_conics[o * 3 + 2], v_comps[o], pg, nullptr);
+      else
+        project_one_vjp(m, q, s, cam, W, H, eps2d, v_means2d[o * 2], v_means2d[o * 2 + 1], v_depths[o], v_conics[o * 3],
+                        v_conics[o * 3 + 1], v_conics[o * 3 + 2], pg);
       for (int i = 0; i < 3; i++) { am[i] += pg.v_mean[i]; as[i] += pg.v_scale[i]; }
       for (int i = 0; i < 4; i++) aq[i] += pg.v_quat[i];
     }
@@ -97,14 +110,17 @@ __global__ __launch_bounds__(kProjBlock) void project_bwd_kernel(
 // the gradients of the RAW parameters.  A culled Gaussian reads only its radius and writes zeros.
 // kReduce: the launch also does the tile stage's first one (visible_reduce_kernel, csrc/tiles.hip): visible Gaussians per workgroup,
 // the sort tables and tiles_per_gauss cleared -- it reads every radius anyway.
-template <bool kReduce>
+// kAA (rasterize_mode "antialiased", models/trainers/base.py:406): the opacity the tile stage and the compositor read is the EFFECTIVE
+// one, sigmoid(logit) * comp -- in the row form the row's slot 7, in the column form the dense [N] array opac_eff; `opacities` keeps
+// sigmoid(logit), which the backward reads.
+template <bool kReduce, bool kAA = false>
 __global__ __launch_bounds__(kProjBlock) void project_view_fwd_kernel(
     int64_t N, const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ log_scales,
     const float *__restrict__ logits, const float *__restrict__ viewmat, const float *__restrict__ K, int W, int H,
     float eps2d, float near_plane, float far_plane, float radius_clip, float *__restrict__ scales,
     float *__restrict__ opacities, int32_t *__restrict__ radii, float *__restrict__ means2d, float *__restrict__ depths,
     float *__restrict__ conics, PrepReduceSlots rs, int32_t *__restrict__ tiles_per_gauss, int rows,
-    const float *__restrict__ block_bounds) {
+    const float *__restrict__ block_bounds, float *__restrict__ opac_eff = nullptr) {
   const int64_t g = (int64_t)blockIdx.x * kProjBlock + threadIdx.x;
   if (kReduce) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *rs.m_total = 0;
@@ -128,6 +144,7 @@ __global__ __launch_bounds__(kProjBlock) void project_view_fwd_kernel(
           means2d[g * 2] = 0.f; means2d[g * 2 + 1] = 0.f;
           depths[g] = 0.f;
           conics[g * 3] = 0.f; conics[g * 3 + 1] = 0.f; conics[g * 3 + 2] = 0.f;
+          if (kAA) opac_eff[g] = 0.f;
         }
         if (kReduce && tiles_per_gauss) tiles_per_gauss[g] = 0;
       }
@@ -149,17 +166,19 @@ __global__ __launch_bounds__(kProjBlock) void project_view_fwd_kernel(
       const float op = 1.f / (1.f + expf(-logits[g]));
       opacities[g] = op;
       Camera cam = load_camera(viewmat, K);
-      Proj p = project_one(m, q, s, cam, W, H, eps2d, near_plane, far_plane, radius_clip);
+      Proj p = project_one(m, q, s, cam, W, H, eps2d, near_plane, far_plane, radius_clip, kAA);
       radius = p.radius;
       radii[g] = p.radius;
+      const float oe = kAA ? op * p.comp : op;
       if (rows) {      // (bds_common.h ProjLayout: one 32-byte row per Gaussian; radii / opacities stay dense arrays as well)
         float4 *row = reinterpret_cast<float4 *>(means2d + g * 8);
         row[0] = make_float4(p.mx, p.my, p.depth, __int_as_float(p.radius));
-        row[1] = make_float4(p.ca, p.cb, p.cc, op);
+        row[1] = make_float4(p.ca, p.cb, p.cc, oe);
       } else {
         means2d[g * 2] = p.mx; means2d[g * 2 + 1] = p.my;
         depths[g] = p.depth;
         conics[g * 3] = p.ca; conics[g * 3 + 1] = p.cb; conics[g * 3 + 2] = p.cc;
+        if (kAA) opac_eff[g] = oe;
       }
       if (tiles_per_gauss) tiles_per_gauss[g] = 0;   // (the counting kernel writes the visible entries only)
     }
@@ -179,16 +198,18 @@ __global__ __launch_bounds__(kProjBlock) void project_view_fwd_kernel(
   const float op = 1.f / (1.f + expf(-logits[g]));
   opacities[g] = op;
   Camera cam = load_camera(viewmat, K);
-  Proj p = project_one(m, q, s, cam, W, H, eps2d, near_plane, far_plane, radius_clip);
+  Proj p = project_one(m, q, s, cam, W, H, eps2d, near_plane, far_plane, radius_clip, kAA);
   radii[g] = p.radius;
+  const float oe = kAA ? op * p.comp : op;
   if (rows) {
     float4 *row = reinterpret_cast<float4 *>(means2d + g * 8);
     row[0] = make_float4(p.mx, p.my, p.depth, __int_as_float(p.radius));
-    row[1] = make_float4(p.ca, p.cb, p.cc, op);
+    row[1] = make_float4(p.ca, p.cb, p.cc, oe);
   } else {
     means2d[g * 2] = p.mx; means2d[g * 2 + 1] = p.my;
     depths[g] = p.depth;
     conics[g * 3] = p.ca; conics[g * 3 + 1] = p.cb; conics[g * 3 + 2] = p.cc;
+    if (kAA) opac_eff[g] = oe;
   }
 }
 
@@ -228,7 +249,9 @@ __device__ __forceinline__ void pose_grad_reduce(const ProjGrad &pg, float (*red
 // (models/trainers/base.py:280-297), and reduces the camera-pose gradient (models/trainers/base.py:328-329,399).
 // kRaw = false (the gsplat-shaped operator, rendering.rasterization): the caller passed ACTIVATED scales / opacities -- their gradients
 // are returned as they are -- and post-activation colours, whose gradient (record channels 0-2) is scattered to v_colors [N,3].
-template <bool kAcc, bool kPose, bool kRaw = true>
+// kAA (rasterize_mode "antialiased"): record channel 11 is the gradient of the EFFECTIVE opacity o * comp.  comp is recomputed in
+// registers by the VJP (no extra bytes read): v_comp = v_eff * o feeds the projection VJP, v_o = v_eff * comp.
+template <bool kAcc, bool kPose, bool kRaw = true, bool kAA = false>
 __global__ __launch_bounds__(kProjBlock) void project_view_bwd_list_kernel(
     int64_t n_cap, const uint64_t *__restrict__ n_dev, const int32_t *__restrict__ ids, const float *__restrict__ means,
     const float *__restrict__ quats, const float *__restrict__ scales, const float *__restrict__ opacities, const float *__restrict__ viewmat,
@@ -263,8 +286,15 @@ __global__ __launch_bounds__(kProjBlock) void project_view_bwd_list_kernel(
       old_l = v_logits[d * gl.sl];
     }
     Camera cam = load_camera(viewmat, K);
-    project_one_vjp(m, q, s, cam, W, H, eps2d, r1.w, r2.x, /*v_depth*/ r0.w, r1.x, r1.y, r1.z, pg);
-    const float al = kRaw ? r2.w * o * (1.f - o) : r2.w;
+    float v_o = r2.w;
+    if (kAA) {
+      float comp = 0.f;
+      project_one_vjp_aa(m, q, s, cam, W, H, eps2d, r1.w, r2.x, /*v_depth*/ r0.w, r1.x, r1.y, r1.z, r2.w * o, pg, &comp);
+      v_o = r2.w * comp;
+    } else {
+      project_one_vjp(m, q, s, cam, W, H, eps2d, r1.w, r2.x, /*v_depth*/ r0.w, r1.x, r1.y, r1.z, pg);
+    }
+    const float al = kRaw ? v_o * o * (1.f - o) : v_o;
 #pragma unroll
     for (int i = 0; i < 3; i++) {
       v_means[d * gl.sm + i] = old_m[i] + pg.v_mean[i];
@@ -367,9 +397,31 @@ extern "C" int bds_project_fwd(int C, int64_t N, const float *means, const float
   BDS_REQUIRE(C >= 1 && N >= 0 && W > 0 && H > 0);
   if (N == 0) return BDS_OK;
   BDS_REQUIRE(means && quats && scales && viewmats && Ks && radii && means2d && depths && conics);
-  hipLaunchKernelGGL(project_fwd_kernel, dim3((unsigned)cdiv(N, kProjBlock)), dim3(kProjBlock), 0, as_stream(stream), C, N,
+  if (compensations)       // rasterize_mode "antialiased": comp as the backward differentiates it (gs_math.h det2d_unblurred)
+    hipLaunchKernelGGL(project_fwd_kernel<true>, dim3((unsigned)cdiv(N, kProjBlock)), dim3(kProjBlock), 0, as_stream(stream), C, N,
+                       means, quats, scales, viewmats, Ks, W, H, eps2d, near_plane, far_plane, radius_clip, radii,
+                       means2d, depths, conics, compensations, static_cast<const float *>(nullptr), static_cast<float *>(nullptr));
+  else
+    hipLaunchKernelGGL(project_fwd_kernel<false>, dim3((unsigned)cdiv(N, kProjBlock)), dim3(kProjBlock), 0, as_stream(stream), C, N,
+                       means, quats, scales, viewmats, Ks, W, H, eps2d, near_plane, far_plane, radius_clip, radii,
+                       means2d, depths, conics, static_cast<float *>(nullptr), static_cast<const float *>(nullptr),
+                       static_cast<float *>(nullptr));
+  BDS_LAUNCH_CHECK();
+  return BDS_OK;
+}
+
+// bds_project_fwd + the effective opacities of rasterize_mode "antialiased" (models/trainers/base.py:406): opac_eff [C,N] =
+// opacities[g] * comp, in the same launch.  compensations (optional) as in bds_project_fwd.
+extern "C" int bds_project_fwd_aa(int C, int64_t N, const float *means, const float *quats, const float *scales,
+                                  const float *opacities, const float *viewmats, const float *Ks, int W, int H, float eps2d,
+                                  float near_plane, float far_plane, float radius_clip, int32_t *radii, float *means2d,
+                                  float *depths, float *conics, float *compensations, float *opac_eff, bds_stream_t stream) {
+  BDS_REQUIRE(C >= 1 && N >= 0 && W > 0 && H > 0);
+  if (N == 0) return BDS_OK;
+  BDS_REQUIRE(means && quats && scales && opacities && viewmats && Ks && radii && means2d && depths && conics && opac_eff);
+  hipLaunchKernelGGL(project_fwd_kernel<true>, dim3((unsigned)cdiv(N, kProjBlock)), dim3(kProjBlock), 0, as_stream(stream), C, N,
                      means, quats, scales, viewmats, Ks, W, H, eps2d, near_plane, far_plane, radius_clip, radii,
-                     means2d, depths, conics, compensations);
+                     means2d, depths, conics, compensations, opacities, opac_eff);
   BDS_LAUNCH_CHECK();
   return BDS_OK;
 }
@@ -382,16 +434,20 @@ extern "C" int bds_project_bwd(int C, int64_t N, const float *means, const float
                                bds_stream_t stream) {
   (void)conics; (void)compensations;
   BDS_REQUIRE(C >= 1 && N >= 0 && W > 0 && H > 0);
-  BDS_REQUIRE(v_compensations == nullptr);  // "antialiased" backward is not on the reference's path
   if (v_viewmats) {
     if (hipMemsetAsync(v_viewmats, 0, sizeof(float) * 16 * C, as_stream(stream)) != hipSuccess) return BDS_ELAUNCH;
   }
   if (N == 0) return BDS_OK;
   BDS_REQUIRE(means && quats && scales && viewmats && Ks && radii && v_means2d && v_depths && v_conics && v_means &&
               v_quats && v_scales);
-  hipLaunchKernelGGL(project_bwd_kernel, dim3((unsigned)cdiv(N, kProjBlock)), dim3(kProjBlock), 0, as_stream(stream), C, N,
-                     means, quats, scales, viewmats, Ks, W, H, eps2d, radii, v_means2d, v_depths, v_conics, v_means,
-                     v_quats, v_scales, v_viewmats);
+  if (v_compensations)      // rasterize_mode "antialiased": the compensations' gradient (recomputed in the VJP, not read)
+    hipLaunchKernelGGL(project_bwd_kernel<true>, dim3((unsigned)cdiv(N, kProjBlock)), dim3(kProjBlock), 0, as_stream(stream), C, N,
+                       means, quats, scales, viewmats, Ks, W, H, eps2d, radii, v_means2d, v_depths, v_conics, v_means,
+                       v_quats, v_scales, v_viewmats, v_compensations);
+  else
+    hipLaunchKernelGGL(project_bwd_kernel<false>, dim3((unsigned)cdiv(N, kProjBlock)), dim3(kProjBlock), 0, as_stream(stream), C, N,
+                       means, quats, scales, viewmats, Ks, W, H, eps2d, radii, v_means2d, v_depths, v_conics, v_means,
+                       v_quats, v_scales, v_viewmats, static_cast<const float *>(nullptr));
   BDS_LAUNCH_CHECK();
   return BDS_OK;
 }
@@ -417,7 +473,8 @@ static int project_view_fwd_impl(int64_t N, const float *means, const float *qua
   if (view_rows(means2d, depths, conics, &rows) != BDS_OK) return BDS_EINVAL;
   hipLaunchKernelGGL(project_view_fwd_kernel<false>, dim3((unsigned)cdiv(N, kProjBlock)), dim3(kProjBlock), 0, as_stream(stream), N,
                      means, quats, log_scales, logits, viewmat, K, W, H, eps2d, near_plane, far_plane, radius_clip, scales,
-                     opacities, radii, means2d, depths, conics, PrepReduceSlots{}, static_cast<int32_t *>(nullptr), rows, block_bounds);
+                     opacities, radii, means2d, depths, conics, PrepReduceSlots{}, static_cast<int32_t *>(nullptr), rows, block_bounds,
+                     static_cast<float *>(nullptr));
   BDS_LAUNCH_CHECK();
   return BDS_OK;
 }
@@ -446,7 +503,7 @@ static int project_view_prepare_fwd_impl(int64_t N, const float *means, const fl
   if (view_rows(means2d, depths, conics, &rows) != BDS_OK) return BDS_EINVAL;
   hipLaunchKernelGGL(project_view_fwd_kernel<true>, dim3((unsigned)cdiv(N, kProjBlock)), dim3(kProjBlock), 0, as_stream(stream), N,
                      means, quats, log_scales, logits, viewmat, K, W, H, eps2d, near_plane, far_plane, radius_clip, scales,
-                     opacities, radii, means2d, depths, conics, rs, tiles_per_gauss, rows, block_bounds);
+                     opacities, radii, means2d, depths, conics, rs, tiles_per_gauss, rows, block_bounds, static_cast<float *>(nullptr));
   BDS_LAUNCH_CHECK();
   return BDS_OK;
 }
@@ -483,6 +540,39 @@ extern "C" int bds_project_view_prepare_fwd_blocks(int64_t N, const float *means
   return project_view_prepare_fwd_impl(N, means, quats, log_scales, logits, viewmat, K, W, H, eps2d, near_plane, far_plane, radius_clip,
                                        scales, opacities, radii, means2d, depths, conics, tiles_per_gauss, prep_ws, prep_ws_bytes,
                                        block_bounds, stream);
+}
+
+// The one-view forward of rasterize_mode "antialiased" (models/trainers/base.py:406, :824): bds_project_view_fwd with the effective
+// opacity sigmoid(logit) * comp where the tile stage and the compositor read it -- the rows' slot 7 in the [N,8] row form, else
+// opac_eff [N] (required then; ignored in the row form).  `opacities` receives sigmoid(logit) (the backward's o).  prep_ws (nullable):
+// the prepare form (bds_project_view_prepare_fwd; BDS_ECAPACITY as there); block_bounds (nullable): the _blocks form.
+extern "C" int bds_project_view_fwd_aa(int64_t N, const float *means, const float *quats, const float *log_scales, const float *logits,
+                                       const float *viewmat, const float *K, int W, int H, float eps2d, float near_plane, float far_plane,
+                                       float radius_clip, float *scales, float *opacities, float *opac_eff, int32_t *radii, float *means2d,
+                                       float *depths, float *conics, int32_t *tiles_per_gauss, void *prep_ws, size_t prep_ws_bytes,
+                                       const float *block_bounds, bds_stream_t stream) {
+  BDS_REQUIRE(N >= 0 && W > 0 && H > 0);
+  BDS_REQUIRE(prep_ws == nullptr || N > 0);
+  if (N == 0) return BDS_OK;
+  BDS_REQUIRE(means && quats && log_scales && logits && viewmat && K && scales && opacities && radii && means2d && depths && conics);
+  int rows = 0;
+  if (view_rows(means2d, depths, conics, &rows) != BDS_OK) return BDS_EINVAL;
+  BDS_REQUIRE(rows || opac_eff);
+  const dim3 grid((unsigned)cdiv(N, kProjBlock)), block(kProjBlock);
+  if (prep_ws) {
+    PrepReduceSlots rs;
+    int rc = prep_reduce_slots(prep_ws, prep_ws_bytes, N, &rs);
+    if (rc != BDS_OK) return rc;
+    hipLaunchKernelGGL((project_view_fwd_kernel<true, true>), grid, block, 0, as_stream(stream), N, means, quats, log_scales, logits,
+                       viewmat, K, W, H, eps2d, near_plane, far_plane, radius_clip, scales, opacities, radii, means2d, depths, conics, rs,
+                       tiles_per_gauss, rows, block_bounds, opac_eff);
+  } else {
+    hipLaunchKernelGGL((project_view_fwd_kernel<false, true>), grid, block, 0, as_stream(stream), N, means, quats, log_scales, logits,
+                       viewmat, K, W, H, eps2d, near_plane, far_plane, radius_clip, scales, opacities, radii, means2d, depths, conics,
+                       PrepReduceSlots{}, static_cast<int32_t *>(nullptr), rows, block_bounds, opac_eff);
+  }
+  BDS_LAUNCH_CHECK();
+  return BDS_OK;
 }
 
 namespace bds {
@@ -599,6 +689,39 @@ extern "C" int bds_project_view_bwd_list_dev(int64_t n_capacity, const uint64_t 
   return project_view_bwd_list_impl(n_capacity, n_dev, ids, means, quats, scales, opacities, viewmat, K, W, H, eps2d, v_records,
                                     v_means, v_quats, v_log_scales, v_logits, v_viewmat_slots, grad2d, absgrad2d, row_map, accumulate,
                                     stream);
+}
+
+// The list-driven one-view backward of rasterize_mode "antialiased" (models/trainers/base.py:406): record channel 11 is the gradient
+// of the effective opacity o * comp; comp is recomputed in the VJP.  flags: BDS_PROJ_AA_ACCUMULATE adds to the gradient rows
+// (bds_project_view_bwd_list's `accumulate`); BDS_PROJ_AA_ACTIVATED is the gsplat-shaped form of bds_project_bwd_list (activated
+// scales / opacities in, their gradients out, v_colors [N,3] scattered; no row_map, no accumulate), else the raw form of
+// bds_project_view_bwd_list (log-scales / logits).  n_dev (nullable): the device-count form (bds_project_view_bwd_list_dev), n_list is
+// then the capacity.
+extern "C" int bds_project_view_bwd_list_aa(int flags, int64_t n_list, const uint64_t *n_dev, const int32_t *ids, const float *means,
+                                            const float *quats, const float *scales, const float *opacities, const float *viewmat,
+                                            const float *K, int W, int H, float eps2d, const float *v_records, float *v_means,
+                                            float *v_quats, float *v_scales, float *v_opacities, float *v_colors, float *v_viewmat_slots,
+                                            float *grad2d, float *absgrad2d, const int32_t *row_map, bds_stream_t stream) {
+  BDS_REQUIRE(n_list >= 0 && W > 0 && H > 0);
+  BDS_REQUIRE((flags & ~(BDS_PROJ_AA_ACCUMULATE | BDS_PROJ_AA_ACTIVATED)) == 0);
+  const bool acc = flags & BDS_PROJ_AA_ACCUMULATE, activated = flags & BDS_PROJ_AA_ACTIVATED;
+  BDS_REQUIRE(!activated || (!acc && row_map == nullptr));
+  if (n_list == 0) return BDS_OK;
+  BDS_REQUIRE(ids && means && quats && scales && opacities && viewmat && K && v_records && aligned16(v_records) && v_means &&
+              v_quats && v_scales && v_opacities);
+  const dim3 grid((unsigned)cdiv(n_list, kProjBlock)), block(kProjBlock);
+  const float4 *v4 = reinterpret_cast<const float4 *>(v_records);
+  const GradLayout gl = activated ? GradLayout{3, 4, 3, 1} : grad_layout(v_means, v_quats, v_scales, v_opacities);
+#define BDS_LIST_AA(A, P, R)                                                                                                          \
+  hipLaunchKernelGGL((project_view_bwd_list_kernel<A, P, R, true>), grid, block, 0, as_stream(stream), n_list, n_dev, ids, means,     \
+                     quats, scales, opacities, viewmat, K, W, H, eps2d, v4, v_means, v_quats, v_scales, v_opacities, v_viewmat_slots,  \
+                     grad2d, absgrad2d, row_map, R ? static_cast<float *>(nullptr) : v_colors, gl)
+  if (activated) { if (v_viewmat_slots) BDS_LIST_AA(false, true, false); else BDS_LIST_AA(false, false, false); }
+  else if (acc)  { if (v_viewmat_slots) BDS_LIST_AA(true, true, true); else BDS_LIST_AA(true, false, true); }
+  else           { if (v_viewmat_slots) BDS_LIST_AA(false, true, true); else BDS_LIST_AA(false, false, true); }
+#undef BDS_LIST_AA
+  BDS_LAUNCH_CHECK();
+  return BDS_OK;
 }
 
 // Bit t of *flags_dev is set when tensors[t] (counts[t] floats) holds a NaN or an Inf (vanilla.py:407-412); the word is cleared first.

@@ -213,6 +213,8 @@ def _front_begin(cfg: dict, means, quats, log_scales, logits, sh, viewmat) -> _F
     caps = cfg.get("caps")                 # ListCapacity: the device-count form (no host wait in this view)
     in_pack = cfg.get("sh_in_pack", SH_IN_PACK if caps is None else SH_IN_PACK_DEV)
     pack_colours = sh_rest is not None or (in_pack and (K * 3) % 4 == 0 and sh.data_ptr() % 16 == 0)
+    aa = bool(cfg.get("antialiased"))     # rasterize_mode "antialiased" (trainers/base.py:406): tiles and compositor read opacity * comp
+    opac_eff = None
     if pack_colours and _PROJ_ROWS and N > 0:
         # the projection's outputs as the columns of ONE [N,8] block of 32-byte rows (csrc/bds_common.h ProjLayout): the tile stage
         # and the record pack gather one line per visible Gaussian instead of one per array; radii / opacities stay dense as well
@@ -220,6 +222,8 @@ def _front_begin(cfg: dict, means, quats, log_scales, logits, sh, viewmat) -> _F
         means2d, depths, conics, opac_row = rows[None, :, 0:2], rows[None, :, 2], rows[None, :, 4:7], rows[:, 7]
     else:
         means2d, depths, conics, opac_row = _empty((1, N, 2), dev), _empty((1, N), dev), _empty((1, N, 3), dev), opac
+        if aa:
+            opac_row = opac_eff = _empty((N,), dev)   # (the effective opacities; `opac` keeps sigmoid(logit) for the backward)
     tiles_per_gauss = _empty((1, N), dev, torch.int32)
     ws_bytes = lib.bds_isect_prepare_workspace_bytes(1, N)
     ws = cfg.get("prep_ws")   # a caller-owned prepare workspace (graph_view: the lists and their counts outlive the view)
@@ -230,7 +234,18 @@ def _front_begin(cfg: dict, means, quats, log_scales, logits, sh, viewmat) -> _F
     pre_reduced = False
     bounds = cfg.get("block_bounds")      # [cdiv(N, 256), 8] of bds_gaussian_block_bounds over THESE means / log_scales (graph_view: once per frame)
     with L.timed("project_fwd"):
-        if cfg.get("caps") is not None and _PROJECT_PREPARES and N > 0:
+        if aa and N > 0:
+            args = (N, L.ptr(means), L.ptr(quats), L.ptr(log_scales), L.ptr(logits), L.ptr(viewmat), L.ptr(Kmat), W, H, cfg["eps2d"],
+                    cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"], L.ptr(scales), L.ptr(opac), L.ptr(opac_eff),
+                    L.ptr(radii), _dp(means2d), _dp(depths), _dp(conics))
+            if cfg.get("caps") is not None and _PROJECT_PREPARES:
+                rc = lib.bds_project_view_fwd_aa(*args, L.ptr(tiles_per_gauss), L.ptr(ws), ws_bytes, L.ptr(bounds), st)
+                pre_reduced = rc == L.BDS_OK
+                if rc not in (L.BDS_OK, L.BDS_ECAPACITY):
+                    L.check(rc, "bds_project_view_fwd_aa")
+            if not pre_reduced:
+                L.check(lib.bds_project_view_fwd_aa(*args, None, None, 0, L.ptr(bounds), st), "bds_project_view_fwd_aa")
+        elif cfg.get("caps") is not None and _PROJECT_PREPARES and N > 0:
             args = (N, L.ptr(means), L.ptr(quats), L.ptr(log_scales), L.ptr(logits), L.ptr(viewmat),
                     L.ptr(Kmat), W, H, cfg["eps2d"], cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"],
                     L.ptr(scales), L.ptr(opac), L.ptr(radii), _dp(means2d), _dp(depths), _dp(conics),
@@ -240,7 +255,7 @@ def _front_begin(cfg: dict, means, quats, log_scales, logits, sh, viewmat) -> _F
             pre_reduced = rc == L.BDS_OK
             if rc not in (L.BDS_OK, L.BDS_ECAPACITY):     # (ECAPACITY: N beyond the short sort path -- the plain projection below)
                 L.check(rc, "bds_project_view_prepare_fwd")
-        if not pre_reduced:
+        if not pre_reduced and not (aa and N > 0):
             args = (N, L.ptr(means), L.ptr(quats), L.ptr(log_scales), L.ptr(logits), L.ptr(viewmat),
                     L.ptr(Kmat), W, H, cfg["eps2d"], cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"],
                     L.ptr(scales), L.ptr(opac), L.ptr(radii), _dp(means2d), _dp(depths), _dp(conics))
@@ -293,7 +308,9 @@ def _front_begin(cfg: dict, means, quats, log_scales, logits, sh, viewmat) -> _F
     f.means, f.quats, f.log_scales, f.sh, f.viewmat, f.cam_pos = means, quats, log_scales, sh, viewmat, cam_pos
     f.sh_rest, f.K = sh_rest, K
     f.scales, f.opac, f.radii, f.means2d, f.depths, f.conics = scales, opac, radii, means2d, depths, conics
-    f.opac_row = opac_row      # (the activated opacities where the tile stage / the pack read them: the rows' column, or `opac` itself)
+    f.opac_row = opac_row      # (the activated opacities where the tile stage / the pack read them: the rows' column, or `opac` itself;
+    #                             antialiased: opacity * comp -- the rows' column or a dense array of its own)
+    f.aa = aa
     f.sh_rgb, f.colors, f.sh_by_rank, f.sh_degree = sh_rgb, colors, False, cfg["sh_degree"]
     f.tiles_per_gauss, f.isect_offsets, f.ws, f.ws_bytes, f.cull = tiles_per_gauss, isect_offsets, ws, ws_bytes, cull
     f.counts, f.ev, f.key, f.cap, f.vcap, f.caps = counts, ev, key, cap, vcap, caps
@@ -730,7 +747,14 @@ class _FusedView(torch.autograd.Function):
             v_vm_slots = (v_rec_all[max(n_vis, 1):max(n_vis, 1) + L.POSE_GRAD_SLOTS].view(L.POSE_GRAD_SLOTS, 4, 4)
                           if want_pose else None)   # camera-pose gradient (base.py:328-329,399)
         with L.timed("project_bwd"):
-            if dev_counts is not None:
+            if cfg.get("antialiased"):     # record channel 11 is the gradient of opacity * comp (include/bds.h bds_project_view_bwd_list_aa)
+                L.check(lib.bds_project_view_bwd_list_aa(L.PROJ_AA_ACCUMULATE if rows == 2 else 0, n_vis,
+                                                         None if dev_counts is None else dev_counts[1], L.ptr(vis_ids), L.ptr(means),
+                                                         L.ptr(quats), L.ptr(scales), L.ptr(opac), L.ptr(viewmat.contiguous()), L.ptr(Kmat), W, H,
+                                                         cfg["eps2d"], L.ptr(v_rec), _dp(v_means), _dp(v_quats), _dp(v_ls), _dp(v_logits), None,
+                                                         L.ptr(v_vm_slots), L.ptr(g2d[0]), L.ptr(g2d[1]), L.ptr(row_map), st),
+                        "bds_project_view_bwd_list_aa")
+            elif dev_counts is not None:
                 L.check(lib.bds_project_view_bwd_list_dev(n_vis, dev_counts[1], L.ptr(vis_ids), L.ptr(means), L.ptr(quats), L.ptr(scales),
                                                           L.ptr(opac), L.ptr(viewmat.contiguous()), L.ptr(Kmat), W, H, cfg["eps2d"], L.ptr(v_rec),
                                                           _dp(v_means), _dp(v_quats), _dp(v_ls), _dp(v_logits), L.ptr(v_vm_slots),
@@ -759,7 +783,7 @@ def fused_view(params: Dict[str, Tensor], viewmat: Tensor, K: Tensor, width: int
                radius_clip: float = 0.0, eps2d: float = 0.3, tile_cull: bool = True,
                grad_arena: Optional[Dict[str, Tensor]] = None, cam_pos: Optional[Tensor] = None,
                img_idx: Optional[int] = None, arena_rows: int = 0, grad_sink=None, list_tile: Optional[int] = None,
-               caps: Optional[ListCapacity] = None, prep_ws: Optional[Tensor] = None):
+               caps: Optional[ListCapacity] = None, prep_ws: Optional[Tensor] = None, antialiased: bool = False):
     """params: means [N,3], quats [N,4] (raw), log_scales [N,3], opacity_logits [N], sh [N,16,3];
     grids: per level [1,12,L,gy,gx] (the current image's grids), or -- with ``img_idx`` -- the full parameters
     [n_img,12,L,gy,gx] of which image ``img_idx`` is used (models/modules.py:507-512); the gradient then comes back in the
@@ -782,14 +806,16 @@ def fused_view(params: Dict[str, Tensor], viewmat: Tensor, K: Tensor, width: int
     ``caps`` (``ListCapacity``): the device-count form -- no host wait at all; the lists are built into buffers of these capacities
     and every kernel takes its counts from device memory (what ``graph_view.ViewGraph`` captures in a hipGraph).  ``info["n_isects"]``
     / ``["n_visible"]`` are then the CAPACITIES (the lists' tensors have those lengths; entries beyond the counts are undefined);
-    the actual counts arrive in ``caps.counts``."""
+    the actual counts arrive in ``caps.counts``.
+    ``antialiased``: rasterize_mode "antialiased" (``render.antialiased``, trainers/base.py:406): every Gaussian is composited with
+    opacity * comp, comp = sqrt(det S2 / det(S2 + eps2d I)), computed and differentiated inside the projection kernels."""
     if cam_pos is None:  # camera centre (vanilla.py:385 uses camtoworlds.data[..., :3, 3]); callers with fixed cameras cache it
         cam_pos = torch.linalg.inv(viewmat.detach())[:3, 3].contiguous()
     cfg = dict(width=int(width), height=int(height), K=K, cam_pos=cam_pos.detach(), factors=tuple(int(f) for f in factors),
                sh_degree=int(sh_degree), near_plane=float(near_plane), far_plane=float(far_plane), radius_clip=float(radius_clip),
                eps2d=float(eps2d), tile_cull=bool(tile_cull), grad_arena=grad_arena, grad_sink=grad_sink,
                img_idx=None if img_idx is None else int(img_idx), arena_rows=int(arena_rows),
-               list_tile=int(LIST_TILE if list_tile is None else list_tile), caps=caps, prep_ws=prep_ws)
+               list_tile=int(LIST_TILE if list_tile is None else list_tile), caps=caps, prep_ws=prep_ws, antialiased=bool(antialiased))
     gs = [g if g.dim() == 5 else g[None] for g in grids]
     # in-place grid gradients only when the arena entries ARE the grids' .grad right now (dist.FrameExchange.begin_frame sets that up)
     if grad_arena is not None and int(arena_rows) >= 1 and grad_sink is None:
@@ -810,7 +836,7 @@ def fused_view(params: Dict[str, Tensor], viewmat: Tensor, K: Tensor, width: int
 def render_classes(params: Dict[str, Tensor], viewmat: Tensor, K: Tensor, width: int, height: int, masks: Dict[str, Tensor],
                    sh_degree: int = 3, near_plane: float = 0.1, far_plane: float = 1e10, radius_clip: float = 0.0, eps2d: float = 0.3,
                    tile_cull: bool = True, cam_pos: Optional[Tensor] = None, include_full: bool = True,
-                   list_tile: Optional[int] = None) -> Dict[str, Tensor]:
+                   list_tile: Optional[int] = None, antialiased: bool = False) -> Dict[str, Tensor]:
     """Evaluation re-renders of Gaussian subsets (per-class and "Dynamic" images, trainers/scene_graph.py:296-313): the reference calls
     its ``render_fn(gaussian_mask)`` once per class, i.e. the whole ``rasterization`` again with ``opacities * mask``
     (trainers/base.py:392-416).  Projection, SH colours, the tile lists and their sort do not depend on the mask, so here they are
@@ -819,13 +845,14 @@ def render_classes(params: Dict[str, Tensor], viewmat: Tensor, K: Tensor, width:
 
     masks: name -> [N] bool / float.  Returns ``{name+"_rgb": [H,W,3] (clamped at 1), name+"_depth": [H,W,1] expected depth,
     name+"_opacity": [H,W,1]}`` for every mask, plus ``rgb_gaussians`` / ``depth`` / ``opacity`` of the unmasked scene with
-    ``include_full``."""
+    ``include_full``.  ``antialiased`` (trainers/base.py:824): the mask multiplies the EFFECTIVE opacity, opacity * comp."""
     if cam_pos is None:
         cam_pos = torch.linalg.inv(viewmat)[:3, 3].contiguous()
     cfg = dict(width=int(width), height=int(height), K=K, cam_pos=cam_pos, sh_degree=int(sh_degree), near_plane=float(near_plane),
                far_plane=float(far_plane), radius_clip=float(radius_clip), eps2d=float(eps2d), tile_cull=bool(tile_cull),
                list_tile=int(LIST_TILE if list_tile is None else list_tile),
-               sh_in_pack=False)   # the colours are evaluated once and packed with every mask's opacities
+               sh_in_pack=False,   # the colours are evaluated once and packed with every mask's opacities
+               antialiased=bool(antialiased))
     f = _view_front(cfg, params["means"].detach(), params["quats"].detach(), params["log_scales"].detach(),
                     params["opacity_logits"].detach(), params["sh"].detach(), viewmat.detach())
 
@@ -839,7 +866,8 @@ def render_classes(params: Dict[str, Tensor], viewmat: Tensor, K: Tensor, width:
         out["rgb_gaussians"], out["depth"], out["opacity"] = image(f.opac)
     for name, m in masks.items():
         assert m.shape == (f.N,), (name, tuple(m.shape), f.N)
-        out[name + "_rgb"], out[name + "_depth"], out[name + "_opacity"] = image(f.opac * m.to(f.opac.dtype))
+        base = f.opac_row if f.aa else f.opac      # (antialiased: opacity * comp, as the reference's render_fn(mask) composites it)
+        out[name + "_rgb"], out[name + "_depth"], out[name + "_opacity"] = image(base * m.to(f.opac.dtype))
     return out
 
 
@@ -914,7 +942,7 @@ def train_view(params: Dict[str, Tensor], viewmat: Tensor, K: Tensor, width: int
     # the TV term over OTHER tensors than the transform's grids: graph_view's replayable view slices staging copies of ONE image's
     # grids (picked by a device-side index) while the regulariser runs over the full [n_img, ...] parameters (modules.py:445)
     tv_grids, tv_grid_grads = kwargs.pop("tv_grids", None), kwargs.pop("tv_grid_grads", None)
-    opts = dict(sh_degree=3, near_plane=0.1, far_plane=1e10, radius_clip=0.0, eps2d=0.3, tile_cull=True)
+    opts = dict(sh_degree=3, near_plane=0.1, far_plane=1e10, radius_clip=0.0, eps2d=0.3, tile_cull=True, antialiased=False)
     opts.update({k: kwargs.pop(k) for k in list(kwargs) if k in opts})
     assert not kwargs, f"unknown arguments {sorted(kwargs)}"
     cfg = dict(width=int(width), height=int(height), K=K, cam_pos=cam_pos.detach(), factors=tuple(int(f) for f in factors),
@@ -923,7 +951,7 @@ def train_view(params: Dict[str, Tensor], viewmat: Tensor, K: Tensor, width: int
                grad_arena=grad_arena, grad_sink=grad_sink, img_idx=None if img_idx is None else int(img_idx), arena_rows=arena_rows,
                list_tile=int(LIST_TILE if list_tile is None else list_tile), caps=caps, prep_ws=prep_ws, g2d_buf=g2d_buf, tail_buf=tail_buf,
                defer_epilogue=defer_epilogue, split_len=split_len, split_cap=split_cap, block_bounds=block_bounds,
-               defer_pose_sum=defer_pose_sum, row_catchup=row_catchup)
+               defer_pose_sum=defer_pose_sum, row_catchup=row_catchup, antialiased=bool(opts["antialiased"]))
     gs = [g if g.dim() == 5 else g[None] for g in grids]
     if grad_arena is not None and (arena_rows >= 1 or grad_sink is not None):
         # (with a sink the arena names the GRID gradients only: the per-Gaussian rows go to the sink's compact buffers)

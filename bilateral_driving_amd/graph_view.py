@@ -61,7 +61,7 @@ class FrameGraph(FrameCapacities):
                  targets: Sequence[Tensor], factors: Sequence[int] = Hn.FACTORS_3, tv_weight: float = 0.01,
                  img_indices: Optional[Sequence[int]] = None, headroom: float = 1.5, list_tile: Optional[int] = None,
                  sh_degree: int = 3, extra_params: Sequence[Tensor] = (), overlap: bool = True, exchange=None, dynamic: bool = False,
-                 calib_cams: Optional[Sequence[Hn.Camera]] = None, clear_grads: bool = True, row_catchup=None):
+                 calib_cams: Optional[Sequence[Hn.Camera]] = None, clear_grads: bool = True, row_catchup=None, antialiased: bool = False):
         """params: the five per-Gaussian leaves (``dist.ROW_NAMES``); grids: per level [n_img,12,L,gy,gx] leaves; cams / skies /
         targets: one per view of the frame; ``img_indices[v]``: the grid image of view v (default v).  ``headroom``: list capacity =
         headroom x the counts of the calibration visit.
@@ -109,6 +109,9 @@ class FrameGraph(FrameCapacities):
         self.factors, self.tv_weight, self.sh_degree = tuple(int(f) for f in factors), float(tv_weight), int(sh_degree)
         self.headroom = float(headroom)
         self.list_tile = int(LIST_TILE if list_tile is None else list_tile)
+        # rasterize_mode "antialiased" (trainers/base.py:406) in every captured view.  The capacities are still calibrated on classic
+        # lists: the visible set is the same (radius-based) and opacity * comp <= opacity only shortens the culled tile lists.
+        self.antialiased = bool(antialiased)
         L.require_gpu(*self.params.values(), *self.grids)
         self.N, self.K = self.params["means"].shape[0], self.params["sh"].shape[1]
         self.names = list(ROW_NAMES) + [f"grid{i}" for i in range(len(self.grids))]
@@ -160,7 +163,7 @@ class FrameGraph(FrameCapacities):
                   sh_degree=self.sh_degree, two_phase=True, lazy_loss=True, split_len=self.split_len[v], split_cap=self.split_cap[v],
                   # two streams: the transform's memory-bound last stage hides behind the other stream's compositor; folded into the
                   # compositor's backward it would lengthen the VALU-bound critical kernel (fused_view._DEFER_EPILOGUE)
-                  defer_epilogue=not self.overlap, block_bounds=self._bounds, row_catchup=self.row_catchup)
+                  defer_epilogue=not self.overlap, block_bounds=self._bounds, row_catchup=self.row_catchup, antialiased=self.antialiased)
         if self.fx is not None:     # rows into view v's compact exchange buffer; the dense tail (grids) accumulates in place in .grad
             kw.update(grad_sink=self.fx.static_sink(v), grid_grads=None)
             if self.dynamic:        # the transform's grid gradient -> the slot's staging slices, the TV term -> the parameters' slices

@@ -106,12 +106,9 @@ class _Projection(torch.autograd.Function):
     @staticmethod
     def backward(ctx, v_radii, v_means2d, v_depths, v_conics, v_comps=None):
         means, quats, scales, viewmats, Ks, radii, conics = ctx.saved_tensors
-        if v_comps is not None and bool((v_comps != 0).any()):
-            raise NotImplementedError("gradient through compensations (rasterize_mode='antialiased') is not on the "
-                                      "reference's path (render.antialiased is false in every shipped config)")
         width, height, eps2d = ctx.cfg
         Cn, N = viewmats.shape[0], means.shape[0]
-        v_means2d, v_depths, v_conics = _f32c(v_means2d), _f32c(v_depths), _f32c(v_conics)
+        v_means2d, v_depths, v_conics, v_comps = _f32c(v_means2d), _f32c(v_depths), _f32c(v_conics), _f32c(v_comps)
         v_means = torch.empty_like(means)
         v_quats = torch.empty_like(quats)
         v_scales = torch.empty_like(scales)
@@ -119,7 +116,7 @@ class _Projection(torch.autograd.Function):
         with L.timed("project_bwd"):
             L.check(L.lib().bds_project_bwd(Cn, N, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(viewmats), L.ptr(Ks), width,
                                             height, eps2d, L.ptr(radii), L.ptr(conics), None, L.ptr(v_means2d), L.ptr(v_depths),
-                                            L.ptr(v_conics), None, L.ptr(v_means), L.ptr(v_quats), L.ptr(v_scales),
+                                            L.ptr(v_conics), L.ptr(v_comps), L.ptr(v_means), L.ptr(v_quats), L.ptr(v_scales),
                                             L.ptr(v_viewmats), L.stream()), "bds_project_bwd")
         g = ctx.needs_input_grad
         return (v_means if g[0] else None, v_quats if g[1] else None, v_scales if g[2] else None, v_viewmats, None, None,

@@ -165,7 +165,7 @@ def set_tile_culling(on: bool) -> None:
     _TILE_CULLING = bool(on)
 
 
-# One camera, post-activation colours [N,3], "RGB" / "RGB+ED", classic mode, no backgrounds -- the reference's two call patterns
+# One camera, post-activation colours [N,3], "RGB" / "RGB+ED", either rasterize_mode, no backgrounds -- the reference's two call patterns
 # (models/trainers/base.py:393-408,811-826) -- run as ONE autograd node over compact lists (BDS_API_FUSED=0: the operator chain below)
 _ONE_VIEW_NODE = os.environ.get("BDS_API_FUSED", "1") != "0"
 _CHECK_FINITE = os.environ.get("BDS_API_CHECK_FINITE", "1") != "0"    # the raw one-view node's NaN / Inf check (vanilla.py:407-412)
@@ -191,14 +191,20 @@ class _RasterizeView(torch.autograd.Function):
         W, H, N = cfg["width"], cfg["height"], means.shape[0]
         radii = torch.empty(1, N, device=dev, dtype=torch.int32)
         means2d, depths, conics = torch.empty(1, N, 2, device=dev), torch.empty(1, N, device=dev), torch.empty(1, N, 3, device=dev)
+        opac_eff = torch.empty(1, N, device=dev) if cfg["aa"] else None      # antialiased: opacity * comp, what tiles and compositor read
         with L.timed("project_fwd"):
-            L.check(lib.bds_project_fwd(1, N, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(viewmat), L.ptr(Kmat), W, H, cfg["eps2d"],
-                                        cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"], L.ptr(radii), L.ptr(means2d), L.ptr(depths),
-                                        L.ptr(conics), None, st), "bds_project_fwd")
+            if opac_eff is not None:
+                L.check(lib.bds_project_fwd_aa(1, N, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(viewmat), L.ptr(Kmat), W, H,
+                                               cfg["eps2d"], cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"], L.ptr(radii), L.ptr(means2d),
+                                               L.ptr(depths), L.ptr(conics), None, L.ptr(opac_eff), st), "bds_project_fwd_aa")
+            else:
+                L.check(lib.bds_project_fwd(1, N, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(viewmat), L.ptr(Kmat), W, H, cfg["eps2d"],
+                                            cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"], L.ptr(radii), L.ptr(means2d), L.ptr(depths),
+                                            L.ptr(conics), None, st), "bds_project_fwd")
         LT = _LIST_TILE
         ltw, lth = math.ceil(W / LT), math.ceil(H / LT)
         tw, th = math.ceil(W / TILE_SIZE), math.ceil(H / TILE_SIZE)
-        opac_c = opacities.view(1, N)
+        opac_c = opacities.view(1, N) if opac_eff is None else opac_eff
         cull = cfg["cull"]
         cptr, optr = (L.ptr(conics), L.ptr(opac_c)) if cull else (None, None)
         tiles_per_gauss = torch.empty(1, N, device=dev, dtype=torch.int32)
@@ -243,7 +249,7 @@ class _RasterizeView(torch.autograd.Function):
                     "bds_isect_build")
         with L.timed("rasterize_fwd"):
             L.check(lib.bds_splat_pack_rgbd(n_vis, L.ptr(vis_ids), L.ptr(means2d), L.ptr(conics), L.ptr(colors3), L.ptr(depths),
-                                            L.ptr(opacities), L.ptr(radii), L.ptr(rec), st), "bds_splat_pack_rgbd")
+                                            L.ptr(opac_c), L.ptr(radii), L.ptr(rec), st), "bds_splat_pack_rgbd")
             L.check(lib.bds_rasterize_fwd(1, n_vis, M, 4, L.ptr(rec), None, W, H, TILE_SIZE, LT, tw, th, L.ptr(isect_offsets), L.ptr(flatten),
                                           L.ptr(render), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), st), "bds_rasterize_fwd")
         ctx.save_for_backward(means, quats, scales, opacities, viewmat, Kmat, rec, vis_ids, ws, flatten, isect_offsets, render, alphas, last_ids)
@@ -254,10 +260,12 @@ class _RasterizeView(torch.autograd.Function):
         else:
             out = render[..., :3] if cfg["channels"] == 3 else render
         ctx.mark_non_differentiable(radii, depths, conics)
+        if opac_eff is not None:
+            ctx.mark_non_differentiable(opac_eff)
         # undefined output gradients stay None: the reference never puts a loss on meta["means2d"], and a materialised [1,N,2] zero
         # tensor would cost a fill, an index_select and an add over the records in every backward
         ctx.set_materialize_grads(False)
-        return out, alphas, means2d, radii, depths, conics
+        return out, alphas, means2d, radii, depths, conics, opac_eff
 
     @staticmethod
     def backward(ctx, v_out, v_alphas, v_means2d_ext, *_):
@@ -293,10 +301,16 @@ class _RasterizeView(torch.autograd.Function):
         v_means, v_quats, v_scales, v_opac, v_colors, g2d, ag2d = outs
         slots = v_rec_all[max(n_vis, 1):].view(L.POSE_GRAD_SLOTS, 4, 4) if want_pose else None
         with L.timed("project_bwd"):
-            L.check(lib.bds_project_bwd_list(n_vis, L.ptr(vis_ids), L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(viewmat),
-                                             L.ptr(Kmat), W, H, cfg["eps2d"], L.ptr(v_rec), L.ptr(v_means), L.ptr(v_quats), L.ptr(v_scales),
-                                             L.ptr(v_opac), L.ptr(v_colors), L.ptr(slots), L.ptr(g2d), L.ptr(ag2d) if cfg["absgrad"] else None, st),
-                    "bds_project_bwd_list")
+            if cfg["aa"]:       # record channel 11: the gradient of opacity * comp (include/bds.h bds_project_view_bwd_list_aa)
+                L.check(lib.bds_project_view_bwd_list_aa(L.PROJ_AA_ACTIVATED, n_vis, None, L.ptr(vis_ids), L.ptr(means), L.ptr(quats), L.ptr(scales),
+                                                         L.ptr(opacities), L.ptr(viewmat), L.ptr(Kmat), W, H, cfg["eps2d"], L.ptr(v_rec), L.ptr(v_means),
+                                                         L.ptr(v_quats), L.ptr(v_scales), L.ptr(v_opac), L.ptr(v_colors), L.ptr(slots), L.ptr(g2d),
+                                                         L.ptr(ag2d) if cfg["absgrad"] else None, None, st), "bds_project_view_bwd_list_aa")
+            else:
+                L.check(lib.bds_project_bwd_list(n_vis, L.ptr(vis_ids), L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(viewmat),
+                                                 L.ptr(Kmat), W, H, cfg["eps2d"], L.ptr(v_rec), L.ptr(v_means), L.ptr(v_quats), L.ptr(v_scales),
+                                                 L.ptr(v_opac), L.ptr(v_colors), L.ptr(slots), L.ptr(g2d), L.ptr(ag2d) if cfg["absgrad"] else None, st),
+                        "bds_project_bwd_list")
         carrier = cfg["_means2d_ref"]() if cfg.get("_means2d_ref") is not None else None
         if carrier is not None:      # the tensor the caller holds in meta["means2d"] (trainers/base.py:280-297 read .absgrad / .grad)
             if cfg["absgrad"]:
@@ -326,7 +340,7 @@ class _RasterizeRawView(torch.autograd.Function):
         W, H, N = cfg["width"], cfg["height"], means.shape[0]
         fcfg = dict(width=W, height=H, K=Kmat, cam_pos=cfg["cam_pos"], sh_degree=cfg["sh_degree"], near_plane=cfg["near_plane"],
                     far_plane=cfg["far_plane"], radius_clip=cfg["radius_clip"], eps2d=cfg["eps2d"], tile_cull=cfg["cull"],
-                    list_tile=_LIST_TILE)
+                    list_tile=_LIST_TILE, antialiased=cfg["aa"])
         flags = None
         if cfg["check_finite"]:
             # in FRONT of the projection: the flag's copy to the host is then older than the event the one wait of this view waits for.
@@ -347,19 +361,20 @@ class _RasterizeRawView(torch.autograd.Function):
         ctx.save_for_backward(f.means, f.quats, f.scales, f.opac, viewmat, Kmat, rec, f.vis_ids, f.ws, f.flatten, f.isect_offsets, render, alphas,
                               last_ids, f.sh_rgb, f.cam_pos)
         ctx.cfg, ctx.M, ctx.shapes = cfg, f.M, (tuple(log_scales.shape), tuple(cfg["logits_shape"]), tuple(dc.shape), tuple(rest.shape))
-        ctx.mark_non_differentiable(f.radii, f.depths, f.conics, f.opac)
+        opac_out = f.opac_row if cfg["aa"] else f.opac      # (meta["opacities"]: what the compositor used -- antialiased: opacity * comp)
+        ctx.mark_non_differentiable(f.radii, f.depths, f.conics, opac_out)
         ctx.set_materialize_grads(False)
         if cfg.get("split"):       # rgb and depth as two outputs (SplitRender): 4-channel modes only
             rgb, depth = torch.empty(H, W, 3, device=dev), torch.empty(H, W, 1, device=dev)
             L.check(lib.bds_expected_depth_split_fwd(H * W, int(cfg["ed"]), L.ptr(render), L.ptr(alphas), L.ptr(rgb), L.ptr(depth), st),
                     "bds_expected_depth_split_fwd")
-            return rgb, depth, alphas, f.means2d, f.radii, f.depths, f.conics, f.opac
+            return rgb, depth, alphas, f.means2d, f.radii, f.depths, f.conics, opac_out
         if cfg["ed"]:
             out = torch.empty_like(render)
             L.check(lib.bds_expected_depth_fwd(H * W, L.ptr(render), L.ptr(alphas), L.ptr(out), st), "bds_expected_depth_fwd")
         else:
             out = render[..., :3] if cfg["channels"] == 3 else render
-        return out, None, alphas, f.means2d, f.radii, f.depths, f.conics, f.opac
+        return out, None, alphas, f.means2d, f.radii, f.depths, f.conics, opac_out
 
     @staticmethod
     def backward(ctx, v_out, v_depth, v_alphas, v_means2d_ext, *_):
@@ -406,10 +421,16 @@ class _RasterizeRawView(torch.autograd.Function):
                                                    L.ptr(v_rec), L.ptr(v_dc), L.ptr(v_rest), 0, st), "bds_sh_view_bwd_list_split")
         slots = v_rec_all[max(n_vis, 1):].view(L.POSE_GRAD_SLOTS, 4, 4) if want_pose else None
         with L.timed("project_bwd"):
-            L.check(lib.bds_project_view_bwd_list(n_vis, L.ptr(vis_ids), L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opac), L.ptr(viewmat),
-                                                  L.ptr(Kmat), W, H, cfg["eps2d"], L.ptr(v_rec), L.ptr(v_means), L.ptr(v_quats), L.ptr(v_ls),
-                                                  L.ptr(v_logits), L.ptr(slots), L.ptr(g2d), L.ptr(ag2d) if cfg["absgrad"] else None, None, 0,
-                                                  st), "bds_project_view_bwd_list")
+            if cfg["aa"]:
+                L.check(lib.bds_project_view_bwd_list_aa(0, n_vis, None, L.ptr(vis_ids), L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opac),
+                                                         L.ptr(viewmat), L.ptr(Kmat), W, H, cfg["eps2d"], L.ptr(v_rec), L.ptr(v_means), L.ptr(v_quats),
+                                                         L.ptr(v_ls), L.ptr(v_logits), None, L.ptr(slots), L.ptr(g2d),
+                                                         L.ptr(ag2d) if cfg["absgrad"] else None, None, st), "bds_project_view_bwd_list_aa")
+            else:
+                L.check(lib.bds_project_view_bwd_list(n_vis, L.ptr(vis_ids), L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opac), L.ptr(viewmat),
+                                                      L.ptr(Kmat), W, H, cfg["eps2d"], L.ptr(v_rec), L.ptr(v_means), L.ptr(v_quats), L.ptr(v_ls),
+                                                      L.ptr(v_logits), L.ptr(slots), L.ptr(g2d), L.ptr(ag2d) if cfg["absgrad"] else None, None, 0,
+                                                      st), "bds_project_view_bwd_list")
         carrier = cfg["_means2d_ref"]() if cfg.get("_means2d_ref") is not None else None
         if carrier is not None:
             if cfg["absgrad"]:
@@ -484,7 +505,7 @@ def rasterization(
         f"tile_size={tile_size}: a multiple of {TILE_SIZE} is required (lists of larger tiles are filtered per 16-px compositing tile)")
     src = lazy_source(means, quats, scales, opacities, colors)     # marshalling.install: a class's raw parameters behind placeholders
     raw_ok = (src is not None and _ONE_VIEW_NODE and viewmats.shape[0] == 1 and sh_degree is None and backgrounds is None
-              and render_mode in ("RGB", "RGB+ED") and rasterize_mode == "classic" and means.shape[0] > 0 and src.features_rest.shape[1] >= 1)
+              and render_mode in ("RGB", "RGB+ED") and means.shape[0] > 0 and src.features_rest.shape[1] >= 1)
     if not raw_ok:
         means, quats, scales, opacities, colors = materialised((means, quats, scales, opacities, colors))
     N = means.shape[0]
@@ -510,7 +531,7 @@ def rasterization(
                    radius_clip=float(radius_clip), ed=render_mode == "RGB+ED", channels=3 if render_mode == "RGB" else 4,
                    absgrad=bool(absgrad), cull=_TILE_CULLING, sh_degree=src.sh_degree, cam_pos=_f32c(src.cam_pos.detach().reshape(3)),
                    logits_shape=tuple(src.logits.shape), step=src.step, check_finite=_CHECK_FINITE,
-                   split=_SPLIT_RENDER and render_mode != "RGB")
+                   split=_SPLIT_RENDER and render_mode != "RGB", aa=rasterize_mode == "antialiased")
         out, depth1, alphas, means2d, radii, depths, conics, opac = _RasterizeRawView.apply(
             src.means, src.quats, src.log_scales, src.logits, src.features_dc, src.features_rest, viewmats[0], Ks[0], cfg)
         if depth1 is not None:      # the render as a placeholder over the node's two image outputs (SplitRender)
@@ -524,15 +545,17 @@ def rasterization(
         return out, alphas, meta
 
     if (_ONE_VIEW_NODE and C == 1 and N > 0 and sh_degree is None and colors.shape[-1] == 3 and backgrounds is None
-            and render_mode in ("RGB", "RGB+ED") and rasterize_mode == "classic"):
+            and render_mode in ("RGB", "RGB+ED")):
         cfg = dict(width=width, height=height, eps2d=float(eps2d), near_plane=float(near_plane), far_plane=float(far_plane),
                    radius_clip=float(radius_clip), ed=render_mode == "RGB+ED", channels=3 if render_mode == "RGB" else 4,
-                   absgrad=bool(absgrad), cull=_TILE_CULLING, colors_shape=tuple(colors.shape))
-        out, alphas, means2d, radii, depths, conics = _RasterizeView.apply(means, quats, scales, opacities, colors, viewmats[0], Ks[0], cfg)
+                   absgrad=bool(absgrad), cull=_TILE_CULLING, colors_shape=tuple(colors.shape), aa=rasterize_mode == "antialiased")
+        out, alphas, means2d, radii, depths, conics, opac_eff = _RasterizeView.apply(means, quats, scales, opacities, colors, viewmats[0], Ks[0],
+                                                                                     cfg)
         cfg["_means2d_ref"] = weakref.ref(means2d)      # the backward attaches .absgrad (and .grad, when retained) to THIS tensor object
         tile_width, tile_height = math.ceil(width / float(tile_size)), math.ceil(height / float(tile_size))
         meta = _Meta({"camera_ids": None, "gaussian_ids": None, "radii": radii, "means2d": means2d, "depths": depths, "conics": conics,
-                      "opacities": opacities.detach()[None, :], "tile_width": tile_width, "tile_height": tile_height,
+                      "opacities": opacities.detach()[None, :] if opac_eff is None else opac_eff, "tile_width": tile_width,
+                      "tile_height": tile_height,
                       "tiles_per_gauss": None, "isect_ids": None, "flatten_ids": None, "isect_offsets": None, "width": width,
                       "height": height, "tile_size": tile_size, "n_cameras": C, "_cull": _TILE_CULLING})
         return out, alphas, meta

@@ -81,7 +81,10 @@ int bds_sh_bwd(int64_t n, int K, int deg, const float *dirs, const float *coeffs
  * conic, 3-sigma radius, near/far/screen culling.
  * means [N,3] quats [N,4] (wxyz, normalised inside) scales [N,3] viewmats [C,4,4] Ks [C,3,3]
  * -> radii [C,N] i32 (0 = culled), means2d [C,N,2], depths [C,N], conics [C,N,3],
- *    compensations [C,N] or NULL ("antialiased" mode only).  Culled entries are zero-filled. */
+ *    compensations [C,N] or NULL.  Culled entries are zero-filled.
+ * compensations (rasterize_mode "antialiased", models/trainers/base.py:406): comp = sqrt(max(0, det S2 / det(S2 + eps2d I))), S2 the
+ * FOV-clamped 2-D covariance before the blur, det S2 formed as a sum of squares (exact for needles, where the difference of the
+ * entries' products is all rounding); the caller composites with opacity * comp. */
 int bds_project_fwd(int C, int64_t N, const float *means, const float *quats, const float *scales,
                     const float *viewmats, const float *Ks, int W, int H, float eps2d, float near_plane,
                     float far_plane, float radius_clip, int32_t *radii, float *means2d, float *depths, float *conics,
@@ -89,12 +92,20 @@ int bds_project_fwd(int C, int64_t N, const float *means, const float *quats, co
 /* v_means [N,3] v_quats [N,4] v_scales [N,3] are written (summed over cameras);
  * v_viewmats [C,4,4] (NULL = not needed) is zeroed and accumulated inside
  * (learnable camera poses: models/trainers/base.py:328-329,399).
- * v_compensations / compensations may be NULL. */
+ * compensations is not read (comp is recomputed) and may be NULL; v_compensations [C,N] or NULL: "antialiased" mode, adds the
+ * compensation's gradient -- gsplat's v_S += v_comp 0.5 / (comp + 1e-6) ((1 - r) conic - eps2d det(conic) I), r = comp^2 (zero where
+ * the clamp is active, r <= 0), evaluated without that cancelling difference (gs_math.h project_one_vjp). */
 int bds_project_bwd(int C, int64_t N, const float *means, const float *quats, const float *scales,
                     const float *viewmats, const float *Ks, int W, int H, float eps2d, const int32_t *radii,
                     const float *conics, const float *compensations, const float *v_means2d, const float *v_depths,
                     const float *v_conics, const float *v_compensations, float *v_means, float *v_quats,
                     float *v_scales, float *v_viewmats, bds_stream_t stream);
+/* bds_project_fwd + the effective opacities of rasterize_mode "antialiased" (models/trainers/base.py:406) in the same launch:
+ * opac_eff [C,N] = opacities[N] * comp (what the tile stage and the compositor read in that mode); compensations may be NULL. */
+int bds_project_fwd_aa(int C, int64_t N, const float *means, const float *quats, const float *scales, const float *opacities,
+                       const float *viewmats, const float *Ks, int W, int H, float eps2d, float near_plane, float far_plane,
+                       float radius_clip, int32_t *radii, float *means2d, float *depths, float *conics, float *compensations,
+                       float *opac_eff, bds_stream_t stream);
 
 /* ---- tile intersection + (tile|depth) ordering -------------------------------------------
  * isect_tiles + radix sort + isect_offset_encode stages of gsplat.rendering.rasterization.
@@ -361,6 +372,16 @@ int bds_project_view_prepare_fwd_blocks(int64_t N, const float *means, const flo
                                         float far_plane, float radius_clip, float *scales, float *opacities, int32_t *radii,
                                         float *means2d, float *depths, float *conics, int32_t *tiles_per_gauss, void *prep_ws,
                                         size_t prep_ws_bytes, const float *block_bounds, bds_stream_t stream);
+/* The one-view forward of rasterize_mode "antialiased" (models/trainers/base.py:406, :824) -- bds_project_view_fwd / _blocks /
+ * _prepare_fwd / _prepare_fwd_blocks in one entry: the opacity the tile stage and the compositor read is the EFFECTIVE one,
+ * sigmoid(logit) * comp -- slot 7 of the [N,8] row form, else opac_eff [N] (required in the column form, ignored in the row form);
+ * opacities [N] receives sigmoid(logit), which the backward reads.  prep_ws (NULL: the plain form) selects the prepare form
+ * (BDS_ECAPACITY as there); block_bounds (NULL: none) the _blocks form. */
+int bds_project_view_fwd_aa(int64_t N, const float *means, const float *quats, const float *log_scales, const float *logits,
+                            const float *viewmat, const float *K, int W, int H, float eps2d, float near_plane, float far_plane,
+                            float radius_clip, float *scales, float *opacities, float *opac_eff, int32_t *radii, float *means2d,
+                            float *depths, float *conics, int32_t *tiles_per_gauss, void *prep_ws, size_t prep_ws_bytes,
+                            const float *block_bounds, bds_stream_t stream);
 /* bds_project_view_fwd that also does the first launch of the tile stage (device-count form, C = 1): the number of visible Gaussians
  * per 256-Gaussian workgroup is left in prep_ws (bds_isect_prepare_workspace_bytes(1, N)), the stage's sort tables and
  * tiles_per_gauss [N] (may be NULL) are cleared.  Follow with bds_isect_prepare_dev(..., compact | 2, ...) on the SAME workspace.
@@ -425,6 +446,20 @@ int bds_project_view_bwd_list(int64_t n_list, const int32_t *ids, const float *m
                               const float *v_records, float *v_means, float *v_quats, float *v_log_scales, float *v_logits,
                               float *v_viewmat_slots, float *grad2d, float *absgrad2d, const int32_t *row_map, int accumulate,
                               bds_stream_t stream);
+/* The list-driven one-view backward of rasterize_mode "antialiased" (models/trainers/base.py:406) -- bds_project_view_bwd_list /
+ * _list_dev / bds_project_bwd_list in one entry.  Record channel 11 is the gradient of the effective opacity o * comp; comp is recomputed
+ * in the VJP: v_comp = v_eff * o enters the projection's gradient, the opacity gets v_eff * comp (times o (1 - o) for logits).
+ * flags: BDS_PROJ_AA_ACCUMULATE = `accumulate` of bds_project_view_bwd_list; BDS_PROJ_AA_ACTIVATED = the gsplat-shaped form of
+ * bds_project_bwd_list (activated scales / opacities, v_colors [N,3] scattered; row_map NULL, no accumulate), else the raw form
+ * (v_scales / v_opacities are the log-scale / logit gradients, v_colors unused).  n_dev (NULL: host count) = the _dev form, n_list is
+ * then the capacity. */
+#define BDS_PROJ_AA_ACCUMULATE 1
+#define BDS_PROJ_AA_ACTIVATED 2
+int bds_project_view_bwd_list_aa(int flags, int64_t n_list, const uint64_t *n_dev, const int32_t *ids, const float *means,
+                                 const float *quats, const float *scales, const float *opacities, const float *viewmat, const float *K,
+                                 int W, int H, float eps2d, const float *v_records, float *v_means, float *v_quats, float *v_scales,
+                                 float *v_opacities, float *v_colors, float *v_viewmat_slots, float *grad2d, float *absgrad2d,
+                                 const int32_t *row_map, bds_stream_t stream);
 /* Zero the rows ids[0..n_list) of the five per-Gaussian gradient arrays (v_sh is [N,K,3]). */
 int bds_view_grads_clear_list(int64_t n_list, const int32_t *ids, int K, float *v_means, float *v_quats, float *v_log_scales,
                               float *v_logits, float *v_sh, bds_stream_t stream);
