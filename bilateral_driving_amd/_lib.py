@@ -34,6 +34,13 @@ class BdsFeatLevel(C.Structure):
     _fields_ = [("grid", C.c_void_p), ("v_grid", C.c_void_p), ("gx", C.c_int32), ("gy", C.c_int32), ("gl", C.c_int32), ("nch", C.c_int32)]
 
 
+class BdsDeformNet(C.Structure):
+    """bds_deform_net / bds_deform_net_grad (same layout)"""
+
+    _fields_ = [("w", C.c_void_p * 8), ("b", C.c_void_p * 8), ("warp_w", C.c_void_p), ("warp_b", C.c_void_p), ("rot_w", C.c_void_p),
+                ("rot_b", C.c_void_p), ("scale_w", C.c_void_p), ("scale_b", C.c_void_p)]
+
+
 _SIGS = {
     "bds_abi_version": (C.c_int, []),
     "bds_strerror": (C.c_char_p, [_i]),
@@ -142,6 +149,11 @@ _SIGS = {
     "bds_mlp_head_bwd_temp_bytes": (_sz, [_i64, _i]),
     "bds_mlp_head_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _f]),
     "bds_mlp_head_bwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _f, _f, _f, _f, _f, _i, _f, _sz, _f]),
+    "bds_deform_supported": (_i, [_i, _i, _i, _i, _i, _i]),
+    "bds_deform_bwd_temp_bytes": (_sz, [_i64, _i]),
+    "bds_deform_fwd": (_i, [_i64, _i, _f, _f, _f, C.POINTER(BdsDeformNet), _f, _f, _f, _f]),
+    "bds_deform_bwd": (_i, [_i64, _i, _f, _f, _f, C.POINTER(BdsDeformNet), _f, _f, _f, _f, _f, _f, C.POINTER(BdsDeformNet), _i, _f, _sz,
+                            _f]),
     "bds_opacity_reset": (_i, [_i64, _f, _fl, _f, _f, _f]),
     "bds_cubemap_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f]),
     "bds_cubemap_bwd": (_i, [_i64, _i, _i, _i, _f, _f, _f, _f, _f]),

@@ -870,6 +870,37 @@ int bds_neural_image_bwd(int H, int W, int n_levels, const bds_feat_level *level
                          const float *w2, const float *w3, int residual, const float *v_out, float *v_rgb, float *v_w1, float *v_w2,
                          float *v_w3, int accumulate_w, void *temp, size_t temp_bytes, bds_stream_t stream);
 
+/* ---- Deformation network of deformable Gaussians -----------------------------------------------------------------------------
+ * ConditionalDeformNetwork / DeformNetwork (models/modules.py:925-1012, encoding `get_embedder` / `Embedder` :874-922) at the shipped
+ * size: D 8, W 256, x_multires = t_multires 10, input_ch 3, embed_dim 16 (DeformableNodes, models/nodes/deformable.py:35-47, 49-143)
+ * or 0 (DeformNetwork: models/gaussians/deformgs.py:62-72, 97-109); bds_deform_supported() != 0, anything else BDS_EINVAL.
+ *   h0 = [emb(x) 63 | emb(t) 21 | cond E] (K0 = 84 + E), 8 x (Linear + ReLU), layer 5 reading [h0 | h4] (skips = [D // 2]),
+ *   d_xyz = gaussian_warp(h), rotation = gaussian_rotation(h), scaling = gaussian_scaling(h).
+ * x [N,3], t [N] (one time per point), cond [N,E] (NULL when E = 0), all float32 contiguous.  Weights in torch's [out, in] layout
+ * (linear.{i}.weight [256, in_i]: in_0 = K0, in_5 = K0 + 256, else 256; heads [3|4|3, 256]); every weight 16-byte aligned.  A head
+ * that is off has NULL weight and bias (ConditionalDeformNetwork deform_quat / deform_scale = False); gaussian_warp is always on.
+ * fwd writes d_xyz [N,3] and rotation [N,4] / scaling [N,3] (each may be NULL).  One kernel on the FP32 matrix cores
+ * (csrc/deform.hip): the hidden activations never reach memory.
+ * bwd takes the output gradients (v_rotation / v_scaling may be NULL = zero), writes v_x [N,3], v_t [N], v_cond [N,E] (each may be
+ * NULL) and the parameter gradients named in `grad` (each may be NULL; stored, or added to when accumulate != 0).  The forward is
+ * recomputed chunk by chunk; temp: bds_deform_bwd_temp_bytes(N, E) bytes, 16-byte aligned (the chunk's activations / pre-activation
+ * gradients and the per-tile partial weight gradients, summed in a fixed order: the result is deterministic, no atomics). */
+typedef struct {
+  const float *w[8], *b[8];                               /* linear.{i}.weight / .bias */
+  const float *warp_w, *warp_b, *rot_w, *rot_b, *scale_w, *scale_b;
+} bds_deform_net;
+typedef struct {
+  float *w[8], *b[8];
+  float *warp_w, *warp_b, *rot_w, *rot_b, *scale_w, *scale_b;
+} bds_deform_net_grad;
+int bds_deform_supported(int D, int W, int x_multires, int t_multires, int input_ch, int embed_dim);
+size_t bds_deform_bwd_temp_bytes(int64_t N, int embed_dim);
+int bds_deform_fwd(int64_t N, int embed_dim, const float *x, const float *t, const float *cond, const bds_deform_net *net, float *d_xyz,
+                   float *rotation, float *scaling, bds_stream_t stream);
+int bds_deform_bwd(int64_t N, int embed_dim, const float *x, const float *t, const float *cond, const bds_deform_net *net,
+                   const float *v_xyz, const float *v_rotation, const float *v_scaling, float *v_x, float *v_t, float *v_cond,
+                   const bds_deform_net_grad *grad, int accumulate, void *temp, size_t temp_bytes, bds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
