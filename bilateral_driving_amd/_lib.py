@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BDS_LIB") or os.path.join(_HERE, "libbds.so")    # (BDS_LIB: an A/B variant built by build.py --variant)
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 _lock = threading.Lock()
 _lib = None
@@ -53,7 +53,7 @@ _SIGS = {
     "bds_last_hip_error": (_i, []),
     "bds_sh_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f]),
     "bds_sh_bwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f, _f, _f]),
-    "bds_project_fwd": (_i, [_i, _i64, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f]),
+    "bds_project_fwd": (_i, [_i, _i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f]),
     "bds_project_bwd": (_i, [_i, _i64, _f, _f, _f, _f, _f, _i, _i, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_isect_prepare_workspace_bytes": (_sz, [_i, _i64]),
     "bds_isect_visible_ids_offset": (_sz, [_i, _i64]),
@@ -73,13 +73,7 @@ _SIGS = {
     "bds_rasterize_bwd": (_i, [_i, _i64, _i64, _i, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _i, _f, _f]),
     "bds_rasterize_kernel_name": (_i, [_i, _i, _i, _i, C.c_char_p, _i]),
     "bds_rasterize_bwd_schedule": (_i, [_i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f]),
-    "bds_project_view_fwd": (_i, [_i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f]),
-    "bds_project_fwd_aa": (_i, [_i, _i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f]),
-    "bds_project_view_fwd_aa": (_i, [_i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _f, _f]),
-    "bds_project_view_bwd_list_aa": (_i, [_i, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
-    "bds_project_view_prepare_fwd": (_i, [_i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _f]),
-    "bds_project_view_prepare_fwd_blocks": (_i, [_i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _f, _f]),
-    "bds_project_view_fwd_blocks": (_i, [_i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "bds_project_view_fwd": (_i, [_i, _i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _f, _f]),
     "bds_gaussian_block_bounds": (_i, [_i64, _f, _f, _f, _f]),
     "bds_sh_view_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_sh_view_bwd_list": (_i, [_i64, _f, _i, _i, _f, _f, _f, _i, _f, _f, _f, _i, _f]),
@@ -88,8 +82,7 @@ _SIGS = {
     "bds_sh_view_bwd_list_split": (_i, [_i64, _f, _i, _i, _f, _f, _f, _i, _f, _f, _f, _i, _f]),
     "bds_nonfinite_flags": (_i, [_i, _f, _f, _f, _f, _f]),
     "bds_nonfinite_flags_kinds": (_i, [_i, _f, _f, _f, _f, _f, _f]),
-    "bds_project_bwd_list": (_i, [_i64, _f, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
-    "bds_project_view_bwd_list": (_i, [_i64, _f, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _f]),
+    "bds_project_view_bwd_list": (_i, [_i, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_view_grads_clear_list": (_i, [_i64, _f, _i, _f, _f, _f, _f, _f, _f]),
     "bds_view_grads_add_list": (_i, [_i64, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_isect_counts_offset": (_sz, [_i]),
@@ -103,7 +96,6 @@ _SIGS = {
     "bds_rasterize_bwd_schedule_sort": (_i, [_i, _i, _i, _f, _f]),
     "bds_rasterize_bwd_dev": (_i, [_i, _i64, _i64, _f, _i, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _i, _f, _i, _i, _i64, _f]),
     "bds_sh_view_bwd_list_dev": (_i, [_i64, _f, _f, _i, _i, _f, _f, _f, _i, _f, _f, _f, _i, _f]),
-    "bds_project_view_bwd_list_dev": (_i, [_i64, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _f]),
     "bds_view_grads_clear_list_dev": (_i, [_i64, _f, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_union_slots_workspace_bytes": (_sz, [_i64]),
     "bds_union_slots": (_i, [_i64, _f, _i64, _i, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _f, _f, _f]),
@@ -210,7 +202,7 @@ def lib():
 
 
 SPLAT_RECORD_FLOATS, GRAD_RECORD_FLOATS, POSE_GRAD_SLOTS = 12, 16, 64
-PROJ_AA_ACCUMULATE, PROJ_AA_ACTIVATED = 1, 2      # include/bds.h bds_project_view_bwd_list_aa flags
+PROJ_ACCUMULATE, PROJ_ACTIVATED, PROJ_ANTIALIASED = 1, 2, 4      # include/bds.h bds_project_view_fwd / _bwd_list flags
 OPT_DEBUG = 3          # profiling only: ablation mask
 OPT_SCHED_BINS = 8     # device-count compositor: 1 [default] = the forward's waves bin the backward's schedule, 0 = a sort launch (include/bds.h)
 OPT_CELLS = 7          # bilateral transform, bit mask [default 3]: 1 = cell-aligned kernels, 2 = one-pass pyramid forward, 0 = general kernels (include/bds.h)

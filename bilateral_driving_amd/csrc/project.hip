@@ -11,7 +11,7 @@ namespace bds {
 
 constexpr int kProjBlock = 256;
 
-// kAA (rasterize_mode "antialiased": bds_project_fwd with compensations, bds_project_fwd_aa): comp from det S2 as a sum of squares
+// kAA (rasterize_mode "antialiased": bds_project_fwd with compensations or opac_eff): comp from det S2 as a sum of squares
 // (gs_math.h det2d_unblurred, what the backward differentiates), and -- with opacities / opac_eff given -- opac_eff[c,g] =
 // opacities[g] * comp, what the tile stage and the compositor read in that mode.
 template <bool kAA = false>
@@ -390,38 +390,22 @@ __global__ __launch_bounds__(kFiniteBlock) void nonfinite_flags_kernel(FiniteArg
 
 using namespace bds;
 
-extern "C" int bds_project_fwd(int C, int64_t N, const float *means, const float *quats, const float *scales,
-                               const float *viewmats, const float *Ks, int W, int H, float eps2d, float near_plane,
-                               float far_plane, float radius_clip, int32_t *radii, float *means2d, float *depths,
-                               float *conics, float *compensations, bds_stream_t stream) {
+// compensations or opac_eff (rasterize_mode "antialiased"): comp as the backward differentiates it (gs_math.h det2d_unblurred);
+// opac_eff [C,N] = opacities[g] * comp, in the same launch
+extern "C" int bds_project_fwd(int C, int64_t N, const float *means, const float *quats, const float *scales, const float *opacities,
+                               const float *viewmats, const float *Ks, int W, int H, float eps2d, float near_plane, float far_plane,
+                               float radius_clip, int32_t *radii, float *means2d, float *depths, float *conics, float *compensations,
+                               float *opac_eff, bds_stream_t stream) {
   BDS_REQUIRE(C >= 1 && N >= 0 && W > 0 && H > 0);
   if (N == 0) return BDS_OK;
   BDS_REQUIRE(means && quats && scales && viewmats && Ks && radii && means2d && depths && conics);
-  if (compensations)       // rasterize_mode "antialiased": comp as the backward differentiates it (gs_math.h det2d_unblurred)
-    hipLaunchKernelGGL(project_fwd_kernel<true>, dim3((unsigned)cdiv(N, kProjBlock)), dim3(kProjBlock), 0, as_stream(stream), C, N,
-                       means, quats, scales, viewmats, Ks, W, H, eps2d, near_plane, far_plane, radius_clip, radii,
-                       means2d, depths, conics, compensations, static_cast<const float *>(nullptr), static_cast<float *>(nullptr));
-  else
-    hipLaunchKernelGGL(project_fwd_kernel<false>, dim3((unsigned)cdiv(N, kProjBlock)), dim3(kProjBlock), 0, as_stream(stream), C, N,
-                       means, quats, scales, viewmats, Ks, W, H, eps2d, near_plane, far_plane, radius_clip, radii,
-                       means2d, depths, conics, static_cast<float *>(nullptr), static_cast<const float *>(nullptr),
-                       static_cast<float *>(nullptr));
-  BDS_LAUNCH_CHECK();
-  return BDS_OK;
-}
-
-// bds_project_fwd + the effective opacities of rasterize_mode "antialiased" (models/trainers/base.py:406): opac_eff [C,N] =
-// opacities[g] * comp, in the same launch.  compensations (optional) as in bds_project_fwd.
-extern "C" int bds_project_fwd_aa(int C, int64_t N, const float *means, const float *quats, const float *scales,
-                                  const float *opacities, const float *viewmats, const float *Ks, int W, int H, float eps2d,
-                                  float near_plane, float far_plane, float radius_clip, int32_t *radii, float *means2d,
-                                  float *depths, float *conics, float *compensations, float *opac_eff, bds_stream_t stream) {
-  BDS_REQUIRE(C >= 1 && N >= 0 && W > 0 && H > 0);
-  if (N == 0) return BDS_OK;
-  BDS_REQUIRE(means && quats && scales && opacities && viewmats && Ks && radii && means2d && depths && conics && opac_eff);
-  hipLaunchKernelGGL(project_fwd_kernel<true>, dim3((unsigned)cdiv(N, kProjBlock)), dim3(kProjBlock), 0, as_stream(stream), C, N,
-                     means, quats, scales, viewmats, Ks, W, H, eps2d, near_plane, far_plane, radius_clip, radii,
-                     means2d, depths, conics, compensations, opacities, opac_eff);
+  BDS_REQUIRE((opacities == nullptr) == (opac_eff == nullptr));
+#define BDS_FWD(AA)                                                                                                                   \
+  hipLaunchKernelGGL(project_fwd_kernel<AA>, dim3((unsigned)cdiv(N, kProjBlock)), dim3(kProjBlock), 0, as_stream(stream), C, N, means, \
+                     quats, scales, viewmats, Ks, W, H, eps2d, near_plane, far_plane, radius_clip, radii, means2d, depths, conics,      \
+                     compensations, opacities, opac_eff)
+  if (compensations || opac_eff) BDS_FWD(true); else BDS_FWD(false);
+#undef BDS_FWD
   BDS_LAUNCH_CHECK();
   return BDS_OK;
 }
@@ -460,117 +444,36 @@ static int view_rows(const float *means2d, const float *depths, const float *con
   return BDS_OK;
 }
 
-static int project_view_fwd_impl(int64_t N, const float *means, const float *quats, const float *log_scales,
-                                 const float *logits, const float *viewmat, const float *K, int W, int H, float eps2d,
-                                 float near_plane, float far_plane, float radius_clip, float *scales, float *opacities,
-                                 int32_t *radii, float *means2d, float *depths, float *conics, const float *block_bounds,
-                                 bds_stream_t stream) {
-  BDS_REQUIRE(N >= 0 && W > 0 && H > 0);
-  if (N == 0) return BDS_OK;
-  BDS_REQUIRE(means && quats && log_scales && logits && viewmat && K && scales && opacities && radii && means2d && depths &&
-              conics);
-  int rows = 0;
-  if (view_rows(means2d, depths, conics, &rows) != BDS_OK) return BDS_EINVAL;
-  hipLaunchKernelGGL(project_view_fwd_kernel<false>, dim3((unsigned)cdiv(N, kProjBlock)), dim3(kProjBlock), 0, as_stream(stream), N,
-                     means, quats, log_scales, logits, viewmat, K, W, H, eps2d, near_plane, far_plane, radius_clip, scales,
-                     opacities, radii, means2d, depths, conics, PrepReduceSlots{}, static_cast<int32_t *>(nullptr), rows, block_bounds,
-                     static_cast<float *>(nullptr));
-  BDS_LAUNCH_CHECK();
-  return BDS_OK;
-}
-
-extern "C" int bds_project_view_fwd(int64_t N, const float *means, const float *quats, const float *log_scales,
-                                    const float *logits, const float *viewmat, const float *K, int W, int H, float eps2d,
-                                    float near_plane, float far_plane, float radius_clip, float *scales, float *opacities,
-                                    int32_t *radii, float *means2d, float *depths, float *conics, bds_stream_t stream) {
-  return project_view_fwd_impl(N, means, quats, log_scales, logits, viewmat, K, W, H, eps2d, near_plane, far_plane, radius_clip, scales,
-                               opacities, radii, means2d, depths, conics, nullptr, stream);
-}
-
-static int project_view_prepare_fwd_impl(int64_t N, const float *means, const float *quats, const float *log_scales,
-                                         const float *logits, const float *viewmat, const float *K, int W, int H, float eps2d,
-                                         float near_plane, float far_plane, float radius_clip, float *scales, float *opacities,
-                                         int32_t *radii, float *means2d, float *depths, float *conics, int32_t *tiles_per_gauss,
-                                         void *prep_ws, size_t prep_ws_bytes, const float *block_bounds, bds_stream_t stream) {
-  BDS_REQUIRE(N > 0 && W > 0 && H > 0);
-  BDS_REQUIRE(means && quats && log_scales && logits && viewmat && K && scales && opacities && radii && means2d && depths &&
-              conics);
-  static_assert(kProjBlock == 256, "the tile stage reads the visible counts per 256 Gaussians");
-  PrepReduceSlots rs;
-  int rc = prep_reduce_slots(prep_ws, prep_ws_bytes, N, &rs);
-  if (rc != BDS_OK) return rc;
-  int rows = 0;
-  if (view_rows(means2d, depths, conics, &rows) != BDS_OK) return BDS_EINVAL;
-  hipLaunchKernelGGL(project_view_fwd_kernel<true>, dim3((unsigned)cdiv(N, kProjBlock)), dim3(kProjBlock), 0, as_stream(stream), N,
-                     means, quats, log_scales, logits, viewmat, K, W, H, eps2d, near_plane, far_plane, radius_clip, scales,
-                     opacities, radii, means2d, depths, conics, rs, tiles_per_gauss, rows, block_bounds, static_cast<float *>(nullptr));
-  BDS_LAUNCH_CHECK();
-  return BDS_OK;
-}
-
-extern "C" int bds_project_view_prepare_fwd(int64_t N, const float *means, const float *quats, const float *log_scales,
-                                            const float *logits, const float *viewmat, const float *K, int W, int H, float eps2d,
-                                            float near_plane, float far_plane, float radius_clip, float *scales, float *opacities,
-                                            int32_t *radii, float *means2d, float *depths, float *conics, int32_t *tiles_per_gauss,
-                                            void *prep_ws, size_t prep_ws_bytes, bds_stream_t stream) {
-  return project_view_prepare_fwd_impl(N, means, quats, log_scales, logits, viewmat, K, W, H, eps2d, near_plane, far_plane, radius_clip,
-                                       scales, opacities, radii, means2d, depths, conics, tiles_per_gauss, prep_ws, prep_ws_bytes, nullptr,
-                                       stream);
-}
-
-// ... with a bound per 256-row block (bds_gaussian_block_bounds over the SAME means / log_scales): blocks no centre of which can come
-// out visible are not read; their rows get the outputs of a culled Gaussian (radius 0, zeros).  scales / opacities of such rows are
-// NOT written (nothing reads them for a culled Gaussian).
-extern "C" int bds_project_view_fwd_blocks(int64_t N, const float *means, const float *quats, const float *log_scales,
-                                           const float *logits, const float *viewmat, const float *K, int W, int H, float eps2d,
-                                           float near_plane, float far_plane, float radius_clip, float *scales, float *opacities,
-                                           int32_t *radii, float *means2d, float *depths, float *conics, const float *block_bounds,
-                                           bds_stream_t stream) {
-  BDS_REQUIRE(block_bounds);
-  return project_view_fwd_impl(N, means, quats, log_scales, logits, viewmat, K, W, H, eps2d, near_plane, far_plane, radius_clip, scales,
-                               opacities, radii, means2d, depths, conics, block_bounds, stream);
-}
-extern "C" int bds_project_view_prepare_fwd_blocks(int64_t N, const float *means, const float *quats, const float *log_scales,
-                                                   const float *logits, const float *viewmat, const float *K, int W, int H, float eps2d,
-                                                   float near_plane, float far_plane, float radius_clip, float *scales,
-                                                   float *opacities, int32_t *radii, float *means2d, float *depths, float *conics,
-                                                   int32_t *tiles_per_gauss, void *prep_ws, size_t prep_ws_bytes,
-                                                   const float *block_bounds, bds_stream_t stream) {
-  BDS_REQUIRE(block_bounds);
-  return project_view_prepare_fwd_impl(N, means, quats, log_scales, logits, viewmat, K, W, H, eps2d, near_plane, far_plane, radius_clip,
-                                       scales, opacities, radii, means2d, depths, conics, tiles_per_gauss, prep_ws, prep_ws_bytes,
-                                       block_bounds, stream);
-}
-
-// The one-view forward of rasterize_mode "antialiased" (models/trainers/base.py:406, :824): bds_project_view_fwd with the effective
-// opacity sigmoid(logit) * comp where the tile stage and the compositor read it -- the rows' slot 7 in the [N,8] row form, else
-// opac_eff [N] (required then; ignored in the row form).  `opacities` receives sigmoid(logit) (the backward's o).  prep_ws (nullable):
-// the prepare form (bds_project_view_prepare_fwd; BDS_ECAPACITY as there); block_bounds (nullable): the _blocks form.
-extern "C" int bds_project_view_fwd_aa(int64_t N, const float *means, const float *quats, const float *log_scales, const float *logits,
-                                       const float *viewmat, const float *K, int W, int H, float eps2d, float near_plane, float far_plane,
-                                       float radius_clip, float *scales, float *opacities, float *opac_eff, int32_t *radii, float *means2d,
-                                       float *depths, float *conics, int32_t *tiles_per_gauss, void *prep_ws, size_t prep_ws_bytes,
-                                       const float *block_bounds, bds_stream_t stream) {
-  BDS_REQUIRE(N >= 0 && W > 0 && H > 0);
+// The one-view forward (include/bds.h): BDS_PROJ_ANTIALIASED selects kAA, prep_ws kReduce, block_bounds the block skip.
+extern "C" int bds_project_view_fwd(int flags, int64_t N, const float *means, const float *quats, const float *log_scales,
+                                    const float *logits, const float *viewmat, const float *K, int W, int H, float eps2d, float near_plane,
+                                    float far_plane, float radius_clip, float *scales, float *opacities, float *opac_eff, int32_t *radii,
+                                    float *means2d, float *depths, float *conics, int32_t *tiles_per_gauss, void *prep_ws,
+                                    size_t prep_ws_bytes, const float *block_bounds, bds_stream_t stream) {
+  BDS_REQUIRE((flags & ~BDS_PROJ_ANTIALIASED) == 0 && N >= 0 && W > 0 && H > 0);
   BDS_REQUIRE(prep_ws == nullptr || N > 0);
   if (N == 0) return BDS_OK;
   BDS_REQUIRE(means && quats && log_scales && logits && viewmat && K && scales && opacities && radii && means2d && depths && conics);
   int rows = 0;
   if (view_rows(means2d, depths, conics, &rows) != BDS_OK) return BDS_EINVAL;
-  BDS_REQUIRE(rows || opac_eff);
-  const dim3 grid((unsigned)cdiv(N, kProjBlock)), block(kProjBlock);
+  const bool aa = flags & BDS_PROJ_ANTIALIASED;
+  BDS_REQUIRE(aa ? (rows || opac_eff) : opac_eff == nullptr);
+  static_assert(kProjBlock == 256, "the tile stage reads the visible counts per 256 Gaussians");
+  PrepReduceSlots rs{};
   if (prep_ws) {
-    PrepReduceSlots rs;
     int rc = prep_reduce_slots(prep_ws, prep_ws_bytes, N, &rs);
     if (rc != BDS_OK) return rc;
-    hipLaunchKernelGGL((project_view_fwd_kernel<true, true>), grid, block, 0, as_stream(stream), N, means, quats, log_scales, logits,
-                       viewmat, K, W, H, eps2d, near_plane, far_plane, radius_clip, scales, opacities, radii, means2d, depths, conics, rs,
-                       tiles_per_gauss, rows, block_bounds, opac_eff);
   } else {
-    hipLaunchKernelGGL((project_view_fwd_kernel<false, true>), grid, block, 0, as_stream(stream), N, means, quats, log_scales, logits,
-                       viewmat, K, W, H, eps2d, near_plane, far_plane, radius_clip, scales, opacities, radii, means2d, depths, conics,
-                       PrepReduceSlots{}, static_cast<int32_t *>(nullptr), rows, block_bounds, opac_eff);
+    tiles_per_gauss = nullptr;
   }
+  const dim3 grid((unsigned)cdiv(N, kProjBlock)), block(kProjBlock);
+#define BDS_VIEW_FWD(R, A)                                                                                                            \
+  hipLaunchKernelGGL((project_view_fwd_kernel<R, A>), grid, block, 0, as_stream(stream), N, means, quats, log_scales, logits, viewmat, \
+                     K, W, H, eps2d, near_plane, far_plane, radius_clip, scales, opacities, radii, means2d, depths, conics, rs,         \
+                     tiles_per_gauss, rows, block_bounds, opac_eff)
+  if (prep_ws) { if (aa) BDS_VIEW_FWD(true, true); else BDS_VIEW_FWD(true, false); }
+  else         { if (aa) BDS_VIEW_FWD(false, true); else BDS_VIEW_FWD(false, false); }
+#undef BDS_VIEW_FWD
   BDS_LAUNCH_CHECK();
   return BDS_OK;
 }
@@ -611,7 +514,7 @@ __global__ __launch_bounds__(kProjBlock) void block_bounds_kernel(int64_t N, con
 }
 }  // namespace bds
 
-// block_bounds [cdiv(N, 256), 8] for bds_project_view_*_fwd_blocks; recompute whenever means / log_scales changed (once per frame)
+// block_bounds [cdiv(N, 256), 8] for bds_project_view_fwd; recompute whenever means / log_scales changed (once per frame)
 extern "C" int bds_gaussian_block_bounds(int64_t N, const float *means, const float *log_scales, float *block_bounds,
                                          bds_stream_t stream) {
   BDS_REQUIRE(N >= 0);
@@ -623,103 +526,38 @@ extern "C" int bds_gaussian_block_bounds(int64_t N, const float *means, const fl
   return BDS_OK;
 }
 
-static int project_view_bwd_list_impl(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, const float *means, const float *quats,
-                                      const float *scales, const float *opacities, const float *viewmat, const float *K, int W,
-                                      int H, float eps2d, const float *v_records, float *v_means, float *v_quats,
-                                      float *v_log_scales, float *v_logits, float *v_viewmat_slots, float *grad2d,
-                                      float *absgrad2d, const int32_t *row_map, int accumulate, bds_stream_t stream) {
+// The list-driven one-view backward (include/bds.h): BDS_PROJ_ACCUMULATE selects kAcc, BDS_PROJ_ACTIVATED !kRaw, BDS_PROJ_ANTIALIASED
+// kAA, v_viewmat_slots kPose; n_dev (nullable) the device-count form.
+extern "C" int bds_project_view_bwd_list(int flags, int64_t n_list, const uint64_t *n_dev, const int32_t *ids, const float *means,
+                                         const float *quats, const float *scales, const float *opacities, const float *viewmat,
+                                         const float *K, int W, int H, float eps2d, const float *v_records, float *v_means, float *v_quats,
+                                         float *v_scales, float *v_opacities, float *v_colors, float *v_viewmat_slots, float *grad2d,
+                                         float *absgrad2d, const int32_t *row_map, bds_stream_t stream) {
   BDS_REQUIRE(n_list >= 0 && W > 0 && H > 0);
+  BDS_REQUIRE((flags & ~(BDS_PROJ_ACCUMULATE | BDS_PROJ_ACTIVATED | BDS_PROJ_ANTIALIASED)) == 0);
+  const bool acc = flags & BDS_PROJ_ACCUMULATE, activated = flags & BDS_PROJ_ACTIVATED, aa = flags & BDS_PROJ_ANTIALIASED;
+  BDS_REQUIRE(!activated || (!acc && row_map == nullptr));
   // (v_viewmat_slots is ADDED to: the caller zero-fills it -- a memset node of 4 KB between two kernels costs ~15 us of idle GPU)
   if (n_list == 0) return BDS_OK;
   BDS_REQUIRE(ids && means && quats && scales && opacities && viewmat && K && v_records && aligned16(v_records) && v_means &&
-              v_quats && v_log_scales && v_logits);
-  const dim3 grid((unsigned)cdiv(n_list, kProjBlock)), block(kProjBlock);
-  const float4 *v4 = reinterpret_cast<const float4 *>(v_records);
-  const GradLayout gl = grad_layout(v_means, v_quats, v_log_scales, v_logits);   // (the [N,16] row form is recognised by the addresses)
-#define BDS_LIST(A, P)                                                                                                                \
-  hipLaunchKernelGGL((project_view_bwd_list_kernel<A, P>), grid, block, 0, as_stream(stream), n_list, n_dev, ids, means, quats, scales, \
-                     opacities, viewmat, K, W, H, eps2d, v4, v_means, v_quats, v_log_scales, v_logits, v_viewmat_slots, grad2d,        \
-                     absgrad2d, row_map, static_cast<float *>(nullptr), gl)
-  if (accumulate) { if (v_viewmat_slots) BDS_LIST(true, true); else BDS_LIST(true, false); }
-  else            { if (v_viewmat_slots) BDS_LIST(false, true); else BDS_LIST(false, false); }
-#undef BDS_LIST
-  BDS_LAUNCH_CHECK();
-  return BDS_OK;
-}
-
-extern "C" int bds_project_view_bwd_list(int64_t n_list, const int32_t *ids, const float *means, const float *quats,
-                                         const float *scales, const float *opacities, const float *viewmat, const float *K, int W,
-                                         int H, float eps2d, const float *v_records, float *v_means, float *v_quats,
-                                         float *v_log_scales, float *v_logits, float *v_viewmat_slots, float *grad2d,
-                                         float *absgrad2d, const int32_t *row_map, int accumulate, bds_stream_t stream) {
-  return project_view_bwd_list_impl(n_list, nullptr, ids, means, quats, scales, opacities, viewmat, K, W, H, eps2d, v_records, v_means,
-                                    v_quats, v_log_scales, v_logits, v_viewmat_slots, grad2d, absgrad2d, row_map, accumulate, stream);
-}
-
-// The gsplat-shaped operator's backward over the visible entries (rendering.rasterization, C = 1): gradients of the ACTIVATED scales
-// and opacities and of the post-activation colours, stored to the visible rows of dense, caller-zeroed arrays.
-extern "C" int bds_project_bwd_list(int64_t n_list, const int32_t *ids, const float *means, const float *quats, const float *scales,
-                                    const float *opacities, const float *viewmat, const float *K, int W, int H, float eps2d,
-                                    const float *v_records, float *v_means, float *v_quats, float *v_scales, float *v_opacities,
-                                    float *v_colors, float *v_viewmat_slots, float *grad2d, float *absgrad2d, bds_stream_t stream) {
-  BDS_REQUIRE(n_list >= 0 && W > 0 && H > 0);
-  if (n_list == 0) return BDS_OK;
-  BDS_REQUIRE(ids && means && quats && scales && opacities && viewmat && K && v_records && aligned16(v_records) && v_means &&
               v_quats && v_scales && v_opacities);
   const dim3 grid((unsigned)cdiv(n_list, kProjBlock)), block(kProjBlock);
   const float4 *v4 = reinterpret_cast<const float4 *>(v_records);
-  if (v_viewmat_slots)
-    hipLaunchKernelGGL((project_view_bwd_list_kernel<false, true, false>), grid, block, 0, as_stream(stream), n_list, nullptr, ids, means,
-                       quats, scales, opacities, viewmat, K, W, H, eps2d, v4, v_means, v_quats, v_scales, v_opacities, v_viewmat_slots,
-                       grad2d, absgrad2d, nullptr, v_colors);
-  else
-    hipLaunchKernelGGL((project_view_bwd_list_kernel<false, false, false>), grid, block, 0, as_stream(stream), n_list, nullptr, ids, means,
-                       quats, scales, opacities, viewmat, K, W, H, eps2d, v4, v_means, v_quats, v_scales, v_opacities, v_viewmat_slots,
-                       grad2d, absgrad2d, nullptr, v_colors);
-  BDS_LAUNCH_CHECK();
-  return BDS_OK;
-}
-
-extern "C" int bds_project_view_bwd_list_dev(int64_t n_capacity, const uint64_t *n_dev, const int32_t *ids, const float *means,
-                                             const float *quats, const float *scales, const float *opacities, const float *viewmat,
-                                             const float *K, int W, int H, float eps2d, const float *v_records, float *v_means,
-                                             float *v_quats, float *v_log_scales, float *v_logits, float *v_viewmat_slots, float *grad2d,
-                                             float *absgrad2d, const int32_t *row_map, int accumulate, bds_stream_t stream) {
-  BDS_REQUIRE(n_dev);
-  return project_view_bwd_list_impl(n_capacity, n_dev, ids, means, quats, scales, opacities, viewmat, K, W, H, eps2d, v_records,
-                                    v_means, v_quats, v_log_scales, v_logits, v_viewmat_slots, grad2d, absgrad2d, row_map, accumulate,
-                                    stream);
-}
-
-// The list-driven one-view backward of rasterize_mode "antialiased" (models/trainers/base.py:406): record channel 11 is the gradient
-// of the effective opacity o * comp; comp is recomputed in the VJP.  flags: BDS_PROJ_AA_ACCUMULATE adds to the gradient rows
-// (bds_project_view_bwd_list's `accumulate`); BDS_PROJ_AA_ACTIVATED is the gsplat-shaped form of bds_project_bwd_list (activated
-// scales / opacities in, their gradients out, v_colors [N,3] scattered; no row_map, no accumulate), else the raw form of
-// bds_project_view_bwd_list (log-scales / logits).  n_dev (nullable): the device-count form (bds_project_view_bwd_list_dev), n_list is
-// then the capacity.
-extern "C" int bds_project_view_bwd_list_aa(int flags, int64_t n_list, const uint64_t *n_dev, const int32_t *ids, const float *means,
-                                            const float *quats, const float *scales, const float *opacities, const float *viewmat,
-                                            const float *K, int W, int H, float eps2d, const float *v_records, float *v_means,
-                                            float *v_quats, float *v_scales, float *v_opacities, float *v_colors, float *v_viewmat_slots,
-                                            float *grad2d, float *absgrad2d, const int32_t *row_map, bds_stream_t stream) {
-  BDS_REQUIRE(n_list >= 0 && W > 0 && H > 0);
-  BDS_REQUIRE((flags & ~(BDS_PROJ_AA_ACCUMULATE | BDS_PROJ_AA_ACTIVATED)) == 0);
-  const bool acc = flags & BDS_PROJ_AA_ACCUMULATE, activated = flags & BDS_PROJ_AA_ACTIVATED;
-  BDS_REQUIRE(!activated || (!acc && row_map == nullptr));
-  if (n_list == 0) return BDS_OK;
-  BDS_REQUIRE(ids && means && quats && scales && opacities && viewmat && K && v_records && aligned16(v_records) && v_means &&
-              v_quats && v_scales && v_opacities);
-  const dim3 grid((unsigned)cdiv(n_list, kProjBlock)), block(kProjBlock);
-  const float4 *v4 = reinterpret_cast<const float4 *>(v_records);
+  // (the raw form's [N,16] row form is recognised by the addresses; the activated form's dense arrays have the kernel's default layout)
   const GradLayout gl = activated ? GradLayout{3, 4, 3, 1} : grad_layout(v_means, v_quats, v_scales, v_opacities);
-#define BDS_LIST_AA(A, P, R)                                                                                                          \
-  hipLaunchKernelGGL((project_view_bwd_list_kernel<A, P, R, true>), grid, block, 0, as_stream(stream), n_list, n_dev, ids, means,     \
-                     quats, scales, opacities, viewmat, K, W, H, eps2d, v4, v_means, v_quats, v_scales, v_opacities, v_viewmat_slots,  \
-                     grad2d, absgrad2d, row_map, R ? static_cast<float *>(nullptr) : v_colors, gl)
-  if (activated) { if (v_viewmat_slots) BDS_LIST_AA(false, true, false); else BDS_LIST_AA(false, false, false); }
-  else if (acc)  { if (v_viewmat_slots) BDS_LIST_AA(true, true, true); else BDS_LIST_AA(true, false, true); }
-  else           { if (v_viewmat_slots) BDS_LIST_AA(false, true, true); else BDS_LIST_AA(false, false, true); }
+  if (!activated) v_colors = nullptr;
+#define BDS_LIST(A, P, R, AA)                                                                                                         \
+  hipLaunchKernelGGL((project_view_bwd_list_kernel<A, P, R, AA>), grid, block, 0, as_stream(stream), n_list, n_dev, ids, means, quats, \
+                     scales, opacities, viewmat, K, W, H, eps2d, v4, v_means, v_quats, v_scales, v_opacities, v_viewmat_slots, grad2d, \
+                     absgrad2d, row_map, v_colors, gl)
+#define BDS_LIST_P(A, R, AA) do { if (v_viewmat_slots) BDS_LIST(A, true, R, AA); else BDS_LIST(A, false, R, AA); } while (0)
+#define BDS_LIST_AA(A, R) do { if (aa) BDS_LIST_P(A, R, true); else BDS_LIST_P(A, R, false); } while (0)
+  if (activated) BDS_LIST_AA(false, false);
+  else if (acc)  BDS_LIST_AA(true, true);
+  else           BDS_LIST_AA(false, true);
 #undef BDS_LIST_AA
+#undef BDS_LIST_P
+#undef BDS_LIST
   BDS_LAUNCH_CHECK();
   return BDS_OK;
 }

@@ -835,7 +835,7 @@ __device__ __forceinline__ void visible_compact_block(VisCompactSh &sh, int vb, 
 #pragma unroll
   for (int t = 0; t < kSpan; t++) h[t][threadIdx.x] = 0;
   uint32_t part = 0;
-  // (sums_per_tile = 8: the counts were left per 256-Gaussian workgroup by the one-view projection, bds_project_view_prepare_fwd)
+  // (sums_per_tile = 8: the counts were left per 256-Gaussian workgroup by the one-view projection, bds_project_view_fwd with prep_ws)
   for (int b = threadIdx.x; b < vb * sums_per_tile; b += kScanBlock) part += tile_sums[b];
   uint32_t my_offset;
   block_excl_scan(part, my_offset, lw);   // total of the partial sums = this tile's offset

@@ -234,33 +234,16 @@ def _front_begin(cfg: dict, means, quats, log_scales, logits, sh, viewmat) -> _F
     pre_reduced = False
     bounds = cfg.get("block_bounds")      # [cdiv(N, 256), 8] of bds_gaussian_block_bounds over THESE means / log_scales (graph_view: once per frame)
     with L.timed("project_fwd"):
-        if aa and N > 0:
-            args = (N, L.ptr(means), L.ptr(quats), L.ptr(log_scales), L.ptr(logits), L.ptr(viewmat), L.ptr(Kmat), W, H, cfg["eps2d"],
-                    cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"], L.ptr(scales), L.ptr(opac), L.ptr(opac_eff),
-                    L.ptr(radii), _dp(means2d), _dp(depths), _dp(conics))
-            if cfg.get("caps") is not None and _PROJECT_PREPARES:
-                rc = lib.bds_project_view_fwd_aa(*args, L.ptr(tiles_per_gauss), L.ptr(ws), ws_bytes, L.ptr(bounds), st)
-                pre_reduced = rc == L.BDS_OK
-                if rc not in (L.BDS_OK, L.BDS_ECAPACITY):
-                    L.check(rc, "bds_project_view_fwd_aa")
-            if not pre_reduced:
-                L.check(lib.bds_project_view_fwd_aa(*args, None, None, 0, L.ptr(bounds), st), "bds_project_view_fwd_aa")
-        elif cfg.get("caps") is not None and _PROJECT_PREPARES and N > 0:
-            args = (N, L.ptr(means), L.ptr(quats), L.ptr(log_scales), L.ptr(logits), L.ptr(viewmat),
-                    L.ptr(Kmat), W, H, cfg["eps2d"], cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"],
-                    L.ptr(scales), L.ptr(opac), L.ptr(radii), _dp(means2d), _dp(depths), _dp(conics),
-                    L.ptr(tiles_per_gauss), L.ptr(ws), ws_bytes)
-            rc = (lib.bds_project_view_prepare_fwd(*args, st) if bounds is None
-                  else lib.bds_project_view_prepare_fwd_blocks(*args, L.ptr(bounds), st))
+        args = (L.PROJ_ANTIALIASED if aa else 0, N, L.ptr(means), L.ptr(quats), L.ptr(log_scales), L.ptr(logits), L.ptr(viewmat),
+                L.ptr(Kmat), W, H, cfg["eps2d"], cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"], L.ptr(scales), L.ptr(opac),
+                L.ptr(opac_eff), L.ptr(radii), _dp(means2d), _dp(depths), _dp(conics))
+        if caps is not None and N > 0:
+            rc = lib.bds_project_view_fwd(*args, L.ptr(tiles_per_gauss), L.ptr(ws), ws_bytes, L.ptr(bounds), st)
             pre_reduced = rc == L.BDS_OK
-            if rc not in (L.BDS_OK, L.BDS_ECAPACITY):     # (ECAPACITY: N beyond the short sort path -- the plain projection below)
-                L.check(rc, "bds_project_view_prepare_fwd")
-        if not pre_reduced and not (aa and N > 0):
-            args = (N, L.ptr(means), L.ptr(quats), L.ptr(log_scales), L.ptr(logits), L.ptr(viewmat),
-                    L.ptr(Kmat), W, H, cfg["eps2d"], cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"],
-                    L.ptr(scales), L.ptr(opac), L.ptr(radii), _dp(means2d), _dp(depths), _dp(conics))
-            L.check(lib.bds_project_view_fwd(*args, st) if bounds is None or N == 0 else lib.bds_project_view_fwd_blocks(*args, L.ptr(bounds), st),
-                    "bds_project_view_fwd")
+            if rc != L.BDS_ECAPACITY:     # (ECAPACITY: N beyond the short sort path -- the plain projection below)
+                L.check(rc, "bds_project_view_fwd")
+        if not pre_reduced:
+            L.check(lib.bds_project_view_fwd(*args, None, None, 0, L.ptr(bounds), st), "bds_project_view_fwd")
     # tile ordering
     LT = cfg.get("list_tile", LIST_TILE)
     tw, th = math.ceil(W / LT), math.ceil(H / LT)      # list tiles
@@ -747,24 +730,12 @@ class _FusedView(torch.autograd.Function):
             v_vm_slots = (v_rec_all[max(n_vis, 1):max(n_vis, 1) + L.POSE_GRAD_SLOTS].view(L.POSE_GRAD_SLOTS, 4, 4)
                           if want_pose else None)   # camera-pose gradient (base.py:328-329,399)
         with L.timed("project_bwd"):
-            if cfg.get("antialiased"):     # record channel 11 is the gradient of opacity * comp (include/bds.h bds_project_view_bwd_list_aa)
-                L.check(lib.bds_project_view_bwd_list_aa(L.PROJ_AA_ACCUMULATE if rows == 2 else 0, n_vis,
-                                                         None if dev_counts is None else dev_counts[1], L.ptr(vis_ids), L.ptr(means),
-                                                         L.ptr(quats), L.ptr(scales), L.ptr(opac), L.ptr(viewmat.contiguous()), L.ptr(Kmat), W, H,
-                                                         cfg["eps2d"], L.ptr(v_rec), _dp(v_means), _dp(v_quats), _dp(v_ls), _dp(v_logits), None,
-                                                         L.ptr(v_vm_slots), L.ptr(g2d[0]), L.ptr(g2d[1]), L.ptr(row_map), st),
-                        "bds_project_view_bwd_list_aa")
-            elif dev_counts is not None:
-                L.check(lib.bds_project_view_bwd_list_dev(n_vis, dev_counts[1], L.ptr(vis_ids), L.ptr(means), L.ptr(quats), L.ptr(scales),
-                                                          L.ptr(opac), L.ptr(viewmat.contiguous()), L.ptr(Kmat), W, H, cfg["eps2d"], L.ptr(v_rec),
-                                                          _dp(v_means), _dp(v_quats), _dp(v_ls), _dp(v_logits), L.ptr(v_vm_slots),
-                                                          L.ptr(g2d[0]), L.ptr(g2d[1]), L.ptr(row_map), int(rows == 2), st),
-                        "bds_project_view_bwd_list_dev")
-            else:
-                L.check(lib.bds_project_view_bwd_list(n_vis, L.ptr(vis_ids), L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opac),
-                                                      L.ptr(viewmat.contiguous()), L.ptr(Kmat), W, H, cfg["eps2d"], L.ptr(v_rec), _dp(v_means),
-                                                      _dp(v_quats), _dp(v_ls), _dp(v_logits), L.ptr(v_vm_slots), L.ptr(g2d[0]), L.ptr(g2d[1]),
-                                                      L.ptr(row_map), int(rows == 2), st), "bds_project_view_bwd_list")
+            flags = (L.PROJ_ACCUMULATE if rows == 2 else 0) | (L.PROJ_ANTIALIASED if cfg.get("antialiased") else 0)
+            L.check(lib.bds_project_view_bwd_list(flags, n_vis, None if dev_counts is None else dev_counts[1], L.ptr(vis_ids), L.ptr(means),
+                                                  L.ptr(quats), L.ptr(scales), L.ptr(opac), L.ptr(viewmat.contiguous()), L.ptr(Kmat), W, H,
+                                                  cfg["eps2d"], L.ptr(v_rec), _dp(v_means), _dp(v_quats), _dp(v_ls), _dp(v_logits), None,
+                                                  L.ptr(v_vm_slots), L.ptr(g2d[0]), L.ptr(g2d[1]), L.ptr(row_map), st),
+                    "bds_project_view_bwd_list")
         carrier = cfg["_means2d_ref"]() if cfg.get("_means2d_ref") is not None else None
         if carrier is not None:  # the tensor the caller holds in info["means2d"] (trainers/base.py:282-284 read .absgrad / .grad)
             carrier.grad = g2d[0:1]
@@ -905,7 +876,6 @@ def _accumulate(p: Tensor, g: Optional[Tensor]) -> None:
 # the compositor's forward (1) or in front of its backward (0).  Measured on the two-stream frame: 937 vs 919 it/s -- in front of the
 # compositor's backward they delay the one kernel whose end closes the phase both compositors share.
 _SCHEDULE_IN_FORWARD = os.environ.get("BDS_SCHEDULE_IN_FORWARD", "1") == "1"
-_PROJECT_PREPARES = os.environ.get("BDS_PROJECT_PREPARES", "1") == "1"   # (A/B: 0 = projection and visible-reduce as two launches)
 _LOSS_TWO_STEP = os.environ.get("BDS_LOSS_TWO_STEP", "0") == "1"   # ablation: the loss as forward + backward launches
 _LOSS_IN_TRANSFORM = os.environ.get("BDS_LOSS_IN_TRANSFORM", "1") == "1"   # the loss rides on the colour transform's launch
 

@@ -93,9 +93,9 @@ class _Projection(torch.autograd.Function):
         conics = torch.empty(Cn, N, 3, device=dev, dtype=torch.float32)
         comps = torch.empty(Cn, N, device=dev, dtype=torch.float32) if calc_compensations else None
         with L.timed("project_fwd"):
-            L.check(L.lib().bds_project_fwd(Cn, N, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(viewmats), L.ptr(Ks), width,
+            L.check(L.lib().bds_project_fwd(Cn, N, L.ptr(means), L.ptr(quats), L.ptr(scales), None, L.ptr(viewmats), L.ptr(Ks), width,
                                             height, eps2d, near_plane, far_plane, radius_clip, L.ptr(radii), L.ptr(means2d),
-                                            L.ptr(depths), L.ptr(conics), L.ptr(comps), L.stream()), "bds_project_fwd")
+                                            L.ptr(depths), L.ptr(conics), L.ptr(comps), None, L.stream()), "bds_project_fwd")
         ctx.save_for_backward(means, quats, scales, viewmats, Ks, radii, conics)
         ctx.cfg = (width, height, eps2d)
         ctx.mark_non_differentiable(radii)

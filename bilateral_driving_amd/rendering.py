@@ -193,14 +193,9 @@ class _RasterizeView(torch.autograd.Function):
         means2d, depths, conics = torch.empty(1, N, 2, device=dev), torch.empty(1, N, device=dev), torch.empty(1, N, 3, device=dev)
         opac_eff = torch.empty(1, N, device=dev) if cfg["aa"] else None      # antialiased: opacity * comp, what tiles and compositor read
         with L.timed("project_fwd"):
-            if opac_eff is not None:
-                L.check(lib.bds_project_fwd_aa(1, N, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(viewmat), L.ptr(Kmat), W, H,
-                                               cfg["eps2d"], cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"], L.ptr(radii), L.ptr(means2d),
-                                               L.ptr(depths), L.ptr(conics), None, L.ptr(opac_eff), st), "bds_project_fwd_aa")
-            else:
-                L.check(lib.bds_project_fwd(1, N, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(viewmat), L.ptr(Kmat), W, H, cfg["eps2d"],
-                                            cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"], L.ptr(radii), L.ptr(means2d), L.ptr(depths),
-                                            L.ptr(conics), None, st), "bds_project_fwd")
+            L.check(lib.bds_project_fwd(1, N, L.ptr(means), L.ptr(quats), L.ptr(scales), None if opac_eff is None else L.ptr(opacities),
+                                        L.ptr(viewmat), L.ptr(Kmat), W, H, cfg["eps2d"], cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"],
+                                        L.ptr(radii), L.ptr(means2d), L.ptr(depths), L.ptr(conics), None, L.ptr(opac_eff), st), "bds_project_fwd")
         LT = _LIST_TILE
         ltw, lth = math.ceil(W / LT), math.ceil(H / LT)
         tw, th = math.ceil(W / TILE_SIZE), math.ceil(H / TILE_SIZE)
@@ -269,54 +264,11 @@ class _RasterizeView(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_out, v_alphas, v_means2d_ext, *_):
-        means, quats, scales, opacities, viewmat, Kmat, rec, vis_ids, _ws, flatten, isect_offsets, render, alphas, last_ids = ctx.saved_tensors
-        cfg, M = ctx.cfg, ctx.M
-        lib, st = L.lib(), L.stream()
-        dev = means.device
-        W, H, N = cfg["width"], cfg["height"], means.shape[0]
-        n_vis = vis_ids.numel()
-        tw, th = math.ceil(W / TILE_SIZE), math.ceil(H / TILE_SIZE)
-        v_render, v_alphas_t = torch.empty_like(render), torch.empty_like(alphas)
-        L.check(lib.bds_expected_depth_bwd(H * W, cfg["channels"], int(cfg["ed"]), L.ptr(render), L.ptr(alphas),
-                                           None if v_out is None else L.ptr(_f32c(v_out)), None if v_alphas is None else L.ptr(_f32c(v_alphas)),
-                                           L.ptr(v_render), L.ptr(v_alphas_t), st), "bds_expected_depth_bwd")
-        v_alphas = v_alphas_t
-        want_pose = bool(ctx.needs_input_grad[5])
-        v_rec_all = torch.zeros(max(n_vis, 1) + (L.POSE_GRAD_SLOTS if want_pose else 0), L.GRAD_RECORD_FLOATS, device=dev)
-        v_rec = v_rec_all[:max(n_vis, 1)]
-        order = bwd_schedule(1, W, H, _LIST_TILE, isect_offsets, last_ids)
-        with L.timed("rasterize_bwd"):
-            L.check(lib.bds_rasterize_bwd(1, n_vis, M, 4, L.ptr(rec), None, W, H, TILE_SIZE, _LIST_TILE, tw, th, L.ptr(isect_offsets),
-                                          L.ptr(flatten), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), L.ptr(v_render), L.ptr(v_alphas), L.ptr(v_rec),
-                                          int(bool(cfg["absgrad"])), L.ptr(order), st), "bds_rasterize_bwd")
-        if v_means2d_ext is not None and n_vis:   # a loss term on meta["means2d"] itself: add its rows to the records
-            v_rec[:n_vis, 7:9] += v_means2d_ext.reshape(N, 2).index_select(0, vis_ids.long())
-        # ONE zero fill for all dense outputs: means 3 | quats 4 | scales 3 | opacities 1 | colours 3 | grad2d 2 | absgrad2d 2
-        dense = torch.zeros(N * 18, device=dev)
-        o = 0
-        outs = []
-        for w in (3, 4, 3, 1, 3, 2, 2):
-            outs.append(dense[o:o + N * w].view(N, w) if w > 1 else dense[o:o + N])
-            o += N * w
-        v_means, v_quats, v_scales, v_opac, v_colors, g2d, ag2d = outs
-        slots = v_rec_all[max(n_vis, 1):].view(L.POSE_GRAD_SLOTS, 4, 4) if want_pose else None
-        with L.timed("project_bwd"):
-            if cfg["aa"]:       # record channel 11: the gradient of opacity * comp (include/bds.h bds_project_view_bwd_list_aa)
-                L.check(lib.bds_project_view_bwd_list_aa(L.PROJ_AA_ACTIVATED, n_vis, None, L.ptr(vis_ids), L.ptr(means), L.ptr(quats), L.ptr(scales),
-                                                         L.ptr(opacities), L.ptr(viewmat), L.ptr(Kmat), W, H, cfg["eps2d"], L.ptr(v_rec), L.ptr(v_means),
-                                                         L.ptr(v_quats), L.ptr(v_scales), L.ptr(v_opac), L.ptr(v_colors), L.ptr(slots), L.ptr(g2d),
-                                                         L.ptr(ag2d) if cfg["absgrad"] else None, None, st), "bds_project_view_bwd_list_aa")
-            else:
-                L.check(lib.bds_project_bwd_list(n_vis, L.ptr(vis_ids), L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(viewmat),
-                                                 L.ptr(Kmat), W, H, cfg["eps2d"], L.ptr(v_rec), L.ptr(v_means), L.ptr(v_quats), L.ptr(v_scales),
-                                                 L.ptr(v_opac), L.ptr(v_colors), L.ptr(slots), L.ptr(g2d), L.ptr(ag2d) if cfg["absgrad"] else None, st),
-                        "bds_project_bwd_list")
-        carrier = cfg["_means2d_ref"]() if cfg.get("_means2d_ref") is not None else None
-        if carrier is not None:      # the tensor the caller holds in meta["means2d"] (trainers/base.py:280-297 read .absgrad / .grad)
-            if cfg["absgrad"]:
-                carrier.absgrad = ag2d.view(1, N, 2)
-            if carrier.retains_grad:
-                carrier.grad = g2d.view(1, N, 2)
+        cfg, want_pose = ctx.cfg, bool(ctx.needs_input_grad[5])
+        # dense outputs: means 3 | quats 4 | scales 3 | opacities 1 | colours 3 | grad2d 2 | absgrad2d 2
+        outs, _, slots = _view_backward(ctx, ctx.saved_tensors, v_out, None, v_alphas, v_means2d_ext, want_pose, (3, 4, 3, 1, 3, 2, 2),
+                                        L.PROJ_ACTIVATED)
+        v_means, v_quats, v_scales, v_opac, v_colors = outs[:5]
         g = ctx.needs_input_grad
         return (v_means if g[0] else None, v_quats if g[1] else None, v_scales if g[2] else None, v_opac if g[3] else None,
                 v_colors.view(cfg["colors_shape"]) if g[4] else None, slots.sum(0) if want_pose else None, None, None)
@@ -378,69 +330,75 @@ class _RasterizeRawView(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_out, v_depth, v_alphas, v_means2d_ext, *_):
-        (means, quats, scales, opac, viewmat, Kmat, rec, vis_ids, _ws, flatten, isect_offsets, render, alphas, last_ids, sh_rgb,
-         cam_pos) = ctx.saved_tensors
-        cfg, M = ctx.cfg, ctx.M
-        lib, st = L.lib(), L.stream()
-        dev = means.device
-        W, H, N = cfg["width"], cfg["height"], means.shape[0]
-        n_vis = vis_ids.numel()
-        tw, th = math.ceil(W / TILE_SIZE), math.ceil(H / TILE_SIZE)
-        v_render, v_alphas_t = torch.empty_like(render), torch.empty_like(alphas)
-        if cfg.get("split"):
-            L.check(lib.bds_expected_depth_split_bwd(H * W, int(cfg["ed"]), L.ptr(render), L.ptr(alphas),
-                                                     None if v_out is None else L.ptr(_f32c(v_out)), None if v_depth is None else L.ptr(_f32c(v_depth)),
-                                                     None if v_alphas is None else L.ptr(_f32c(v_alphas)), L.ptr(v_render), L.ptr(v_alphas_t), st),
-                    "bds_expected_depth_split_bwd")
-        else:
-            L.check(lib.bds_expected_depth_bwd(H * W, cfg["channels"], int(cfg["ed"]), L.ptr(render), L.ptr(alphas),
-                                               None if v_out is None else L.ptr(_f32c(v_out)), None if v_alphas is None else L.ptr(_f32c(v_alphas)),
-                                               L.ptr(v_render), L.ptr(v_alphas_t), st), "bds_expected_depth_bwd")
-        want_pose = bool(ctx.needs_input_grad[6])
-        v_rec_all = torch.zeros(max(n_vis, 1) + (L.POSE_GRAD_SLOTS if want_pose else 0), L.GRAD_RECORD_FLOATS, device=dev)
-        v_rec = v_rec_all[:max(n_vis, 1)]
-        order = bwd_schedule(1, W, H, _LIST_TILE, isect_offsets, last_ids)
-        with L.timed("rasterize_bwd"):
-            L.check(lib.bds_rasterize_bwd(1, n_vis, M, 4, L.ptr(rec), None, W, H, TILE_SIZE, _LIST_TILE, tw, th, L.ptr(isect_offsets),
-                                          L.ptr(flatten), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), L.ptr(v_render), L.ptr(v_alphas_t), L.ptr(v_rec),
-                                          int(bool(cfg["absgrad"])), L.ptr(order), st), "bds_rasterize_bwd")
-        if v_means2d_ext is not None and n_vis:
-            v_rec[:n_vis, 7:9] += v_means2d_ext.reshape(N, 2).index_select(0, vis_ids.long())
+        saved = ctx.saved_tensors
+        means, vis_ids, sh_rgb, cam_pos = saved[0], saved[7], saved[14], saved[15]
+        cfg, want_pose = ctx.cfg, bool(ctx.needs_input_grad[6])
         ls_shape, lg_shape, dc_shape, rest_shape = ctx.shapes
         K = 1 + rest_shape[1]
-        # ONE zero fill for all dense outputs: means 3 | quats 4 | log_scales 3 | logits 1 | dc 3 | rest 3 (K - 1) | grad2d 2 | absgrad2d 2
-        widths = (3, 4, 3, 1, 3, 3 * (K - 1), 2, 2)
-        dense = torch.zeros(N * sum(widths), device=dev)
-        outs, o = [], 0
-        for w in widths:
-            outs.append(dense[o:o + N * w].view(N, w))
-            o += N * w
-        v_means, v_quats, v_ls, v_logits, v_dc, v_rest, g2d, ag2d = outs
+        widths = (3, 4, 3, 1, 3, 3 * (K - 1), 2, 2)   # means | quats | log_scales | logits | dc | rest | grad2d | absgrad2d
+        outs, v_rec, slots = _view_backward(ctx, saved, v_out, v_depth, v_alphas, v_means2d_ext, want_pose, widths, 0)
+        v_means, v_quats, v_ls, v_logits, v_dc, v_rest = outs[:6]
         with L.timed("sh_bwd"):
-            L.check(lib.bds_sh_view_bwd_list_split(n_vis, L.ptr(vis_ids), K, cfg["sh_degree"], L.ptr(means), L.ptr(cam_pos), L.ptr(sh_rgb), 1,
-                                                   L.ptr(v_rec), L.ptr(v_dc), L.ptr(v_rest), 0, st), "bds_sh_view_bwd_list_split")
-        slots = v_rec_all[max(n_vis, 1):].view(L.POSE_GRAD_SLOTS, 4, 4) if want_pose else None
-        with L.timed("project_bwd"):
-            if cfg["aa"]:
-                L.check(lib.bds_project_view_bwd_list_aa(0, n_vis, None, L.ptr(vis_ids), L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opac),
-                                                         L.ptr(viewmat), L.ptr(Kmat), W, H, cfg["eps2d"], L.ptr(v_rec), L.ptr(v_means), L.ptr(v_quats),
-                                                         L.ptr(v_ls), L.ptr(v_logits), None, L.ptr(slots), L.ptr(g2d),
-                                                         L.ptr(ag2d) if cfg["absgrad"] else None, None, st), "bds_project_view_bwd_list_aa")
-            else:
-                L.check(lib.bds_project_view_bwd_list(n_vis, L.ptr(vis_ids), L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opac), L.ptr(viewmat),
-                                                      L.ptr(Kmat), W, H, cfg["eps2d"], L.ptr(v_rec), L.ptr(v_means), L.ptr(v_quats), L.ptr(v_ls),
-                                                      L.ptr(v_logits), L.ptr(slots), L.ptr(g2d), L.ptr(ag2d) if cfg["absgrad"] else None, None, 0,
-                                                      st), "bds_project_view_bwd_list")
-        carrier = cfg["_means2d_ref"]() if cfg.get("_means2d_ref") is not None else None
-        if carrier is not None:
-            if cfg["absgrad"]:
-                carrier.absgrad = ag2d.view(1, N, 2)
-            if carrier.retains_grad:
-                carrier.grad = g2d.view(1, N, 2)
+            L.check(L.lib().bds_sh_view_bwd_list_split(vis_ids.numel(), L.ptr(vis_ids), K, cfg["sh_degree"], L.ptr(means), L.ptr(cam_pos),
+                                                       L.ptr(sh_rgb), 1, L.ptr(v_rec), L.ptr(v_dc), L.ptr(v_rest), 0, L.stream()),
+                    "bds_sh_view_bwd_list_split")
         g = ctx.needs_input_grad
         return (v_means if g[0] else None, v_quats if g[1] else None, v_ls.view(ls_shape) if g[2] else None,
                 v_logits.view(lg_shape) if g[3] else None, v_dc.view(dc_shape) if g[4] else None, v_rest.view(rest_shape) if g[5] else None,
                 slots.sum(0) if want_pose else None, None, None)
+
+
+def _view_backward(ctx, saved, v_out, v_depth, v_alphas, v_means2d_ext, want_pose: bool, widths, flags: int):
+    """The backward both one-view nodes share: expected depth -> compositor -> gradient records of the visible Gaussians (+ a loss on
+    meta["means2d"]) -> ONE zero fill of the dense outputs, ``widths`` floats per Gaussian (the four parameter gradients first, grad2d |
+    absgrad2d last) -> list-driven projection backward (bds_project_view_bwd_list, ``flags``; ACTIVATED scatters the colour gradient to
+    the fifth output) -> the means2d carrier.  Returns (dense outputs, gradient records, camera-pose slots or None)."""
+    means, quats, scales, opac, viewmat, Kmat, rec, vis_ids, _ws, flatten, isect_offsets, render, alphas, last_ids = saved[:14]
+    cfg, M = ctx.cfg, ctx.M
+    lib, st = L.lib(), L.stream()
+    dev = means.device
+    W, H, N = cfg["width"], cfg["height"], means.shape[0]
+    n_vis = vis_ids.numel()
+    tw, th = math.ceil(W / TILE_SIZE), math.ceil(H / TILE_SIZE)
+    v_render, v_alphas_t = torch.empty_like(render), torch.empty_like(alphas)
+    if cfg.get("split"):
+        L.check(lib.bds_expected_depth_split_bwd(H * W, int(cfg["ed"]), L.ptr(render), L.ptr(alphas),
+                                                 None if v_out is None else L.ptr(_f32c(v_out)), None if v_depth is None else L.ptr(_f32c(v_depth)),
+                                                 None if v_alphas is None else L.ptr(_f32c(v_alphas)), L.ptr(v_render), L.ptr(v_alphas_t), st),
+                "bds_expected_depth_split_bwd")
+    else:
+        L.check(lib.bds_expected_depth_bwd(H * W, cfg["channels"], int(cfg["ed"]), L.ptr(render), L.ptr(alphas),
+                                           None if v_out is None else L.ptr(_f32c(v_out)), None if v_alphas is None else L.ptr(_f32c(v_alphas)),
+                                           L.ptr(v_render), L.ptr(v_alphas_t), st), "bds_expected_depth_bwd")
+    v_rec_all = torch.zeros(max(n_vis, 1) + (L.POSE_GRAD_SLOTS if want_pose else 0), L.GRAD_RECORD_FLOATS, device=dev)
+    v_rec = v_rec_all[:max(n_vis, 1)]
+    order = bwd_schedule(1, W, H, _LIST_TILE, isect_offsets, last_ids)
+    with L.timed("rasterize_bwd"):
+        L.check(lib.bds_rasterize_bwd(1, n_vis, M, 4, L.ptr(rec), None, W, H, TILE_SIZE, _LIST_TILE, tw, th, L.ptr(isect_offsets),
+                                      L.ptr(flatten), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), L.ptr(v_render), L.ptr(v_alphas_t),
+                                      L.ptr(v_rec), int(bool(cfg["absgrad"])), L.ptr(order), st), "bds_rasterize_bwd")
+    if v_means2d_ext is not None and n_vis:   # a loss term on meta["means2d"] itself: add its rows to the records
+        v_rec[:n_vis, 7:9] += v_means2d_ext.reshape(N, 2).index_select(0, vis_ids.long())
+    dense = torch.zeros(N * sum(widths), device=dev)      # ONE zero fill for all dense outputs
+    outs, o = [], 0
+    for w in widths:
+        outs.append(dense[o:o + N * w].view(N, w) if w != 1 else dense[o:o + N])
+        o += N * w
+    v_means, v_quats, v_scales, v_opac, g2d, ag2d = *outs[:4], outs[-2], outs[-1]
+    slots = v_rec_all[max(n_vis, 1):].view(L.POSE_GRAD_SLOTS, 4, 4) if want_pose else None
+    with L.timed("project_bwd"):   # (antialiased: record channel 11 is the gradient of opacity * comp)
+        L.check(lib.bds_project_view_bwd_list(flags | (L.PROJ_ANTIALIASED if cfg["aa"] else 0), n_vis, None, L.ptr(vis_ids), L.ptr(means),
+                                              L.ptr(quats), L.ptr(scales), L.ptr(opac), L.ptr(viewmat), L.ptr(Kmat), W, H, cfg["eps2d"],
+                                              L.ptr(v_rec), L.ptr(v_means), L.ptr(v_quats), L.ptr(v_scales), L.ptr(v_opac),
+                                              L.ptr(outs[4]) if flags & L.PROJ_ACTIVATED else None, L.ptr(slots), L.ptr(g2d),
+                                              L.ptr(ag2d) if cfg["absgrad"] else None, None, st), "bds_project_view_bwd_list")
+    carrier = cfg["_means2d_ref"]() if cfg.get("_means2d_ref") is not None else None
+    if carrier is not None:      # the tensor the caller holds in meta["means2d"] (trainers/base.py:280-297 read .absgrad / .grad)
+        if cfg["absgrad"]:
+            carrier.absgrad = ag2d.view(1, N, 2)
+        if carrier.retains_grad:
+            carrier.grad = g2d.view(1, N, 2)
+    return outs, v_rec, slots
 
 
 _FINITE_WORDS: Dict[torch.device, tuple] = {}

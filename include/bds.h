@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-#define BDS_ABI_VERSION 2   /* 2: round 5 changed exported signatures (split_len / split_cap, error_pinned) + the round-6 entries */
+#define BDS_ABI_VERSION 3   /* 3: the projection's entries folded into four (bds_project_fwd, bds_project_view_fwd and
+                               bds_project_view_bwd_list changed signatures) */
 
 #define BDS_OK 0
 #define BDS_EINVAL (-1)      /* null / misaligned pointer, bad shape or unsupported parameter */
@@ -84,11 +85,13 @@ int bds_sh_bwd(int64_t n, int K, int deg, const float *dirs, const float *coeffs
  *    compensations [C,N] or NULL.  Culled entries are zero-filled.
  * compensations (rasterize_mode "antialiased", models/trainers/base.py:406): comp = sqrt(max(0, det S2 / det(S2 + eps2d I))), S2 the
  * FOV-clamped 2-D covariance before the blur, det S2 formed as a sum of squares (exact for needles, where the difference of the
- * entries' products is all rounding); the caller composites with opacity * comp. */
-int bds_project_fwd(int C, int64_t N, const float *means, const float *quats, const float *scales,
-                    const float *viewmats, const float *Ks, int W, int H, float eps2d, float near_plane,
-                    float far_plane, float radius_clip, int32_t *radii, float *means2d, float *depths, float *conics,
-                    float *compensations, bds_stream_t stream);
+ * entries' products is all rounding); the caller composites with opacity * comp.
+ * opacities [N] and opac_eff [C,N] (both NULL or both set): the effective opacities of that mode in the same launch, opac_eff =
+ * opacities * comp (what the tile stage and the compositor read then); compensations may be NULL with them. */
+int bds_project_fwd(int C, int64_t N, const float *means, const float *quats, const float *scales, const float *opacities,
+                    const float *viewmats, const float *Ks, int W, int H, float eps2d, float near_plane, float far_plane,
+                    float radius_clip, int32_t *radii, float *means2d, float *depths, float *conics, float *compensations,
+                    float *opac_eff, bds_stream_t stream);
 /* v_means [N,3] v_quats [N,4] v_scales [N,3] are written (summed over cameras);
  * v_viewmats [C,4,4] (NULL = not needed) is zeroed and accumulated inside
  * (learnable camera poses: models/trainers/base.py:328-329,399).
@@ -100,12 +103,6 @@ int bds_project_bwd(int C, int64_t N, const float *means, const float *quats, co
                     const float *conics, const float *compensations, const float *v_means2d, const float *v_depths,
                     const float *v_conics, const float *v_compensations, float *v_means, float *v_quats,
                     float *v_scales, float *v_viewmats, bds_stream_t stream);
-/* bds_project_fwd + the effective opacities of rasterize_mode "antialiased" (models/trainers/base.py:406) in the same launch:
- * opac_eff [C,N] = opacities[N] * comp (what the tile stage and the compositor read in that mode); compensations may be NULL. */
-int bds_project_fwd_aa(int C, int64_t N, const float *means, const float *quats, const float *scales, const float *opacities,
-                       const float *viewmats, const float *Ks, int W, int H, float eps2d, float near_plane, float far_plane,
-                       float radius_clip, int32_t *radii, float *means2d, float *depths, float *conics, float *compensations,
-                       float *opac_eff, bds_stream_t stream);
 
 /* ---- tile intersection + (tile|depth) ordering -------------------------------------------
  * isect_tiles + radix sort + isect_offset_encode stages of gsplat.rendering.rasterization.
@@ -348,48 +345,36 @@ int bds_l1_tv_train(int64_t n, const float *a, const float *b, int nlevels, cons
 /* ROW FORM of the projection's outputs (optional, recognised by the addresses -- no argument says so): means2d, depths and conics may
  * be the COLUMNS of one 16-byte aligned [N,8] block of 32-byte rows {m2d.x, m2d.y, depth, radius (int bits) | conic a, b, c, opacity}:
  * pass means2d = block, depths = block + 2, conics = block + 4 (both or neither; separate arrays of more than one row can not have
- * these addresses).  bds_project_view_fwd / _prepare_fwd then write whole rows (radii [N] and opacities [N] are written as dense
- * arrays as well), and bds_isect_prepare* / bds_isect_build* / bds_splat_pack_sh* given the same three pointers (and opacities =
- * block + 7, or any dense [N] array of other opacities) gather ONE line per visible Gaussian instead of one per array. */
-int bds_project_view_fwd(int64_t N, const float *means, const float *quats, const float *log_scales, const float *logits,
-                         const float *viewmat, const float *K, int W, int H, float eps2d, float near_plane,
-                         float far_plane, float radius_clip, float *scales, float *opacities, int32_t *radii,
-                         float *means2d, float *depths, float *conics, bds_stream_t stream);
+ * these addresses).  bds_project_view_fwd then writes whole rows (radii [N] and opacities [N] are written as dense arrays as well),
+ * and bds_isect_prepare* / bds_isect_build* / bds_splat_pack_sh* given the same three pointers (and opacities = block + 7, or any
+ * dense [N] array of other opacities) gather ONE line per visible Gaussian instead of one per array. */
 /* Block bounds: rows kept in spatial order (Morton order of the centres: the host side's densify.spatial_order) make every 256-row
  * block a small box, and a camera then rejects most of the ~85 % of the Gaussians it does not see a BLOCK at a time.
  * bds_gaussian_block_bounds: block_bounds [cdiv(N, 256), 8] = {lo.xyz, largest activated scale | hi.xyz, -} of the centres of rows
- * [256 b, 256 (b + 1)); recompute whenever means / log_scales changed (once per frame).  The _blocks forms of the two projections
- * below skip a block when no centre inside its box can come out visible (conservative: csrc/gs_math.h box_may_be_visible follows
- * the tests of the projection itself) -- its rows get a culled Gaussian's outputs (radius 0, zeros) without being read; scales /
- * opacities of such rows are not written.  Results are identical to the plain forms. */
+ * [256 b, 256 (b + 1)); recompute whenever means / log_scales changed (once per frame). */
 int bds_gaussian_block_bounds(int64_t N, const float *means, const float *log_scales, float *block_bounds, bds_stream_t stream);
-int bds_project_view_fwd_blocks(int64_t N, const float *means, const float *quats, const float *log_scales, const float *logits,
-                                const float *viewmat, const float *K, int W, int H, float eps2d, float near_plane, float far_plane,
-                                float radius_clip, float *scales, float *opacities, int32_t *radii, float *means2d, float *depths,
-                                float *conics, const float *block_bounds, bds_stream_t stream);
-int bds_project_view_prepare_fwd_blocks(int64_t N, const float *means, const float *quats, const float *log_scales, const float *logits,
-                                        const float *viewmat, const float *K, int W, int H, float eps2d, float near_plane,
-                                        float far_plane, float radius_clip, float *scales, float *opacities, int32_t *radii,
-                                        float *means2d, float *depths, float *conics, int32_t *tiles_per_gauss, void *prep_ws,
-                                        size_t prep_ws_bytes, const float *block_bounds, bds_stream_t stream);
-/* The one-view forward of rasterize_mode "antialiased" (models/trainers/base.py:406, :824) -- bds_project_view_fwd / _blocks /
- * _prepare_fwd / _prepare_fwd_blocks in one entry: the opacity the tile stage and the compositor read is the EFFECTIVE one,
- * sigmoid(logit) * comp -- slot 7 of the [N,8] row form, else opac_eff [N] (required in the column form, ignored in the row form);
- * opacities [N] receives sigmoid(logit), which the backward reads.  prep_ws (NULL: the plain form) selects the prepare form
- * (BDS_ECAPACITY as there); block_bounds (NULL: none) the _blocks form. */
-int bds_project_view_fwd_aa(int64_t N, const float *means, const float *quats, const float *log_scales, const float *logits,
-                            const float *viewmat, const float *K, int W, int H, float eps2d, float near_plane, float far_plane,
-                            float radius_clip, float *scales, float *opacities, float *opac_eff, int32_t *radii, float *means2d,
-                            float *depths, float *conics, int32_t *tiles_per_gauss, void *prep_ws, size_t prep_ws_bytes,
-                            const float *block_bounds, bds_stream_t stream);
-/* bds_project_view_fwd that also does the first launch of the tile stage (device-count form, C = 1): the number of visible Gaussians
- * per 256-Gaussian workgroup is left in prep_ws (bds_isect_prepare_workspace_bytes(1, N)), the stage's sort tables and
- * tiles_per_gauss [N] (may be NULL) are cleared.  Follow with bds_isect_prepare_dev(..., compact | 2, ...) on the SAME workspace.
- * BDS_ECAPACITY when N is beyond the short sort path (use bds_project_view_fwd then). */
-int bds_project_view_prepare_fwd(int64_t N, const float *means, const float *quats, const float *log_scales, const float *logits,
-                                 const float *viewmat, const float *K, int W, int H, float eps2d, float near_plane, float far_plane,
-                                 float radius_clip, float *scales, float *opacities, int32_t *radii, float *means2d, float *depths,
-                                 float *conics, int32_t *tiles_per_gauss, void *prep_ws, size_t prep_ws_bytes, bds_stream_t stream);
+/* Flags of the one-view projection entries (bds_project_view_fwd takes BDS_PROJ_ANTIALIASED only). */
+#define BDS_PROJ_ACCUMULATE 1
+#define BDS_PROJ_ACTIVATED 2
+#define BDS_PROJ_ANTIALIASED 4
+/* The one-view forward (C = 1): scales [N] = exp(log_scales), opacities [N] = sigmoid(logits), and the projection's outputs.
+ *   flags & BDS_PROJ_ANTIALIASED: rasterize_mode "antialiased" (models/trainers/base.py:406, :824) -- the opacity the tile stage and the
+ *       compositor read is the EFFECTIVE one, sigmoid(logit) * comp: slot 7 of the [N,8] row form, else opac_eff [N] (required in the
+ *       column form, ignored in the row form); `opacities` keeps sigmoid(logit), which the backward reads.  Without the flag opac_eff
+ *       must be NULL (the row form's slot 7 then holds sigmoid(logit)).
+ *   prep_ws (NULL: none) also does the first launch of the tile stage (device-count form; N > 0): the number of visible Gaussians per
+ *       256-Gaussian workgroup is left in prep_ws (bds_isect_prepare_workspace_bytes(1, N)), the stage's sort tables and
+ *       tiles_per_gauss [N] (may be NULL) are cleared.  Follow with bds_isect_prepare_dev(..., compact | 2, ...) on the SAME workspace.
+ *       BDS_ECAPACITY when N is beyond the short sort path (call again with prep_ws = NULL then).  tiles_per_gauss is not touched
+ *       without prep_ws.
+ *   block_bounds (NULL: none) of bds_gaussian_block_bounds over the SAME means / log_scales: a 256-row block no centre of which can come
+ *       out visible (conservative: csrc/gs_math.h box_may_be_visible follows the tests of the projection itself) is not read -- its
+ *       rows get a culled Gaussian's outputs (radius 0, zeros; scales / opacities zero too).  Results are identical to the form without. */
+int bds_project_view_fwd(int flags, int64_t N, const float *means, const float *quats, const float *log_scales, const float *logits,
+                         const float *viewmat, const float *K, int W, int H, float eps2d, float near_plane, float far_plane,
+                         float radius_clip, float *scales, float *opacities, float *opac_eff, int32_t *radii, float *means2d,
+                         float *depths, float *conics, int32_t *tiles_per_gauss, void *prep_ws, size_t prep_ws_bytes,
+                         const float *block_bounds, bds_stream_t stream);
 int bds_sh_view_fwd(int64_t N, int K, int degrees_to_use, const float *means, const float *cam_pos, const float *coeffs,
                     const int32_t *radii, const float *depths, float *sh_rgb, float *colors, bds_stream_t stream);
 /* Backward of the one-view forms over the VISIBLE entries only, list-driven (no reference counterpart; the reference's dense
@@ -398,19 +383,14 @@ int bds_sh_view_fwd(int64_t N, int K, int degrees_to_use, const float *means, co
  * accumulate = 0 STORES the rows ids[.] of the gradient arrays (all other rows are the caller's business: zero-filled, or kept zero
  * with bds_view_grads_clear_list), accumulate = 1 ADDS to them (several views summed into one buffer before one exchange).
  *   sh_view_bwd_list     : v_coeffs [N,K,3] rows (colour clamp of vanilla.py:389 applied through sh_rgb).
- *   project_view_bwd_list: v_means [N,3] v_quats [N,4] v_log_scales [N,3] v_logits [N] rows; optionally (may be NULL)
- *       grad2d / absgrad2d [N,2]: the screen-space gradient and the sum over pixels of its absolute value scattered to the
- *       dense arrays models/trainers/base.py:280-297 reads (rows of culled Gaussians untouched);
- *       v_viewmat_slots [BDS_POSE_GRAD_SLOTS,4,4]: camera-pose gradient partials, ADDED to (the caller zero-fills them, e.g. as the
- *       tail of the gradient-record allocation; replicated accumulators: one address would serialise in L2); the sum over the slots
- *       is d(loss)/d(viewmat), models/trainers/base.py:328-329,399.
+ *   project_view_bwd_list: v_means [N,3] v_quats [N,4] v_log_scales [N,3] v_logits [N] rows (see there).
  * row_map (may be NULL) [N] i32: the parameter-gradient row of Gaussian g is row_map[g] instead of g -- the rows then land in a
  * compact exchange buffer (multi-GPU: the slot of g in the union of the ranks' visible sets) instead of the dense arrays. */
 #define BDS_POSE_GRAD_SLOTS 64
 /* ROW FORM of the four small parameter gradients (optional, recognised by the addresses like the projection's row form): v_means,
  * v_quats, v_log_scales, v_logits may be the columns of one 16-byte aligned [N,16] block of 64-byte rows {v_mean 3, v_logit | v_quat 4 |
  * v_log_scale 3, - | - - - -}: pass v_means = block, v_logits = block + 3, v_quats = block + 4, v_log_scales = block + 8.
- * bds_project_view_bwd_list* then update, and bds_view_grads_clear_list* clear, ONE line per visible Gaussian instead of four partly
+ * bds_project_view_bwd_list then updates, and bds_view_grads_clear_list* clear, ONE line per visible Gaussian instead of four partly
  * used ones; bds_adam_step_rows reads such columns. */
 /* sh_rgb: the un-clamped colours the forward left -- [N,3] indexed by Gaussian (bds_sh_view_fwd), or, with sh_rgb_by_rank != 0,
  * [n_list,3] in list order (bds_splat_pack_sh). */
@@ -433,33 +413,30 @@ int bds_nonfinite_flags(int n_tensors, const float *const *tensors, const int64_
  * 16-byte aligned (NaN / Inf components, or a row whose squared norm is 0 in fp32: 0/0, x/0) | 3 argument of sigmoid (NaN only). */
 int bds_nonfinite_flags_kinds(int n_tensors, const float *const *tensors, const int64_t *counts, const int *kinds, uint32_t *flags_dev,
                               uint32_t *flags_pinned, bds_stream_t stream);
-/* Backward of gsplat's rasterization() over the visible entries, C = 1 (models/trainers/base.py:393-408: the trainer passes ACTIVATED
- * scales / opacities and post-activation colours [N,3]): what bds_project_view_bwd_list does, with the gradients of the activated
- * scales and opacities returned as they are and the colour gradient (record channels 0-2) scattered to v_colors [N,3] (may be
- * NULL).  Store mode: the caller zero-fills the dense arrays; rows of culled Gaussians stay zero. */
-int bds_project_bwd_list(int64_t n_list, const int32_t *ids, const float *means, const float *quats, const float *scales,
-                         const float *opacities, const float *viewmat, const float *K, int W, int H, float eps2d,
-                         const float *v_records, float *v_means, float *v_quats, float *v_scales, float *v_opacities, float *v_colors,
-                         float *v_viewmat_slots, float *grad2d, float *absgrad2d, bds_stream_t stream);
-int bds_project_view_bwd_list(int64_t n_list, const int32_t *ids, const float *means, const float *quats, const float *scales,
-                              const float *opacities, const float *viewmat, const float *K, int W, int H, float eps2d,
-                              const float *v_records, float *v_means, float *v_quats, float *v_log_scales, float *v_logits,
-                              float *v_viewmat_slots, float *grad2d, float *absgrad2d, const int32_t *row_map, int accumulate,
-                              bds_stream_t stream);
-/* The list-driven one-view backward of rasterize_mode "antialiased" (models/trainers/base.py:406) -- bds_project_view_bwd_list /
- * _list_dev / bds_project_bwd_list in one entry.  Record channel 11 is the gradient of the effective opacity o * comp; comp is recomputed
- * in the VJP: v_comp = v_eff * o enters the projection's gradient, the opacity gets v_eff * comp (times o (1 - o) for logits).
- * flags: BDS_PROJ_AA_ACCUMULATE = `accumulate` of bds_project_view_bwd_list; BDS_PROJ_AA_ACTIVATED = the gsplat-shaped form of
- * bds_project_bwd_list (activated scales / opacities, v_colors [N,3] scattered; row_map NULL, no accumulate), else the raw form
- * (v_scales / v_opacities are the log-scale / logit gradients, v_colors unused).  n_dev (NULL: host count) = the _dev form, n_list is
- * then the capacity. */
-#define BDS_PROJ_AA_ACCUMULATE 1
-#define BDS_PROJ_AA_ACTIVATED 2
-int bds_project_view_bwd_list_aa(int flags, int64_t n_list, const uint64_t *n_dev, const int32_t *ids, const float *means,
-                                 const float *quats, const float *scales, const float *opacities, const float *viewmat, const float *K,
-                                 int W, int H, float eps2d, const float *v_records, float *v_means, float *v_quats, float *v_scales,
-                                 float *v_opacities, float *v_colors, float *v_viewmat_slots, float *grad2d, float *absgrad2d,
-                                 const int32_t *row_map, bds_stream_t stream);
+/* The list-driven projection backward over the visible entries (C = 1; ids, v_records, `accumulate` and row_map as above): the rows of
+ * v_means [N,3] v_quats [N,4] v_scales [N,3] v_opacities [N].
+ *   flags & BDS_PROJ_ACCUMULATE: ADD to the rows (accumulate = 1 above) instead of storing them.
+ *   flags & BDS_PROJ_ACTIVATED: the backward of gsplat's rasterization() (models/trainers/base.py:393-408: the trainer passes ACTIVATED
+ *       scales / opacities and post-activation colours [N,3]): the gradients of the activated scales and opacities are returned as they
+ *       are and the colour gradient (record channels 0-2) is scattered to v_colors [N,3] (may be NULL).  Excludes BDS_PROJ_ACCUMULATE
+ *       and row_map: the caller zero-fills the dense arrays; rows of culled Gaussians stay zero.
+ *       Without it, the raw form of bds_project_view_fwd: scales / opacities are the activated values that forward left, v_scales /
+ *       v_opacities receive the log-scale / logit gradients, v_colors is not used.
+ *   flags & BDS_PROJ_ANTIALIASED: rasterize_mode "antialiased" (models/trainers/base.py:406).  Record channel 11 is the gradient of the
+ *       effective opacity o * comp; comp is recomputed in the VJP: v_comp = v_eff * o enters the projection's gradient, the opacity
+ *       gets v_eff * comp (times o (1 - o) for logits).
+ *   n_dev (NULL: n_list is the count): the device-count form -- the count is read from n_dev (visible effective), n_list is then the
+ *       capacity.
+ *   grad2d / absgrad2d [N,2] (may be NULL): the screen-space gradient and the sum over pixels of its absolute value scattered to the
+ *       dense arrays models/trainers/base.py:280-297 reads (rows of culled Gaussians untouched).
+ *   v_viewmat_slots [BDS_POSE_GRAD_SLOTS,4,4] (may be NULL): camera-pose gradient partials, ADDED to (the caller zero-fills them, e.g.
+ *       as the tail of the gradient-record allocation; replicated accumulators: one address would serialise in L2); the sum over the
+ *       slots is d(loss)/d(viewmat), models/trainers/base.py:328-329,399. */
+int bds_project_view_bwd_list(int flags, int64_t n_list, const uint64_t *n_dev, const int32_t *ids, const float *means,
+                              const float *quats, const float *scales, const float *opacities, const float *viewmat, const float *K,
+                              int W, int H, float eps2d, const float *v_records, float *v_means, float *v_quats, float *v_scales,
+                              float *v_opacities, float *v_colors, float *v_viewmat_slots, float *grad2d, float *absgrad2d,
+                              const int32_t *row_map, bds_stream_t stream);
 /* Zero the rows ids[0..n_list) of the five per-Gaussian gradient arrays (v_sh is [N,K,3]). */
 int bds_view_grads_clear_list(int64_t n_list, const int32_t *ids, int K, float *v_means, float *v_quats, float *v_log_scales,
                               float *v_logits, float *v_sh, bds_stream_t stream);
@@ -524,7 +501,7 @@ int bds_rasterize_kernel_name(int backward, int CH, int absgrad, int list_tile_s
  * overflow; written by the GPU; may be NULL) whenever it likes, provisions more and repeats the view.  Launches are sized by the
  * capacities; surplus workgroups see no elements.  Packed lists only (n_visible_capacity <= 2^(32 - bits(C*tiles))), else
  * BDS_ECAPACITY.  Lists, offsets and images are bit-identical to the host-count forms.  `compact`: bit 0 as in bds_isect_prepare,
- * bit 1 = the workspace already holds the visible counts and cleared tables of bds_project_view_prepare_fwd (one launch less). */
+ * bit 1 = the workspace already holds the visible counts and cleared tables of bds_project_view_fwd's prep_ws (one launch less). */
 size_t bds_isect_counts_offset(int which);
 int bds_isect_prepare_dev(int C, int64_t N, const float *means2d, const int32_t *radii, const float *depths, const float *conics,
                           const float *opacities, int tile_size, int tile_w, int tile_h, int32_t *tiles_per_gauss, void *ws,
@@ -585,11 +562,6 @@ int bds_rasterize_bwd_dev(int C, int64_t n_records, int64_t M_capacity, const ui
 int bds_sh_view_bwd_list_dev(int64_t n_capacity, const uint64_t *n_dev, const int32_t *ids, int K, int degrees_to_use,
                              const float *means, const float *cam_pos, const float *sh_rgb, int sh_rgb_by_rank,
                              const float *v_records, float *v_coeffs, const int32_t *row_map, int accumulate, bds_stream_t stream);
-int bds_project_view_bwd_list_dev(int64_t n_capacity, const uint64_t *n_dev, const int32_t *ids, const float *means,
-                                  const float *quats, const float *scales, const float *opacities, const float *viewmat,
-                                  const float *K, int W, int H, float eps2d, const float *v_records, float *v_means, float *v_quats,
-                                  float *v_log_scales, float *v_logits, float *v_viewmat_slots, float *grad2d, float *absgrad2d,
-                                  const int32_t *row_map, int accumulate, bds_stream_t stream);
 /* (grad2d / absgrad2d [N,2], optional: the same rows of a view's PERSISTENT screen-space gradient arrays are cleared as well -- the
  * list-driven projection backward stores the visible rows, so a buffer cleared by the previous visit's list needs no dense fill.
  * The five parameter-gradient pointers may ALL be NULL: only the screen-space arrays are cleared then -- a loop whose optimizer

@@ -24,15 +24,20 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(bds_[a-z0-9_]+)\s*\(", src)))
 
 
-def test_header_symbols_are_exported(libpath):
+def test_header_and_library_symbols_match_abi_3(libpath):
     names = _declared_symbols()
     assert len(names) >= 19
     h = ctypes.CDLL(libpath)
     for n in names:
         assert hasattr(h, n), f"{n} declared in include/bds.h but not exported by libbds.so"
+    out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--dyn-syms", "-W", libpath], capture_output=True, text=True, check=True).stdout
+    rows = [line.split() for line in out.splitlines()]    # Num: Value Size Type Bind Vis Ndx Name
+    exported = {r[7] for r in rows if len(r) >= 8 and r[7].startswith("bds_") and r[6] != "UND"}
+    assert len(exported) >= 19
+    assert not exported - set(names), f"exported by libbds.so but not declared in include/bds.h: {sorted(exported - set(names))}"
     h.bds_abi_version.restype = ctypes.c_int
     from bilateral_driving_amd import _lib as _L
-    assert h.bds_abi_version() == _L.ABI_VERSION == 2
+    assert h.bds_abi_version() == _L.ABI_VERSION == 3
     h.bds_strerror.restype = ctypes.c_char_p
     assert b"workspace" in h.bds_strerror(-2)
 

@@ -29,7 +29,7 @@ def _scene(N, W, H, seed):
 
 
 @pytest.mark.parametrize("seed,N,W,H", [(0, 3000, 320, 200), (1, 257, 96, 64)])
-def test_project_view_equals_general_form_with_activations(env, seed, N, W, H):
+def test_project_view_flag_forms_equal_general_form_with_activations(env, seed, N, W, H):
     ops, L = env
     lib, st = L.lib(), L.stream()
     s = _scene(N, W, H, seed)
@@ -37,8 +37,9 @@ def test_project_view_equals_general_form_with_activations(env, seed, N, W, H):
     scales, opac = torch.empty(N, 3, device="cuda"), torch.empty(N, device="cuda")
     radii = torch.empty(1, N, dtype=torch.int32, device="cuda")
     m2, dep, con = torch.empty(1, N, 2, device="cuda"), torch.empty(1, N, device="cuda"), torch.empty(1, N, 3, device="cuda")
-    L.check(lib.bds_project_view_fwd(N, L.ptr(s["means"]), L.ptr(s["quats"]), L.ptr(s["log_scales"]), L.ptr(s["logits"]), L.ptr(vm), L.ptr(K),
-                                     W, H, 0.3, 0.01, 1e10, 0.0, L.ptr(scales), L.ptr(opac), L.ptr(radii), L.ptr(m2), L.ptr(dep), L.ptr(con), st), "fwd")
+    L.check(lib.bds_project_view_fwd(0, N, L.ptr(s["means"]), L.ptr(s["quats"]), L.ptr(s["log_scales"]), L.ptr(s["logits"]), L.ptr(vm),
+                                     L.ptr(K), W, H, 0.3, 0.01, 1e10, 0.0, L.ptr(scales), L.ptr(opac), None, L.ptr(radii), L.ptr(m2), L.ptr(dep),
+                                     L.ptr(con), None, None, 0, None, st), "fwd")
     ref_scales, ref_opac = torch.exp(s["log_scales"]), torch.sigmoid(s["logits"])
     assert torch.allclose(scales, ref_scales, rtol=2e-6, atol=0) and torch.allclose(opac, ref_opac, rtol=2e-6, atol=1e-7)
     r2, rm2, rdep, rcon, _ = ops.fully_fused_projection(s["means"], s["quats"], scales, vm[None], K[None], W, H)
@@ -64,9 +65,9 @@ def test_project_view_equals_general_form_with_activations(env, seed, N, W, H):
         out = [torch.full((N, k), 7.0, device="cuda") for k in (3, 4, 3)] + [torch.full((N,), 7.0, device="cuda")]
         slots = torch.zeros(L.POSE_GRAD_SLOTS, 4, 4, device="cuda")                # camera-pose gradient partials (trainers/base.py:328-329,399)
         g2d, ag2d = torch.full((N, 2), 7.0, device="cuda"), torch.full((N, 2), 7.0, device="cuda")
-        L.check(lib.bds_project_view_bwd_list(n, L.ptr(ids), L.ptr(s["means"]), L.ptr(s["quats"]), L.ptr(scales), L.ptr(opac), L.ptr(vm), L.ptr(K),
-                                              W, H, 0.3, L.ptr(v_rec), L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]), L.ptr(slots),
-                                              L.ptr(g2d), L.ptr(ag2d), None, acc, st), "bwd list")
+        L.check(lib.bds_project_view_bwd_list(L.PROJ_ACCUMULATE if acc else 0, n, None, L.ptr(ids), L.ptr(s["means"]), L.ptr(s["quats"]),
+                                              L.ptr(scales), L.ptr(opac), L.ptr(vm), L.ptr(K), W, H, 0.3, L.ptr(v_rec), L.ptr(out[0]), L.ptr(out[1]),
+                                              L.ptr(out[2]), L.ptr(out[3]), None, L.ptr(slots), L.ptr(g2d), L.ptr(ag2d), None, st), "bwd list")
         base = 7.0 * acc
         # (two separately compiled kernels: fused multiply-adds differ in the last bits, and the projection vjp cancels)
         for a, b in ((out[0], ref[0]), (out[1], ref[1]), (out[2], ref[2] * scales)):
@@ -84,9 +85,9 @@ def test_project_view_equals_general_form_with_activations(env, seed, N, W, H):
     out3 = [torch.zeros(N, k, device="cuda") for k in (3, 4, 3)] + [torch.zeros(N, device="cuda")]
     slots = torch.zeros(L.POSE_GRAD_SLOTS, 4, 4, device="cuda")
     for o, sl in ((out2, None), (out3, slots)):
-        L.check(lib.bds_project_view_bwd_list(n, L.ptr(ids), L.ptr(s["means"]), L.ptr(s["quats"]), L.ptr(scales), L.ptr(opac), L.ptr(vm), L.ptr(K),
-                                              W, H, 0.3, L.ptr(v_rec), L.ptr(o[0]), L.ptr(o[1]), L.ptr(o[2]), L.ptr(o[3]), L.ptr(sl), None, None,
-                                              None, 0, st), "bwd list (pose on / off)")
+        L.check(lib.bds_project_view_bwd_list(0, n, None, L.ptr(ids), L.ptr(s["means"]), L.ptr(s["quats"]), L.ptr(scales), L.ptr(opac), L.ptr(vm),
+                                              L.ptr(K), W, H, 0.3, L.ptr(v_rec), L.ptr(o[0]), L.ptr(o[1]), L.ptr(o[2]), L.ptr(o[3]), None, L.ptr(sl),
+                                              None, None, None, st), "bwd list (pose on / off)")
     for a, b in zip(out2, out3):   # two template instantiations: fused multiply-adds differ in the last bits and the vjp cancels
         assert float((a - b).norm()) <= 1e-4 * float(b.norm())
 

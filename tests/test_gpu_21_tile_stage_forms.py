@@ -112,7 +112,7 @@ def test_row_form_of_the_projection_outputs_changes_nothing(mods, monkeypatch, d
 @pytest.mark.parametrize("ordered", [True, False], ids=["spatial_order", "given_order"])
 @pytest.mark.parametrize("device_counts", [False, True])
 def test_block_bounds_skip_blocks_without_changing_anything(mods, ordered, device_counts):
-    """bds_gaussian_block_bounds + bds_project_view_{,prepare_}fwd_blocks: a projection that skips the 256-row blocks it can not see
+    """bds_gaussian_block_bounds + bds_project_view_fwd with block_bounds (with and without prep_ws): a projection that skips the 256-row blocks it can not see
     leaves the same radii, lists, images and gradients as the one that reads every row -- with the rows in spatial order (where
     most blocks go) and in the generator's order (where hardly any does), for cameras all round the rig."""
     L, FV, GV, Hn = mods

@@ -204,7 +204,7 @@ def test_axis_cell_is_slice_cell_with_the_last_node_folded_into_the_last_cell(hm
 
 
 def test_block_bound_never_rejects_a_box_that_holds_a_visible_gaussian(hm):
-    """csrc/gs_math.h box_may_be_visible (the bound behind bds_project_view_*_fwd_blocks) against project_one itself: whenever a box is
+    """csrc/gs_math.h box_may_be_visible (the bound behind bds_project_view_fwd's block_bounds) against project_one itself: whenever a box is
     rejected, NO Gaussian with its centre inside the box and scales up to the box's maximum comes out of the projection with a
     radius -- for boxes in front of, beside, behind and around the camera, near-plane straddlers and large splats included.  And the
     bound does reject: most boxes well outside the frustum go."""
