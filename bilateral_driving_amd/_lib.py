@@ -146,6 +146,9 @@ _SIGS = {
     "bds_deform_fwd": (_i, [_i64, _i, _f, _f, _f, C.POINTER(BdsDeformNet), _f, _f, _f, _f]),
     "bds_deform_bwd": (_i, [_i64, _i, _f, _f, _f, C.POINTER(BdsDeformNet), _f, _f, _f, _f, _f, _f, C.POINTER(BdsDeformNet), _i, _f, _sz,
                             _f]),
+    "bds_node_pose_bwd_temp_bytes": (_sz, [_i64, _i]),
+    "bds_node_pose_fwd": (_i, [_i64, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "bds_node_pose_bwd": (_i, [_i64, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _f]),
     "bds_opacity_reset": (_i, [_i64, _f, _fl, _f, _f, _f]),
     "bds_cubemap_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f]),
     "bds_cubemap_bwd": (_i, [_i64, _i, _i, _i, _f, _f, _f, _f, _f]),

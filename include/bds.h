@@ -873,6 +873,32 @@ int bds_deform_bwd(int64_t N, int embed_dim, const float *x, const float *t, con
                    const float *v_xyz, const float *v_rotation, const float *v_scaling, float *v_x, float *v_t, float *v_cond,
                    const bds_deform_net_grad *grad, int accumulate, void *temp, size_t temp_bytes, bds_stream_t stream);
 
+/* ---- Pose transform of the node classes -------------------------------------------------------------------------------------------
+ * RigidNodes.transform_means / transform_quats / get_pts_valid_mask and the activations of get_gaussians (models/nodes/rigid.py:28-32,
+ * 385-493), the same for DeformableNodes (models/nodes/deformable.py:49-114, which calls them on the deformed means / quaternions).
+ * Point p of instance i = point_ids[p] (int64 [N], the [N,1] column) at frame f = cur_frame, q_i = instances_quats[f,i] ([F,I,4]),
+ * t_i = instances_trans[f,i] ([F,I,3]), instances_fv [F,I] (bool, one byte each):
+ *   world_means[p] = R(q_i) means[p] + t_i                       (R: the normalising quat_to_rotmat of quat_act(q_i))
+ *   world_quats[p] = n(quat_mult(n(q_i), n(quats[p])))          (n = quat_act, q / |q|: a zero quaternion gives NaN, as the reference)
+ *   opacities[p]   = sigmoid(logits[p]) * instances_fv[f,i]
+ * interpolate != 0: the test-set form (rigid.py:392-432), allowed only when cur_frame - 1 > 0 and cur_frame + 1 < F (else BDS_EINVAL):
+ * the means' rotation is interpolate_quats(q[f-1], q[f+1]) (models/gaussians/basics.py:17-45) and the translation
+ * (t[f-1] + t[f+1]) / 2 where instances_fv[f-1] & instances_fv[f+1], else frame f's; world_quats and the mask keep frame f.
+ * An id outside [0, I) reads nothing: that point's outputs are NaN and bit 0 of *bad_ids (may be NULL) is raised, never cleared.
+ * N = 0 launches nothing and writes nothing.  All arrays contiguous float32 unless said otherwise.
+ * bwd (non-interpolated form only; the reference cannot differentiate the other): v_means [N,3], v_quats [N,4], v_logits [N] stored per
+ * point (zero for an out-of-range id); v_instances_quats [F,I,4] / v_instances_trans [F,I,3] stored dense, zero outside frame f.  The
+ * instance sums are reduced per wave in a fixed order into a [waves, I, 16] slab in temp (bds_node_pose_bwd_temp_bytes(N, I) bytes,
+ * 16-byte aligned) and summed per instance in a fixed order: the result is deterministic, no float atomics. */
+size_t bds_node_pose_bwd_temp_bytes(int64_t N, int I);
+int bds_node_pose_fwd(int64_t N, int F, int I, int cur_frame, int interpolate, const float *means, const float *quats, const float *logits,
+                      const int64_t *point_ids, const float *instances_quats, const float *instances_trans, const uint8_t *instances_fv,
+                      float *world_means, float *world_quats, float *opacities, uint32_t *bad_ids, bds_stream_t stream);
+int bds_node_pose_bwd(int64_t N, int F, int I, int cur_frame, const float *means, const float *quats, const float *logits,
+                      const int64_t *point_ids, const float *instances_quats, const uint8_t *instances_fv, const float *v_world_means,
+                      const float *v_world_quats, const float *v_opacities, float *v_means, float *v_quats, float *v_logits,
+                      float *v_instances_quats, float *v_instances_trans, void *temp, size_t temp_bytes, bds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
