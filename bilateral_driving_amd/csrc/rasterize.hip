@@ -50,7 +50,7 @@ __device__ __forceinline__ int wave_max_i32(int v) {
 //   binned (tag 0): [0 | count[8][32] | list[8][32][total / 8 + 1]] -- device-count form: every compositing wave of the FORWARD drops
 //                   its tile into the bin of its visited length (32 bins a factor 2^(1/4) apart, longest first) of its XCD's range
 //                   with one atomic; the backward's workgroup resolves (range, slot) -> bin by a prefix walk over the 32 counts.  No sort launch
-//                   between the passes; the header is cleared by the record pack in front of the forward (bds_splat_pack*_dev).
+//                   between the passes; the header is cleared by the record pack in front of the forward (bds_splat_pack / bds_splat_pack_sh).
 constexpr int kSchedXcd = 8, kSchedLogBins = 32, kSchedHeader = 1 + kSchedXcd * kSchedLogBins;
 __host__ __device__ __forceinline__ int sched_stride(int total) { return total / kSchedXcd + 1; }
 __device__ __forceinline__ int sched_bin(int w) {   // 0 = longest ... kSchedLogBins - 1 = nothing to do
@@ -319,7 +319,7 @@ __device__ __forceinline__ void rasterize_fwd_wave_body(
     const ListGeom &lg, int32_t *__restrict__ tile_work, float4 *sA, float4 *sB, float4 *sC, int item_in = -1, int ov_start = -1,
     int ov_end = -1) {
   // (ov_start / ov_end: the tile's list is [ov_start, ov_end) of `flatten` instead of its list tile's -- a long tile's REFINED list)
-  const int64_t M = M_dev ? (int64_t)*M_dev : M_host;   // (the list length may live on the device: bds_rasterize_fwd_dev)
+  const int64_t M = M_dev ? (int64_t)*M_dev : M_host;   // (the list length may live on the device: M_dev of bds_rasterize_fwd)
   const int n_tiles = tile_w * tile_h;
   const int item = item_in >= 0 ? item_in : xcd_contiguous(bid, C * n_tiles);
   const int cam = item / n_tiles, tile = item - cam * n_tiles;
@@ -980,9 +980,9 @@ __global__ __launch_bounds__(kSchedThreads) void tile_order_kernel(int total, co
 
 using namespace bds;
 
-static int splat_pack_impl(int64_t n, const uint64_t *n_dev, int CH, const int32_t *ids, const float *means2d, const float *conics,
-                           const float *colors, const float *opacities, const int32_t *radii, float *records, float *zero_records,
-                           float *zero_tail, int64_t zero_tail_floats, int32_t *schedule, bds_stream_t stream) {
+extern "C" int bds_splat_pack(int64_t n, const uint64_t *n_dev, int CH, const int32_t *ids, const float *means2d, const float *conics,
+                              const float *colors, const float *opacities, const int32_t *radii, float *records, float *zero_records,
+                              float *zero_tail, int64_t zero_tail_floats, int32_t *schedule, bds_stream_t stream) {
   BDS_REQUIRE(n >= 0 && (CH == 1 || CH == 3 || CH == 4));
   BDS_REQUIRE(zero_tail_floats >= 0 && zero_tail_floats % 4 == 0 && zero_tail_floats < ((int64_t)1 << 24));
   BDS_REQUIRE(!zero_records || aligned16(zero_records));
@@ -1142,25 +1142,12 @@ extern "C" int bds_expected_depth_split_bwd(int64_t P, int expected_depth, const
   return BDS_OK;
 }
 
-extern "C" int bds_splat_pack(int64_t n, int CH, const int32_t *ids, const float *means2d, const float *conics, const float *colors,
-                              const float *opacities, const int32_t *radii, float *records, bds_stream_t stream) {
-  return splat_pack_impl(n, nullptr, CH, ids, means2d, conics, colors, opacities, radii, records, nullptr, nullptr, 0, nullptr, stream);
-}
-
-extern "C" int bds_splat_pack_dev(int64_t n_capacity, const uint64_t *n_dev, int CH, const int32_t *ids, const float *means2d,
-                                  const float *conics, const float *colors, const float *opacities, const int32_t *radii,
-                                  float *records, float *zero_records, float *zero_tail, int64_t zero_tail_floats,
-                                  int32_t *schedule, bds_stream_t stream) {
-  BDS_REQUIRE(n_dev);
-  return splat_pack_impl(n_capacity, n_dev, CH, ids, means2d, conics, colors, opacities, radii, records, zero_records, zero_tail,
-                         zero_tail_floats, schedule, stream);
-}
-
-static int splat_pack_sh_impl(int64_t n, const uint64_t *n_dev, const int32_t *ids, int K, int deg, const float *means,
-                              const float *cam_pos, const float *coeffs, const float *means2d, const float *conics, const float *depths,
-                              const float *opacities, const int32_t *radii, float *records, float *sh_rgb, float *zero_records,
-                              float *zero_tail, int64_t zero_tail_floats, int32_t *schedule, bds_stream_t stream,
-                              const float *coeffs_rest = nullptr) {
+// coeffs_rest != NULL: the split storage (coeffs = band 0 [N,3], coeffs_rest = bands 1.. [N,K-1,3])
+extern "C" int bds_splat_pack_sh(int64_t n, const uint64_t *n_dev, const int32_t *ids, int K, int deg, const float *means,
+                                 const float *cam_pos, const float *coeffs, const float *coeffs_rest, const float *means2d,
+                                 const float *conics, const float *depths, const float *opacities, const int32_t *radii, float *records,
+                                 float *sh_rgb, float *zero_records, float *zero_tail, int64_t zero_tail_floats, int32_t *schedule,
+                                 bds_stream_t stream) {
   BDS_REQUIRE(n >= 0 && deg >= 0 && deg <= 3 && K >= (deg + 1) * (deg + 1) && K <= 16);
   BDS_REQUIRE(zero_tail_floats >= 0 && zero_tail_floats % 4 == 0 && zero_tail_floats < ((int64_t)1 << 24));
   BDS_REQUIRE((!zero_records || aligned16(zero_records)) && (!zero_tail || aligned16(zero_tail)));
@@ -1194,33 +1181,6 @@ static int splat_pack_sh_impl(int64_t n, const uint64_t *n_dev, const int32_t *i
   return BDS_OK;
 }
 
-extern "C" int bds_splat_pack_sh(int64_t n, const int32_t *ids, int K, int deg, const float *means, const float *cam_pos,
-                                 const float *coeffs, const float *means2d, const float *conics, const float *depths,
-                                 const float *opacities, const int32_t *radii, float *records, float *sh_rgb, bds_stream_t stream) {
-  return splat_pack_sh_impl(n, nullptr, ids, K, deg, means, cam_pos, coeffs, means2d, conics, depths, opacities, radii, records, sh_rgb,
-                            nullptr, nullptr, 0, nullptr, stream);
-}
-
-extern "C" int bds_splat_pack_sh_split(int64_t n, const int32_t *ids, int K, int deg, const float *means, const float *cam_pos,
-                                       const float *coeffs_dc, const float *coeffs_rest, const float *means2d, const float *conics,
-                                       const float *depths, const float *opacities, const int32_t *radii, float *records, float *sh_rgb,
-                                       bds_stream_t stream) {
-  BDS_REQUIRE(n == 0 || (coeffs_dc && (coeffs_rest || K == 1)));
-  if (K == 1) coeffs_rest = coeffs_dc;   // band 0 only (never read: degree 0 takes three floats of coeffs_dc per row)
-  return splat_pack_sh_impl(n, nullptr, ids, K, deg, means, cam_pos, coeffs_dc, means2d, conics, depths, opacities, radii, records, sh_rgb,
-                            nullptr, nullptr, 0, nullptr, stream, coeffs_rest);
-}
-
-extern "C" int bds_splat_pack_sh_dev(int64_t n_capacity, const uint64_t *n_dev, const int32_t *ids, int K, int deg, const float *means,
-                                     const float *cam_pos, const float *coeffs, const float *means2d, const float *conics,
-                                     const float *depths, const float *opacities, const int32_t *radii, float *records, float *sh_rgb,
-                                     float *zero_records, float *zero_tail, int64_t zero_tail_floats, int32_t *schedule,
-                                     bds_stream_t stream) {
-  BDS_REQUIRE(n_dev);
-  return splat_pack_sh_impl(n_capacity, n_dev, ids, K, deg, means, cam_pos, coeffs, means2d, conics, depths, opacities, radii, records,
-                            sh_rgb, zero_records, zero_tail, zero_tail_floats, schedule, stream);
-}
-
 // list geometry of a launch: list tiles of list_tile_size px (a multiple of the 16-px compositing tile)
 static bool list_geom(int C, int W, int H, int list_tile_size, ListGeom &lg) {
   if (list_tile_size < kTile || list_tile_size % kTile) return false;
@@ -1232,11 +1192,17 @@ static bool list_geom(int C, int W, int H, int list_tile_size, ListGeom &lg) {
   return true;
 }
 
-static int rasterize_fwd_impl(int C, int64_t n_records, int64_t M, const uint64_t *M_dev, int CH, const float *records,
-                              const float *backgrounds, int W, int H, int tile_size, int list_tile_size, int tile_w, int tile_h,
-                              const int32_t *isect_offsets, const int32_t *flatten, float *render, float *alphas, float *t_final,
-                              int32_t *last_ids, bds_stream_t stream, int32_t *tile_work = nullptr, bool binned = false,
-                              int split_len = 0, int split_cap = 0, int64_t split_pool = 0) {
+extern "C" int bds_rasterize_fwd(int C, int64_t n_records, int64_t M, const uint64_t *M_dev, int CH, const float *records,
+                                 const float *backgrounds, int W, int H, int tile_size, int list_tile_size, int tile_w, int tile_h,
+                                 const int32_t *isect_offsets, const int32_t *flatten, float *render, float *alphas, float *t_final,
+                                 int32_t *last_ids, int32_t *tile_order, int split_len, int split_cap, int64_t split_pool,
+                                 bds_stream_t stream) {
+  // (the host-count form never writes a schedule: the lists it serves are scheduled by bds_rasterize_bwd_schedule)
+  BDS_REQUIRE(M_dev ? (M > 0 && split_len >= 0 && split_cap >= 0 && split_pool >= 0) : (!tile_order && split_len == 0));
+  // tile_order (optional, bds_rasterize_schedule_ints words): the compositing waves leave the backward's schedule themselves --
+  // binned form (option 8, default; header cleared by the record pack in front), or their tiles' keys for bds_rasterize_bwd_schedule_sort
+  const bool binned = M_dev && option_get(kOptSchedBins) != 0;
+  int32_t *tile_work = !tile_order ? nullptr : (binned ? tile_order : tile_order + 1 + (int64_t)C * tile_w * tile_h);
   BDS_REQUIRE(C >= 1 && n_records >= 0 && M >= 0 && W > 0 && H > 0);
   BDS_REQUIRE(tile_size == kTile);
   ListGeom lg;
@@ -1283,29 +1249,6 @@ static int rasterize_fwd_impl(int C, int64_t n_records, int64_t M, const uint64_
   return BDS_OK;
 }
 
-extern "C" int bds_rasterize_fwd(int C, int64_t n_records, int64_t M, int CH, const float *records, const float *backgrounds,
-                                 int W, int H, int tile_size, int list_tile_size, int tile_w, int tile_h,
-                                 const int32_t *isect_offsets, const int32_t *flatten, float *render, float *alphas, float *t_final,
-                                 int32_t *last_ids, bds_stream_t stream) {
-  return rasterize_fwd_impl(C, n_records, M, nullptr, CH, records, backgrounds, W, H, tile_size, list_tile_size, tile_w, tile_h,
-                            isect_offsets, flatten, render, alphas, t_final, last_ids, stream);
-}
-
-extern "C" int bds_rasterize_fwd_dev(int C, int64_t n_records, int64_t M_capacity, const uint64_t *M_dev, int CH, const float *records,
-                                     const float *backgrounds, int W, int H, int tile_size, int list_tile_size, int tile_w,
-                                     int tile_h, const int32_t *isect_offsets, const int32_t *flatten, float *render, float *alphas,
-                                     float *t_final, int32_t *last_ids, int32_t *tile_order, int split_len, int split_cap, int64_t split_pool,
-                                     bds_stream_t stream) {
-  BDS_REQUIRE(M_dev && M_capacity > 0 && split_len >= 0 && split_cap >= 0 && split_pool >= 0);
-  // tile_order (optional, bds_rasterize_schedule_ints words): the compositing waves leave the backward's schedule themselves --
-  // binned form (option 8, default; header cleared by the record pack in front), or their tiles' keys for bds_rasterize_bwd_schedule_sort
-  const bool binned = option_get(kOptSchedBins) != 0;
-  return rasterize_fwd_impl(C, n_records, M_capacity, M_dev, CH, records, backgrounds, W, H, tile_size, list_tile_size, tile_w, tile_h,
-                            isect_offsets, flatten, render, alphas, t_final, last_ids, stream,
-                            !tile_order ? nullptr : (binned ? tile_order : tile_order + 1 + (int64_t)C * tile_w * tile_h), binned, split_len,
-                            split_cap, split_pool);
-}
-
 extern "C" int64_t bds_rasterize_split_pool_ints(int C, int tile_w, int tile_h, int split_cap, int64_t split_pool, int64_t M_capacity) {
   if (C < 1 || tile_w < 1 || tile_h < 1 || split_cap < 0 || split_pool < 0 || M_capacity < 0) return 0;
   const int64_t total = (int64_t)C * tile_w * tile_h, cap = split_cap < total ? split_cap : total;
@@ -1321,7 +1264,7 @@ extern "C" int64_t bds_rasterize_schedule_ints(int C, int tile_w, int tile_h) {
 
 extern "C" int bds_rasterize_bwd_schedule_sort(int C, int tile_w, int tile_h, int32_t *tile_order, bds_stream_t stream) {
   BDS_REQUIRE(C >= 1 && tile_w > 0 && tile_h > 0 && tile_order);
-  if (option_get(kOptSchedBins) != 0) return BDS_OK;   // (binned form: bds_rasterize_fwd_dev left the finished schedule)
+  if (option_get(kOptSchedBins) != 0) return BDS_OK;   // (binned form: bds_rasterize_fwd left the finished schedule)
   const int total = C * tile_w * tile_h;
   hipLaunchKernelGGL(tile_order_kernel, dim3(8), dim3(kSchedThreads), 0, as_stream(stream), total, tile_order + 1 + total, tile_order + 1,
                      tile_order);
@@ -1333,8 +1276,8 @@ static int rasterize_bwd_impl(int C, int64_t n_records, int64_t M, const uint64_
                               const float *backgrounds, int W, int H, int tile_size, int list_tile_size, int tile_w, int tile_h,
                               const int32_t *isect_offsets, const int32_t *flatten, const float *alphas, const float *t_final,
                               const int32_t *last_ids, const float *v_render, const float *v_alphas, float *v_records, int absgrad,
-                              const int32_t *tile_order, bds_stream_t stream, const EdEpilogue *epi = nullptr, int split_len = 0,
-                              int split_cap = 0, int64_t split_pool = 0) {
+                              const int32_t *tile_order, int split_len, int split_cap, int64_t split_pool, bds_stream_t stream,
+                              const EdEpilogue *epi) {
   BDS_REQUIRE(C >= 1 && n_records >= 0 && M >= 0 && W > 0 && H > 0);
   BDS_REQUIRE(tile_size == kTile);
   ListGeom lg;
@@ -1394,25 +1337,16 @@ static int rasterize_bwd_impl(int C, int64_t n_records, int64_t M, const uint64_
   return BDS_OK;
 }
 
-extern "C" int bds_rasterize_bwd(int C, int64_t n_records, int64_t M, int CH, const float *records, const float *backgrounds,
-                                 int W, int H, int tile_size, int list_tile_size, int tile_w, int tile_h,
+extern "C" int bds_rasterize_bwd(int C, int64_t n_records, int64_t M, const uint64_t *M_dev, int CH, const float *records,
+                                 const float *backgrounds, int W, int H, int tile_size, int list_tile_size, int tile_w, int tile_h,
                                  const int32_t *isect_offsets, const int32_t *flatten, const float *alphas, const float *t_final,
                                  const int32_t *last_ids, const float *v_render, const float *v_alphas, float *v_records, int absgrad,
-                                 const int32_t *tile_order, bds_stream_t stream) {
-  return rasterize_bwd_impl(C, n_records, M, nullptr, CH, records, backgrounds, W, H, tile_size, list_tile_size, tile_w, tile_h,
-                            isect_offsets, flatten, alphas, t_final, last_ids, v_render, v_alphas, v_records, absgrad, tile_order, stream);
-}
-
-extern "C" int bds_rasterize_bwd_dev(int C, int64_t n_records, int64_t M_capacity, const uint64_t *M_dev, int CH, const float *records,
-                                     const float *backgrounds, int W, int H, int tile_size, int list_tile_size, int tile_w,
-                                     int tile_h, const int32_t *isect_offsets, const int32_t *flatten, const float *alphas,
-                                     const float *t_final, const int32_t *last_ids, const float *v_render, const float *v_alphas, float *v_records,
-                                     int absgrad, const int32_t *tile_order, int split_len, int split_cap, int64_t split_pool,
-                                     bds_stream_t stream) {
-  BDS_REQUIRE(M_dev && M_capacity > 0 && split_len >= 0 && split_cap >= 0 && split_pool >= 0 && split_pool < ((int64_t)1 << 31));
-  return rasterize_bwd_impl(C, n_records, M_capacity, M_dev, CH, records, backgrounds, W, H, tile_size, list_tile_size, tile_w, tile_h,
-                            isect_offsets, flatten, alphas, t_final, last_ids, v_render, v_alphas, v_records, absgrad, tile_order, stream, nullptr,
-                            split_len, split_cap, split_pool);
+                                 const int32_t *tile_order, int split_len, int split_cap, int64_t split_pool, bds_stream_t stream) {
+  // (the long-tile list of a split launch is left by the device-count forward: the host-count form has none)
+  BDS_REQUIRE(M_dev ? (M > 0 && split_len >= 0 && split_cap >= 0 && split_pool >= 0 && split_pool < ((int64_t)1 << 31)) : split_len == 0);
+  return rasterize_bwd_impl(C, n_records, M, M_dev, CH, records, backgrounds, W, H, tile_size, list_tile_size, tile_w, tile_h, isect_offsets,
+                            flatten, alphas, t_final, last_ids, v_render, v_alphas, v_records, absgrad, tile_order, split_len, split_cap,
+                            split_pool, stream, nullptr);
 }
 
 extern "C" int bds_rasterize_bwd_ms(int64_t n_records, int64_t M_capacity, const uint64_t *M_dev, const float *records, int W, int H,
@@ -1427,7 +1361,7 @@ extern "C" int bds_rasterize_bwd_ms(int64_t n_records, int64_t M_capacity, const
   if (rc != BDS_OK) return rc;
   e.v_direct = v_direct; e.render = render; e.sky = sky; e.v_depth = v_depth; e.v_alpha_in = v_alpha_in; e.v_sky = v_sky;
   return rasterize_bwd_impl(1, n_records, M_capacity, M_dev, 4, records, nullptr, W, H, tile_size, list_tile_size, tile_w, tile_h,
-                            isect_offsets, flatten, alphas, t_final, last_ids, nullptr, nullptr, v_records, absgrad, tile_order, stream, &e);
+                            isect_offsets, flatten, alphas, t_final, last_ids, nullptr, nullptr, v_records, absgrad, tile_order, 0, 0, 0, stream, &e);
 }
 
 extern "C" int bds_rasterize_bwd_schedule(int C, int W, int H, int tile_size, int list_tile_size, int tile_w, int tile_h,

@@ -573,12 +573,15 @@ static void launch_view_bwd_list(bool vec, bool acc, int grid, size_t lds, hipSt
 #undef BDS_LIST
 }
 
-static int sh_view_bwd_list_impl(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, int K, int deg, const float *means,
-                                 const float *cam_pos, const float *sh_rgb, int sh_rgb_by_rank, const float *v_records, float *v_coeffs,
-                                 const int32_t *row_map, int accumulate, bds_stream_t stream, float *v_rest = nullptr) {
+// v_coeffs_rest != NULL: the split storage (v_coeffs = band 0 [N,3], v_coeffs_rest = bands 1.. [N,K-1,3]; ignored for K = 1)
+extern "C" int bds_sh_view_bwd_list(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, int K, int deg, const float *means,
+                                    const float *cam_pos, const float *sh_rgb, int sh_rgb_by_rank, const float *v_records, float *v_coeffs,
+                                    float *v_coeffs_rest, const int32_t *row_map, int accumulate, bds_stream_t stream) {
   BDS_REQUIRE(n_list >= 0 && deg >= 0 && deg <= 3 && K >= (deg + 1) * (deg + 1) && K <= 16);
+  BDS_REQUIRE(!(v_coeffs_rest && row_map));   // (the split storage holds dense parameter gradients: no exchange-buffer rows)
   if (n_list == 0) return BDS_OK;
   BDS_REQUIRE(ids && means && cam_pos && sh_rgb && v_records && v_coeffs && aligned16(v_records));
+  float *v_rest = K == 1 ? nullptr : v_coeffs_rest;
   const int grid = (int)cdiv(n_list, kShBlock);
   const size_t lds = (size_t)kShBlock * (K * 3 + 1) * sizeof(float);
   const bool vec = ((K * 3) % 4 == 0) && aligned16(v_coeffs) && v_rest == nullptr;
@@ -594,32 +597,9 @@ static int sh_view_bwd_list_impl(int64_t n_list, const uint64_t *n_dev, const in
   return BDS_OK;
 }
 
-extern "C" int bds_sh_view_bwd_list(int64_t n_list, const int32_t *ids, int K, int deg, const float *means, const float *cam_pos,
-                                    const float *sh_rgb, int sh_rgb_by_rank, const float *v_records, float *v_coeffs,
-                                    const int32_t *row_map, int accumulate, bds_stream_t stream) {
-  return sh_view_bwd_list_impl(n_list, nullptr, ids, K, deg, means, cam_pos, sh_rgb, sh_rgb_by_rank, v_records, v_coeffs, row_map,
-                               accumulate, stream);
-}
-
-extern "C" int bds_sh_view_bwd_list_split(int64_t n_list, const int32_t *ids, int K, int deg, const float *means, const float *cam_pos,
-                                          const float *sh_rgb, int sh_rgb_by_rank, const float *v_records, float *v_coeffs_dc,
-                                          float *v_coeffs_rest, int accumulate, bds_stream_t stream) {
-  BDS_REQUIRE(n_list == 0 || (v_coeffs_dc && (v_coeffs_rest || K == 1)));
-  return sh_view_bwd_list_impl(n_list, nullptr, ids, K, deg, means, cam_pos, sh_rgb, sh_rgb_by_rank, v_records, v_coeffs_dc, nullptr,
-                               accumulate, stream, K == 1 ? nullptr : v_coeffs_rest);
-}
-
-extern "C" int bds_sh_view_bwd_list_dev(int64_t n_capacity, const uint64_t *n_dev, const int32_t *ids, int K, int deg, const float *means,
-                                        const float *cam_pos, const float *sh_rgb, int sh_rgb_by_rank, const float *v_records,
-                                        float *v_coeffs, const int32_t *row_map, int accumulate, bds_stream_t stream) {
-  BDS_REQUIRE(n_dev);
-  return sh_view_bwd_list_impl(n_capacity, n_dev, ids, K, deg, means, cam_pos, sh_rgb, sh_rgb_by_rank, v_records, v_coeffs, row_map,
-                               accumulate, stream);
-}
-
-static int view_grads_clear_list_impl(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, int K, float *v_means, float *v_quats,
-                                      float *v_log_scales, float *v_logits, float *v_sh, bds_stream_t stream, float *grad2d = nullptr,
-                                      float *absgrad2d = nullptr) {
+extern "C" int bds_view_grads_clear_list(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, int K, float *v_means, float *v_quats,
+                                         float *v_log_scales, float *v_logits, float *v_sh, float *grad2d, float *absgrad2d,
+                                         bds_stream_t stream) {
   BDS_REQUIRE(n_list >= 0 && K >= 1 && K <= 16);
   if (n_list == 0) return BDS_OK;
   const bool params = v_means || v_quats || v_log_scales || v_logits || v_sh;    // all five, or none (then the screen-space arrays only)
@@ -637,18 +617,6 @@ static int view_grads_clear_list_impl(int64_t n_list, const uint64_t *n_dev, con
                        v_log_scales, v_logits, v_sh, g2, a2, gl);
   BDS_LAUNCH_CHECK();
   return BDS_OK;
-}
-
-extern "C" int bds_view_grads_clear_list(int64_t n_list, const int32_t *ids, int K, float *v_means, float *v_quats,
-                                         float *v_log_scales, float *v_logits, float *v_sh, bds_stream_t stream) {
-  return view_grads_clear_list_impl(n_list, nullptr, ids, K, v_means, v_quats, v_log_scales, v_logits, v_sh, stream);
-}
-
-extern "C" int bds_view_grads_clear_list_dev(int64_t n_capacity, const uint64_t *n_dev, const int32_t *ids, int K, float *v_means,
-                                             float *v_quats, float *v_log_scales, float *v_logits, float *v_sh, float *grad2d,
-                                             float *absgrad2d, bds_stream_t stream) {
-  BDS_REQUIRE(n_dev);
-  return view_grads_clear_list_impl(n_capacity, n_dev, ids, K, v_means, v_quats, v_log_scales, v_logits, v_sh, stream, grad2d, absgrad2d);
 }
 
 extern "C" int bds_view_grads_add_list(int64_t n_list, const int32_t *ids, int K, const float *s_means, const float *s_quats,

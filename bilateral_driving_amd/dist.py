@@ -137,8 +137,8 @@ class FlatGradients:
             #  addresses, csrc/bds_common.h GradLayout -- so their base addresses go in as they are)
             addr = (lambda t: t.data_ptr()) if self.row_block else L.ptr
             for ids in self._dirty:
-                L.check(L.lib().bds_view_grads_clear_list(ids.numel(), L.ptr(ids.contiguous()), K, addr(row["means"]), addr(row["quats"]),
-                                                          addr(row["log_scales"]), addr(row["opacity_logits"]), L.ptr(row["sh"]),
+                L.check(L.lib().bds_view_grads_clear_list(ids.numel(), None, L.ptr(ids.contiguous()), K, addr(row["means"]), addr(row["quats"]),
+                                                          addr(row["log_scales"]), addr(row["opacity_logits"]), L.ptr(row["sh"]), None, None,
                                                           L.stream()), "bds_view_grads_clear_list")
             # the other slices are dense: pack() / autograd overwrite (or zero) them before they are read
         elif self._dirty is not None and not flat.is_cuda:   # CPU tensors (the gloo tests of the exchange logic): same effect

@@ -388,56 +388,33 @@ def _composite(f: _Front, opac: Tensor, images=None, zero_grad_records: Optional
     n_vis, M, W, H = f.n_vis, f.M, f.W, f.H
     if opac is f.opac:          # (the view's own opacities: read from the rows; a masked copy -- render_classes -- is a dense array)
         opac = f.opac_row
-    if f.m_dev is not None:
-        if f.rec_buf is not None:
-            rec, f.rec_buf = f.rec_buf[:n_vis], None
-        else:
-            rec = _empty((n_vis, L.SPLAT_RECORD_FLOATS), dev)
-        render, alphas, last_ids = images if images is not None else _image_buffers(W, H, dev)
-        zr = zero_grad_records
-        tail = zero_tail if zero_tail is not None else (None if zr is None or zr.shape[0] <= n_vis else zr[n_vis:])
-        with L.timed("rasterize_fwd"):
-            if f.colors is None:   # SH colours evaluated by the pack (visible Gaussians only); un-clamped values kept in list order
-                f.sh_rgb, f.sh_by_rank = _empty((max(n_vis, 1), 3), dev), True
-                if f.cfg.get("row_catchup") is not None:
-                    # a row-lazy optimizer (optim.DeferredRowAdam) brings the coefficient rows of THIS view's visible Gaussians up to
-                    # its current step before the pack reads them: (capacity, device count, device id list)
-                    f.cfg["row_catchup"](n_vis, f.nvis_dev, L.ptr(f.vis_ids))
-                L.check(lib.bds_splat_pack_sh_dev(n_vis, f.nvis_dev, L.ptr(f.vis_ids), f.sh.shape[1], f.sh_degree, L.ptr(f.means),
-                                                  L.ptr(f.cam_pos), L.ptr(f.sh), _dp(f.means2d), _dp(f.conics), _dp(f.depths),
-                                                  _dp(opac), L.ptr(f.radii), L.ptr(rec), L.ptr(f.sh_rgb), L.ptr(zr), L.ptr(tail),
-                                                  0 if tail is None else tail.numel(), L.ptr(tile_order), st), "bds_splat_pack_sh_dev")
-            else:
-                L.check(lib.bds_splat_pack_dev(n_vis, f.nvis_dev, 4, L.ptr(f.vis_ids), L.ptr(f.means2d), L.ptr(f.conics), L.ptr(f.colors),
-                                               L.ptr(opac), L.ptr(f.radii), L.ptr(rec), L.ptr(zr), L.ptr(tail),
-                                               0 if tail is None else tail.numel(), L.ptr(tile_order), st), "bds_splat_pack_dev")
-            # (tile_order: the backward's schedule is left by the compositing waves themselves; its header was cleared by the pack)
-            L.check(lib.bds_rasterize_fwd_dev(1, n_vis, M, f.m_dev, 4, L.ptr(rec), None, W, H, TILE, f.list_tile, f.tw, f.th,
-                                              L.ptr(f.isect_offsets), L.ptr(f.flatten), L.ptr(render), L.ptr(alphas), _tfinal_ptr(alphas),
-                                              L.ptr(last_ids), L.ptr(tile_order), *_split(f.cfg, f.list_tile, f.tw * f.th, tile_order is not None), st),
-                    "bds_rasterize_fwd_dev")
-        return rec, render, alphas, last_ids
     if f.rec_buf is not None:      # provisioned before the wait (first composite over this front only)
         rec, f.rec_buf = f.rec_buf[:n_vis], None
     else:
         rec = _empty((n_vis, L.SPLAT_RECORD_FLOATS), dev)
     render, alphas, last_ids = images if images is not None else _image_buffers(W, H, dev)
+    # f.nvis_dev / f.m_dev: None in the host-count form, whose callers pass no clearing arguments and no schedule buffer
+    zr = zero_grad_records
+    tail = zero_tail if zero_tail is not None else (None if zr is None or zr.shape[0] <= n_vis else zr[n_vis:])
+    clear = (L.ptr(zr), L.ptr(tail), 0 if tail is None else tail.numel(), L.ptr(tile_order))
     with L.timed("rasterize_fwd"):
-        if f.colors is None:       # SH colours evaluated on the way; their un-clamped values stay in list order for the backward
+        if f.colors is None:   # SH colours evaluated by the pack (visible Gaussians only); un-clamped values kept in list order
             f.sh_rgb, f.sh_by_rank = _empty((max(n_vis, 1), 3), dev), True
-            if f.sh_rest is not None:
-                L.check(lib.bds_splat_pack_sh_split(n_vis, L.ptr(f.vis_ids), f.K, f.sh_degree, L.ptr(f.means), L.ptr(f.cam_pos), L.ptr(f.sh),
-                                                    L.ptr(f.sh_rest), _dp(f.means2d), _dp(f.conics), _dp(f.depths), _dp(opac),
-                                                    L.ptr(f.radii), L.ptr(rec), L.ptr(f.sh_rgb), st), "bds_splat_pack_sh_split")
-            else:
-                L.check(lib.bds_splat_pack_sh(n_vis, L.ptr(f.vis_ids), f.sh.shape[1], f.sh_degree, L.ptr(f.means), L.ptr(f.cam_pos),
-                                              L.ptr(f.sh), _dp(f.means2d), _dp(f.conics), _dp(f.depths), _dp(opac), L.ptr(f.radii),
-                                              L.ptr(rec), L.ptr(f.sh_rgb), st), "bds_splat_pack_sh")
+            if f.m_dev is not None and f.cfg.get("row_catchup") is not None:
+                # a row-lazy optimizer (optim.DeferredRowAdam) brings the coefficient rows of THIS view's visible Gaussians up to
+                # its current step before the pack reads them: (capacity, device count, device id list)
+                f.cfg["row_catchup"](n_vis, f.nvis_dev, L.ptr(f.vis_ids))
+            L.check(lib.bds_splat_pack_sh(n_vis, f.nvis_dev, L.ptr(f.vis_ids), f.K, f.sh_degree, L.ptr(f.means), L.ptr(f.cam_pos),
+                                          L.ptr(f.sh), L.ptr(f.sh_rest), _dp(f.means2d), _dp(f.conics), _dp(f.depths), _dp(opac),
+                                          L.ptr(f.radii), L.ptr(rec), L.ptr(f.sh_rgb), *clear, st), "bds_splat_pack_sh")
         else:
-            L.check(lib.bds_splat_pack(n_vis, 4, L.ptr(f.vis_ids), L.ptr(f.means2d), L.ptr(f.conics), L.ptr(f.colors), L.ptr(opac),
-                                       L.ptr(f.radii), L.ptr(rec), st), "bds_splat_pack")
-        L.check(lib.bds_rasterize_fwd(1, n_vis, M, 4, L.ptr(rec), None, W, H, TILE, f.list_tile, f.tw, f.th, L.ptr(f.isect_offsets), L.ptr(f.flatten),
-                                      L.ptr(render), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), st), "bds_rasterize_fwd")
+            L.check(lib.bds_splat_pack(n_vis, f.nvis_dev, 4, L.ptr(f.vis_ids), L.ptr(f.means2d), L.ptr(f.conics), L.ptr(f.colors),
+                                       L.ptr(opac), L.ptr(f.radii), L.ptr(rec), *clear, st), "bds_splat_pack")
+        # (tile_order: the backward's schedule is left by the compositing waves themselves; its header was cleared by the pack)
+        L.check(lib.bds_rasterize_fwd(1, n_vis, M, f.m_dev, 4, L.ptr(rec), None, W, H, TILE, f.list_tile, f.tw, f.th,
+                                      L.ptr(f.isect_offsets), L.ptr(f.flatten), L.ptr(render), L.ptr(alphas), _tfinal_ptr(alphas),
+                                      L.ptr(last_ids), L.ptr(tile_order), *_split(f.cfg, f.list_tile, f.tw * f.th, tile_order is not None), st),
+                "bds_rasterize_fwd")
     return rec, render, alphas, last_ids
 
 
@@ -634,7 +611,7 @@ class _FusedView(torch.autograd.Function):
         # The transform's backward leaves its last stage -- guidance route, clamp / sky blend / expected-depth backward: a per-pixel
         # function -- to the compositor's backward wherever the configuration allows it (include/bds.h bds_rasterize_bwd_ms): v_render
         # then holds the direct-route gradient only, v_alphas is not touched, and one launch over the image is gone.
-        # (a split launch -- long tiles strip by strip -- keeps those tiles out of the schedule: only bds_rasterize_bwd_dev finds them)
+        # (a split launch -- long tiles strip by strip -- keeps those tiles out of the schedule: only bds_rasterize_bwd finds them)
         split = _split(cfg, ctx.list_tile, tw * th, getattr(ctx, "split_ok", False)) if getattr(ctx, "dev_counts", None) is not None else (0, 0, 0)
         defer = (_DEFER_EPILOGUE and cfg.get("defer_epilogue", True) and M > 0 and n_vis > 0 and split[0] == 0
                  and bool(lib.bds_bilagrid_ms_ed_bwd_deferrable(len(grids), lv, H, W)))
@@ -668,14 +645,10 @@ class _FusedView(torch.autograd.Function):
                                                  L.ptr(isect_offsets), L.ptr(flatten), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), L.ptr(v_rec), 1,
                                                  L.ptr(order), len(grids), lv, L.ptr(bws), bws.numel(), L.ptr(render), L.ptr(sky),
                                                  L.ptr(v_depth), L.ptr(v_opacity), L.ptr(v_render), L.ptr(v_sky), st), "bds_rasterize_bwd_ms")
-            elif dev_counts is not None:
-                L.check(lib.bds_rasterize_bwd_dev(1, n_vis, M, dev_counts[0], 4, L.ptr(rec), None, W, H, TILE, LT, tw, th, L.ptr(isect_offsets),
-                                                  L.ptr(flatten), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), L.ptr(v_render),
-                                                  L.ptr(v_alphas), L.ptr(v_rec), 1, L.ptr(order), *split, st), "bds_rasterize_bwd_dev")
             else:
-                L.check(lib.bds_rasterize_bwd(1, n_vis, M, 4, L.ptr(rec), None, W, H, TILE, LT, tw, th, L.ptr(isect_offsets), L.ptr(flatten),
-                                              L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), L.ptr(v_render), L.ptr(v_alphas), L.ptr(v_rec), 1,
-                                              L.ptr(order), st), "bds_rasterize_bwd")
+                L.check(lib.bds_rasterize_bwd(1, n_vis, M, None if dev_counts is None else dev_counts[0], 4, L.ptr(rec), None, W, H, TILE, LT,
+                                              tw, th, L.ptr(isect_offsets), L.ptr(flatten), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids),
+                                              L.ptr(v_render), L.ptr(v_alphas), L.ptr(v_rec), 1, L.ptr(order), *split, st), "bds_rasterize_bwd")
         if v_means2d_ext is not None and n_vis:   # a loss term on info["means2d"] itself: add its rows to the records
             v_rec[:n_vis, 7:9] += v_means2d_ext.reshape(N, 2).index_select(0, vis_ids.long())
         yield
@@ -710,15 +683,9 @@ class _FusedView(torch.autograd.Function):
         v_sh = out_like("sh", sh)
         with L.timed("sh_bwd"):
             st = L.stream()
-            if dev_counts is not None:
-                L.check(lib.bds_sh_view_bwd_list_dev(n_vis, dev_counts[1], L.ptr(vis_ids), K, cfg["sh_degree"], L.ptr(means), L.ptr(cam_pos),
-                                                     L.ptr(sh_rgb), int(bool(getattr(ctx, "sh_by_rank", False))), L.ptr(v_rec), L.ptr(v_sh),
-                                                     L.ptr(row_map), int(rows == 2), st),
-                        "bds_sh_view_bwd_list_dev")
-            else:
-                L.check(lib.bds_sh_view_bwd_list(n_vis, L.ptr(vis_ids), K, cfg["sh_degree"], L.ptr(means), L.ptr(cam_pos), L.ptr(sh_rgb),
-                                                 int(bool(getattr(ctx, "sh_by_rank", False))), L.ptr(v_rec), L.ptr(v_sh), L.ptr(row_map),
-                                                 int(rows == 2), st), "bds_sh_view_bwd_list")
+            L.check(lib.bds_sh_view_bwd_list(n_vis, None if dev_counts is None else dev_counts[1], L.ptr(vis_ids), K, cfg["sh_degree"],
+                                             L.ptr(means), L.ptr(cam_pos), L.ptr(sh_rgb), int(bool(getattr(ctx, "sh_by_rank", False))),
+                                             L.ptr(v_rec), L.ptr(v_sh), None, L.ptr(row_map), int(rows == 2), st), "bds_sh_view_bwd_list")
         st = L.stream()
         v_means, v_quats = out_like("means", means), out_like("quats", quats)
         v_ls, v_logits = out_like("log_scales", log_scales), out_like("opacity_logits", opac)

@@ -55,7 +55,7 @@ def split_len_for(info):
     """(split_len, split_cap) for a camera from the lists of a host-count visit ((0, 0) = off): one wave per tile runs as long as the
     tile's list, so a view in which a few list tiles hold several times the entries of a typical busy one (the vanishing point of a
     street full of small splats) waits for those waves; their tiles are then composited by four waves (include/bds.h
-    bds_rasterize_fwd_dev).  Off unless some list reaches ``SPLIT_LIST_LEN`` entries AND four times the mean list: a view of evenly
+    bds_rasterize_fwd).  Off unless some list reaches ``SPLIT_LIST_LEN`` entries AND four times the mean list: a view of evenly
     long lists gains nothing from more workgroups.  Capacity: twice the 16-px tiles of the lists that long now, + 64."""
     if SPLIT_LIST_LEN <= 0:
         return 0, 0

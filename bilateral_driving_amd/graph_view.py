@@ -224,8 +224,8 @@ class FrameGraph(FrameCapacities):
             g2 = self.g2d[v]      # (the view's persistent screen-space gradient arrays: the same rows, no dense fill per view)
             row_clear = self.clear_grads and self._frame_fx is None   # (per-frame exchange: step() clears the flat buffer densely)
             pa = [a[k].data_ptr() if row_clear else None for k in ("means", "quats", "log_scales", "opacity_logits", "sh")]
-            L.check(lib.bds_view_grads_clear_list_dev(self.caps[v].nvis_cap, ws.data_ptr() + self._nvis_off, L.ptr(ids), self.K, *pa,
-                                                      L.ptr(g2[0]), L.ptr(g2[1]), st), "bds_view_grads_clear_list_dev")
+            L.check(lib.bds_view_grads_clear_list(self.caps[v].nvis_cap, ws.data_ptr() + self._nvis_off, L.ptr(ids), self.K, *pa,
+                                                  L.ptr(g2[0]), L.ptr(g2[1]), st), "bds_view_grads_clear_list")
         if self._tail.numel() and tail and self.clear_grads and self._frame_fx is None:
             self._tail.zero_()
 

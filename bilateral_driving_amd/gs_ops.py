@@ -231,11 +231,11 @@ class _RasterizeToPixels(torch.autograd.Function):
         alphas, t_final = a2[0], a2[1]
         last_ids = torch.empty(Cn, height, width, device=dev, dtype=torch.int32)
         with L.timed("rasterize_fwd"):
-            L.check(lib.bds_splat_pack(Cn * N, CH, None, L.ptr(means2d_c), L.ptr(conics), L.ptr(colors), L.ptr(opacities), None, L.ptr(rec), st),
-                    "bds_splat_pack")
-            L.check(lib.bds_rasterize_fwd(Cn, Cn * N, M, CH, L.ptr(rec), L.ptr(backgrounds), width, height, TILE_SIZE, tile_size, tw, th,
-                                          L.ptr(isect_offsets), L.ptr(flatten_ids), L.ptr(render), L.ptr(alphas), L.ptr(t_final), L.ptr(last_ids), st),
-                    "bds_rasterize_fwd")
+            L.check(lib.bds_splat_pack(Cn * N, None, CH, None, L.ptr(means2d_c), L.ptr(conics), L.ptr(colors), L.ptr(opacities), None, L.ptr(rec),
+                                       None, None, 0, None, st), "bds_splat_pack")
+            L.check(lib.bds_rasterize_fwd(Cn, Cn * N, M, None, CH, L.ptr(rec), L.ptr(backgrounds), width, height, TILE_SIZE, tile_size, tw, th,
+                                          L.ptr(isect_offsets), L.ptr(flatten_ids), L.ptr(render), L.ptr(alphas), L.ptr(t_final), L.ptr(last_ids),
+                                          None, 0, 0, 0, st), "bds_rasterize_fwd")
         ctx.save_for_backward(means2d, rec, backgrounds, isect_offsets, flatten_ids, alphas, last_ids, t_final)
         ctx.cfg = (width, height, tile_size, absgrad, CH)
         return render, alphas
@@ -252,9 +252,9 @@ class _RasterizeToPixels(torch.autograd.Function):
         v_rec = torch.zeros(Cn * N, L.GRAD_RECORD_FLOATS, device=rec.device, dtype=torch.float32)
         order = bwd_schedule(Cn, width, height, tile_size, isect_offsets, last_ids)
         with L.timed("rasterize_bwd"):
-            L.check(L.lib().bds_rasterize_bwd(Cn, Cn * N, M, CH, L.ptr(rec), L.ptr(backgrounds), width, height, TILE_SIZE, tile_size, tw, th,
+            L.check(L.lib().bds_rasterize_bwd(Cn, Cn * N, M, None, CH, L.ptr(rec), L.ptr(backgrounds), width, height, TILE_SIZE, tile_size, tw, th,
                                               L.ptr(isect_offsets), L.ptr(flatten_ids), L.ptr(alphas), L.ptr(t_final), L.ptr(last_ids), L.ptr(v_render),
-                                              L.ptr(v_alphas), L.ptr(v_rec), int(bool(absgrad)), L.ptr(order), L.stream()),
+                                              L.ptr(v_alphas), L.ptr(v_rec), int(bool(absgrad)), L.ptr(order), 0, 0, 0, L.stream()),
                     "bds_rasterize_bwd")
         v = v_rec.view(Cn, N, L.GRAD_RECORD_FLOATS)
         v_colors, v_conics, v_means2d, v_opac = v[..., 0:CH], v[..., 4:7], v[..., 7:9], v[..., 11]

@@ -245,8 +245,8 @@ class _RasterizeView(torch.autograd.Function):
         with L.timed("rasterize_fwd"):
             L.check(lib.bds_splat_pack_rgbd(n_vis, L.ptr(vis_ids), L.ptr(means2d), L.ptr(conics), L.ptr(colors3), L.ptr(depths),
                                             L.ptr(opac_c), L.ptr(radii), L.ptr(rec), st), "bds_splat_pack_rgbd")
-            L.check(lib.bds_rasterize_fwd(1, n_vis, M, 4, L.ptr(rec), None, W, H, TILE_SIZE, LT, tw, th, L.ptr(isect_offsets), L.ptr(flatten),
-                                          L.ptr(render), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), st), "bds_rasterize_fwd")
+            L.check(lib.bds_rasterize_fwd(1, n_vis, M, None, 4, L.ptr(rec), None, W, H, TILE_SIZE, LT, tw, th, L.ptr(isect_offsets), L.ptr(flatten),
+                                          L.ptr(render), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), None, 0, 0, 0, st), "bds_rasterize_fwd")
         ctx.save_for_backward(means, quats, scales, opacities, viewmat, Kmat, rec, vis_ids, ws, flatten, isect_offsets, render, alphas, last_ids)
         ctx.cfg, ctx.M = cfg, M
         if cfg["ed"]:      # expected depth: D / clamp(alpha, 1e-10) (gsplat "ED")
@@ -278,8 +278,8 @@ class _RasterizeRawView(torch.autograd.Function):
     """rasterization() for one camera over a class's RAW parameters (``lazy_gaussians``: the reference's unmodified call sequence
     with ``marshalling.install``): what ``_RasterizeView`` does, with sigmoid / exp / quaternion normalisation inside the projection
     kernel (bds_project_view_fwd), the SH colours (+0.5, clamp) evaluated by the record pack for the VISIBLE Gaussians only, straight
-    from the class's two SH parameters (bds_splat_pack_sh_split: no concatenation, no dense SH pass over all N), and the backward
-    list-driven into the raw parameters' gradients (bds_sh_view_bwd_list_split, bds_project_view_bwd_list).  The reference's NaN /
+    from the class's two SH parameters (bds_splat_pack_sh with coeffs_rest: no concatenation, no dense SH pass over all N), and the backward
+    list-driven into the raw parameters' gradients (bds_sh_view_bwd_list with v_coeffs_rest, bds_project_view_bwd_list).  The reference's NaN /
     Inf check (vanilla.py:407-412) is one streaming launch whose flag word arrives with the list counts."""
 
     @staticmethod
@@ -339,9 +339,9 @@ class _RasterizeRawView(torch.autograd.Function):
         outs, v_rec, slots = _view_backward(ctx, saved, v_out, v_depth, v_alphas, v_means2d_ext, want_pose, widths, 0)
         v_means, v_quats, v_ls, v_logits, v_dc, v_rest = outs[:6]
         with L.timed("sh_bwd"):
-            L.check(L.lib().bds_sh_view_bwd_list_split(vis_ids.numel(), L.ptr(vis_ids), K, cfg["sh_degree"], L.ptr(means), L.ptr(cam_pos),
-                                                       L.ptr(sh_rgb), 1, L.ptr(v_rec), L.ptr(v_dc), L.ptr(v_rest), 0, L.stream()),
-                    "bds_sh_view_bwd_list_split")
+            L.check(L.lib().bds_sh_view_bwd_list(vis_ids.numel(), None, L.ptr(vis_ids), K, cfg["sh_degree"], L.ptr(means), L.ptr(cam_pos),
+                                                 L.ptr(sh_rgb), 1, L.ptr(v_rec), L.ptr(v_dc), L.ptr(v_rest), None, 0, L.stream()),
+                    "bds_sh_view_bwd_list")
         g = ctx.needs_input_grad
         return (v_means if g[0] else None, v_quats if g[1] else None, v_ls.view(ls_shape) if g[2] else None,
                 v_logits.view(lg_shape) if g[3] else None, v_dc.view(dc_shape) if g[4] else None, v_rest.view(rest_shape) if g[5] else None,
@@ -374,9 +374,9 @@ def _view_backward(ctx, saved, v_out, v_depth, v_alphas, v_means2d_ext, want_pos
     v_rec = v_rec_all[:max(n_vis, 1)]
     order = bwd_schedule(1, W, H, _LIST_TILE, isect_offsets, last_ids)
     with L.timed("rasterize_bwd"):
-        L.check(lib.bds_rasterize_bwd(1, n_vis, M, 4, L.ptr(rec), None, W, H, TILE_SIZE, _LIST_TILE, tw, th, L.ptr(isect_offsets),
+        L.check(lib.bds_rasterize_bwd(1, n_vis, M, None, 4, L.ptr(rec), None, W, H, TILE_SIZE, _LIST_TILE, tw, th, L.ptr(isect_offsets),
                                       L.ptr(flatten), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), L.ptr(v_render), L.ptr(v_alphas_t),
-                                      L.ptr(v_rec), int(bool(cfg["absgrad"])), L.ptr(order), st), "bds_rasterize_bwd")
+                                      L.ptr(v_rec), int(bool(cfg["absgrad"])), L.ptr(order), 0, 0, 0, st), "bds_rasterize_bwd")
     if v_means2d_ext is not None and n_vis:   # a loss term on meta["means2d"] itself: add its rows to the records
         v_rec[:n_vis, 7:9] += v_means2d_ext.reshape(N, 2).index_select(0, vis_ids.long())
     dense = torch.zeros(N * sum(widths), device=dev)      # ONE zero fill for all dense outputs

@@ -25,8 +25,10 @@
 extern "C" {
 #endif
 
-#define BDS_ABI_VERSION 3   /* 3: the projection's entries folded into four (bds_project_fwd, bds_project_view_fwd and
-                               bds_project_view_bwd_list changed signatures) */
+#define BDS_ABI_VERSION 4   /* 3: the projection's entries folded into four (bds_project_fwd, bds_project_view_fwd and
+                               bds_project_view_bwd_list changed signatures)
+                               4: the view path's host-count / device-count / split-storage twins folded into one entry each
+                               (bds_splat_pack, bds_splat_pack_sh, bds_rasterize_fwd / _bwd, bds_sh_view_bwd_list, bds_view_grads_clear_list) */
 
 #define BDS_OK 0
 #define BDS_EINVAL (-1)      /* null / misaligned pointer, bad shape or unsupported parameter */
@@ -205,26 +207,56 @@ int bds_expected_depth_split_fwd(int64_t P, int expected_depth, const float *ren
                                  bds_stream_t stream);
 int bds_expected_depth_split_bwd(int64_t P, int expected_depth, const float *render4, const float *alphas, const float *v_rgb3,
                                  const float *v_depth1, const float *v_alphas_in, float *v_render4, float *v_alphas, bds_stream_t stream);
-int bds_splat_pack(int64_t n, int CH, const int32_t *ids, const float *means2d, const float *conics, const float *colors,
-                   const float *opacities, const int32_t *radii /* [n entries] or NULL */, float *records, bds_stream_t stream);
+/* n_dev (here and in every entry below that takes one; NULL: n is the count): the device-count form -- the count is read from n_dev
+ * (visible effective, see "device-count forms"), n is then the capacity and sizes the launch.
+ * Optionally clears, on the way, the gradient record of every packed row (zero_records [n, BDS_GRAD_RECORD_FLOATS]: what
+ * bds_rasterize_bwd accumulates into) and a tail of zero_tail_floats (multiple of 4) floats (the camera-pose gradient slots): no fill
+ * launches of their own.  schedule (optional): the schedule buffer the following bds_rasterize_fwd fills in its binned form -- its
+ * header is cleared here too.  (The clearing arguments serve the device-count view; the kernel takes them with a host count as well.) */
+int bds_splat_pack(int64_t n, const uint64_t *n_dev, int CH, const int32_t *ids, const float *means2d, const float *conics,
+                   const float *colors, const float *opacities, const int32_t *radii /* [n entries] or NULL */, float *records,
+                   float *zero_records, float *zero_tail, int64_t zero_tail_floats, int32_t *schedule, bds_stream_t stream);
 /* Splat records of the fused view with the SH colour evaluated on the way (vanilla.py:383-389: SH of normalise(means - cam_pos), + 0.5,
- * clamp to [0,1]; channel 3 = depth): record r = visible Gaussian ids[r]; coeffs [N,K,3] with K*3 a multiple of 4 and 16-byte aligned
- * rows; sh_rgb [n,3] receives the un-clamped colours in list order (for bds_sh_view_bwd_list with sh_rgb_by_rank).  Replaces
- * bds_sh_view_fwd + bds_splat_pack on that path: the colours of the ~85 % culled Gaussians are never evaluated or stored. */
-int bds_splat_pack_sh(int64_t n, const int32_t *ids, int K, int degrees_to_use, const float *means, const float *cam_pos,
-                      const float *coeffs, const float *means2d, const float *conics, const float *depths, const float *opacities,
-                      const int32_t *radii, float *records, float *sh_rgb, bds_stream_t stream);
-/* The same with the coefficients where the reference's Gaussian classes hold them (models/gaussians/vanilla.py:96-104: `_features_dc`
- * [N,3] and `_features_rest` [N,K-1,3], two parameters with their own learning rates; :382 concatenates them on every call --
- * 192 bytes per Gaussian written and read back before anything is culled): band 0 from coeffs_dc, bands 1.. from coeffs_rest
- * (ignored for K = 1), rows of 4-byte alignment, visible rows only. */
-int bds_splat_pack_sh_split(int64_t n, const int32_t *ids, int K, int degrees_to_use, const float *means, const float *cam_pos,
-                            const float *coeffs_dc, const float *coeffs_rest, const float *means2d, const float *conics,
-                            const float *depths, const float *opacities, const int32_t *radii, float *records, float *sh_rgb,
-                            bds_stream_t stream);
-int bds_rasterize_fwd(int C, int64_t n_records, int64_t M, int CH, const float *records, const float *backgrounds, int W, int H,
-                      int tile_size, int list_tile_size, int tile_w, int tile_h, const int32_t *isect_offsets,
-                      const int32_t *flatten, float *render, float *alphas, float *t_final, int32_t *last_ids, bds_stream_t stream);
+ * clamp to [0,1]; channel 3 = depth): record r = visible Gaussian ids[r]; sh_rgb [n,3] receives the un-clamped colours in list order
+ * (for bds_sh_view_bwd_list with sh_rgb_by_rank).  Replaces bds_sh_view_fwd + bds_splat_pack on that path: the colours of the ~85 %
+ * culled Gaussians are never evaluated or stored.  n_dev and the clearing arguments as bds_splat_pack.
+ *   coeffs_rest NULL: coeffs [N,K,3] with K*3 a multiple of 4 and 16-byte aligned rows.
+ *   coeffs_rest non-NULL (K >= 2): the coefficients where the reference's Gaussian classes hold them (models/gaussians/vanilla.py:96-104:
+ *       `_features_dc` [N,3] and `_features_rest` [N,K-1,3], two parameters with their own learning rates; :382 concatenates them on
+ *       every call -- 192 bytes per Gaussian written and read back before anything is culled): band 0 from coeffs, bands 1.. from
+ *       coeffs_rest, rows of 4-byte alignment, visible rows only. */
+int bds_splat_pack_sh(int64_t n, const uint64_t *n_dev, const int32_t *ids, int K, int degrees_to_use, const float *means,
+                      const float *cam_pos, const float *coeffs, const float *coeffs_rest, const float *means2d, const float *conics,
+                      const float *depths, const float *opacities, const int32_t *radii, float *records, float *sh_rgb,
+                      float *zero_records, float *zero_tail, int64_t zero_tail_floats, int32_t *schedule, bds_stream_t stream);
+/* M_dev (forward and backward; NULL: M is the list length): the device-count form -- the length is read from M_dev (M effective, see
+ * "device-count forms"), M is then the capacity (> 0).  tile_order, split_len, split_cap and split_pool belong to that form: without
+ * M_dev the forward takes tile_order = NULL and split_len = 0 only (it never writes a schedule: bds_rasterize_bwd_schedule serves
+ * those lists), the backward split_len = 0 only.
+ * tile_order of the forward (optional: the schedule buffer of bds_rasterize_bwd_schedule): every compositing wave knows how far into its
+ * list its tile blended when it ends, and leaves the backward's schedule itself: BINNED form (bds_set_option(8, 1), default) -- one
+ * atomic drops the tile into the bin of its length (32 bins a factor 2^(1/4) apart, longest first) of its XCD's range of tiles, the
+ * backward's workgroups find their tile by a prefix walk over the 32 counts, NO launch between the passes; the header must be clear when
+ * the forward starts (the record pack's `schedule` argument).  bds_set_option(8, 0): the waves leave their keys and
+ * bds_rasterize_bwd_schedule_sort -- one launch, a no-op in the binned form -- writes the sorted schedule.
+ * split_len (> 0: one camera, four channels, lists of tiles larger than 16 px, the binned schedule, i.e. the fused view; 0 = off): a
+ * tile whose list-tile list holds >= split_len entries is composited by FOUR waves, one 16 x 4 strip each (one pixel per lane; the
+ * candidates filtered per strip), instead of one: a one-workgroup kernel lists those tiles behind the schedule words (at most
+ * split_cap of them; a long tile beyond that is taken by one wave like any other) and the launch is [4 x split_cap strip workgroups,
+ * first | one workgroup per tile].  For views in which a few tiles collect thousands of small splats (the vanishing point of a
+ * street: the launch waits for those waves).  Same pixels in the same order: images bit-identical, gradients to the order of their
+ * atomics.  Pass the SAME values and the same tile_order buffer to the backward.  No reference counterpart (gsplat runs 256 threads
+ * per tile everywhere).
+ * split_pool (> 0, with split_len; 0 = off): int32 words of a pool behind the schedule words -- the tile_order buffer then holds
+ * bds_rasterize_schedule_ints(..) + bds_rasterize_split_pool_ints(.., split_cap, split_pool, M) words.  The long tiles of a list tile
+ * share one walk of its list (per entry the mask of the sub-tiles it reaches), then one workgroup per long tile leaves the tile's own
+ * candidates in the pool, in list order; the tile's strips (forward and backward) walk that instead of the whole list-tile list (the
+ * front camera of a lidar-initialised street: 36 k entries per strip wave -> the ~8 k that reach the tile).  A tile the pool has no
+ * room for keeps the list-tile list: never an error.  last_ids of a refined tile are positions in the pool. */
+int bds_rasterize_fwd(int C, int64_t n_records, int64_t M, const uint64_t *M_dev, int CH, const float *records, const float *backgrounds,
+                      int W, int H, int tile_size, int list_tile_size, int tile_w, int tile_h, const int32_t *isect_offsets,
+                      const int32_t *flatten, float *render, float *alphas, float *t_final, int32_t *last_ids, int32_t *tile_order,
+                      int split_len, int split_cap, int64_t split_pool, bds_stream_t stream);
 /* (t_final [C,H,W], optional -- NULL: not written: every pixel's final transmittance ITSELF.  alphas = 1 - T rounds the low bits of a
  * small T away (T = 1e-4: 6e-4 relative), and the backward divides its way up from T: handed the same buffer, the backward starts
  * from the exact value -- element-wise gradient errors of dense scenes drop from ~1e-2 to the fp32 formulation's ~1e-3,
@@ -233,17 +265,18 @@ int bds_rasterize_fwd(int C, int64_t n_records, int64_t M, int CH, const float *
  * atomics), in the units of the un-scaled inputs:
  *     0-3 d/d colour | 4-6 d/d conic (a, b, c) | 7-8 d/d mean2d | 9-10 sum over pixels of |d/d mean2d| (absgrad != 0) |
  *     11 d/d opacity | 12-15 unused.
- * tile_order may be NULL (tiles are taken in image order, one contiguous band per XCD) or the schedule written by
- * bds_rasterize_bwd_schedule. */
-int bds_rasterize_bwd(int C, int64_t n_records, int64_t M, int CH, const float *records, const float *backgrounds, int W, int H,
-                      int tile_size, int list_tile_size, int tile_w, int tile_h, const int32_t *isect_offsets,
+ * tile_order may be NULL (tiles are taken in image order, one contiguous band per XCD), the schedule written by
+ * bds_rasterize_bwd_schedule, or the buffer the device-count forward filled; M_dev and split_* as the forward's. */
+int bds_rasterize_bwd(int C, int64_t n_records, int64_t M, const uint64_t *M_dev, int CH, const float *records, const float *backgrounds,
+                      int W, int H, int tile_size, int list_tile_size, int tile_w, int tile_h, const int32_t *isect_offsets,
                       const int32_t *flatten, const float *alphas, const float *t_final, const int32_t *last_ids, const float *v_render,
-                      const float *v_alphas, float *v_records, int absgrad, const int32_t *tile_order, bds_stream_t stream);
+                      const float *v_alphas, float *v_records, int absgrad, const int32_t *tile_order, int split_len, int split_cap,
+                      int64_t split_pool, bds_stream_t stream);
 /* Launch schedule for bds_rasterize_bwd (no reference counterpart; results do not depend on it).  One wave owns a
  * tile and the chip holds only about two rounds of tiles, so the launch ends with a tail of long tiles that started
  * late.  After the forward pass each tile's visited length is known exactly (max last_id - list start); this call
  * orders every XCD's contiguous range of tiles longest-first.  tile_order: int32[bds_rasterize_schedule_ints(C, tile_w, tile_h)]:
- * word 0 tags the form (1 = sorted: the order follows, then scratch; 0 = binned, written by bds_rasterize_fwd_dev), which the
+ * word 0 tags the form (1 = sorted: the order follows, then scratch; 0 = binned, written by bds_rasterize_fwd with M_dev), which the
  * backward kernels read -- hand the buffer over as it is. */
 int64_t bds_rasterize_schedule_ints(int C, int tile_w, int tile_h);
 int bds_rasterize_bwd_schedule(int C, int W, int H, int tile_size, int list_tile_size, int tile_w, int tile_h, const int32_t *isect_offsets,
@@ -346,7 +379,7 @@ int bds_l1_tv_train(int64_t n, const float *a, const float *b, int nlevels, cons
  * be the COLUMNS of one 16-byte aligned [N,8] block of 32-byte rows {m2d.x, m2d.y, depth, radius (int bits) | conic a, b, c, opacity}:
  * pass means2d = block, depths = block + 2, conics = block + 4 (both or neither; separate arrays of more than one row can not have
  * these addresses).  bds_project_view_fwd then writes whole rows (radii [N] and opacities [N] are written as dense arrays as well),
- * and bds_isect_prepare* / bds_isect_build* / bds_splat_pack_sh* given the same three pointers (and opacities = block + 7, or any
+ * and bds_isect_prepare* / bds_isect_build* / bds_splat_pack_sh given the same three pointers (and opacities = block + 7, or any
  * dense [N] array of other opacities) gather ONE line per visible Gaussian instead of one per array. */
 /* Block bounds: rows kept in spatial order (Morton order of the centres: the host side's densify.spatial_order) make every 256-row
  * block a small box, and a camera then rejects most of the ~85 % of the Gaussians it does not see a BLOCK at a time.
@@ -390,17 +423,16 @@ int bds_sh_view_fwd(int64_t N, int K, int degrees_to_use, const float *means, co
 /* ROW FORM of the four small parameter gradients (optional, recognised by the addresses like the projection's row form): v_means,
  * v_quats, v_log_scales, v_logits may be the columns of one 16-byte aligned [N,16] block of 64-byte rows {v_mean 3, v_logit | v_quat 4 |
  * v_log_scale 3, - | - - - -}: pass v_means = block, v_logits = block + 3, v_quats = block + 4, v_log_scales = block + 8.
- * bds_project_view_bwd_list then updates, and bds_view_grads_clear_list* clear, ONE line per visible Gaussian instead of four partly
+ * bds_project_view_bwd_list then updates, and bds_view_grads_clear_list clears, ONE line per visible Gaussian instead of four partly
  * used ones; bds_adam_step_rows reads such columns. */
 /* sh_rgb: the un-clamped colours the forward left -- [N,3] indexed by Gaussian (bds_sh_view_fwd), or, with sh_rgb_by_rank != 0,
- * [n_list,3] in list order (bds_splat_pack_sh). */
-int bds_sh_view_bwd_list(int64_t n_list, const int32_t *ids, int K, int degrees_to_use, const float *means, const float *cam_pos,
-                         const float *sh_rgb, int sh_rgb_by_rank, const float *v_records, float *v_coeffs, const int32_t *row_map,
-                         int accumulate, bds_stream_t stream);
-/* ... into the split storage of bds_splat_pack_sh_split: v_coeffs_dc [N,3], v_coeffs_rest [N,K-1,3] (visible rows stored or added to). */
-int bds_sh_view_bwd_list_split(int64_t n_list, const int32_t *ids, int K, int degrees_to_use, const float *means, const float *cam_pos,
-                               const float *sh_rgb, int sh_rgb_by_rank, const float *v_records, float *v_coeffs_dc,
-                               float *v_coeffs_rest, int accumulate, bds_stream_t stream);
+ * [n_list,3] in list order (bds_splat_pack_sh).
+ * v_coeffs_rest (NULL: v_coeffs is [N,K,3]): the split storage of bds_splat_pack_sh -- v_coeffs [N,3], v_coeffs_rest [N,K-1,3]
+ * (visible rows stored or added to; ignored for K = 1).  Dense arrays only: not together with row_map.
+ * n_dev (NULL: n_list is the count): the device-count form, as bds_project_view_bwd_list's. */
+int bds_sh_view_bwd_list(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, int K, int degrees_to_use, const float *means,
+                         const float *cam_pos, const float *sh_rgb, int sh_rgb_by_rank, const float *v_records, float *v_coeffs,
+                         float *v_coeffs_rest, const int32_t *row_map, int accumulate, bds_stream_t stream);
 /* NaN / Inf check of the tensors a Gaussian class hands to the rasterizer (models/gaussians/vanilla.py:407-412 raises ValueError per
  * tensor; two reductions and two host waits each there): ONE streaming launch over up to 8 tensors; bit t of *flags_dev (cleared
  * first) is set when tensors[t] (counts[t] floats) holds a non-finite value; flags_pinned (optional, page-locked) receives a copy
@@ -437,9 +469,15 @@ int bds_project_view_bwd_list(int flags, int64_t n_list, const uint64_t *n_dev, 
                               int W, int H, float eps2d, const float *v_records, float *v_means, float *v_quats, float *v_scales,
                               float *v_opacities, float *v_colors, float *v_viewmat_slots, float *grad2d, float *absgrad2d,
                               const int32_t *row_map, bds_stream_t stream);
-/* Zero the rows ids[0..n_list) of the five per-Gaussian gradient arrays (v_sh is [N,K,3]). */
-int bds_view_grads_clear_list(int64_t n_list, const int32_t *ids, int K, float *v_means, float *v_quats, float *v_log_scales,
-                              float *v_logits, float *v_sh, bds_stream_t stream);
+/* Zero the rows ids[0..n_list) of the five per-Gaussian gradient arrays (v_sh is [N,K,3]); n_dev (NULL: n_list is the count): the
+ * device-count form, as above.
+ * grad2d / absgrad2d [N,2], optional: the same rows of a view's PERSISTENT screen-space gradient arrays are cleared as well -- the
+ * list-driven projection backward stores the visible rows, so a buffer cleared by the previous visit's list needs no dense fill.
+ * The five parameter-gradient pointers may ALL be NULL: only the screen-space arrays are cleared then -- a loop whose optimizer
+ * clears the gradients as it consumes them, bds_adam_step_consume.  (Both serve the device-count view; the kernel takes them with a
+ * host count as well.) */
+int bds_view_grads_clear_list(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, int K, float *v_means, float *v_quats,
+                              float *v_log_scales, float *v_logits, float *v_sh, float *grad2d, float *absgrad2d, bds_stream_t stream);
 /* v_*[ids[s]] += s_*[s]: compact rows (s_means [n_list,3] s_quats [n_list,4] s_log_scales [n_list,3] s_logits [n_list]
  * s_sh [n_list,K,3], e.g. a reduced exchange buffer) added to the dense arrays; entries with ids[s] < 0 are skipped. */
 int bds_view_grads_add_list(int64_t n_list, const int32_t *ids, int K, const float *s_means, const float *s_quats,
@@ -466,7 +504,7 @@ int bds_bilagrid_select_bwd(int nlevels, const bds_bilagrid_level_t *levels, con
  * 172 MB at 1080p) disappears.  _deferrable: 1 when every level has one grid (gl <= 8) and a factor that is 1 or a power of two
  * dividing H and W (and bit 2 of bds_set_option(7, ..) is clear), else 0 -- use bds_bilagrid_ms_ed_bwd then.  _deferred: v_direct
  * [H,W,4] receives the direct-route gradient (channels 0-2); the grids' gradients are complete on return.  bds_rasterize_bwd_ms:
- * bds_rasterize_bwd / _dev (M_dev NULL: M_capacity is the host-side count) for C = 1, CH = 4, no backgrounds, with the image
+ * bds_rasterize_bwd (M_dev NULL: M_capacity is the host-side count; no split launch) for C = 1, CH = 4, no backgrounds, with the image
  * gradient formed from (levels, ms_ws: the transform's workspace), render [H,W,4] (the compositor's forward output), sky,
  * v_depth / v_alpha_in (may be NULL) and v_direct; writes v_sky [H,W,3] (may be NULL). */
 int bds_bilagrid_ms_ed_bwd_deferrable(int nlevels, const bds_bilagrid_level_t *levels, int H, int W);
@@ -501,7 +539,10 @@ int bds_rasterize_kernel_name(int backward, int CH, int absgrad, int list_tile_s
  * overflow; written by the GPU; may be NULL) whenever it likes, provisions more and repeats the view.  Launches are sized by the
  * capacities; surplus workgroups see no elements.  Packed lists only (n_visible_capacity <= 2^(32 - bits(C*tiles))), else
  * BDS_ECAPACITY.  Lists, offsets and images are bit-identical to the host-count forms.  `compact`: bit 0 as in bds_isect_prepare,
- * bit 1 = the workspace already holds the visible counts and cleared tables of bds_project_view_fwd's prep_ws (one launch less). */
+ * bit 1 = the workspace already holds the visible counts and cleared tables of bds_project_view_fwd's prep_ws (one launch less).
+ * Behind the tile stage the view takes the same entries as the host-count form, handed a count pointer: n_dev = visible effective
+ * (bds_splat_pack, bds_splat_pack_sh, bds_sh_view_bwd_list, bds_project_view_bwd_list, bds_view_grads_clear_list), M_dev = M effective
+ * (bds_rasterize_fwd / _bwd / _bwd_ms); the two helpers of the forward-written schedule follow the tile stage below. */
 size_t bds_isect_counts_offset(int which);
 int bds_isect_prepare_dev(int C, int64_t N, const float *means2d, const int32_t *radii, const float *depths, const float *conics,
                           const float *opacities, int tile_size, int tile_w, int tile_h, int32_t *tiles_per_gauss, void *ws,
@@ -512,63 +553,10 @@ int bds_isect_build_dev(int C, int64_t N, int64_t M_capacity, int64_t n_visible_
                         const float *depths, const float *conics, const float *opacities, int tile_size, int tile_w, int tile_h,
                         const void *ws, size_t ws_bytes, void *ws2, size_t ws2_bytes, int32_t *flatten_ids, int32_t *isect_offsets,
                         int compact, bds_stream_t stream);
-/* bds_splat_pack with the record count on the device (n_dev -> visible effective).  Optionally clears, on the way, the gradient
- * record of every packed row (zero_records [n_capacity, BDS_GRAD_RECORD_FLOATS]: what bds_rasterize_bwd accumulates into) and a
- * tail of zero_tail_floats (multiple of 4) floats (the camera-pose gradient slots): no fill launches of their own.  schedule
- * (optional): the schedule buffer the following bds_rasterize_fwd_dev fills in its binned form -- its header is cleared here too. */
-int bds_splat_pack_dev(int64_t n_capacity, const uint64_t *n_dev, int CH, const int32_t *ids, const float *means2d, const float *conics,
-                       const float *colors, const float *opacities, const int32_t *radii, float *records, float *zero_records,
-                       float *zero_tail, int64_t zero_tail_floats, int32_t *schedule, bds_stream_t stream);
-/* bds_splat_pack_sh with the record count on the device and the clearing options of bds_splat_pack_dev: the SH colours of the visible
- * Gaussians are evaluated by the pack itself (no pass over all N, no dense colour arrays); sh_rgb [n_capacity, 3] in list order. */
-int bds_splat_pack_sh_dev(int64_t n_capacity, const uint64_t *n_dev, const int32_t *ids, int K, int degrees_to_use, const float *means,
-                          const float *cam_pos, const float *coeffs, const float *means2d, const float *conics, const float *depths,
-                          const float *opacities, const int32_t *radii, float *records, float *sh_rgb, float *zero_records,
-                          float *zero_tail, int64_t zero_tail_floats, int32_t *schedule, bds_stream_t stream);
-/* bds_rasterize_fwd / _bwd with the list length on the device (M_dev -> M effective) */
-/* (tile_order, optional: the schedule buffer of bds_rasterize_bwd_schedule.  Every compositing wave knows how far into its list its
- * tile blended when it ends, and leaves the backward's schedule itself: BINNED form (bds_set_option(8, 1), default) -- one atomic
- * drops the tile into the bin of its length (32 bins a factor 2^(1/4) apart, longest first) of its XCD's range of tiles, the
- * backward's workgroups find their tile by a prefix walk over the 32 counts, NO launch between the passes; the header must be clear when the
- * forward starts (the record pack's `schedule` argument).  bds_set_option(8, 0): the waves leave their keys and
- * bds_rasterize_bwd_schedule_sort -- one launch, a no-op in the binned form -- writes the sorted schedule.)
- * split_len (> 0: one camera, four channels, lists of tiles larger than 16 px, the binned schedule, i.e. the fused view; 0 = off): a
- * tile whose list-tile list holds >= split_len entries is composited by FOUR waves, one 16 x 4 strip each (one pixel per lane; the
- * candidates filtered per strip), instead of one: a one-workgroup kernel lists those tiles behind the schedule words (at most
- * split_cap of them; a long tile beyond that is taken by one wave like any other) and the launch is [4 x split_cap strip workgroups,
- * first | one workgroup per tile].  For views in which a few tiles collect thousands of small splats (the vanishing point of a
- * street: the launch waits for those waves).  Same pixels in the same order: images bit-identical, gradients to the order of their
- * atomics.  Pass the SAME values and the same tile_order buffer to the backward.  No reference counterpart (gsplat runs 256 threads
- * per tile everywhere).
- * split_pool (> 0, with split_len; 0 = off): int32 words of a pool behind the schedule words -- the tile_order buffer then holds
- * bds_rasterize_schedule_ints(..) + bds_rasterize_split_pool_ints(.., split_cap, split_pool, M_capacity) words.  The long tiles of a
- * list tile share one walk of its list (per entry the mask of the sub-tiles it reaches), then one workgroup per long tile leaves the
- * tile's own candidates in the pool, in list order; the tile's strips (forward and
- * backward) walk that instead of the whole list-tile list (the front camera of a lidar-initialised street: 36 k entries per strip
- * wave -> the ~8 k that reach the tile).  A tile the pool has no room for keeps the list-tile list: never an error.  last_ids of a
- * refined tile are positions in the pool. */
-int bds_rasterize_fwd_dev(int C, int64_t n_records, int64_t M_capacity, const uint64_t *M_dev, int CH, const float *records,
-                          const float *backgrounds, int W, int H, int tile_size, int list_tile_size, int tile_w, int tile_h,
-                          const int32_t *isect_offsets, const int32_t *flatten, float *render, float *alphas, float *t_final,
-                          int32_t *last_ids, int32_t *tile_order, int split_len, int split_cap, int64_t split_pool, bds_stream_t stream);
+/* Words of the refined-list pool behind the schedule words (bds_rasterize_fwd: split_pool), and the sort of the keys the forward's
+ * waves left (bds_set_option(8, 0); a no-op in the binned form). */
 int64_t bds_rasterize_split_pool_ints(int C, int tile_w, int tile_h, int split_cap, int64_t split_pool, int64_t M_capacity);
 int bds_rasterize_bwd_schedule_sort(int C, int tile_w, int tile_h, int32_t *tile_order, bds_stream_t stream);
-int bds_rasterize_bwd_dev(int C, int64_t n_records, int64_t M_capacity, const uint64_t *M_dev, int CH, const float *records,
-                          const float *backgrounds, int W, int H, int tile_size, int list_tile_size, int tile_w, int tile_h,
-                          const int32_t *isect_offsets, const int32_t *flatten, const float *alphas, const float *t_final,
-                          const int32_t *last_ids, const float *v_render, const float *v_alphas, float *v_records, int absgrad,
-                          const int32_t *tile_order, int split_len, int split_cap, int64_t split_pool, bds_stream_t stream);
-/* the list-driven backward kernels and the row-wise clear with the list length on the device (n_dev -> visible effective) */
-int bds_sh_view_bwd_list_dev(int64_t n_capacity, const uint64_t *n_dev, const int32_t *ids, int K, int degrees_to_use,
-                             const float *means, const float *cam_pos, const float *sh_rgb, int sh_rgb_by_rank,
-                             const float *v_records, float *v_coeffs, const int32_t *row_map, int accumulate, bds_stream_t stream);
-/* (grad2d / absgrad2d [N,2], optional: the same rows of a view's PERSISTENT screen-space gradient arrays are cleared as well -- the
- * list-driven projection backward stores the visible rows, so a buffer cleared by the previous visit's list needs no dense fill.
- * The five parameter-gradient pointers may ALL be NULL: only the screen-space arrays are cleared then -- a loop whose optimizer
- * clears the gradients as it consumes them, bds_adam_step_consume) */
-int bds_view_grads_clear_list_dev(int64_t n_capacity, const uint64_t *n_dev, const int32_t *ids, int K, float *v_means,
-                                  float *v_quats, float *v_log_scales, float *v_logits, float *v_sh, float *grad2d, float *absgrad2d,
-                                  bds_stream_t stream);
 
 /* ---- multi-GPU exchange of the visible rows (no reference counterpart; dist.FrameExchange) ---------------------------------------
  * mask [N] uint8: the element-wise OR over the ranks of "this rank's view sees Gaussian g" (radii > 0).  In two launches:

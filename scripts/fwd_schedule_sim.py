@@ -57,11 +57,12 @@ with torch.no_grad():
         col = torch.rand(1, N, 4, device=dev)
         rec = torch.empty(N, L.SPLAT_RECORD_FLOATS, device=dev)
         st = L.stream()
-        L.check(L.lib().bds_splat_pack(N, 4, None, L.ptr(m2), L.ptr(con), L.ptr(col), L.ptr(op), L.ptr(radii), L.ptr(rec), st), "pack")
+        L.check(L.lib().bds_splat_pack(N, None, 4, None, L.ptr(m2), L.ptr(con), L.ptr(col), L.ptr(op), L.ptr(radii), L.ptr(rec), None, None, 0, None,
+                                       st), "pack")
         render, alphas = torch.empty(1, H, W, 4, device=dev), torch.empty(1, H, W, 1, device=dev)
         last = torch.zeros(1, H, W, dtype=torch.int32, device=dev)
-        L.check(L.lib().bds_rasterize_fwd(1, N, M, 4, L.ptr(rec), None, W, H, 16, 16, tw, th, L.ptr(offs), L.ptr(fids), L.ptr(render), L.ptr(alphas),
-                                          None, L.ptr(last), st), "fwd")
+        L.check(L.lib().bds_rasterize_fwd(1, N, M, None, 4, L.ptr(rec), None, W, H, 16, 16, tw, th, L.ptr(offs), L.ptr(fids), L.ptr(render), L.ptr(alphas),
+                                          None, L.ptr(last), None, 0, 0, 0, st), "fwd")
         order = ops.bwd_schedule(1, W, H, 16, offs, last)
         torch.cuda.synchronize()
         work = order[1 + total:1 + 2 * total].cpu().tolist()

@@ -24,7 +24,7 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(bds_[a-z0-9_]+)\s*\(", src)))
 
 
-def test_header_and_library_symbols_match_abi_3(libpath):
+def test_header_and_library_symbols_match_abi_4(libpath):
     names = _declared_symbols()
     assert len(names) >= 19
     h = ctypes.CDLL(libpath)
@@ -37,7 +37,7 @@ def test_header_and_library_symbols_match_abi_3(libpath):
     assert not exported - set(names), f"exported by libbds.so but not declared in include/bds.h: {sorted(exported - set(names))}"
     h.bds_abi_version.restype = ctypes.c_int
     from bilateral_driving_amd import _lib as _L
-    assert h.bds_abi_version() == _L.ABI_VERSION == 3
+    assert h.bds_abi_version() == _L.ABI_VERSION == 4
     h.bds_strerror.restype = ctypes.c_char_p
     assert b"workspace" in h.bds_strerror(-2)
 
@@ -62,15 +62,28 @@ def test_argument_validation_without_gpu(libpath):
     h = _lib.lib()
     assert h.bds_sh_fwd(10, 16, 7, None, None, None, None, None) == -1        # degree > 3
     assert h.bds_sh_fwd(0, 16, 3, None, None, None, None, None) == 0          # empty input is fine
-    assert h.bds_rasterize_fwd(1, 10, 0, 5, None, None, 64, 64, 16, 16, 4, 4, None, None, None, None, None, None, None) == -1    # CH = 5
-    assert h.bds_rasterize_fwd(1, 10, 0, 3, None, None, 64, 64, 8, 8, 8, 8, None, None, None, None, None, None, None) == -1     # tile size 8
-    assert h.bds_rasterize_fwd(1, 10, 0, 3, None, None, 64, 64, 16, 24, 4, 4, None, None, None, None, None, None, None) == -1   # list tile not a multiple of 16
-    assert h.bds_splat_pack(0, 4, None, None, None, None, None, None, None, None) == 0 and h.bds_splat_pack(5, 2, None, None, None, None, None, None, None, None, None) == -1
-    assert h.bds_sh_view_bwd_list(0, None, 16, 3, None, None, None, 0, None, None, None, 0, None) == 0
-    assert h.bds_sh_view_bwd_list(4, None, 16, 3, None, None, None, 0, None, None, None, 0, None) == -1               # null list
-    assert h.bds_splat_pack_sh(0, None, 16, 3, None, None, None, None, None, None, None, None, None, None, None) == 0
-    assert h.bds_splat_pack_sh(4, None, 16, 3, None, None, None, None, None, None, None, None, None, None, None, None) == -1   # null list
-    assert h.bds_splat_pack_sh(4, None, 15, 3, None, None, None, None, None, None, None, None, None, None, None, None) == -1   # K < 16 bases
+    fwd_tail = (None, None, None, None, None, None, None, 0, 0, 0, None)   # isect_offsets .. last_ids, tile_order, split_*, stream
+    assert h.bds_rasterize_fwd(1, 10, 0, None, 5, None, None, 64, 64, 16, 16, 4, 4, *fwd_tail) == -1    # CH = 5
+    assert h.bds_rasterize_fwd(1, 10, 0, None, 3, None, None, 64, 64, 8, 8, 8, 8, *fwd_tail) == -1     # tile size 8
+    assert h.bds_rasterize_fwd(1, 10, 0, None, 3, None, None, 64, 64, 16, 24, 4, 4, *fwd_tail) == -1   # list tile not a multiple of 16
+    assert h.bds_splat_pack(0, None, 4, None, None, None, None, None, None, None, None, None, 0, None, None) == 0
+    assert h.bds_splat_pack(5, None, 2, None, None, None, None, None, None, None, None, None, 0, None, None) == -1
+    assert h.bds_sh_view_bwd_list(0, None, None, 16, 3, None, None, None, 0, None, None, None, None, 0, None) == 0
+    assert h.bds_sh_view_bwd_list(4, None, None, 16, 3, None, None, None, 0, None, None, None, None, 0, None) == -1               # null list
+    pack_sh_tail = (None,) * 11 + (0, None, None)    # coeffs .. zero_tail, zero_tail_floats, schedule, stream
+    assert h.bds_splat_pack_sh(0, None, None, 16, 3, None, None, *pack_sh_tail) == 0
+    assert h.bds_splat_pack_sh(4, None, None, 16, 3, None, None, *pack_sh_tail) == -1   # null list
+    assert h.bds_splat_pack_sh(4, None, None, 15, 3, None, None, *pack_sh_tail) == -1   # K < 16 bases
+    # combinations the merged entries refuse (every other argument acceptable: p stands for any 16-byte aligned device address)
+    p = 4096
+    img = (64, 64, 16, 16, 4, 4, p, p, p, p, p, p)     # W .. tile_h, isect_offsets, flatten, render, alphas, t_final, last_ids
+    assert h.bds_rasterize_fwd(1, 10, 0, p, 3, p, None, *img, None, 0, 0, 0, None) == -1        # M_dev with capacity 0
+    assert h.bds_rasterize_fwd(1, 10, 5, None, 3, p, None, *img, p, 0, 0, 0, None) == -1        # host count with a tile_order
+    assert h.bds_rasterize_fwd(1, 10, 5, None, 4, p, None, *img, None, 64, 8, 0, None) == -1    # host count with split_len
+    grad = (64, 64, 16, 16, 4, 4, p, p, p, p, p, p, p, p, 0)   # W .. tile_h, isect_offsets .. last_ids, v_render, v_alphas, v_records, absgrad
+    assert h.bds_rasterize_bwd(1, 10, 0, p, 3, p, None, *grad, None, 0, 0, 0, None) == -1       # M_dev with capacity 0
+    assert h.bds_rasterize_bwd(1, 10, 5, None, 4, p, None, *grad, p, 64, 8, 0, None) == -1      # host count with split_len
+    assert h.bds_sh_view_bwd_list(4, None, p, 16, 3, p, p, p, 0, p, p, p, p, 0, None) == -1     # v_coeffs_rest together with row_map
     assert h.bds_isect_prepare_workspace_bytes(1, 1000) > 5 * 4000
     assert h.bds_isect_build_workspace_bytes(1, 1000, 50000) > 3 * 4 * 50000
     lv = (_lib.BdsLevel * 1)()

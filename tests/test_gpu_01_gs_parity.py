@@ -528,10 +528,10 @@ def test_backward_schedule_is_a_permutation_and_invisible(ops, seed, N, W, H, C)
     rr, aa = torch.empty(Cn, H, W, 3, device="cuda"), torch.empty(Cn, H, W, 1, device="cuda")
     M = fids.numel()
     rec = torch.empty(Cn * N, L.SPLAT_RECORD_FLOATS, device="cuda")
-    L.check(L.lib().bds_splat_pack(Cn * N, 3, None, L.ptr(m2.detach()), L.ptr(con.detach()), L.ptr(col.detach()), L.ptr(op.detach()), None, L.ptr(rec),
-                                   L.stream()), "pack")
-    L.check(L.lib().bds_rasterize_fwd(Cn, Cn * N, M, 3, L.ptr(rec), None, W, H, 16, 16, tw, th, L.ptr(offs), L.ptr(fids), L.ptr(rr), L.ptr(aa),
-                                      None, L.ptr(last), L.stream()), "fwd")
+    L.check(L.lib().bds_splat_pack(Cn * N, None, 3, None, L.ptr(m2.detach()), L.ptr(con.detach()), L.ptr(col.detach()), L.ptr(op.detach()), None,
+                                   L.ptr(rec), None, None, 0, None, L.stream()), "pack")
+    L.check(L.lib().bds_rasterize_fwd(Cn, Cn * N, M, None, 3, L.ptr(rec), None, W, H, 16, 16, tw, th, L.ptr(offs), L.ptr(fids), L.ptr(rr), L.ptr(aa),
+                                      None, L.ptr(last), None, 0, 0, 0, L.stream()), "fwd")
     order = ops.bwd_schedule(Cn, W, H, 16, offs, last)
     total = Cn * tw * th
     assert int(order[0]) == 1                         # [tag = sorted | order | work] (csrc/rasterize.hip: pick_item)

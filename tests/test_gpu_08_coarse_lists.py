@@ -94,7 +94,7 @@ def test_fused_view_list_tile_64_equals_16(W, H, N):
 
 @pytest.mark.parametrize("list_tile", [16, 64])
 def test_schedule_keys_left_by_the_forward_compositor(list_tile):
-    """bds_rasterize_fwd_dev(tile_order=...) + bds_rasterize_bwd_schedule_sort == bds_rasterize_bwd_schedule (keys re-derived from
+    """bds_rasterize_fwd(M_dev, tile_order=...) + bds_rasterize_bwd_schedule_sort == bds_rasterize_bwd_schedule (keys re-derived from
     last_ids by a launch of its own): same per-tile keys, same schedule."""
     import math
     from bilateral_driving_amd import _lib as L
@@ -115,7 +115,8 @@ def test_schedule_keys_left_by_the_forward_compositor(list_tile):
         M = fids.numel()
         col = torch.rand(1, N, 4, device=dev)
         rec = torch.empty(N, L.SPLAT_RECORD_FLOATS, device=dev)
-        L.check(lib.bds_splat_pack(N, 4, None, L.ptr(m2), L.ptr(con), L.ptr(col), L.ptr(op), L.ptr(radii), L.ptr(rec), st), "pack")
+        L.check(lib.bds_splat_pack(N, None, 4, None, L.ptr(m2), L.ptr(con), L.ptr(col), L.ptr(op), L.ptr(radii), L.ptr(rec), None, None, 0, None, st),
+                "pack")
         render, alphas = torch.empty(1, H, W, 4, device=dev), torch.empty(1, H, W, 1, device=dev)
         last = torch.zeros(1, H, W, dtype=torch.int32, device=dev)
         m_dev = torch.tensor([M], dtype=torch.int64, device=dev)
@@ -123,8 +124,8 @@ def test_schedule_keys_left_by_the_forward_compositor(list_tile):
         total, NB = tw * th, 32          # (bins per XCD range: csrc/rasterize.hip kSchedLogBins)
 
         def forward(order):
-            L.check(lib.bds_rasterize_fwd_dev(1, N, M + 100, m_dev.data_ptr(), 4, L.ptr(rec), None, W, H, 16, list_tile, tw, th, L.ptr(offs),
-                                              L.ptr(fids), L.ptr(render), L.ptr(alphas), None, L.ptr(last), L.ptr(order), 0, 0, 0, st), "fwd")
+            L.check(lib.bds_rasterize_fwd(1, N, M + 100, m_dev.data_ptr(), 4, L.ptr(rec), None, W, H, 16, list_tile, tw, th, L.ptr(offs),
+                                          L.ptr(fids), L.ptr(render), L.ptr(alphas), None, L.ptr(last), L.ptr(order), 0, 0, 0, st), "fwd")
             L.check(lib.bds_rasterize_bwd_schedule_sort(1, tw, th, L.ptr(order), st), "sort")
 
         # sorted form (option 8 = 0): the waves leave their keys, one launch sorts them

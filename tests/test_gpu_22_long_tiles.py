@@ -1,4 +1,4 @@
-"""-m gpu: long tiles composited strip by strip (include/bds.h bds_rasterize_fwd_dev / _bwd_dev ``split_len``): a tile whose list
+"""-m gpu: long tiles composited strip by strip (include/bds.h bds_rasterize_fwd / _bwd ``split_len``): a tile whose list
 holds at least split_len entries (the first split_cap of them) is taken by FOUR waves, one 16 x 4 strip each, the candidates filtered per strip -- against the
 one-wave-per-tile form that tests/test_gpu_01 / test_gpu_03 tie to the oracle.  Same pixels in the same order: images and last-id maps
 bit-identical, gradients equal to the order of their atomics."""

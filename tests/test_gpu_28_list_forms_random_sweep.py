@@ -1,8 +1,8 @@
 """-m gpu: the fused view's list forms against each other on the random scenes of tests/test_gpu_25: list tiles of 16 / 32 / 64 /
 128 px (the compositor filters a larger list tile's candidates per 16-px tile), long tiles composited strip by strip from a random
 threshold on (``split_len``), with a capped long-tile list (``split_cap``) and refined candidate lists from a pool that is ample,
-tiny (runs out after a few tiles: the rest fall back to the list-tile list) or absent -- include/bds.h bds_rasterize_fwd_dev /
-_bwd_dev.  Every form composites the same (pixel, Gaussian) pairs in the same order: images BIT-identical, gradients to the
+tiny (runs out after a few tiles: the rest fall back to the list-tile list) or absent -- include/bds.h bds_rasterize_fwd /
+_bwd with M_dev.  Every form composites the same (pixel, Gaussian) pairs in the same order: images BIT-identical, gradients to the
 re-association of their atomics.  tests/test_gpu_08 / test_gpu_22 hold the same on the benchmark and lidar scenes.
 
 BDS_SWEEP_CASES (default 8) scenes x 4 forms."""
