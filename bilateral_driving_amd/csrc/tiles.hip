@@ -1335,79 +1335,48 @@ static int prepare_enqueue(int C, int64_t N, const float *means2d, const int32_t
   return BDS_OK;
 }
 
+// The one prepare entry; how the counts reach the caller (include/bds.h "tile intersection"):
+//   capacities < 0, no event: `counts` (int64[2], any host memory) = {M, visible} after a stream synchronise;
+//   capacities < 0, an event: the GPU writes them into the page-locked `counts` and the event is recorded behind that;
+//   capacities >= 0         : nothing is read back.  The counts stay in the first words of the workspace -- {M, visible, M effective,
+//                             visible effective, overflow} as uint64 (bds_isect_counts_offset) -- where the later stages read them;
+//                             `counts` (optional, page-locked int64[3]: M, visible, overflow) is written by the GPU for the host to
+//                             look at whenever it likes (e.g. one frame later).  Capturable in a hipGraph.
 extern "C" int bds_isect_prepare(int C, int64_t N, const float *means2d, const int32_t *radii, const float *depths,
                                  const float *conics, const float *opacities, int tile_size, int tile_w, int tile_h,
-                                 int32_t *tiles_per_gauss, void *ws,
-                                 size_t ws_bytes, int64_t *n_isects, int64_t *n_visible, int compact, bds_stream_t stream) {
-  BDS_REQUIRE(n_isects);
-  *n_isects = 0;
-  if (n_visible) *n_visible = 0;
-  uint64_t *counts_dev = nullptr;
-  const uint32_t *btot = nullptr;
-  int nblocks = 0;
-  int rc = prepare_enqueue(C, N, means2d, radii, depths, conics, opacities, tile_size, tile_w, tile_h, tiles_per_gauss, ws, ws_bytes,
-                           compact, stream, &counts_dev, &btot, &nblocks);
-  if (rc != BDS_OK || counts_dev == nullptr) return rc;
-  hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(finish_counts_kernel, dim3(1), dim3(256), 0, st, btot, nblocks, counts_dev, static_cast<volatile int64_t *>(nullptr),
-                     (int64_t)-1, (int64_t)-1);
-  BDS_LAUNCH_CHECK();
-  uint64_t total[2] = {0, 0};   // M, visible entries
-  if (hipMemcpyAsync(total, counts_dev, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st) != hipSuccess) return BDS_ELAUNCH;
-  if (hipStreamSynchronize(st) != hipSuccess) return BDS_ELAUNCH;
-  *n_isects = (int64_t)total[0];
-  if (n_visible) *n_visible = (int64_t)total[1];
-  return BDS_OK;
-}
-
-extern "C" int bds_isect_prepare_async(int C, int64_t N, const float *means2d, const int32_t *radii, const float *depths,
-                                       const float *conics, const float *opacities, int tile_size, int tile_w, int tile_h,
-                                       int32_t *tiles_per_gauss, void *ws, size_t ws_bytes, int64_t *counts_pinned,
-                                       void *event, int compact, bds_stream_t stream) {
-  BDS_REQUIRE(counts_pinned && event);
-  uint64_t *counts_dev = nullptr;
-  const uint32_t *btot = nullptr;
-  int nblocks = 0;
-  int rc = prepare_enqueue(C, N, means2d, radii, depths, conics, opacities, tile_size, tile_w, tile_h, tiles_per_gauss, ws, ws_bytes,
-                           compact, stream, &counts_dev, &btot, &nblocks);
-  if (rc != BDS_OK) return rc;
-  hipStream_t st = as_stream(stream);
-  if (counts_dev == nullptr) {
-    counts_pinned[0] = 0; counts_pinned[1] = 0;
+                                 int32_t *tiles_per_gauss, void *ws, size_t ws_bytes, int64_t M_capacity, int64_t n_visible_capacity,
+                                 int64_t *counts, void *event, int compact, bds_stream_t stream) {
+  BDS_REQUIRE((M_capacity < 0) == (n_visible_capacity < 0));
+  const bool dev = M_capacity >= 0, sync = !dev && !event;
+  if (dev) {
+    BDS_REQUIRE(!event && (int64_t)C * N > 0);
   } else {
-    void *mapped = nullptr;   // device view of the caller's page-locked buffer (the same address under unified addressing)
-    if (hipHostGetDevicePointer(&mapped, counts_pinned, 0) != hipSuccess) { (void)hipGetLastError(); mapped = nullptr; }
-    hipLaunchKernelGGL(finish_counts_kernel, dim3(1), dim3(256), 0, st, btot, nblocks, counts_dev, static_cast<volatile int64_t *>(mapped),
-                       (int64_t)-1, (int64_t)-1);
-    BDS_LAUNCH_CHECK();
-    if (mapped == nullptr &&   // not mapped: the copy engine
-        hipMemcpyAsync(counts_pinned, counts_dev, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st) != hipSuccess)
-      return BDS_ELAUNCH;
+    BDS_REQUIRE(counts);
+    counts[0] = 0; counts[1] = 0;
   }
-  if (hipEventRecord(static_cast<hipEvent_t>(event), st) != hipSuccess) return BDS_ELAUNCH;
-  return BDS_OK;
-}
-
-// Device-count form of the prepare stage: nothing is read back.  The counts stay in the first words of the workspace --
-// {M, visible, M effective, visible effective, overflow} as uint64 -- where the `_dev` entry points of the later stages read them
-// (bds_isect_counts_offset(which)); `counts_pinned` (optional, page-locked int64[3]: M, visible, overflow) is written by the GPU
-// itself for the host to look at whenever it likes (e.g. one frame later).  Capturable in a hipGraph.
-extern "C" int bds_isect_prepare_dev(int C, int64_t N, const float *means2d, const int32_t *radii, const float *depths,
-                                     const float *conics, const float *opacities, int tile_size, int tile_w, int tile_h,
-                                     int32_t *tiles_per_gauss, void *ws, size_t ws_bytes, int64_t M_capacity,
-                                     int64_t n_visible_capacity, int64_t *counts_pinned, int compact, bds_stream_t stream) {
-  BDS_REQUIRE(M_capacity >= 0 && n_visible_capacity >= 0 && (int64_t)C * N > 0);
   uint64_t *counts_dev = nullptr;
   const uint32_t *btot = nullptr;
   int nblocks = 0;
   int rc = prepare_enqueue(C, N, means2d, radii, depths, conics, opacities, tile_size, tile_w, tile_h, tiles_per_gauss, ws, ws_bytes,
-                           compact, stream, &counts_dev, &btot, &nblocks, n_visible_capacity);
+                           compact, stream, &counts_dev, &btot, &nblocks, dev ? n_visible_capacity : (int64_t)-1);
   if (rc != BDS_OK) return rc;
-  void *mapped = nullptr;
-  if (counts_pinned && hipHostGetDevicePointer(&mapped, counts_pinned, 0) != hipSuccess) { (void)hipGetLastError(); return BDS_EINVAL; }
-  hipLaunchKernelGGL(finish_counts_kernel, dim3(1), dim3(256), 0, as_stream(stream), btot, nblocks, counts_dev,
-                     static_cast<volatile int64_t *>(mapped), M_capacity, n_visible_capacity);
-  BDS_LAUNCH_CHECK();
+  hipStream_t st = as_stream(stream);
+  if (counts_dev != nullptr) {   // (else C*N == 0: nothing was enqueued and the counts are the zeros above)
+    void *mapped = nullptr;      // device view of the caller's page-locked buffer (the same address under unified addressing)
+    if (!sync && counts && hipHostGetDevicePointer(&mapped, counts, 0) != hipSuccess) {
+      (void)hipGetLastError();
+      if (dev) return BDS_EINVAL;
+      mapped = nullptr;
+    }
+    hipLaunchKernelGGL(finish_counts_kernel, dim3(1), dim3(256), 0, st, btot, nblocks, counts_dev, static_cast<volatile int64_t *>(mapped),
+                       M_capacity, n_visible_capacity);
+    BDS_LAUNCH_CHECK();
+    if (!dev && mapped == nullptr &&   // synchronous form, or not mapped: the copy engine
+        hipMemcpyAsync(counts, counts_dev, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st) != hipSuccess)
+      return BDS_ELAUNCH;
+    if (sync && hipStreamSynchronize(st) != hipSuccess) return BDS_ELAUNCH;
+  }
+  if (event && hipEventRecord(static_cast<hipEvent_t>(event), st) != hipSuccess) return BDS_ELAUNCH;
   return BDS_OK;
 }
 
@@ -1416,13 +1385,15 @@ extern "C" size_t bds_isect_counts_offset(int which) {
   return (which >= 0 && which <= kCountOverflow) ? (size_t)which * sizeof(uint64_t) : (size_t)0;
 }
 
-// dev = true: M / n_visible are CAPACITIES (launch sizes, buffer sizes); the actual counts are read on the device from the
+// device_counts != 0: M / n_visible are CAPACITIES (launch sizes, buffer sizes); the actual counts are read on the device from the
 // "effective" slots of the prepare workspace (kCountMEff / kCountVisEff: zero when a count outgrew its capacity)
-static int isect_build_impl(int C, int64_t N, int64_t M, int64_t n_visible, const float *means2d, const int32_t *radii,
-                            const float *depths, const float *conics, const float *opacities, int tile_size,
-                            int tile_w, int tile_h, const void *ws,
-                            size_t ws_bytes, void *ws2, size_t ws2_bytes, int64_t *isect_ids, int32_t *flatten_ids,
-                            int32_t *isect_offsets, int32_t *visible_ids, int compact, bds_stream_t stream, bool dev) {
+extern "C" int bds_isect_build(int C, int64_t N, int64_t M, int64_t n_visible, const float *means2d, const int32_t *radii,
+                               const float *depths, const float *conics, const float *opacities, int tile_size,
+                               int tile_w, int tile_h, const void *ws,
+                               size_t ws_bytes, void *ws2, size_t ws2_bytes, int64_t *isect_ids, int32_t *flatten_ids,
+                               int32_t *isect_offsets, int32_t *visible_ids, int device_counts, int compact, bds_stream_t stream) {
+  const bool dev = device_counts != 0;
+  if (dev) BDS_REQUIRE(M > 0 && n_visible > 0 && !isect_ids && !visible_ids);
   BDS_REQUIRE(C >= 1 && N >= 0 && M >= 0 && tile_size > 0 && tile_w > 0 && tile_h > 0 && isect_offsets);
   BDS_REQUIRE(!(compact && isect_ids));          // the 64-bit keys need the Gaussian ids
   BDS_REQUIRE(!visible_ids || n_visible >= 0);
@@ -1529,37 +1500,19 @@ static int isect_build_impl(int C, int64_t N, int64_t M, int64_t n_visible, cons
   return BDS_OK;
 }
 
-extern "C" int bds_isect_build(int C, int64_t N, int64_t M, int64_t n_visible, const float *means2d, const int32_t *radii,
-                               const float *depths, const float *conics, const float *opacities, int tile_size,
-                               int tile_w, int tile_h, const void *ws,
-                               size_t ws_bytes, void *ws2, size_t ws2_bytes, int64_t *isect_ids, int32_t *flatten_ids,
-                               int32_t *isect_offsets, int32_t *visible_ids, int compact, bds_stream_t stream) {
-  return isect_build_impl(C, N, M, n_visible, means2d, radii, depths, conics, opacities, tile_size, tile_w, tile_h, ws, ws_bytes, ws2,
-                          ws2_bytes, isect_ids, flatten_ids, isect_offsets, visible_ids, compact, stream, false);
-}
-
-extern "C" int bds_isect_build_dev(int C, int64_t N, int64_t M_capacity, int64_t n_visible_capacity, const float *means2d,
-                                   const int32_t *radii, const float *depths, const float *conics, const float *opacities,
-                                   int tile_size, int tile_w, int tile_h, const void *ws, size_t ws_bytes, void *ws2,
-                                   size_t ws2_bytes, int32_t *flatten_ids, int32_t *isect_offsets, int compact, bds_stream_t stream) {
-  BDS_REQUIRE(M_capacity > 0 && n_visible_capacity > 0);
-  return isect_build_impl(C, N, M_capacity, n_visible_capacity, means2d, radii, depths, conics, opacities, tile_size, tile_w, tile_h, ws,
-                          ws_bytes, ws2, ws2_bytes, nullptr, flatten_ids, isect_offsets, nullptr, compact, stream, true);
-}
-
 extern "C" int bds_isect_tiles(int C, int64_t N, const float *means2d, const int32_t *radii, const float *depths,
                                const float *conics, const float *opacities, int tile_size, int tile_w, int tile_h,
                                int32_t *tiles_per_gauss, void *ws, size_t ws_bytes, void *ws2, size_t ws2_bytes,
                                int64_t flatten_capacity, int64_t *isect_ids, int32_t *flatten_ids, int32_t *isect_offsets,
                                int64_t *n_isects, int64_t *n_visible, bds_stream_t stream) {
   BDS_REQUIRE(flatten_capacity >= 0 && n_isects);
-  int64_t nvis_local = 0;
-  if (!n_visible) n_visible = &nvis_local;
+  int64_t counts[2];   // M, visible entries
   int rc = bds_isect_prepare(C, N, means2d, radii, depths, conics, opacities, tile_size, tile_w, tile_h, tiles_per_gauss, ws,
-                             ws_bytes, n_isects, n_visible, 0, stream);
+                             ws_bytes, -1, -1, counts, nullptr, 0, stream);
+  const int64_t M = *n_isects = counts[0];
+  if (n_visible) *n_visible = counts[1];
   if (rc != BDS_OK) return rc;
-  const int64_t M = *n_isects;
   if (M > flatten_capacity || (M > 0 && ws2_bytes < build_layout(nullptr, M).bytes)) return BDS_ECAPACITY;
-  return bds_isect_build(C, N, M, *n_visible, means2d, radii, depths, conics, opacities, tile_size, tile_w, tile_h, ws, ws_bytes, ws2,
-                         ws2_bytes, isect_ids, flatten_ids, isect_offsets, nullptr, 0, stream);
+  return bds_isect_build(C, N, M, counts[1], means2d, radii, depths, conics, opacities, tile_size, tile_w, tile_h, ws, ws_bytes, ws2,
+                         ws2_bytes, isect_ids, flatten_ids, isect_offsets, nullptr, 0, 0, stream);
 }

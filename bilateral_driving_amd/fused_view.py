@@ -53,8 +53,8 @@ _SYNC: Dict[torch.device, list] = {}
 
 
 def _host_sync_objects(dev):
-    """(page-locked int64[3], event) used to read the two list counts back without draining the stream.  A front OWNS its pair from
-    ``_front_begin`` until ``_front_finish`` has read the counts (``_release_sync_objects``): any number of fronts may be in flight
+    """(page-locked int64[3], event) used to read the two list counts back without draining the stream.  A tile stage OWNS its pair
+    from ``_lists_begin`` until ``_lists_finish`` has read the counts (``_release_sync_objects``): any number of views may be in flight
     (``render_classes`` next to a training view)."""
     free = _SYNC.setdefault(dev, [])
     if free:
@@ -106,7 +106,9 @@ class ListCapacity:
         return bool(self.counts.np[2])
 
 
-_LIST_CAPACITY: Dict[tuple, int] = {}   # (N, W, H, culling) -> entries to provision for the intersection lists
+# (N, W, H, culling, list tile) -> [list entries, visible Gaussians] seen so far: the lists and the splat records are provisioned
+# before the wait
+_CAPACITY: Dict[tuple, list] = {}
 
 
 class _Info(dict):
@@ -148,12 +150,14 @@ class _Front:
     forward and by the evaluation re-renders (``render_classes``), which composite several opacity masks over ONE front.
     ``_front_begin`` fills the first half (nothing there depends on the host), ``_front_finish`` waits for the two list counts and
     adds the lists.  Plain attribute bag: inputs (means, quats, log_scales, sh, viewmat, cam_pos), projection outputs (scales, opac,
-    radii, means2d, depths, conics), colours (sh_rgb, colors / sh_by_rank), tile-stage state (ws, counts, ev, capacities ...) and,
-    after ``_front_finish``: flatten, vis_ids, isect_offsets, M, n_vis."""
+    radii, means2d, depths, conics), colours (sh_rgb, colors / sh_by_rank), the tile stage (``lists``: ``_Lists``; ws, tiles_per_gauss,
+    isect_offsets) and, after ``_front_finish``, its results: flatten, vis_ids, M, n_vis, m_dev, nvis_dev, rec_buf."""
     pass
 
 
-_VIS_CAPACITY: Dict[tuple, int] = {}   # visible-Gaussian count seen per configuration: the splat records are provisioned before the wait
+class _Lists:
+    """The tile stage of one view between ``_lists_begin`` and ``_lists_finish``; attribute bag."""
+    pass
 
 
 SPLIT_POOL_PER_TILE = int(os.environ.get("BDS_SPLIT_POOL_PER_TILE", "4096"))   # refined-list pool: int32 words per long tile of the capacity (0 = no refinement)
@@ -194,8 +198,8 @@ def _view_front(cfg: dict, means, quats, log_scales, logits, sh, viewmat, before
 
 
 def _front_begin(cfg: dict, means, quats, log_scales, logits, sh, viewmat) -> _Front:
-    """First half of a view's forward: activations + projection, visibility compaction, depth order, tile counts (whose totals travel
-    to the host asynchronously) and the SH colours.  Nothing here depends on the host."""
+    """First half of a view's forward: activations + projection, the tile stage's first half (``_lists_begin``) and the SH colours.
+    Nothing here depends on the host."""
     sh_rest = None
     if isinstance(sh, (tuple, list)):     # split storage, as the reference's classes hold it: (band 0 [N,3], bands 1.. [N,K-1,3])
         sh, sh_rest = sh[0].contiguous(), sh[1].contiguous()
@@ -244,49 +248,17 @@ def _front_begin(cfg: dict, means, quats, log_scales, logits, sh, viewmat) -> _F
                 L.check(rc, "bds_project_view_fwd")
         if not pre_reduced:
             L.check(lib.bds_project_view_fwd(*args, None, None, 0, L.ptr(bounds), st), "bds_project_view_fwd")
-    # tile ordering
-    LT = cfg.get("list_tile", LIST_TILE)
-    tw, th = math.ceil(W / LT), math.ceil(H / LT)      # list tiles
-    cull = cfg["tile_cull"]
-    isect_offsets = _empty((1, th, tw), dev, torch.int32)
-    cptr, optr = (_dp(conics), _dp(opac_row)) if cull else (None, None)
-    if caps is not None:
-        counts, ev = caps.counts, None
-        _tile_stage_options()
-        with L.timed("isect_prepare"):
-            L.check(lib.bds_isect_prepare_dev(1, N, _dp(means2d), L.ptr(radii), _dp(depths), cptr, optr, LT, tw, th,
-                                              L.ptr(tiles_per_gauss), L.ptr(ws), ws_bytes, caps.m_cap, caps.nvis_cap,
-                                              counts.data_ptr(), 3 if pre_reduced else 1, st), "bds_isect_prepare_dev")
-    else:
-        counts, ev = _host_sync_objects(dev)
-        with L.timed("isect_prepare"):
-            L.check(lib.bds_isect_prepare_async(1, N, _dp(means2d), L.ptr(radii), _dp(depths), cptr, optr, LT, tw, th,
-                                                L.ptr(tiles_per_gauss), L.ptr(ws), ws_bytes, counts.data_ptr(), ev.cuda_event, 1, st),
-                    "bds_isect_prepare_async")
+    f = _Front()
+    f.list_tile = cfg.get("list_tile", LIST_TILE)
+    f.lists = _lists_begin(means2d, radii, depths, (_dp(conics), _dp(opac_row)) if cfg["tile_cull"] else None, W, H, f.list_tile, caps,
+                           ws, ws_bytes, tiles_per_gauss, pre_reduced)
     # While the host waits for the two counts, the GPU evaluates the SH colours (vanilla.py:384-389), which do not
-    # depend on the lists; the list buffers are provisioned beforehand from the largest count seen so far.
+    # depend on the lists.
     cam_pos = cfg["cam_pos"].contiguous()
     if pack_colours:
         sh_rgb, colors = None, None        # evaluated by the record pack, for the visible Gaussians only (_composite)
     else:
         sh_rgb, colors = _empty((N, 3), dev), _empty((1, N, 4), dev)
-        if caps is None or os.environ.get("BDS_SH_BEFORE_BUILD") == "1":
-            with L.timed("sh_fwd"):
-                L.check(lib.bds_sh_view_fwd(N, K, cfg["sh_degree"], L.ptr(means), L.ptr(cam_pos), L.ptr(sh), L.ptr(radii), L.ptr(depths),
-                                            L.ptr(sh_rgb), L.ptr(colors), st), "bds_sh_view_fwd")
-        # (device-count form: nobody waits, and the SH pass is enqueued BEHIND the list build -- _front_finish_dev: next to another
-        # stream's compositor backward the build's five small launches crawl, a streaming pass over the coefficients does not)
-    key = (N, W, H, bool(cull), LT)
-    cap = _LIST_CAPACITY.get(key, 0) if caps is None else caps.m_cap
-    buf, ws2, ws2_bytes = None, None, 0
-    if cap:
-        buf = _empty((cap,), dev, torch.int32)
-        ws2_bytes = lib.bds_isect_build_workspace_bytes(1, N, cap)
-        ws2 = _empty((max(ws2_bytes, 16),), dev, torch.uint8)
-    vcap = _VIS_CAPACITY.get(key, 0) if caps is None else caps.nvis_cap
-    rec_buf = _empty((vcap, L.SPLAT_RECORD_FLOATS), dev) if vcap else None
-    off = lib.bds_isect_visible_ids_offset(1, N)
-    f = _Front()
     f.cfg = cfg
     f.means, f.quats, f.log_scales, f.sh, f.viewmat, f.cam_pos = means, quats, log_scales, sh, viewmat, cam_pos
     f.sh_rest, f.K = sh_rest, K
@@ -295,73 +267,110 @@ def _front_begin(cfg: dict, means, quats, log_scales, logits, sh, viewmat) -> _F
     #                             antialiased: opacity * comp -- the rows' column or a dense array of its own)
     f.aa = aa
     f.sh_rgb, f.colors, f.sh_by_rank, f.sh_degree = sh_rgb, colors, False, cfg["sh_degree"]
-    f.tiles_per_gauss, f.isect_offsets, f.ws, f.ws_bytes, f.cull = tiles_per_gauss, isect_offsets, ws, ws_bytes, cull
-    f.counts, f.ev, f.key, f.cap, f.vcap, f.caps = counts, ev, key, cap, vcap, caps
-    f.buf, f.ws2, f.ws2_bytes, f.rec_buf, f.ids_offset = buf, ws2, ws2_bytes, rec_buf, off
-    f.list_tile, f.list_tw, f.list_th = LT, tw, th
+    f.tiles_per_gauss, f.isect_offsets, f.ws = tiles_per_gauss, f.lists.isect_offsets, ws
     f.W, f.H, f.N = W, H, N
     f.tw, f.th = math.ceil(W / TILE), math.ceil(H / TILE)   # compositing tiles
+    # (device-count form: nobody waits, and the SH pass is enqueued BEHIND the list build: next to another stream's compositor backward
+    # the build's five small launches crawl, a streaming pass over the coefficients does not)
+    f.sh_behind_build = caps is not None and os.environ.get("BDS_SH_BEFORE_BUILD") != "1"
+    if colors is not None and not f.sh_behind_build:
+        _sh_dense(f)
     return f
+
+
+def _sh_dense(f: _Front) -> None:
+    """SH colours of all N Gaussians (the views whose record pack does not evaluate them)."""
+    with L.timed("sh_fwd"):
+        L.check(L.lib().bds_sh_view_fwd(f.N, f.sh.shape[1], f.sh_degree, L.ptr(f.means), L.ptr(f.cam_pos), L.ptr(f.sh), L.ptr(f.radii),
+                                        L.ptr(f.depths), L.ptr(f.sh_rgb), L.ptr(f.colors), L.stream()), "bds_sh_view_fwd")
 
 
 def _front_finish(f: _Front, before_wait=None) -> _Front:
-    """Second half: the one host wait of a view (list counts), then the per-tile lists."""
-    lib, st = L.lib(), L.stream()
-    dev, N = f.means.device, f.N
-    cptr, optr = (_dp(f.conics), _dp(f.opac_row)) if f.cull else (None, None)
+    """Second half: the caller's ``before_wait`` work, then the tile stage's second half with the one host wait of a view."""
     f.pre = before_wait() if before_wait is not None else None
-    if f.caps is not None:
-        return _front_finish_dev(f)
-    f.ev.synchronize()
-    M, n_vis = int(f.counts.np[0]), int(f.counts.np[1])
-    _release_sync_objects(dev, (f.counts, f.ev))
-    if f.rec_buf is None or n_vis > f.vcap:
-        f.rec_buf = _empty((n_vis, L.SPLAT_RECORD_FLOATS), dev)
-    if n_vis + n_vis // 16 > f.vcap:
-        _VIS_CAPACITY[f.key] = n_vis + n_vis // 6 + 1024
-    buf, ws2, ws2_bytes = f.buf, f.ws2, f.ws2_bytes
-    if M > f.cap or buf is None:   # first call of this configuration, or the lists outgrew the expectation
-        buf = _empty((M,), dev, torch.int32)
-        ws2_bytes = lib.bds_isect_build_workspace_bytes(1, N, M)
-        ws2 = _empty((max(ws2_bytes, 16),), dev, torch.uint8)
-    f.flatten = buf[:M]                                # per-tile lists of COMPACT positions (they address the splat records)
-    # ascending ids of the visible Gaussians: compact position -> id, the work list of everything downstream (walks memory in
-    # order).  Read in place from the prepare workspace (which this view keeps alive): no copy node between the kernels.
-    f.vis_ids = f.ws[f.ids_offset:f.ids_offset + 4 * n_vis].view(torch.int32)
-    with L.timed("isect_build"):
-        L.check(lib.bds_isect_build(1, N, M, n_vis, _dp(f.means2d), L.ptr(f.radii), _dp(f.depths), cptr, optr, f.list_tile, f.list_tw,
-                                    f.list_th, L.ptr(f.ws), f.ws_bytes, L.ptr(ws2), ws2_bytes, None, L.ptr(f.flatten),
-                                    L.ptr(f.isect_offsets), None, 1, st), "bds_isect_build")
-    if M + M // 16 > f.cap:
-        _LIST_CAPACITY[f.key] = M + M // 6 + 4096
-    f.buf = f.ws2 = None
-    f.M, f.n_vis = M, n_vis
-    f.m_dev = f.nvis_dev = None
+    s = _lists_finish(f.lists)
+    if f.colors is not None and f.sh_behind_build:
+        _sh_dense(f)
+    f.flatten, f.vis_ids, f.M, f.n_vis, f.m_dev, f.nvis_dev, f.rec_buf = s.flatten, s.vis_ids, s.M, s.n_vis, s.m_dev, s.nvis_dev, s.rec_buf
+    f.lists = None
     return f
 
 
-def _front_finish_dev(f: _Front) -> _Front:
-    """Device-count form of the second half: no wait.  The lists are built into buffers of the capacities, every kernel downstream
-    reads the two EFFECTIVE counts from the first words of the prepare workspace (f.m_dev / f.nvis_dev: device addresses)."""
+def _lists_begin(means2d, radii, depths, cull, W: int, H: int, list_tile: int, caps: Optional[ListCapacity] = None, ws=None,
+                 ws_bytes: int = 0, tiles_per_gauss=None, pre_reduced: bool = False) -> _Lists:
+    """First half of one camera's tile stage, whatever projection made ``means2d`` [1,N,2] / ``radii`` [1,N] / ``depths`` [1,N]:
+    visibility compaction, depth order and tile counts, whose two totals travel to the host asynchronously -- or, with ``caps``, stay on
+    the device (include/bds.h "tile intersection").  ``cull``: (conics, opacities) device addresses for the exact tile cull, or None.
+    ``ws`` / ``ws_bytes``: the prepare workspace where the caller has made it already (``pre_reduced``: the projection has left the
+    visible counts in it), ``tiles_per_gauss`` likewise; else allocated here.  Nothing here depends on the host."""
     lib, st = L.lib(), L.stream()
-    N = f.N
-    cptr, optr = (_dp(f.conics), _dp(f.opac_row)) if f.cull else (None, None)
-    M, n_vis = f.caps.m_cap, f.caps.nvis_cap
-    f.flatten = f.buf
-    f.vis_ids = f.ws[f.ids_offset:f.ids_offset + 4 * n_vis].view(torch.int32)
+    dev, N = radii.device, radii.shape[1]
+    s = _Lists()
+    if ws is None:
+        ws_bytes = lib.bds_isect_prepare_workspace_bytes(1, N)
+        ws = _empty((max(ws_bytes, 16),), dev, torch.uint8)
+    if tiles_per_gauss is None:
+        tiles_per_gauss = _empty((1, N), dev, torch.int32)
+    tw, th = math.ceil(W / list_tile), math.ceil(H / list_tile)      # list tiles
+    s.isect_offsets = _empty((1, th, tw), dev, torch.int32)
+    s.args = (_dp(means2d), L.ptr(radii), _dp(depths), *(cull or (None, None)), list_tile, tw, th)      # shared by prepare and build
+    if caps is not None:
+        s.counts, s.ev = caps.counts, None
+        _tile_stage_options()
+        mode = (caps.m_cap, caps.nvis_cap, s.counts.data_ptr(), None, 3 if pre_reduced else 1)
+    else:
+        s.counts, s.ev = _host_sync_objects(dev)
+        mode = (-1, -1, s.counts.data_ptr(), s.ev.cuda_event, 1)
+    with L.timed("isect_prepare"):
+        L.check(lib.bds_isect_prepare(1, N, *s.args, L.ptr(tiles_per_gauss), L.ptr(ws), ws_bytes, *mode, st), "bds_isect_prepare")
+    s.N, s.caps, s.ws, s.ws_bytes, s.tiles_per_gauss = N, caps, ws, ws_bytes, tiles_per_gauss
+    s.key = (N, W, H, cull is not None, list_tile)
+    return s
+
+
+def _lists_finish(s: _Lists) -> _Lists:
+    """Second half: buffers from the capacity cache (or of ``caps``), the one host wait of a view (none with ``caps``), the per-tile
+    lists.  Adds flatten [M] (COMPACT positions: they address the splat records), vis_ids [n_vis], M, n_vis, rec_buf (splat records,
+    at least n_vis rows) and m_dev / nvis_dev: None, or with ``caps`` the device addresses of the two EFFECTIVE counts in the first
+    words of the prepare workspace, which every kernel downstream reads -- M / n_vis are then the capacities."""
+    lib, st = L.lib(), L.stream()
+    dev, N, caps = s.ws.device, s.N, s.caps
+
+    def list_buffers(m):
+        nbytes = lib.bds_isect_build_workspace_bytes(1, N, m)
+        return _empty((m,), dev, torch.int32), _empty((max(nbytes, 16),), dev, torch.uint8), nbytes
+
+    seen = _CAPACITY.setdefault(s.key, [0, 0]) if caps is None else (caps.m_cap, caps.nvis_cap)
+    M, n_vis = cap, vcap = seen
+    buf, ws2, ws2_bytes = list_buffers(cap) if cap else (None, None, 0)
+    rec_buf = _empty((vcap, L.SPLAT_RECORD_FLOATS), dev) if vcap else None
+    if caps is None:
+        s.ev.synchronize()
+        M, n_vis = int(s.counts.np[0]), int(s.counts.np[1])
+        _release_sync_objects(dev, (s.counts, s.ev))
+        if M + M // 16 > cap:
+            seen[0] = M + M // 6 + 4096
+        if n_vis + n_vis // 16 > vcap:
+            seen[1] = n_vis + n_vis // 6 + 1024
+    if buf is None or M > cap:   # first call of this configuration, or the lists outgrew the expectation
+        buf, ws2, ws2_bytes = list_buffers(M)
+    if rec_buf is None or n_vis > vcap:
+        rec_buf = _empty((n_vis, L.SPLAT_RECORD_FLOATS), dev)
+    s.rec_buf = rec_buf
+    s.flatten = buf[:M]
+    # ascending ids of the visible Gaussians: compact position -> id, the work list of everything downstream (walks memory in
+    # order).  Read in place from the prepare workspace (which the view keeps alive): no copy node between the kernels.
+    off = lib.bds_isect_visible_ids_offset(1, N)
+    s.vis_ids = s.ws[off:off + 4 * n_vis].view(torch.int32)
     with L.timed("isect_build"):
-        L.check(lib.bds_isect_build_dev(1, N, M, n_vis, _dp(f.means2d), L.ptr(f.radii), _dp(f.depths), cptr, optr, f.list_tile,
-                                        f.list_tw, f.list_th, L.ptr(f.ws), f.ws_bytes, L.ptr(f.ws2), f.ws2_bytes, L.ptr(f.flatten),
-                                        L.ptr(f.isect_offsets), 1, st), "bds_isect_build_dev")
-    if f.colors is not None and os.environ.get("BDS_SH_BEFORE_BUILD") != "1":
-        with L.timed("sh_fwd"):
-            L.check(lib.bds_sh_view_fwd(N, f.sh.shape[1], f.sh_degree, L.ptr(f.means), L.ptr(f.cam_pos), L.ptr(f.sh), L.ptr(f.radii),
-                                        L.ptr(f.depths), L.ptr(f.sh_rgb), L.ptr(f.colors), st), "bds_sh_view_fwd")
-    f.buf = f.ws2 = None
-    f.M, f.n_vis = M, n_vis
-    base = f.ws.data_ptr()
-    f.m_dev, f.nvis_dev = base + lib.bds_isect_counts_offset(2), base + lib.bds_isect_counts_offset(3)
-    return f
+        L.check(lib.bds_isect_build(1, N, M, n_vis, *s.args, L.ptr(s.ws), s.ws_bytes, L.ptr(ws2), ws2_bytes, None, L.ptr(s.flatten),
+                                    L.ptr(s.isect_offsets), None, int(caps is not None), 1, st), "bds_isect_build")
+    s.M, s.n_vis = M, n_vis
+    s.m_dev = s.nvis_dev = None
+    if caps is not None:
+        base = s.ws.data_ptr()
+        s.m_dev, s.nvis_dev = base + lib.bds_isect_counts_offset(2), base + lib.bds_isect_counts_offset(3)
+    return s
 
 
 def _image_buffers(W: int, H: int, dev):

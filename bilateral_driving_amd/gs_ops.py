@@ -166,23 +166,23 @@ def isect_tiles(means2d: Tensor, radii: Tensor, depths: Tensor, tile_size: int, 
     tiles_per_gauss = torch.empty(Cn, N, device=dev, dtype=torch.int32)
     ws_bytes = lib.bds_isect_prepare_workspace_bytes(Cn, N)
     ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
-    m, nv = C.c_int64(0), C.c_int64(0)
+    counts = (C.c_int64 * 2)()      # M, visible entries: the synchronous form
     with L.timed("isect_prepare"):
         L.check(lib.bds_isect_prepare(Cn, N, L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(conics), L.ptr(opacities),
                                       tile_size, tile_width, tile_height,
-                                      L.ptr(tiles_per_gauss), L.ptr(ws), ws_bytes, C.byref(m), C.byref(nv), 0, L.stream()),
+                                      L.ptr(tiles_per_gauss), L.ptr(ws), ws_bytes, -1, -1, counts, None, 0, L.stream()),
                 "bds_isect_prepare")
-    M = int(m.value)
+    M, n_vis = counts
     flatten_ids = torch.empty(M, device=dev, dtype=torch.int32)
     isect_ids = torch.empty(M, device=dev, dtype=torch.int64) if want_isect_ids else None
     isect_offsets = torch.empty(Cn, tile_height, tile_width, device=dev, dtype=torch.int32)
     ws2_bytes = lib.bds_isect_build_workspace_bytes(Cn, N, M)
     ws2 = torch.empty(max(ws2_bytes, 16), device=dev, dtype=torch.uint8)
     with L.timed("isect_build"):
-        L.check(lib.bds_isect_build(Cn, N, M, int(nv.value), L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(conics), L.ptr(opacities),
+        L.check(lib.bds_isect_build(Cn, N, M, n_vis, L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(conics), L.ptr(opacities),
                                     tile_size, tile_width, tile_height,
                                     L.ptr(ws), ws_bytes, L.ptr(ws2), ws2_bytes, L.ptr(isect_ids), L.ptr(flatten_ids),
-                                    L.ptr(isect_offsets), None, 0, L.stream()), "bds_isect_build")
+                                    L.ptr(isect_offsets), None, 0, 0, L.stream()), "bds_isect_build")
     return tiles_per_gauss, isect_ids, flatten_ids, isect_offsets
 
 

@@ -21,11 +21,6 @@ from . import _lib as L
 from .lazy_gaussians import lazy_source, materialised
 
 
-def _tfinal_ptr(alphas):       # (the T_final plane behind an ``alphas`` tensor: fused_view._tfinal_ptr)
-    from .fused_view import _tfinal_ptr as f
-    return f(alphas)
-
-
 _SPLIT_RENDER = os.environ.get("BDS_API_SPLIT_RENDER", "1") == "1"
 
 
@@ -107,6 +102,7 @@ def _split_materialised(x):
     if isinstance(x, dict):
         return {k: _split_materialised(v) for k, v in x.items()}
     return x
+from .fused_view import _composite, _image_buffers, _lists_begin, _lists_finish, _tfinal_ptr, _view_front
 from .gs_ops import (TILE_SIZE, _f32c, bwd_schedule, fully_fused_projection, isect_tiles, rasterize_to_pixels, spherical_harmonics)
 
 
@@ -170,7 +166,6 @@ def set_tile_culling(on: bool) -> None:
 _ONE_VIEW_NODE = os.environ.get("BDS_API_FUSED", "1") != "0"
 _CHECK_FINITE = os.environ.get("BDS_API_CHECK_FINITE", "1") != "0"    # the raw one-view node's NaN / Inf check (vanilla.py:407-412)
 _LIST_TILE = 64          # list tiles of the one-view node (the splat records carry the radii: the image is the 16-px one)
-_CAPACITY: Dict[tuple, list] = {}      # (N, W, H) -> [list entries, visible Gaussians] seen so far: buffers provisioned before the wait
 
 
 class _RasterizeView(torch.autograd.Function):
@@ -183,7 +178,6 @@ class _RasterizeView(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means, quats, scales, opacities, colors, viewmat, Kmat, cfg):
-        from .fused_view import _host_sync_objects, _release_sync_objects
         L.require_gpu(means, quats, scales, opacities, colors, viewmat, Kmat)
         means, quats, scales, opacities, colors, viewmat, Kmat = map(_f32c, (means, quats, scales, opacities, colors, viewmat, Kmat))
         lib, st = L.lib(), L.stream()
@@ -196,57 +190,19 @@ class _RasterizeView(torch.autograd.Function):
             L.check(lib.bds_project_fwd(1, N, L.ptr(means), L.ptr(quats), L.ptr(scales), None if opac_eff is None else L.ptr(opacities),
                                         L.ptr(viewmat), L.ptr(Kmat), W, H, cfg["eps2d"], cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"],
                                         L.ptr(radii), L.ptr(means2d), L.ptr(depths), L.ptr(conics), None, L.ptr(opac_eff), st), "bds_project_fwd")
-        LT = _LIST_TILE
-        ltw, lth = math.ceil(W / LT), math.ceil(H / LT)
-        tw, th = math.ceil(W / TILE_SIZE), math.ceil(H / TILE_SIZE)
         opac_c = opacities.view(1, N) if opac_eff is None else opac_eff
-        cull = cfg["cull"]
-        cptr, optr = (L.ptr(conics), L.ptr(opac_c)) if cull else (None, None)
-        tiles_per_gauss = torch.empty(1, N, device=dev, dtype=torch.int32)
-        ws_bytes = lib.bds_isect_prepare_workspace_bytes(1, N)
-        ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
-        counts, ev = _host_sync_objects(dev)
-        with L.timed("isect_prepare"):
-            L.check(lib.bds_isect_prepare_async(1, N, L.ptr(means2d), L.ptr(radii), L.ptr(depths), cptr, optr, LT, ltw, lth,
-                                                L.ptr(tiles_per_gauss), L.ptr(ws), ws_bytes, counts.data_ptr(), ev.cuda_event, 1, st),
-                    "bds_isect_prepare_async")
-        # while the two counts travel to the host: every buffer whose size is known
-        colors3 = colors.reshape(N, 3)
-        key = (N, W, H)
-        cap = _CAPACITY.setdefault(key, [0, 0])
-        flat_buf = torch.empty(cap[0], device=dev, dtype=torch.int32) if cap[0] else None
-        ws2_bytes = lib.bds_isect_build_workspace_bytes(1, N, cap[0]) if cap[0] else 0
-        ws2 = torch.empty(max(ws2_bytes, 16), device=dev, dtype=torch.uint8) if cap[0] else None
-        rec_buf = torch.empty(cap[1], L.SPLAT_RECORD_FLOATS, device=dev) if cap[1] else None
-        isect_offsets = torch.empty(1, lth, ltw, device=dev, dtype=torch.int32)
-        render = torch.empty(1, H, W, 4, device=dev)
-        alphas = torch.empty(2, H, W, 1, device=dev)[0:1]     # (second plane: every pixel's final transmittance, fused_view._tfinal_ptr)
-        last_ids = torch.empty(1, H, W, device=dev, dtype=torch.int32)
-        ev.synchronize()
-        M, n_vis = int(counts.np[0]), int(counts.np[1])
-        _release_sync_objects(dev, (counts, ev))
-        if flat_buf is None or M > cap[0]:
-            flat_buf = torch.empty(M, device=dev, dtype=torch.int32)
-            ws2_bytes = lib.bds_isect_build_workspace_bytes(1, N, M)
-            ws2 = torch.empty(max(ws2_bytes, 16), device=dev, dtype=torch.uint8)
-        if rec_buf is None or n_vis > cap[1]:
-            rec_buf = torch.empty(n_vis, L.SPLAT_RECORD_FLOATS, device=dev)
-        if M + M // 16 > cap[0]:
-            cap[0] = M + M // 6 + 4096
-        if n_vis + n_vis // 16 > cap[1]:
-            cap[1] = n_vis + n_vis // 6 + 1024
-        flatten, rec = flat_buf[:M], rec_buf[:n_vis]
-        off = lib.bds_isect_visible_ids_offset(1, N)
-        vis_ids = ws[off:off + 4 * n_vis].view(torch.int32)       # ascending ids of the visible Gaussians, read in place
-        with L.timed("isect_build"):
-            L.check(lib.bds_isect_build(1, N, M, n_vis, L.ptr(means2d), L.ptr(radii), L.ptr(depths), cptr, optr, LT, ltw, lth, L.ptr(ws),
-                                        ws_bytes, L.ptr(ws2), ws2_bytes, None, L.ptr(flatten), L.ptr(isect_offsets), None, 1, st),
-                    "bds_isect_build")
+        lists = _lists_begin(means2d, radii, depths, (L.ptr(conics), L.ptr(opac_c)) if cfg["cull"] else None, W, H, _LIST_TILE)
+        render, alphas, last_ids = _image_buffers(W, H, dev)     # (while the two counts travel to the host)
+        _lists_finish(lists)
+        M, n_vis, vis_ids, ws, flatten, isect_offsets = lists.M, lists.n_vis, lists.vis_ids, lists.ws, lists.flatten, lists.isect_offsets
+        rec = lists.rec_buf[:n_vis]
+        tw, th = math.ceil(W / TILE_SIZE), math.ceil(H / TILE_SIZE)
         with L.timed("rasterize_fwd"):
-            L.check(lib.bds_splat_pack_rgbd(n_vis, L.ptr(vis_ids), L.ptr(means2d), L.ptr(conics), L.ptr(colors3), L.ptr(depths),
+            L.check(lib.bds_splat_pack_rgbd(n_vis, L.ptr(vis_ids), L.ptr(means2d), L.ptr(conics), L.ptr(colors.reshape(N, 3)), L.ptr(depths),
                                             L.ptr(opac_c), L.ptr(radii), L.ptr(rec), st), "bds_splat_pack_rgbd")
-            L.check(lib.bds_rasterize_fwd(1, n_vis, M, None, 4, L.ptr(rec), None, W, H, TILE_SIZE, LT, tw, th, L.ptr(isect_offsets), L.ptr(flatten),
-                                          L.ptr(render), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), None, 0, 0, 0, st), "bds_rasterize_fwd")
+            L.check(lib.bds_rasterize_fwd(1, n_vis, M, None, 4, L.ptr(rec), None, W, H, TILE_SIZE, _LIST_TILE, tw, th, L.ptr(isect_offsets),
+                                          L.ptr(flatten), L.ptr(render), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), None, 0, 0, 0, st),
+                    "bds_rasterize_fwd")
         ctx.save_for_backward(means, quats, scales, opacities, viewmat, Kmat, rec, vis_ids, ws, flatten, isect_offsets, render, alphas, last_ids)
         ctx.cfg, ctx.M = cfg, M
         if cfg["ed"]:      # expected depth: D / clamp(alpha, 1e-10) (gsplat "ED")
@@ -284,7 +240,6 @@ class _RasterizeRawView(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means, quats, log_scales, logits, dc, rest, viewmat, Kmat, cfg):
-        from .fused_view import _composite, _image_buffers, _view_front
         L.require_gpu(means, quats, log_scales, logits, dc, rest, viewmat, Kmat)
         means, quats, log_scales, logits, dc, rest, viewmat, Kmat = map(_f32c, (means, quats, log_scales, logits, dc, rest, viewmat, Kmat))
         lib, st = L.lib(), L.stream()

@@ -10,8 +10,8 @@
  * Conventions
  *   - every pointer is a DEVICE pointer to contiguous row-major memory (fp32 unless noted),
  *     owned by the caller (the torch caching allocator); nothing is allocated inside;
- *   - every call is asynchronous on `stream` (a hipStream_t passed as void*), except
- *     bds_isect_prepare which must hand the intersection count back to the host;
+ *   - every call is asynchronous on `stream` (a hipStream_t passed as void*), except the
+ *     synchronous form of bds_isect_prepare, which hands the intersection count back to the host;
  *   - return value: BDS_OK or a negative BDS_E* code; never throws, never exits;
  *   - C = cameras, N = Gaussians, M = tile intersections, H/W = image size, tile = 16.
  */
@@ -25,10 +25,11 @@
 extern "C" {
 #endif
 
-#define BDS_ABI_VERSION 4   /* 3: the projection's entries folded into four (bds_project_fwd, bds_project_view_fwd and
+#define BDS_ABI_VERSION 5   /* 3: the projection's entries folded into four (bds_project_fwd, bds_project_view_fwd and
                                bds_project_view_bwd_list changed signatures)
                                4: the view path's host-count / device-count / split-storage twins folded into one entry each
-                               (bds_splat_pack, bds_splat_pack_sh, bds_rasterize_fwd / _bwd, bds_sh_view_bwd_list, bds_view_grads_clear_list) */
+                               (bds_splat_pack, bds_splat_pack_sh, bds_rasterize_fwd / _bwd, bds_sh_view_bwd_list, bds_view_grads_clear_list)
+                               5: the tile stage's five entries folded into two (bds_isect_prepare and bds_isect_build changed signatures) */
 
 #define BDS_OK 0
 #define BDS_EINVAL (-1)      /* null / misaligned pointer, bad shape or unsupported parameter */
@@ -108,17 +109,31 @@ int bds_project_bwd(int C, int64_t N, const float *means, const float *quats, co
 
 /* ---- tile intersection + (tile|depth) ordering -------------------------------------------
  * isect_tiles + radix sort + isect_offset_encode stages of gsplat.rendering.rasterization.
- * Two calls because the host must size the [M] outputs:
+ * Two calls because somebody must size the [M] outputs:
  *   bds_isect_prepare : depth-orders the visible Gaussians, counts their tiles in that order (per-member
- *                       records and per-256-member totals stay in `ws`); synchronises `stream` and
- *                       returns M in *n_isects.
+ *                       records and per-256-member totals stay in `ws`) and leaves the two counts, M and the
+ *                       number of visible entries, where the caller asked for them (below).
  *   bds_isect_build   : emits (camera*tiles+tile, id) pairs in depth order, stable-sorts them
  *                       by tile, writes flatten_ids [M] i32 (= cam*N+gaussian), isect_offsets
  *                       [C,th,tw] i32 and, if not NULL, isect_ids [M] i64
  *                       (cam|tile id << 32 | fp32 depth bits), identical to sorting the 64-bit
  *                       keys directly.
  * `ws` (bds_isect_prepare_workspace_bytes) must stay alive and untouched between the two calls;
- * `ws2` (bds_isect_build_workspace_bytes) is scratch for build.  M must be < 2^31. */
+ * `ws2` (bds_isect_build_workspace_bytes) is scratch for build.  M must be < 2^31.
+ *
+ * THREE WAYS OF GETTING THE COUNTS, selected by M_capacity / n_visible_capacity (both negative, or both >= 0) and `event`:
+ *   synchronous  (capacities < 0, event NULL): `counts` = int64[2] in any host memory, zeroed on entry; the call synchronises
+ *                `stream` and returns with counts = {M, visible entries}.
+ *   asynchronous (capacities < 0, an event): same work, but instead of synchronising the GPU itself writes {M, visible entries}
+ *                into `counts` (int64[2], page-locked host memory; a buffer the device cannot address is filled by the copy
+ *                engine) and `event` (a hipEvent_t) is recorded on the stream.  The caller may enqueue independent work, then
+ *                waits for the event, reads the counts and calls bds_isect_build: the GPU keeps running that work while the
+ *                host sizes the lists.
+ *   device-count (capacities >= 0; event must be NULL, C*N > 0): nothing is read back; see "device-count forms" below for the
+ *                effective counts and overflow.  `counts` = page-locked int64[3] {M, visible entries, overflow} written by the
+ *                GPU, or NULL (a buffer the device cannot address: BDS_EINVAL).  bds_isect_build is then called with
+ *                device_counts = 1 and the same capacities as M / n_visible (both > 0; isect_ids and visible_ids NULL).
+ * Any other combination is BDS_EINVAL. */
 size_t bds_isect_prepare_workspace_bytes(int C, int64_t N);
 /* Byte offset, inside the prepare workspace, of the ascending id list of the visible entries (int32 [n_visible], compact mode):
  * a caller that keeps `ws` alive reads the list in place and passes visible_ids = NULL to bds_isect_build (no copy). */
@@ -128,32 +143,26 @@ size_t bds_isect_build_workspace_bytes(int C, int64_t N, int64_t M);
  * pixel centre can reach alpha >= 1/255 are dropped ("exact tile culling"): rendered images and
  * gradients are unchanged, M shrinks; when NULL the lists are gsplat's bounding-square lists.
  * tiles_per_gauss [C,N] i32 may be NULL (the per-Gaussian counts are then not written). */
-/* n_visible (may be NULL): number of (camera, Gaussian) entries with radii > 0.  Handing it to bds_isect_build
+/* n_visible: number of (camera, Gaussian) entries with radii > 0.  Handing it to bds_isect_build
  * (or -1 when unknown) lets the build use PACKED lists when every entry's depth rank fits next to the tile key in one
  * 32-bit word (rank < 2^(32 - bits(C*tiles))): the tile sort then moves 4 bytes per entry instead of 8.  Same outputs. */
 int bds_isect_prepare(int C, int64_t N, const float *means2d, const int32_t *radii, const float *depths,
                       const float *conics, const float *opacities, int tile_size, int tile_w, int tile_h,
-                      int32_t *tiles_per_gauss, void *ws, size_t ws_bytes, int64_t *n_isects, int64_t *n_visible, int compact,
-                      bds_stream_t stream);
+                      int32_t *tiles_per_gauss, void *ws, size_t ws_bytes, int64_t M_capacity, int64_t n_visible_capacity,
+                      int64_t *counts, void *event, int compact, bds_stream_t stream);
 int bds_isect_build(int C, int64_t N, int64_t M, int64_t n_visible, const float *means2d, const int32_t *radii,
                     const float *depths,
                     const float *conics, const float *opacities, int tile_size, int tile_w, int tile_h, const void *ws,
                     size_t ws_bytes, void *ws2,
                     size_t ws2_bytes, int64_t *isect_ids, int32_t *flatten_ids, int32_t *isect_offsets,
-                    int32_t *visible_ids, int compact, bds_stream_t stream);
-/* COMPACT lists (no reference counterpart).  compact != 0 (the same value in prepare and build; isect_ids must be NULL): every
+                    int32_t *visible_ids, int device_counts, int compact, bds_stream_t stream);
+/* COMPACT lists (no reference counterpart).  compact bit 0 (the same value in prepare and build; isect_ids must be NULL): every
  * intersection's list value is the entry's POSITION in the ascending list of the visible entries instead of its id cam*N+g
  * (same list order).  visible_ids (may be NULL; needs n_visible >= 0) receives that ascending list (position -> id) in either
  * mode.  Compact lists address splat records packed through visible_ids (bds_splat_pack), the compositor's gradient records
  * come back in that order, and everything downstream walks the visible ~15 % of the scene in memory order.
- * Asynchronous prepare: same work, but instead of synchronising it copies {M, n_visible} into `counts_pinned`
- * (int64[2], page-locked host memory) and records `event` (a hipEvent_t) on the stream.  The caller may enqueue
- * independent work, then waits for the event, reads the counts and calls bds_isect_build: the GPU keeps running that
- * work while the host sizes the lists. */
-int bds_isect_prepare_async(int C, int64_t N, const float *means2d, const int32_t *radii, const float *depths,
-                            const float *conics, const float *opacities, int tile_size, int tile_w, int tile_h,
-                            int32_t *tiles_per_gauss, void *ws, size_t ws_bytes, int64_t *counts_pinned, void *event,
-                            int compact, bds_stream_t stream);
+ * compact bit 1 (prepare only): the workspace already holds the visible counts and cleared tables of bds_project_view_fwd's
+ * prep_ws (one launch less). */
 /* One-call form: bds_isect_prepare and then, without returning to the caller in between, bds_isect_build into
  * buffers sized for an EXPECTED count (flatten_ids / isect_ids hold flatten_capacity entries, ws2 is
  * bds_isect_build_workspace_bytes(C, N, flatten_capacity)).  M <= flatten_capacity: BDS_OK, *n_isects = M, lists
@@ -379,7 +388,7 @@ int bds_l1_tv_train(int64_t n, const float *a, const float *b, int nlevels, cons
  * be the COLUMNS of one 16-byte aligned [N,8] block of 32-byte rows {m2d.x, m2d.y, depth, radius (int bits) | conic a, b, c, opacity}:
  * pass means2d = block, depths = block + 2, conics = block + 4 (both or neither; separate arrays of more than one row can not have
  * these addresses).  bds_project_view_fwd then writes whole rows (radii [N] and opacities [N] are written as dense arrays as well),
- * and bds_isect_prepare* / bds_isect_build* / bds_splat_pack_sh given the same three pointers (and opacities = block + 7, or any
+ * and bds_isect_prepare / bds_isect_build / bds_splat_pack_sh given the same three pointers (and opacities = block + 7, or any
  * dense [N] array of other opacities) gather ONE line per visible Gaussian instead of one per array. */
 /* Block bounds: rows kept in spatial order (Morton order of the centres: the host side's densify.spatial_order) make every 256-row
  * block a small box, and a camera then rejects most of the ~85 % of the Gaussians it does not see a BLOCK at a time.
@@ -397,7 +406,7 @@ int bds_gaussian_block_bounds(int64_t N, const float *means, const float *log_sc
  *       must be NULL (the row form's slot 7 then holds sigmoid(logit)).
  *   prep_ws (NULL: none) also does the first launch of the tile stage (device-count form; N > 0): the number of visible Gaussians per
  *       256-Gaussian workgroup is left in prep_ws (bds_isect_prepare_workspace_bytes(1, N)), the stage's sort tables and
- *       tiles_per_gauss [N] (may be NULL) are cleared.  Follow with bds_isect_prepare_dev(..., compact | 2, ...) on the SAME workspace.
+ *       tiles_per_gauss [N] (may be NULL) are cleared.  Follow with the device-count form of bds_isect_prepare(..., compact | 2, ...) on the SAME workspace.
  *       BDS_ECAPACITY when N is beyond the short sort path (call again with prep_ws = NULL then).  tiles_per_gauss is not touched
  *       without prep_ws.
  *   block_bounds (NULL: none) of bds_gaussian_block_bounds over the SAME means / log_scales: a 256-row block no centre of which can come
@@ -535,24 +544,16 @@ int bds_rasterize_kernel_name(int backward, int CH, int absgrad, int list_tile_s
  * head-room) and the actual counts from device memory: the first words of the prepare workspace hold, as uint64,
  * {M, visible entries, M effective, visible effective, overflow} (byte offsets: bds_isect_counts_offset(0..4)).  The effective
  * counts are what every later stage sizes itself by; both are ZERO when a count outgrew its capacity -- the view then renders
- * nothing instead of overrunning a buffer, and the host, which looks at `counts_pinned` (page-locked int64[3] = M, visible,
+ * nothing instead of overrunning a buffer, and the host, which looks at the prepare call's `counts` (page-locked int64[3] = M, visible,
  * overflow; written by the GPU; may be NULL) whenever it likes, provisions more and repeats the view.  Launches are sized by the
  * capacities; surplus workgroups see no elements.  Packed lists only (n_visible_capacity <= 2^(32 - bits(C*tiles))), else
- * BDS_ECAPACITY.  Lists, offsets and images are bit-identical to the host-count forms.  `compact`: bit 0 as in bds_isect_prepare,
- * bit 1 = the workspace already holds the visible counts and cleared tables of bds_project_view_fwd's prep_ws (one launch less).
+ * BDS_ECAPACITY.  Lists, offsets and images are bit-identical to the host-count forms.  The tile stage's two calls are the ones of
+ * "tile intersection" above (bds_isect_prepare with capacities, bds_isect_build with device_counts = 1; ws2 =
+ * bds_isect_build_workspace_bytes(C, N, M_capacity), flatten_ids [M_capacity]).
  * Behind the tile stage the view takes the same entries as the host-count form, handed a count pointer: n_dev = visible effective
  * (bds_splat_pack, bds_splat_pack_sh, bds_sh_view_bwd_list, bds_project_view_bwd_list, bds_view_grads_clear_list), M_dev = M effective
- * (bds_rasterize_fwd / _bwd / _bwd_ms); the two helpers of the forward-written schedule follow the tile stage below. */
+ * (bds_rasterize_fwd / _bwd / _bwd_ms); the two helpers of the forward-written schedule follow below. */
 size_t bds_isect_counts_offset(int which);
-int bds_isect_prepare_dev(int C, int64_t N, const float *means2d, const int32_t *radii, const float *depths, const float *conics,
-                          const float *opacities, int tile_size, int tile_w, int tile_h, int32_t *tiles_per_gauss, void *ws,
-                          size_t ws_bytes, int64_t M_capacity, int64_t n_visible_capacity, int64_t *counts_pinned, int compact,
-                          bds_stream_t stream);
-/* ws2: bds_isect_build_workspace_bytes(C, N, M_capacity); flatten_ids [M_capacity] */
-int bds_isect_build_dev(int C, int64_t N, int64_t M_capacity, int64_t n_visible_capacity, const float *means2d, const int32_t *radii,
-                        const float *depths, const float *conics, const float *opacities, int tile_size, int tile_w, int tile_h,
-                        const void *ws, size_t ws_bytes, void *ws2, size_t ws2_bytes, int32_t *flatten_ids, int32_t *isect_offsets,
-                        int compact, bds_stream_t stream);
 /* Words of the refined-list pool behind the schedule words (bds_rasterize_fwd: split_pool), and the sort of the keys the forward's
  * waves left (bds_set_option(8, 0); a no-op in the binned form). */
 int64_t bds_rasterize_split_pool_ints(int C, int tile_w, int tile_h, int split_cap, int64_t split_pool, int64_t M_capacity);

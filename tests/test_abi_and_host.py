@@ -24,7 +24,7 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(bds_[a-z0-9_]+)\s*\(", src)))
 
 
-def test_header_and_library_symbols_match_abi_4(libpath):
+def test_header_and_library_symbols_match_abi_5(libpath):
     names = _declared_symbols()
     assert len(names) >= 19
     h = ctypes.CDLL(libpath)
@@ -37,7 +37,7 @@ def test_header_and_library_symbols_match_abi_4(libpath):
     assert not exported - set(names), f"exported by libbds.so but not declared in include/bds.h: {sorted(exported - set(names))}"
     h.bds_abi_version.restype = ctypes.c_int
     from bilateral_driving_amd import _lib as _L
-    assert h.bds_abi_version() == _L.ABI_VERSION == 4
+    assert h.bds_abi_version() == _L.ABI_VERSION == 5
     h.bds_strerror.restype = ctypes.c_char_p
     assert b"workspace" in h.bds_strerror(-2)
 
@@ -84,6 +84,21 @@ def test_argument_validation_without_gpu(libpath):
     assert h.bds_rasterize_bwd(1, 10, 0, p, 3, p, None, *grad, None, 0, 0, 0, None) == -1       # M_dev with capacity 0
     assert h.bds_rasterize_bwd(1, 10, 5, None, 4, p, None, *grad, p, 64, 8, 0, None) == -1      # host count with split_len
     assert h.bds_sh_view_bwd_list(4, None, p, 16, 3, p, p, p, 0, p, p, p, p, 0, None) == -1     # v_coeffs_rest together with row_map
+    # the tile stage's folded entries: mixed modes, and the requirements of each mode that are checked before any launch
+    cnt = (ctypes.c_int64 * 3)()
+    prep = (1, 1000, p, p, p, p, p, 16, 4, 4, p, p, 1 << 30)    # C, N, means2d .. opacities, tile_size, tile_w, tile_h, tiles_per_gauss, ws, ws_bytes
+    assert h.bds_isect_prepare(*prep, 100, 100, cnt, p, 1, None) == -1      # an event together with capacities
+    assert h.bds_isect_prepare(*prep, 100, -1, cnt, None, 1, None) == -1    # exactly one capacity negative
+    assert h.bds_isect_prepare(*prep, -1, 100, cnt, None, 1, None) == -1
+    assert h.bds_isect_prepare(*prep, -1, -1, None, p, 1, None) == -1       # asynchronous form without counts
+    assert h.bds_isect_prepare(*prep, -1, -1, None, None, 1, None) == -1    # synchronous form without counts
+    assert h.bds_isect_prepare(1, 0, *prep[2:], 100, 100, cnt, None, 1, None) == -1    # device-count form with C*N == 0
+    assert h.bds_isect_prepare(1, 0, *prep[2:], -1, -1, cnt, None, 1, None) == 0 and list(cnt[:2]) == [0, 0]     # (host counts: empty input is fine)
+    build = (p, p, p, p, p, 16, 4, 4, p, 1 << 30, p, 1 << 30)   # means2d .. opacities, tile_size, tile_w, tile_h, ws, ws_bytes, ws2, ws2_bytes
+    assert h.bds_isect_build(1, 1000, 0, 100, *build, None, p, p, None, 1, 1, None) == -1      # device counts with capacity 0
+    assert h.bds_isect_build(1, 1000, 100, 0, *build, None, p, p, None, 1, 1, None) == -1
+    assert h.bds_isect_build(1, 1000, 100, 100, *build, p, p, p, None, 1, 0, None) == -1       # isect_ids with device counts
+    assert h.bds_isect_build(1, 1000, 100, 100, *build, None, p, p, p, 1, 1, None) == -1       # visible_ids with device counts
     assert h.bds_isect_prepare_workspace_bytes(1, 1000) > 5 * 4000
     assert h.bds_isect_build_workspace_bytes(1, 1000, 50000) > 3 * 4 * 50000
     lv = (_lib.BdsLevel * 1)()

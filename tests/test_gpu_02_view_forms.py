@@ -220,8 +220,8 @@ def test_isect_prepare_async_reports_the_same_counts(env):
     ev = torch.cuda.Event()
     ev.record()
     tpg = torch.empty(1, N, dtype=torch.int32, device="cuda")
-    L.check(lib.bds_isect_prepare_async(1, N, L.ptr(m2), L.ptr(radii), L.ptr(d), L.ptr(con), L.ptr(op), 16, tw, th, L.ptr(tpg), L.ptr(ws), wsb,
-                                        counts.data_ptr(), ev.cuda_event, 0, st), "prepare_async")
+    L.check(lib.bds_isect_prepare(1, N, L.ptr(m2), L.ptr(radii), L.ptr(d), L.ptr(con), L.ptr(op), 16, tw, th, L.ptr(tpg), L.ptr(ws), wsb,
+                                  -1, -1, counts.data_ptr(), ev.cuda_event, 0, st), "prepare, asynchronous form")
     ev.synchronize()
     M, nv = int(counts[0]), int(counts[1])
     assert M == fids_ref.numel() and nv == int((radii > 0).sum()) and torch.equal(tpg, tpg_ref)
@@ -229,7 +229,7 @@ def test_isect_prepare_async_reports_the_same_counts(env):
     ws2 = torch.empty(max(ws2b, 16), dtype=torch.uint8, device="cuda")
     fids, offs = torch.empty(M, dtype=torch.int32, device="cuda"), torch.empty(1, th, tw, dtype=torch.int32, device="cuda")
     L.check(lib.bds_isect_build(1, N, M, nv, L.ptr(m2), L.ptr(radii), L.ptr(d), L.ptr(con), L.ptr(op), 16, tw, th, L.ptr(ws), wsb, L.ptr(ws2),
-                                ws2b, None, L.ptr(fids), L.ptr(offs), None, 0, st), "build")
+                                ws2b, None, L.ptr(fids), L.ptr(offs), None, 0, 0, st), "build")
     assert torch.equal(fids, fids_ref) and torch.equal(offs, offs_ref)
 
 
