@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BDS_LIB") or os.path.join(_HERE, "libbds.so")    # (BDS_LIB: an A/B variant built by build.py --variant)
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _lock = threading.Lock()
 _lib = None
@@ -77,8 +77,7 @@ _SIGS = {
     "bds_sh_view_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_sh_view_bwd_list": (_i, [_i64, _f, _f, _i, _i, _f, _f, _f, _i, _f, _f, _f, _f, _i, _f]),
     "bds_splat_pack_sh": (_i, [_i64, _f, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i64, _f, _f]),
-    "bds_nonfinite_flags": (_i, [_i, _f, _f, _f, _f, _f]),
-    "bds_nonfinite_flags_kinds": (_i, [_i, _f, _f, _f, _f, _f, _f]),
+    "bds_nonfinite_flags": (_i, [_i, _f, _f, _f, _f, _f, _f]),
     "bds_project_view_bwd_list": (_i, [_i, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_view_grads_clear_list": (_i, [_i64, _f, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_view_grads_add_list": (_i, [_i64, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
@@ -94,16 +93,12 @@ _SIGS = {
     "bds_bilagrid_select": (_i, [_i, C.POINTER(BdsLevel), _f, C.POINTER(C.c_void_p), _f, _f]),
     "bds_bilagrid_select_bwd": (_i, [_i, C.POINTER(BdsLevel), _f, C.POINTER(C.c_void_p), _f, _f]),
     "bds_bilagrid_kernel_names": (_i, [_i, C.POINTER(BdsLevel), _i, _i, _i, _i, C.c_char_p, _i]),
-    "bds_bilagrid_ms_fwd": (_i, [_i, C.POINTER(BdsLevel), _i, _i, _f, _f, _f, _f, _sz, _f, C.POINTER(C.c_void_p), _f]),
-    "bds_bilagrid_ms_bwd": (_i, [_i, C.POINTER(BdsLevel), _i, _i, _f, _f, _f, _f, _sz, _f, _f, _f, _f, _f]),
-    "bds_bilagrid_ms_ed_train_fwd": (_i, [_i, C.POINTER(BdsLevel), _i, _i, _f, _f, _f, _f, _sz, _f, _f, _f, _i, C.POINTER(BdsLevel),
-                                          C.POINTER(C.c_float), _fl, _f, _i, _f, _f]),
-    "bds_bilagrid_ms_ed_fwd": (_i, [_i, C.POINTER(BdsLevel), _i, _i, _f, _f, _f, _f, _sz, _f, _f, _f]),
-    "bds_bilagrid_ms_ed_bwd_deferrable": (_i, [_i, C.POINTER(BdsLevel), _i, _i]),
-    "bds_bilagrid_ms_ed_bwd_deferred": (_i, [_i, C.POINTER(BdsLevel), _i, _i, _f, _f, _f, _f, _sz, _f, _f, _f]),
+    "bds_bilagrid_ms_fwd": (_i, [_i, C.POINTER(BdsLevel), _i, _i, _i, _f, _f, _f, _f, _sz, _f, _f, C.POINTER(C.c_void_p), _f, _i,
+                                 C.POINTER(BdsLevel), C.POINTER(C.c_float), _fl, _f, _i, _f, _f]),
+    "bds_bilagrid_ms_bwd": (_i, [_i, C.POINTER(BdsLevel), _i, _i, _i, _f, _f, _f, _f, _sz, _f, _f, _f, _f, _f, _f, _i, _f]),
+    "bds_bilagrid_ms_bwd_deferrable": (_i, [_i, C.POINTER(BdsLevel), _i, _i]),
     "bds_rasterize_bwd_ms": (_i, [_i64, _i64, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _f, _i, C.POINTER(BdsLevel), _f, _sz,
                                   _f, _f, _f, _f, _f, _f, _f]),
-    "bds_bilagrid_ms_ed_bwd": (_i, [_i, C.POINTER(BdsLevel), _i, _i, _f, _f, _f, _f, _sz, _f, _f, _f, _f, _f, _f, _f]),
     "bds_l1_tv_train": (_i, [_i64, _f, _f, _i, C.POINTER(BdsLevel), C.POINTER(C.c_float), _fl, _f, _i, _f, _f]),
     "bds_l1_mean_fwd": (_i, [_i64, _f, _f, _f, _f]),
     "bds_l1_mean_bwd": (_i, [_i64, _f, _f, _f, _f, _f]),
@@ -142,9 +137,7 @@ _SIGS = {
     "bds_cubemap_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f]),
     "bds_cubemap_bwd": (_i, [_i64, _i, _i, _i, _f, _f, _f, _f, _f]),
     "bds_color_correct_step": (_i, [_i64, _f, _f, _f, _fl, _f, _f, _f, _f]),
-    "bds_adam_step": (_i, [_i64, _f, _f, _f, _f, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i64, _f]),
-    "bds_adam_step_consume": (_i, [_i64, _f, _f, _f, _f, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i64, _f]),
-    "bds_adam_step_rows": (_i, [_i64, _i, _i64, _f, _f, _f, _f, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i64, _i, _f]),
+    "bds_adam_step": (_i, [_i64, _i, _i64, _f, _f, _f, _f, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i64, _i, _f]),
     "bds_adam_step_rowblock": (_i, [_i64, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _f]),
     "bds_adam_step_multi": (_i, [_i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _f]),
     "bds_adam_rows_advance": (_i, [_i64, _f, _f, _i64, _i, _i, _f, _f, _i, _f, _f, _f, _f, _i64, _i, _f, _i, C.c_double, C.c_double,
@@ -155,8 +148,6 @@ _SIGS = {
     "bds_grid_tv_bwd": (_i, [_i64, _i, _i, _i, _i, _f, _fl, _f, _f, _f]),
     "bds_bilagrid_tv_ms_fwd": (_i, [_i, C.POINTER(BdsLevel), C.POINTER(C.c_float), _f, _f]),
     "bds_bilagrid_tv_ms_bwd": (_i, [_i, C.POINTER(BdsLevel), C.POINTER(C.c_float), _f, _f]),
-    "bds_bilagrid_tv_fwd": (_i, [_i64, _i, _i, _i, _f, _fl, _f, _f]),
-    "bds_bilagrid_tv_bwd": (_i, [_i64, _i, _i, _i, _f, _fl, _f, _f, _f]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -310,8 +310,8 @@ class _BilagridTransform(torch.autograd.Function):
         maps = [torch.empty(H, W, 12, device=rgb.device, dtype=torch.float32) for _ in range(n)] if want_maps else []
         maps_arr = (C.c_void_p * n)(*[m.data_ptr() for m in maps]) if want_maps else None
         with L.timed("bilagrid_fwd"):
-            L.check(lib.bds_bilagrid_ms_fwd(n, lv, H, W, L.ptr(rgb), L.ptr(alpha), L.ptr(sky), L.ptr(ws), ws_bytes, L.ptr(out),
-                                            maps_arr, L.stream()), "bds_bilagrid_ms_fwd")
+            L.check(lib.bds_bilagrid_ms_fwd(n, lv, H, W, 3, L.ptr(rgb), L.ptr(alpha), L.ptr(sky), L.ptr(ws), ws_bytes, L.ptr(out), None,
+                                            maps_arr, None, 0, None, None, 0.0, None, 0, None, L.stream()), "bds_bilagrid_ms_fwd")
         ctx.save_for_backward(rgb, alpha, sky, ws, *grids)
         ctx.factors = tuple(int(f) for f in factors)
         ctx.n = n
@@ -332,8 +332,8 @@ class _BilagridTransform(torch.autograd.Function):
         v_alpha = torch.empty_like(alpha) if sky is not None else None
         v_sky = torch.empty_like(sky) if sky is not None else None
         with L.timed("bilagrid_bwd"):
-            L.check(lib.bds_bilagrid_ms_bwd(n, lv, H, W, L.ptr(rgb), L.ptr(alpha), L.ptr(sky), L.ptr(ws), ws.numel(),
-                                            L.ptr(v_out), L.ptr(v_rgb), L.ptr(v_alpha), L.ptr(v_sky), L.stream()),
+            L.check(lib.bds_bilagrid_ms_bwd(n, lv, H, W, 3, L.ptr(rgb), L.ptr(alpha), L.ptr(sky), L.ptr(ws), ws.numel(),
+                                            L.ptr(v_out), None, None, L.ptr(v_rgb), L.ptr(v_alpha), L.ptr(v_sky), 0, L.stream()),
                     "bds_bilagrid_ms_bwd")
         return (v_rgb, v_alpha, v_sky, None, None, *v_grids)
 

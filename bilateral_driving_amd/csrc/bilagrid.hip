@@ -1015,6 +1015,14 @@ static MsLayout ms_layout(int nlevels, const bds_bilagrid_level_t *lv, int H, in
   return L;
 }
 
+// a level's low-res size, and the shift of a power-of-two factor that divides the image (0: the general taps)
+static void level_geometry(int H, int W, int f, int &Hd, int &Wd, int &dn_shift) {
+  Hd = H / f; Wd = W / f;
+  dn_shift = 0;
+  if (f >= 2 && (f & (f - 1)) == 0 && Hd * f == H && Wd * f == W)
+    while ((1 << dn_shift) < f) dn_shift++;
+}
+
 static int ms_fill(MsParams &p, int nlevels, const bds_bilagrid_level_t *lv, int H, int W, const float *rgb,
                    const float *alpha, const float *sky, void *ws, size_t ws_bytes, float *const *affine_out) {
   BDS_REQUIRE(nlevels >= 1 && nlevels <= BDS_MAX_LEVELS && lv && H > 0 && W > 0 && rgb && ws);
@@ -1041,20 +1049,11 @@ static int ms_fill(MsParams &p, int nlevels, const bds_bilagrid_level_t *lv, int
     d.aff_out = affine_out ? affine_out[l] : nullptr;
     BDS_REQUIRE(d.aff_out == nullptr || aligned16(d.aff_out));
     d.gx = lv[l].gx; d.gy = lv[l].gy; d.gl = lv[l].gl; d.factor = lv[l].factor; d.n_avg = lv[l].n_avg;
-    d.Hd = H / lv[l].factor; d.Wd = W / lv[l].factor;
+    level_geometry(H, W, lv[l].factor, d.Hd, d.Wd, d.dn_shift);
     d.up_x = (float)d.Wd / (float)W; d.up_y = (float)d.Hd / (float)H;
     d.dn_x = (float)W / (float)d.Wd; d.dn_y = (float)H / (float)d.Hd;
     d.lin_x = d.Wd > 1 ? 1.0f / (float)(d.Wd - 1) : 0.f; d.lin_y = d.Hd > 1 ? 1.0f / (float)(d.Hd - 1) : 0.f;
     d.magic_wd = divmod_magic(d.Wd);
-    d.dn_shift = 0;
-    {
-      const int f = lv[l].factor;
-      if (f >= 2 && (f & (f - 1)) == 0 && d.Hd * f == H && d.Wd * f == W) {
-        int sh = 0;
-        while ((1 << sh) < f) sh++;
-        d.dn_shift = sh;
-      }
-    }
   }
   p.magic_w = divmod_magic(W);
   return BDS_OK;
@@ -1071,17 +1070,45 @@ extern "C" size_t bds_bilagrid_ms_workspace_bytes(int nlevels, const bds_bilagri
   return ms_layout(nlevels, levels, H, W).bytes;
 }
 
-static int l1_tv_train_launch(int64_t n, const float *a, const float *b, const TvLevels &T, int tv_blocks, float v_loss, float *loss_out,
-                              int loss_slots, float *v_a, hipStream_t st);
+static int tv_train_levels(TvLevels &T, int &tv_blocks, int nlevels, const bds_bilagrid_level_t *levels, const float *weights);
 
-static int ms_fwd_impl(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, const float *rgb, int cs,
-                       const float *alpha, const float *sky, void *ws, size_t ws_bytes, float *rgb_out, float *depth_out,
-                       float *const *affine_out, bds_stream_t stream, const TrainLoss *train = nullptr) {
+// Launch KERNEL<NL TAIL> with NL = nlevels up to 4 levels and BDS_MAX_LEVELS above: NL bounds the static unrolling of the kernels' level
+// loops.  TAIL: further template arguments, each behind MS_COMMA, or empty.  The arguments after it are hipLaunchKernelGGL's.
+#define MS_COMMA ,
+#define MS_LAUNCH_NL(KERNEL, TAIL, ...)                                                     \
+  switch (nlevels) {                                                                        \
+    case 1: hipLaunchKernelGGL((KERNEL<1 TAIL>), __VA_ARGS__); break;                       \
+    case 2: hipLaunchKernelGGL((KERNEL<2 TAIL>), __VA_ARGS__); break;                       \
+    case 3: hipLaunchKernelGGL((KERNEL<3 TAIL>), __VA_ARGS__); break;                       \
+    case 4: hipLaunchKernelGGL((KERNEL<4 TAIL>), __VA_ARGS__); break;                       \
+    default: hipLaunchKernelGGL((KERNEL<BDS_MAX_LEVELS TAIL>), __VA_ARGS__); break;         \
+  }
+
+extern "C" int bds_bilagrid_ms_fwd(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, int channels, const float *in,
+                                   const float *alpha, const float *sky, void *ws, size_t ws_bytes, float *rgb_out, float *depth_out,
+                                   float *const *affine_out, const float *target, int tv_nlevels,
+                                   const bds_bilagrid_level_t *tv_levels, const float *tv_weights, float v_loss, float *loss_out,
+                                   int loss_slots, float *v_rgb_out, bds_stream_t stream) {
+  BDS_REQUIRE(channels == 3 || channels == 4);
+  if (channels == 3) BDS_REQUIRE(!depth_out && !target);
+  else BDS_REQUIRE(alpha && depth_out && !affine_out);
+  TrainLoss tl{};
+  const TrainLoss *train = target ? &tl : nullptr;
+  int rc;
+  if (train) {   // the training loss and its gradient on the application's launch
+    BDS_REQUIRE(loss_out && v_rgb_out && H > 0 && W > 0);
+    BDS_REQUIRE(loss_slots >= 1 && (loss_slots & (loss_slots - 1)) == 0);
+    BDS_REQUIRE(aligned16(target) && aligned16(v_rgb_out) && aligned16(rgb_out));
+    rc = tv_train_levels(tl.T, tl.tv_blocks, tv_nlevels, tv_levels, tv_weights);
+    if (rc != BDS_OK) return rc;
+    tl.target = target; tl.v_out = v_rgb_out; tl.loss = loss_out; tl.loss_slots = loss_slots;
+    tl.inv_n = 1.0f / (float)((int64_t)H * W * 3); tl.v_loss = v_loss;
+  }
   MsParams p;
-  int rc = ms_fill(p, nlevels, levels, H, W, rgb, alpha, sky, ws, ws_bytes, affine_out);
+  rc = ms_fill(p, nlevels, levels, H, W, in, alpha, sky, ws, ws_bytes, affine_out);
   if (rc != BDS_OK) return rc;
   BDS_REQUIRE(rgb_out);
-  p.cs = cs; p.depth_out = depth_out;
+  p.cs = channels; p.depth_out = depth_out;
   hipStream_t st = as_stream(stream);
   const bool cells = (option_get(kOptCells) & 1) != 0;
   if (cells && cells_fused_ok(p))   // one level at full resolution: slice + application (+ loss) in one launch, no maps in memory
@@ -1123,44 +1150,16 @@ static int ms_fwd_impl(int nlevels, const bds_bilagrid_level_t *levels, int H, i
     const int pix_blocks = (int)cdiv((int64_t)H * W, kBgBlock);
     const dim3 block(kBgBlock);
     if (train) {   // the loss rides on the launch: L1 in the pixel workgroups' epilogue, TV in extra workgroups behind them
-      TrainLoss tl = *train;
       tl.pix_blocks = pix_blocks;
       const dim3 grid((unsigned)(pix_blocks + tl.tv_blocks));
-      switch (nlevels) {
-        case 1: hipLaunchKernelGGL((ms_apply_fwd_kernel<1, true>), grid, block, 0, st, p, rgb_out, tl); break;
-        case 2: hipLaunchKernelGGL((ms_apply_fwd_kernel<2, true>), grid, block, 0, st, p, rgb_out, tl); break;
-        case 3: hipLaunchKernelGGL((ms_apply_fwd_kernel<3, true>), grid, block, 0, st, p, rgb_out, tl); break;
-        case 4: hipLaunchKernelGGL((ms_apply_fwd_kernel<4, true>), grid, block, 0, st, p, rgb_out, tl); break;
-        default: hipLaunchKernelGGL((ms_apply_fwd_kernel<BDS_MAX_LEVELS, true>), grid, block, 0, st, p, rgb_out, tl); break;
-      }
-      BDS_LAUNCH_CHECK();
-      return BDS_OK;
-    }
-    const dim3 grid((unsigned)pix_blocks);
-    TrainLoss none{};
-    switch (nlevels) {
-      case 1: hipLaunchKernelGGL((ms_apply_fwd_kernel<1, false>), grid, block, 0, st, p, rgb_out, none); break;
-      case 2: hipLaunchKernelGGL((ms_apply_fwd_kernel<2, false>), grid, block, 0, st, p, rgb_out, none); break;
-      case 3: hipLaunchKernelGGL((ms_apply_fwd_kernel<3, false>), grid, block, 0, st, p, rgb_out, none); break;
-      case 4: hipLaunchKernelGGL((ms_apply_fwd_kernel<4, false>), grid, block, 0, st, p, rgb_out, none); break;
-      default: hipLaunchKernelGGL((ms_apply_fwd_kernel<BDS_MAX_LEVELS, false>), grid, block, 0, st, p, rgb_out, none); break;
+      MS_LAUNCH_NL(ms_apply_fwd_kernel, MS_COMMA true, grid, block, 0, st, p, rgb_out, tl);
+    } else {
+      const dim3 grid((unsigned)pix_blocks);
+      MS_LAUNCH_NL(ms_apply_fwd_kernel, MS_COMMA false, grid, block, 0, st, p, rgb_out, tl);
     }
   }
   BDS_LAUNCH_CHECK();
   return BDS_OK;
-}
-
-extern "C" int bds_bilagrid_ms_fwd(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, const float *rgb,
-                                   const float *alpha, const float *sky, void *ws, size_t ws_bytes, float *rgb_out,
-                                   float *const *affine_out, bds_stream_t stream) {
-  return ms_fwd_impl(nlevels, levels, H, W, rgb, 3, alpha, sky, ws, ws_bytes, rgb_out, nullptr, affine_out, stream);
-}
-
-extern "C" int bds_bilagrid_ms_ed_fwd(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, const float *render,
-                                      const float *alpha, const float *sky, void *ws, size_t ws_bytes, float *rgb_out,
-                                      float *depth_out, bds_stream_t stream) {
-  BDS_REQUIRE(alpha && depth_out);
-  return ms_fwd_impl(nlevels, levels, H, W, render, 4, alpha, sky, ws, ws_bytes, rgb_out, depth_out, nullptr, stream);
 }
 
 // The backward's last stage can move into the compositor's backward (ed_epilogue.h) when every level takes the cell-aligned low-res
@@ -1188,21 +1187,25 @@ int ed_epilogue_fill(int nlevels, const bds_bilagrid_level_t *levels, int H, int
 }
 }  // namespace bds
 
-static int ms_bwd_impl(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, const float *rgb, int cs,
-                       const float *alpha, const float *sky, void *ws, size_t ws_bytes, const float *v_rgb_out,
-                       const float *v_depth, const float *v_alpha_in, float *v_rgb, float *v_alpha, float *v_sky,
-                       bds_stream_t stream, bool defer_epilogue = false) {
+extern "C" int bds_bilagrid_ms_bwd(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, int channels, const float *in,
+                                   const float *alpha, const float *sky, void *ws, size_t ws_bytes, const float *v_rgb_out,
+                                   const float *v_depth, const float *v_opacity, float *v_in, float *v_alpha, float *v_sky, int defer,
+                                   bds_stream_t stream) {
+  BDS_REQUIRE(channels == 3 || channels == 4);
+  if (channels == 3) BDS_REQUIRE(!v_depth && !v_opacity && !defer);
+  else if (defer) BDS_REQUIRE(alpha && v_in && !v_depth && !v_opacity && !v_alpha && !v_sky);
+  else BDS_REQUIRE(alpha && v_alpha);
   MsParams p;
-  int rc = ms_fill(p, nlevels, levels, H, W, rgb, alpha, sky, ws, ws_bytes, nullptr);
+  int rc = ms_fill(p, nlevels, levels, H, W, in, alpha, sky, ws, ws_bytes, nullptr);
   if (rc != BDS_OK) return rc;
-  BDS_REQUIRE(v_rgb_out && v_rgb);
-  if (defer_epilogue) BDS_REQUIRE(epilogue_deferrable(p));
-  p.cs = cs; p.v_depth = v_depth; p.v_alpha_in = v_alpha_in;
+  BDS_REQUIRE(v_rgb_out && v_in);
+  if (defer) BDS_REQUIRE(epilogue_deferrable(p));
+  p.cs = channels; p.v_depth = v_depth; p.v_alpha_in = v_opacity;
   hipStream_t st = as_stream(stream);
   const int64_t HW = (int64_t)H * W;
   const bool cells = (option_get(kOptCells) & 1) != 0;
   if (cells && cells_fused_ok(p))   // one level at full resolution: the whole backward in one launch, no scratch
-    return cells_fused_bwd(p, v_rgb_out, v_rgb, v_alpha, v_sky, st);
+    return cells_fused_bwd(p, v_rgb_out, v_in, v_alpha, v_sky, st);
   // fused x pass when some level is up-sampled and the widest support fits the workgroup's halo
   float smax = 1.f;
   bool any_up = false;
@@ -1217,25 +1220,11 @@ static int ms_bwd_impl(int nlevels, const bds_bilagrid_level_t *levels, int H, i
     const int stride = kBgBlock - 2 * halo;
     const int nbx = (int)cdiv(W, stride);
     const dim3 grid((unsigned)((int64_t)H * nbx)), block(kBgBlock);
-    switch (nlevels) {
-      case 1: hipLaunchKernelGGL((ms_apply_bwd_x_kernel<1>), grid, block, 0, st, p, v_rgb_out, v_rgb, halo, nbx, option_get(kOptDebug)); break;
-      case 2: hipLaunchKernelGGL((ms_apply_bwd_x_kernel<2>), grid, block, 0, st, p, v_rgb_out, v_rgb, halo, nbx, option_get(kOptDebug)); break;
-      case 3: hipLaunchKernelGGL((ms_apply_bwd_x_kernel<3>), grid, block, 0, st, p, v_rgb_out, v_rgb, halo, nbx, option_get(kOptDebug)); break;
-      case 4: hipLaunchKernelGGL((ms_apply_bwd_x_kernel<4>), grid, block, 0, st, p, v_rgb_out, v_rgb, halo, nbx, option_get(kOptDebug)); break;
-      default: hipLaunchKernelGGL((ms_apply_bwd_x_kernel<BDS_MAX_LEVELS>), grid, block, 0, st, p, v_rgb_out, v_rgb, halo, nbx, option_get(kOptDebug)); break;
-    }
+    MS_LAUNCH_NL(ms_apply_bwd_x_kernel, , grid, block, 0, st, p, v_rgb_out, v_in, halo, nbx, option_get(kOptDebug));
     BDS_LAUNCH_CHECK();
   } else {
-    {
-      const dim3 grid((unsigned)cdiv(HW, kBgBlock)), block(kBgBlock);
-      switch (nlevels) {
-        case 1: hipLaunchKernelGGL((ms_apply_bwd_kernel<1>), grid, block, 0, st, p, v_rgb_out, v_rgb); break;
-        case 2: hipLaunchKernelGGL((ms_apply_bwd_kernel<2>), grid, block, 0, st, p, v_rgb_out, v_rgb); break;
-        case 3: hipLaunchKernelGGL((ms_apply_bwd_kernel<3>), grid, block, 0, st, p, v_rgb_out, v_rgb); break;
-        case 4: hipLaunchKernelGGL((ms_apply_bwd_kernel<4>), grid, block, 0, st, p, v_rgb_out, v_rgb); break;
-        default: hipLaunchKernelGGL((ms_apply_bwd_kernel<BDS_MAX_LEVELS>), grid, block, 0, st, p, v_rgb_out, v_rgb); break;
-      }
-    }
+    const dim3 grid((unsigned)cdiv(HW, kBgBlock)), block(kBgBlock);
+    MS_LAUNCH_NL(ms_apply_bwd_kernel, , grid, block, 0, st, p, v_rgb_out, v_in);
     BDS_LAUNCH_CHECK();
     {  // x pass of the up-sampler adjoint, all up-sampled levels in one launch
       LevelSched sc{};
@@ -1274,7 +1263,7 @@ static int ms_bwd_impl(int nlevels, const bds_bilagrid_level_t *levels, int H, i
       if (gbytes > kMaxGridLds) {  // grid gradient too large for LDS: direct global atomics, own launch
         LevelSched one{};
         one.n = 1; one.level[0] = l; one.nblk[0] = (int)need; one.blk_off[1] = (int)need;
-        hipLaunchKernelGGL((ms_lowres_bwd_kernel<false>), dim3((unsigned)need), dim3(kBgBlock), 0, st, p, one, v_rgb, partials,
+        hipLaunchKernelGGL((ms_lowres_bwd_kernel<false>), dim3((unsigned)need), dim3(kBgBlock), 0, st, p, one, v_in, partials,
                            option_get(kOptDebug), 0);
         BDS_LAUNCH_CHECK();
         continue;
@@ -1306,24 +1295,18 @@ static int ms_bwd_impl(int nlevels, const bds_bilagrid_level_t *levels, int H, i
           return BDS_ELAUNCH;
       }
       // (unroll 2 of the y pass -- 128 instead of 147 VGPRs, a fourth resident wave -- measured slower: the loop wants the loads in flight)
-      hipLaunchKernelGGL((ms_lowres_bwd_kernel<true>), dim3((unsigned)sc.blk_off[sc.n]), dim3(kBgBlock), lds_bytes, st, p, sc, v_rgb,
+      hipLaunchKernelGGL((ms_lowres_bwd_kernel<true>), dim3((unsigned)sc.blk_off[sc.n]), dim3(kBgBlock), lds_bytes, st, p, sc, v_in,
                          partials, option_get(kOptDebug), (int)(lds_bytes / sizeof(float)));
       BDS_LAUNCH_CHECK();
       if (red.blk_off[red.n] > 0) { pj.sc = sc; pj.red = red; pj.partials = partials; extra_blocks = red.blk_off[red.n]; }
     }
   }
-  if (defer_epilogue) return BDS_OK;   // (the compositor's backward finishes the pixel: bds_rasterize_bwd_ms)
+  if (defer) return BDS_OK;   // (the compositor's backward finishes the pixel: bds_rasterize_bwd_ms)
   {
     // (the reduction of the partial grids rides on this launch as extra workgroups)
     pj.pix_blocks = (int)cdiv(HW, kBgBlock);
     const dim3 grid((unsigned)(pj.pix_blocks + extra_blocks)), block(kBgBlock);
-    switch (nlevels) {
-      case 1: hipLaunchKernelGGL((ms_guidance_blend_bwd_kernel<1>), grid, block, 0, st, p, v_rgb, v_alpha, v_sky, option_get(kOptDebug), pj); break;
-      case 2: hipLaunchKernelGGL((ms_guidance_blend_bwd_kernel<2>), grid, block, 0, st, p, v_rgb, v_alpha, v_sky, option_get(kOptDebug), pj); break;
-      case 3: hipLaunchKernelGGL((ms_guidance_blend_bwd_kernel<3>), grid, block, 0, st, p, v_rgb, v_alpha, v_sky, option_get(kOptDebug), pj); break;
-      case 4: hipLaunchKernelGGL((ms_guidance_blend_bwd_kernel<4>), grid, block, 0, st, p, v_rgb, v_alpha, v_sky, option_get(kOptDebug), pj); break;
-      default: hipLaunchKernelGGL((ms_guidance_blend_bwd_kernel<BDS_MAX_LEVELS>), grid, block, 0, st, p, v_rgb, v_alpha, v_sky, option_get(kOptDebug), pj); break;
-    }
+    MS_LAUNCH_NL(ms_guidance_blend_bwd_kernel, , grid, block, 0, st, p, v_in, v_alpha, v_sky, option_get(kOptDebug), pj);
     BDS_LAUNCH_CHECK();
   }
   return BDS_OK;
@@ -1408,13 +1391,9 @@ extern "C" int bds_bilagrid_kernel_names(int nlevels, const bds_bilagrid_level_t
     BDS_REQUIRE(levels[l].factor >= 1);
     LevelDev &d = p.lv[l];
     d.gx = levels[l].gx; d.gy = levels[l].gy; d.gl = levels[l].gl; d.factor = levels[l].factor; d.n_avg = levels[l].n_avg;
-    d.Hd = H / levels[l].factor; d.Wd = W / levels[l].factor;
+    level_geometry(H, W, d.factor, d.Hd, d.Wd, d.dn_shift);
     d.aff_out = nullptr;
     const size_t gbytes = sizeof(float) * 12 * d.gl * d.gy * d.gx * d.n_avg;
-    {
-      const int f = d.factor;
-      d.dn_shift = (f >= 2 && (f & (f - 1)) == 0 && d.Hd * f == H && d.Wd * f == W) ? 1 : 0;   // (non-zero is all tile_fwd_ok asks)
-    }
     if ((option_get(kOptCells) & 1) && cells_level_ok(d)) any_cell = true;
     else if (gbytes <= (backward ? kMaxGridLds : (size_t)32 * 1024)) any_lds = true;
     else any_gather = true;
@@ -1442,46 +1421,19 @@ extern "C" int bds_bilagrid_kernel_names(int nlevels, const bds_bilagrid_level_t
   return BDS_OK;
 }
 
-extern "C" int bds_bilagrid_ms_bwd(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, const float *rgb,
-                                   const float *alpha, const float *sky, void *ws, size_t ws_bytes,
-                                   const float *v_rgb_out, float *v_rgb, float *v_alpha, float *v_sky,
-                                   bds_stream_t stream) {
-  return ms_bwd_impl(nlevels, levels, H, W, rgb, 3, alpha, sky, ws, ws_bytes, v_rgb_out, nullptr, nullptr, v_rgb, v_alpha, v_sky,
-                     stream);
-}
-
-extern "C" int bds_bilagrid_ms_ed_bwd(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, const float *render,
-                                      const float *alpha, const float *sky, void *ws, size_t ws_bytes,
-                                      const float *v_rgb_out, const float *v_depth, const float *v_opacity, float *v_render,
-                                      float *v_alpha, float *v_sky, bds_stream_t stream) {
-  BDS_REQUIRE(alpha && v_alpha);
-  return ms_bwd_impl(nlevels, levels, H, W, render, 4, alpha, sky, ws, ws_bytes, v_rgb_out, v_depth, v_opacity, v_render, v_alpha,
-                     v_sky, stream);
-}
-
 // 1 when this configuration's backward can leave its last stage to the compositor's backward (bds_rasterize_bwd_ms), else 0
-extern "C" int bds_bilagrid_ms_ed_bwd_deferrable(int nlevels, const bds_bilagrid_level_t *levels, int H, int W) {
+extern "C" int bds_bilagrid_ms_bwd_deferrable(int nlevels, const bds_bilagrid_level_t *levels, int H, int W) {
   if (nlevels < 1 || nlevels > BDS_MAX_LEVELS || !levels || H <= 0 || W <= 0) return 0;
   MsParams p{};
   p.nlevels = nlevels; p.H = H; p.W = W;
   for (int l = 0; l < nlevels; l++) {
     if (levels[l].factor < 1) return 0;
     LevelDev &d = p.lv[l];
-    const int f = levels[l].factor;
-    d.gx = levels[l].gx; d.gy = levels[l].gy; d.gl = levels[l].gl; d.factor = f; d.n_avg = levels[l].n_avg;
-    d.Hd = H / f; d.Wd = W / f;
+    d.gx = levels[l].gx; d.gy = levels[l].gy; d.gl = levels[l].gl; d.factor = levels[l].factor; d.n_avg = levels[l].n_avg;
+    level_geometry(H, W, d.factor, d.Hd, d.Wd, d.dn_shift);
     d.aff_out = nullptr;
-    d.dn_shift = (f >= 2 && (f & (f - 1)) == 0 && d.Hd * f == H && d.Wd * f == W) ? 1 : 0;
   }
   return epilogue_deferrable(p) ? 1 : 0;
-}
-
-extern "C" int bds_bilagrid_ms_ed_bwd_deferred(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, const float *render,
-                                               const float *alpha, const float *sky, void *ws, size_t ws_bytes,
-                                               const float *v_rgb_out, float *v_direct, bds_stream_t stream) {
-  BDS_REQUIRE(alpha && v_direct);
-  return ms_bwd_impl(nlevels, levels, H, W, render, 4, alpha, sky, ws, ws_bytes, v_rgb_out, nullptr, nullptr, v_direct, nullptr, nullptr,
-                     stream, true);
 }
 
 extern "C" int bds_bilagrid_slice_fwd(int64_t P, const float *grid, int gx, int gy, int gl, const float *xy,
@@ -1507,38 +1459,13 @@ extern "C" int bds_bilagrid_slice_bwd(int64_t P, const float *grid, int gx, int 
   return BDS_OK;
 }
 
-static void tv_scales(int64_t n, int gx, int gy, int gl, float weight, float &sl, float &sy, float &sx, int channels = 12) {
+static void tv_scales(int64_t n, int gx, int gy, int gl, float weight, float &sl, float &sy, float &sx, int channels) {
   // lib_bilagrid.py:147-168: each axis' squared differences are divided by the element count of
   // the differenced tensor (per batch item, floor 1); the sum is divided by the batch size.
   auto cnt = [channels](int64_t a, int64_t b, int64_t c) { double v = (double)channels * a * b * c; return v < 1.0 ? 1.0 : v; };
   sl = (float)(weight / (cnt(gl - 1, gy, gx) * (double)n));
   sy = (float)(weight / (cnt(gl, gy - 1, gx) * (double)n));
   sx = (float)(weight / (cnt(gl, gy, gx - 1) * (double)n));
-}
-
-extern "C" int bds_bilagrid_tv_fwd(int64_t n, int gx, int gy, int gl, const float *grids, float weight, float *tv_out,
-                                   bds_stream_t stream) {
-  BDS_REQUIRE(n >= 1 && gx >= 1 && gy >= 1 && gl >= 1 && grids && tv_out);
-  float sl, sy, sx;
-  tv_scales(n, gx, gy, gl, weight, sl, sy, sx);
-  const int64_t total = n * 12 * gl * gy * gx;
-  const int64_t blocks = cdiv(total, kBgBlock);
-  hipLaunchKernelGGL(tv_fwd_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(kBgBlock), 0, as_stream(stream), total,
-                     gx, gy, gl, grids, sl, sy, sx, tv_out);
-  BDS_LAUNCH_CHECK();
-  return BDS_OK;
-}
-
-extern "C" int bds_bilagrid_tv_bwd(int64_t n, int gx, int gy, int gl, const float *grids, float weight, const float *v_tv,
-                                   float *v_grids, bds_stream_t stream) {
-  BDS_REQUIRE(n >= 1 && gx >= 1 && gy >= 1 && gl >= 1 && grids && v_tv && v_grids);
-  float sl, sy, sx;
-  tv_scales(n, gx, gy, gl, weight, sl, sy, sx);
-  const int64_t total = n * 12 * gl * gy * gx;
-  hipLaunchKernelGGL(tv_bwd_kernel, dim3((unsigned)cdiv(total, kBgBlock)), dim3(kBgBlock), 0, as_stream(stream), total, gx, gy,
-                     gl, grids, sl, sy, sx, v_tv, v_grids);
-  BDS_LAUNCH_CHECK();
-  return BDS_OK;
 }
 
 // ---- L1 + TV training loss, value AND gradient in one launch (the direct step: d(loss) is known to be `v_loss` before the value is) ----
@@ -1594,7 +1521,7 @@ static int tv_levels_fill(TvLevels &T, int nlevels, const bds_bilagrid_level_t *
     T.x[l] = lv[l].grid; T.v_x[l] = lv[l].v_grid;
     T.gx[l] = lv[l].gx; T.gy[l] = lv[l].gy; T.gl[l] = lv[l].gl;
     T.total[l] = (long long)lv[l].n_avg * 12 * lv[l].gl * lv[l].gy * lv[l].gx;
-    tv_scales(lv[l].n_avg, lv[l].gx, lv[l].gy, lv[l].gl, weights[l], T.sl[l], T.sy[l], T.sx[l]);
+    tv_scales(lv[l].n_avg, lv[l].gx, lv[l].gy, lv[l].gl, weights[l], T.sl[l], T.sy[l], T.sx[l], 12);
     int64_t nb = cdiv(T.total[l], kBgBlock);
     if (cap > 0 && nb > cap) nb = cap;
     T.blk_off[l + 1] = T.blk_off[l] + (int)nb;
@@ -1656,22 +1583,6 @@ extern "C" int bds_l1_tv_train(int64_t n, const float *a, const float *b, int nl
   int rc = tv_train_levels(T, tv_blocks, nlevels, levels, weights);
   if (rc != BDS_OK) return rc;
   return l1_tv_train_launch(n, a, b, T, tv_blocks, v_loss, loss_out, loss_slots, v_a, as_stream(stream));
-}
-
-extern "C" int bds_bilagrid_ms_ed_train_fwd(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, const float *render,
-                                            const float *alpha, const float *sky, void *ws, size_t ws_bytes, float *rgb_out,
-                                            float *depth_out, const float *target, int tv_nlevels,
-                                            const bds_bilagrid_level_t *tv_levels, const float *tv_weights, float v_loss,
-                                            float *loss_out, int loss_slots, float *v_rgb_out, bds_stream_t stream) {
-  BDS_REQUIRE(alpha && depth_out && target && loss_out && v_rgb_out && H > 0 && W > 0);
-  BDS_REQUIRE(loss_slots >= 1 && (loss_slots & (loss_slots - 1)) == 0);
-  BDS_REQUIRE(aligned16(target) && aligned16(v_rgb_out) && aligned16(rgb_out));
-  TrainLoss tl{};
-  int rc = tv_train_levels(tl.T, tl.tv_blocks, tv_nlevels, tv_levels, tv_weights);
-  if (rc != BDS_OK) return rc;
-  tl.target = target; tl.v_out = v_rgb_out; tl.loss = loss_out; tl.loss_slots = loss_slots;
-  tl.inv_n = 1.0f / (float)((int64_t)H * W * 3); tl.v_loss = v_loss;
-  return ms_fwd_impl(nlevels, levels, H, W, render, 4, alpha, sky, ws, ws_bytes, rgb_out, depth_out, nullptr, stream, &tl);
 }
 
 extern "C" int bds_bilagrid_slice_feat_fwd(int64_t P, int NC, const float *grid, int gx, int gy, int gl, const float *xy,

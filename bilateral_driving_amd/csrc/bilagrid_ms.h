@@ -129,7 +129,7 @@ __device__ __forceinline__ float tv_train_element(const TvLevels &L, int bid, fl
   return acc;
 }
 
-// the training loss folded into the full-resolution forward (bds_bilagrid_ms_ed_train_fwd): L1 against `target` over the pixels this
+// the training loss folded into the full-resolution forward (bds_bilagrid_ms_fwd with a `target`): L1 against `target` over the pixels this
 // launch produces, TV of the grids by tv_blocks extra workgroups behind the pix_blocks pixel workgroups
 constexpr int kLossSlotStride = BDS_LOSS_SLOT_STRIDE;   // floats between two slots: every slot in a 256-byte segment of its own
 struct TrainLoss {

@@ -84,59 +84,36 @@ __global__ __launch_bounds__(kOptBlock) void adam_step_rows_kernel(int64_t n, in
 
 using namespace bds;
 
-extern "C" int bds_adam_step_rows(int64_t n_rows, int width, int64_t grad_stride, float *param, float *grad, float *exp_avg,
-                                  float *exp_avg_sq, double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
-                                  int consume, bds_stream_t stream) {
-  BDS_REQUIRE(n_rows >= 0 && width >= 1 && grad_stride >= width && step >= 1);
+// width == 0: the gradient is n_rows contiguous floats (grad_stride is ignored; 16-byte vectors when every array is aligned).
+// width >= 1: the parameter is [n_rows, width] and its gradient a column range of a row block (adam_step_rows_kernel).
+extern "C" int bds_adam_step(int64_t n_rows, int width, int64_t grad_stride, float *param, float *grad, float *exp_avg, float *exp_avg_sq,
+                             double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step, int consume,
+                             bds_stream_t stream) {
+  BDS_REQUIRE(n_rows >= 0 && width >= 0 && (width == 0 || grad_stride >= width) && step >= 1);
   if (n_rows == 0) return BDS_OK;
-  BDS_REQUIRE(param && grad && exp_avg && exp_avg_sq);
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  const float step_size = (float)(lr / bc1), bc2_sqrt = (float)sqrt(bc2);
-  const int64_t n = n_rows * width;
-  int64_t blocks = cdiv(n, kOptBlock * 2);
-  if (blocks > 8192) blocks = 8192;
-  hipStream_t st = as_stream(stream);
-#define BDS_ADAM_ROWS(C)                                                                                                              \
-  hipLaunchKernelGGL((adam_step_rows_kernel<C>), dim3((unsigned)blocks), dim3(kOptBlock), 0, st, n, width, grad_stride, param, grad,   \
-                     exp_avg, exp_avg_sq, step_size, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), bc2_sqrt, (float)eps,   \
-                     (float)weight_decay)
-  if (consume) BDS_ADAM_ROWS(true); else BDS_ADAM_ROWS(false);
-#undef BDS_ADAM_ROWS
-  BDS_LAUNCH_CHECK();
-  return BDS_OK;
-}
-
-static int adam_step_impl(int64_t n, float *param, float *grad, float *exp_avg, float *exp_avg_sq, double lr, double beta1, double beta2,
-                          double eps, double weight_decay, int64_t step, bool clear, bds_stream_t stream) {
-  BDS_REQUIRE(n >= 0 && step >= 1);
-  if (n == 0) return BDS_OK;
   BDS_REQUIRE(param && grad && exp_avg && exp_avg_sq);
   // scalars in double like Python's float arithmetic in torch/optim/adam.py (1 - beta, bias corrections), each rounded
   // to fp32 once where torch hands it to an fp32 element-wise kernel
   const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
   const float step_size = (float)(lr / bc1), bc2_sqrt = (float)sqrt(bc2);
-  const bool vec = aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq);
+  const bool vec = width == 0 && aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq);
+  const int64_t n = width == 0 ? n_rows : n_rows * width;
   int64_t blocks = cdiv(vec ? cdiv(n, 4) : n, kOptBlock * 2);
   if (blocks > 8192) blocks = 8192;
   if (blocks < 1) blocks = 1;
   hipStream_t st = as_stream(stream);
-#define BDS_ADAM(V, C)                                                                                                                   \
-  hipLaunchKernelGGL((adam_step_kernel<V, C>), dim3((unsigned)blocks), dim3(kOptBlock), 0, st, n, param, grad, exp_avg, exp_avg_sq, step_size, \
+#define BDS_ADAM(KERNEL, ...)                                                                                                             \
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)blocks), dim3(kOptBlock), 0, st, n, __VA_ARGS__, exp_avg, exp_avg_sq, step_size,             \
                      (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), bc2_sqrt, (float)eps, (float)weight_decay)
-  if (vec) { if (clear) BDS_ADAM(true, true); else BDS_ADAM(true, false); }
-  else     { if (clear) BDS_ADAM(false, true); else BDS_ADAM(false, false); }
+  if (width > 0 && consume) BDS_ADAM((adam_step_rows_kernel<true>), width, grad_stride, param, grad);
+  else if (width > 0) BDS_ADAM((adam_step_rows_kernel<false>), width, grad_stride, param, grad);
+  else if (vec && consume) BDS_ADAM((adam_step_kernel<true, true>), param, grad);
+  else if (vec) BDS_ADAM((adam_step_kernel<true, false>), param, grad);
+  else if (consume) BDS_ADAM((adam_step_kernel<false, true>), param, grad);
+  else BDS_ADAM((adam_step_kernel<false, false>), param, grad);
 #undef BDS_ADAM
   BDS_LAUNCH_CHECK();
   return BDS_OK;
-}
-
-extern "C" int bds_adam_step(int64_t n, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, double lr,
-                             double beta1, double beta2, double eps, double weight_decay, int64_t step, bds_stream_t stream) {
-  return adam_step_impl(n, param, const_cast<float *>(grad), exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, false, stream);
-}
-extern "C" int bds_adam_step_consume(int64_t n, float *param, float *grad, float *exp_avg, float *exp_avg_sq, double lr, double beta1,
-                                     double beta2, double eps, double weight_decay, int64_t step, bds_stream_t stream) {
-  return adam_step_impl(n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, true, stream);
 }
 
 // ---- deferred ("row-lazy") Adam: the SAME numbers as the dense pass, bytes proportional to the rows a step touches ---------------
@@ -172,7 +149,7 @@ __device__ __forceinline__ void adam_upd(float &pp, float gg, float &mm, float &
 // The reference's optimizer holds ~10 small groups next to the two SH tensors (xyz, rotation, scaling, opacity, the bilateral grids of
 // every level, sky, poses: models/trainers/base.py:201-226); one launch per tensor is ~8 us of launch gap each for microseconds of
 // work.  bds_adam_step_multi takes up to kAdamMulti tensors with their own hyper-parameters, steps and gradient layouts (contiguous,
-// or a column range of a row block as bds_adam_step_rows) and gives every tensor a contiguous range of the workgroups.
+// or a column range of a row block, as bds_adam_step) and gives every tensor a contiguous range of the workgroups.
 constexpr int kAdamMulti = 12;
 struct AdamMultiArgs {
   float *p[kAdamMulti], *g[kAdamMulti], *m[kAdamMulti], *v[kAdamMulti];

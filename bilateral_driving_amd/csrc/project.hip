@@ -317,7 +317,7 @@ __global__ __launch_bounds__(kProjBlock) void project_view_bwd_list_kernel(
 struct FiniteArgs {
   const uint32_t *p[8];
   int64_t n[8];
-  int kind[8];   // BDS_FINITE_*: what makes the ACTIVATED value of an element non-finite (bds_nonfinite_flags_kinds)
+  int kind[8];   // BDS_FINITE_*: what makes the ACTIVATED value of an element non-finite (bds_nonfinite_flags)
   int count;
 };
 constexpr int kFiniteBlock = 256;
@@ -564,16 +564,10 @@ extern "C" int bds_project_view_bwd_list(int flags, int64_t n_list, const uint64
 
 // Bit t of *flags_dev is set when tensors[t] (counts[t] floats) holds a NaN or an Inf (vanilla.py:407-412); the word is cleared first.
 // flags_pinned (optional, page-locked): receives a copy behind the launch -- the host reads it after its next wait on the stream.
-extern "C" int bds_nonfinite_flags_kinds(int n_tensors, const float *const *tensors, const int64_t *counts, const int *kinds,
-                                         uint32_t *flags_dev, uint32_t *flags_pinned, bds_stream_t stream);
-extern "C" int bds_nonfinite_flags(int n_tensors, const float *const *tensors, const int64_t *counts, uint32_t *flags_dev,
-                                   uint32_t *flags_pinned, bds_stream_t stream) {
-  return bds_nonfinite_flags_kinds(n_tensors, tensors, counts, nullptr, flags_dev, flags_pinned, stream);
-}
 // kinds (optional, [n_tensors]): 0 plain | 1 argument of exp | 2 quaternion rows [n/4, 4] (16-byte aligned) | 3 argument of sigmoid:
 // the bit then says "the ACTIVATED tensor would hold a NaN / Inf" (vanilla.py:393-395 activations, :407-412 check)
-extern "C" int bds_nonfinite_flags_kinds(int n_tensors, const float *const *tensors, const int64_t *counts, const int *kinds,
-                                         uint32_t *flags_dev, uint32_t *flags_pinned, bds_stream_t stream) {
+extern "C" int bds_nonfinite_flags(int n_tensors, const float *const *tensors, const int64_t *counts, const int *kinds,
+                                   uint32_t *flags_dev, uint32_t *flags_pinned, bds_stream_t stream) {
   BDS_REQUIRE(n_tensors >= 0 && n_tensors <= 8 && flags_dev && (n_tensors == 0 || (tensors && counts)));
   FiniteArgs A;
   A.count = n_tensors;

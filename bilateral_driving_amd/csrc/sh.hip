@@ -366,7 +366,7 @@ __global__ __launch_bounds__(kShBlock) void view_grads_clear_list_kernel(int64_t
     const int64_t g = ids[r0 + tid];
     s_g[tid] = (int32_t)g;
     if (g >= 0) {   // negative ids: padding of a fixed-capacity list
-      if (v_means) {   // (null: only the screen-space arrays -- the parameter gradients are cleared by their consumer, bds_adam_step_consume)
+      if (v_means) {   // (null: only the screen-space arrays -- the parameter gradients are cleared by their consumer, bds_adam_step with `consume`)
         if (gl.sm == 16) {      // row form (bds_common.h GradLayout): the whole 64-byte row
           float4 *row = reinterpret_cast<float4 *>(v_means + g * 16);
           row[0] = row[1] = row[2] = row[3] = make_float4(0.f, 0.f, 0.f, 0.f);

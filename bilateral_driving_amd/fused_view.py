@@ -517,6 +517,7 @@ class _FusedView(torch.autograd.Function):
         tl = cfg.get("train_loss")     # train_view: the L1 + TV loss (value and gradients) rides on the full-resolution launch
         ctx.train_loss = None
         with L.timed("bilagrid_fwd"):
+            loss_args = (None, 0, None, None, 0.0, None, 0, None)
             if tl is not None:
                 from .losses import loss_slots
                 v_rgb_loss = _empty((H, W, 3), dev)
@@ -524,14 +525,11 @@ class _FusedView(torch.autograd.Function):
                     loss_acc = ctx.tail[ctx.tail.shape[0] - ctx.loss_rows:].view(-1)
                 else:
                     loss_acc = loss_slots(dev)
-                L.check(lib.bds_bilagrid_ms_ed_train_fwd(len(grids), lv, H, W, L.ptr(render), L.ptr(alphas), L.ptr(sky), L.ptr(bws), bws_bytes,
-                                                         L.ptr(rgb), L.ptr(depth), L.ptr(tl["target"]), len(tl["grids"]), tl["levels"],
-                                                         tl["weights"], 1.0, L.ptr(loss_acc), L.LOSS_SLOTS, L.ptr(v_rgb_loss), st),
-                        "bds_bilagrid_ms_ed_train_fwd")
+                loss_args = (L.ptr(tl["target"]), len(tl["grids"]), tl["levels"], tl["weights"], 1.0, L.ptr(loss_acc), L.LOSS_SLOTS,
+                             L.ptr(v_rgb_loss))
                 ctx.train_loss = (loss_acc, v_rgb_loss)     # (slotted accumulator: train_view sums it off the critical chain)
-            else:
-                L.check(lib.bds_bilagrid_ms_ed_fwd(len(grids), lv, H, W, L.ptr(render), L.ptr(alphas), L.ptr(sky), L.ptr(bws), bws_bytes,
-                                                   L.ptr(rgb), L.ptr(depth), st), "bds_bilagrid_ms_ed_fwd")
+            L.check(lib.bds_bilagrid_ms_fwd(len(grids), lv, H, W, 4, L.ptr(render), L.ptr(alphas), L.ptr(sky), L.ptr(bws), bws_bytes,
+                                            L.ptr(rgb), L.ptr(depth), None, *loss_args, st), "bds_bilagrid_ms_fwd")
         rgb_g = render[0, :, :, :3]   # view: the Gaussians' colour before clamp / sky / transform (clamped on access, see _Out)
         # The backward's first launch (bilateral transform) is prepared HERE when its gradient targets are already known (in-place
         # grid gradients): at that point of a step the host is only tens of microseconds ahead of the GPU, and every allocation
@@ -623,15 +621,12 @@ class _FusedView(torch.autograd.Function):
         # (a split launch -- long tiles strip by strip -- keeps those tiles out of the schedule: only bds_rasterize_bwd finds them)
         split = _split(cfg, ctx.list_tile, tw * th, getattr(ctx, "split_ok", False)) if getattr(ctx, "dev_counts", None) is not None else (0, 0, 0)
         defer = (_DEFER_EPILOGUE and cfg.get("defer_epilogue", True) and M > 0 and n_vis > 0 and split[0] == 0
-                 and bool(lib.bds_bilagrid_ms_ed_bwd_deferrable(len(grids), lv, H, W)))
+                 and bool(lib.bds_bilagrid_ms_bwd_deferrable(len(grids), lv, H, W)))
         with L.timed("bilagrid_bwd"):
-            if defer:
-                L.check(lib.bds_bilagrid_ms_ed_bwd_deferred(len(grids), lv, H, W, L.ptr(render), L.ptr(alphas), L.ptr(sky), L.ptr(bws),
-                                                            bws.numel(), L.ptr(v_rgb), L.ptr(v_render), st), "bds_bilagrid_ms_ed_bwd_deferred")
-            else:
-                L.check(lib.bds_bilagrid_ms_ed_bwd(len(grids), lv, H, W, L.ptr(render), L.ptr(alphas), L.ptr(sky), L.ptr(bws), bws.numel(),
-                                                   L.ptr(v_rgb), L.ptr(v_depth), L.ptr(v_opacity), L.ptr(v_render), L.ptr(v_alphas),
-                                                   L.ptr(v_sky), st), "bds_bilagrid_ms_ed_bwd")
+            # (deferred: v_depth, v_opacity and v_sky go to the compositor's backward below instead)
+            late = (None, None, v_render, None, None) if defer else (v_depth, v_opacity, v_render, v_alphas, v_sky)
+            L.check(lib.bds_bilagrid_ms_bwd(len(grids), lv, H, W, 4, L.ptr(render), L.ptr(alphas), L.ptr(sky), L.ptr(bws), bws.numel(),
+                                            L.ptr(v_rgb), *map(L.ptr, late), int(defer), st), "bds_bilagrid_ms_bwd")
         # compositing: gradient records of the visible Gaussians, in the order of vis_ids (64 bytes each)
         # (+ the camera-pose gradient slots of the projection backward behind them: one zero fill for both)
         want_pose = bool(ctx.needs_input_grad[7])

@@ -55,7 +55,7 @@ class RawGaussians:
             else:
                 raise KeyError(field)
             # the reference raises on a NaN / Inf in ANY of the activated tensors (vanilla.py:407-412).  The one-view node checks the
-            # raw parameters itself (bds_nonfinite_flags_kinds); every OTHER route to an activated tensor -- several classes
+            # raw parameters itself (bds_nonfinite_flags with kinds); every OTHER route to an activated tensor -- several classes
             # concatenated, opacity masks, backgrounds, the fall-back of rasterization() -- comes through here, once per field
             v = t.detach()
             if bool((~torch.isfinite(v)).any()):

@@ -158,7 +158,7 @@ def _finite_check(self, gs: dict, flags: Tensor) -> None:
     ts = [gs[k] for k in GS_KEYS]
     ptrs = (L.C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
     cnts = (L.C.c_int64 * len(ts))(*[t.numel() for t in ts])
-    L.check(L.lib().bds_nonfinite_flags_kinds(len(ts), ptrs, cnts, None, flags.data_ptr(), None, L.stream()), "bds_nonfinite_flags_kinds")
+    L.check(L.lib().bds_nonfinite_flags(len(ts), ptrs, cnts, None, flags.data_ptr(), None, L.stream()), "bds_nonfinite_flags")
     word, bad = (int(v) for v in flags.cpu())
     if bad:
         raise IndexError(f"point_ids holds an instance id outside [0, {self.instances_fv.shape[1]})")

@@ -16,7 +16,7 @@ class FusedAdam(torch.optim.Optimizer):
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  consume_grads: bool = False):
-        """``consume_grads``: every gradient is cleared by the pass that reads it (bds_adam_step_consume) -- for loops whose backward
+        """``consume_grads``: every gradient is cleared by the pass that reads it (bds_adam_step with ``consume``) -- for loops whose backward
         accumulates into persistent ``.grad`` buffers (``graph_view.FrameGraph(clear_grads=False)``): no ``zero_grad()`` pass."""
         self.consume_grads = bool(consume_grads)
         # the small groups (xyz, rotation, scaling, opacity, the grids of every level, ...) step in ONE launch (include/bds.h
@@ -87,8 +87,8 @@ class FusedAdam(torch.optim.Optimizer):
                     if self.multi_tensor:
                         batch.append((p, gr.data_ptr(), m, v, p.numel(), width, int(gr.stride(0)), *hyper))
                         continue
-                    L.check(lib.bds_adam_step_rows(p.shape[0], width, int(gr.stride(0)), L.ptr(p), gr.data_ptr(), L.ptr(m), L.ptr(v),
-                                                   *hyper[:5], hyper[5], int(self.consume_grads), st), "bds_adam_step_rows")
+                    L.check(lib.bds_adam_step(p.shape[0], width, int(gr.stride(0)), L.ptr(p), gr.data_ptr(), L.ptr(m), L.ptr(v), *hyper,
+                                              int(self.consume_grads), st), "bds_adam_step")
                     continue
                 g = p.grad.contiguous()
                 consume = self.consume_grads and g.data_ptr() == p.grad.data_ptr()     # (clearing a contiguous COPY would clear nothing)
@@ -97,8 +97,7 @@ class FusedAdam(torch.optim.Optimizer):
                     if g is not p.grad:
                         batch[-1] = batch[-1] + (g,)     # (keep the contiguous copy alive until the launch)
                     continue
-                fn = lib.bds_adam_step_consume if consume else lib.bds_adam_step
-                L.check(fn(p.numel(), L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), *hyper, st), "bds_adam_step")
+                L.check(lib.bds_adam_step(p.numel(), 0, 0, L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), *hyper, int(consume), st), "bds_adam_step")
                 if self.consume_grads and not consume:
                     p.grad.zero_()
         # tensors whose gradients are column ranges of ONE [N,16] row block (dist.FlatGradients(row_block=True)) step together through

@@ -259,7 +259,7 @@ class _RasterizeRawView(torch.autograd.Function):
             ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
             cnts = (ctypes.c_int64 * len(ts))(*[t.numel() for t in ts])
             kinds = (ctypes.c_int * len(ts))(0, 2 if quats.data_ptr() % 16 == 0 else 0, 1, 3, 0, 0)
-            L.check(lib.bds_nonfinite_flags_kinds(len(ts), ptrs, cnts, kinds, flags[0].data_ptr(), flags[1].data_ptr(), st), "bds_nonfinite_flags")
+            L.check(lib.bds_nonfinite_flags(len(ts), ptrs, cnts, kinds, flags[0].data_ptr(), flags[1].data_ptr(), st), "bds_nonfinite_flags")
         f = _view_front(fcfg, means, quats, log_scales, logits.reshape(N), (dc, rest), viewmat, lambda: _image_buffers(W, H, dev))
         if flags is not None and int(flags[1][0]):
             bad = [n for i, n in enumerate(("means", "quats", "scales", "opacities", "features_dc", "features_rest")) if int(flags[1][0]) >> i & 1]

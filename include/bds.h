@@ -25,11 +25,16 @@
 extern "C" {
 #endif
 
-#define BDS_ABI_VERSION 5   /* 3: the projection's entries folded into four (bds_project_fwd, bds_project_view_fwd and
+#define BDS_ABI_VERSION 6   /* 3: the projection's entries folded into four (bds_project_fwd, bds_project_view_fwd and
                                bds_project_view_bwd_list changed signatures)
                                4: the view path's host-count / device-count / split-storage twins folded into one entry each
                                (bds_splat_pack, bds_splat_pack_sh, bds_rasterize_fwd / _bwd, bds_sh_view_bwd_list, bds_view_grads_clear_list)
-                               5: the tile stage's five entries folded into two (bds_isect_prepare and bds_isect_build changed signatures) */
+                               5: the tile stage's five entries folded into two (bds_isect_prepare and bds_isect_build changed signatures)
+                               6: the colour transform's forward / backward, Adam's single-tensor step and the NaN / Inf check are one
+                               entry each (bds_bilagrid_ms_fwd, bds_bilagrid_ms_bwd, bds_adam_step, bds_nonfinite_flags changed
+                               signatures; bds_bilagrid_ms_ed_fwd, _ms_ed_train_fwd, _ms_ed_bwd, _ms_ed_bwd_deferred,
+                               bds_adam_step_consume, bds_adam_step_rows, bds_nonfinite_flags_kinds and the unused
+                               bds_bilagrid_tv_fwd / _bwd are gone; bds_bilagrid_ms_ed_bwd_deferrable is bds_bilagrid_ms_bwd_deferrable) */
 
 #define BDS_OK 0
 #define BDS_EINVAL (-1)      /* null / misaligned pointer, bad shape or unsupported parameter */
@@ -53,7 +58,7 @@ const char *bds_strerror(int code);
  * 7 = bilateral transform, bit mask [default 3]: bit 0 = the cell-aligned kernels (csrc/bilagrid_cells.hip) wherever a level
  *     qualifies (one grid per level); bit 1 = the pyramid forward as one pass over the image (csrc/bilagrid_tile.hip) when every
  *     factor is a power of two >= 2 dividing the image; bit 2 = do NOT defer the backward's last stage to the compositor
- *     (bds_bilagrid_ms_ed_bwd_deferrable returns 0); 0 = the general kernels everywhere (what levels averaged over several
+ *     (bds_bilagrid_ms_bwd_deferrable returns 0); 0 = the general kernels everywhere (what levels averaged over several
  *     grids always take).  Same results.
  * Other indices are unused. */
 int bds_set_option(int which, int value);
@@ -337,23 +342,38 @@ typedef struct {
 } bds_bilagrid_level_t;
 
 size_t bds_bilagrid_ms_workspace_bytes(int nlevels, const bds_bilagrid_level_t *levels, int H, int W);
-/* ws keeps the low-resolution affine maps (fwd -> bwd). affine_out (NULL or nlevels x [H,W,12]
- * pointers) receives the full-resolution per-level maps the reference module returns. */
-int bds_bilagrid_ms_fwd(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, const float *rgb,
-                        const float *alpha, const float *sky, void *ws, size_t ws_bytes, float *rgb_out,
-                        float *const *affine_out, bds_stream_t stream);
-/* v_rgb [H,W,3] written; v_alpha [H,W], v_sky [H,W,3] written when sky != NULL. */
-int bds_bilagrid_ms_bwd(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, const float *rgb,
-                        const float *alpha, const float *sky, void *ws, size_t ws_bytes, const float *v_rgb_out,
-                        float *v_rgb, float *v_alpha, float *v_sky, bds_stream_t stream);
+/* Forward.  ws keeps the low-resolution affine maps (fwd -> bwd).  The forms, by `channels` (any other value, or a mix: BDS_EINVAL):
+ *   3: `in` is the colour [H,W,3].  affine_out (NULL or nlevels x [H,W,12] pointers) receives the full-resolution per-level maps the
+ *      reference module returns.  depth_out and target must be NULL.
+ *   4: the RGB+ED form.  `in` is the compositor's 4-channel render [H*W,4] (RGB + accumulated depth, gsplat render_mode "RGB+ED");
+ *      alpha and depth_out are required: depth_out [H*W] = in[.,3] / max(alpha, 1e-10) (the normalise inside gsplat's
+ *      rasterization(); split as in models/trainers/base.py:414-419).  affine_out must be NULL.
+ *   4 with target != NULL: the training loss of the direct step rides on the same launch (no further pass over the image).  The
+ *      full-resolution kernel also compares the pixel it just produced with target [H*W,3] -- loss_out (required; loss_slots a power
+ *      of two, slotted as in bds_l1_tv_train) += mean|rgb_out - target|, v_rgb_out [H*W,3] (required) = sign(rgb_out - target) *
+ *      v_loss / (3 H W) -- and tv_nlevels (may be 0) extra levels' worth of workgroups add sum_l tv_weights[l] *
+ *      TV(tv_levels[l].grid) to loss_out and v_loss * its gradient to tv_levels[l].v_grid (atomics; may be NULL).  target, v_rgb_out
+ *      and rgb_out 16-byte aligned.  Same result as the form without a target followed by bds_l1_tv_train.
+ *      (models/trainers/base.py:518-565 rgb term + `losses.affine`, models/modules.py:445,466-472.)
+ *   With target == NULL the arguments from tv_nlevels to v_rgb_out are ignored. */
+int bds_bilagrid_ms_fwd(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, int channels, const float *in,
+                        const float *alpha, const float *sky, void *ws, size_t ws_bytes, float *rgb_out, float *depth_out,
+                        float *const *affine_out, const float *target, int tv_nlevels, const bds_bilagrid_level_t *tv_levels,
+                        const float *tv_weights, float v_loss, float *loss_out, int loss_slots, float *v_rgb_out, bds_stream_t stream);
+/* Backward, same workspace.  The forms, by `channels` (any other value, or a mix: BDS_EINVAL):
+ *   3: v_in [H,W,3] written; v_alpha [H,W], v_sky [H,W,3] written when sky != NULL.  v_depth, v_opacity NULL and defer 0.
+ *   4: the RGB+ED form.  Returns v_in [H*W,4] and, in v_alpha (required, as alpha), the TOTAL alpha gradient: colour transform (sky
+ *      blend) + expected depth + the caller's own v_opacity; v_depth / v_opacity / v_sky may be NULL.
+ *   4 with defer != 0: the backward WITHOUT its last stage, see bds_bilagrid_ms_bwd_deferrable below.  v_in [H*W,4] receives the
+ *      direct-route gradient (channels 0-2); v_depth, v_opacity, v_alpha and v_sky must be NULL; BDS_EINVAL for a configuration that
+ *      is not deferrable. */
+int bds_bilagrid_ms_bwd(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, int channels, const float *in,
+                        const float *alpha, const float *sky, void *ws, size_t ws_bytes, const float *v_rgb_out, const float *v_depth,
+                        const float *v_opacity, float *v_in, float *v_alpha, float *v_sky, int defer, bds_stream_t stream);
 
-/* TV regulariser: bilateral/lib_bilagrid.py:152-168 total_variation_loss on [n,12,L,gy,gx].
- * tv_out [1] is accumulated (caller zero-fills) with weight*tv; v_grids += weight*v_tv*dtv/dgrid. */
-int bds_bilagrid_tv_fwd(int64_t n, int gx, int gy, int gl, const float *grids, float weight, float *tv_out,
-                        bds_stream_t stream);
-int bds_bilagrid_tv_bwd(int64_t n, int gx, int gy, int gl, const float *grids, float weight, const float *v_tv,
-                        float *v_grids, bds_stream_t stream);
-/* ... and for grids with `channels` != 12 (NeuralBilateralGrid.tv_loss): grids [n, channels, gl, gy, gx] */
+/* TV regulariser: bilateral/lib_bilagrid.py:152-168 total_variation_loss on grids [n, channels, gl, gy, gx] (12 channels there;
+ * NeuralBilateralGrid.tv_loss has others).  tv_out [1] is accumulated (caller zero-fills) with weight*tv; v_grids +=
+ * weight*v_tv*dtv/dgrid. */
 int bds_grid_tv_fwd(int64_t n, int channels, int gx, int gy, int gl, const float *grids, float weight, float *tv_out,
                     bds_stream_t stream);
 int bds_grid_tv_bwd(int64_t n, int channels, int gx, int gy, int gl, const float *grids, float weight, const float *v_tv,
@@ -433,7 +453,7 @@ int bds_sh_view_fwd(int64_t N, int K, int degrees_to_use, const float *means, co
  * v_quats, v_log_scales, v_logits may be the columns of one 16-byte aligned [N,16] block of 64-byte rows {v_mean 3, v_logit | v_quat 4 |
  * v_log_scale 3, - | - - - -}: pass v_means = block, v_logits = block + 3, v_quats = block + 4, v_log_scales = block + 8.
  * bds_project_view_bwd_list then updates, and bds_view_grads_clear_list clears, ONE line per visible Gaussian instead of four partly
- * used ones; bds_adam_step_rows reads such columns. */
+ * used ones; bds_adam_step with a width reads such columns. */
 /* sh_rgb: the un-clamped colours the forward left -- [N,3] indexed by Gaussian (bds_sh_view_fwd), or, with sh_rgb_by_rank != 0,
  * [n_list,3] in list order (bds_splat_pack_sh).
  * v_coeffs_rest (NULL: v_coeffs is [N,K,3]): the split storage of bds_splat_pack_sh -- v_coeffs [N,3], v_coeffs_rest [N,K-1,3]
@@ -445,15 +465,13 @@ int bds_sh_view_bwd_list(int64_t n_list, const uint64_t *n_dev, const int32_t *i
 /* NaN / Inf check of the tensors a Gaussian class hands to the rasterizer (models/gaussians/vanilla.py:407-412 raises ValueError per
  * tensor; two reductions and two host waits each there): ONE streaming launch over up to 8 tensors; bit t of *flags_dev (cleared
  * first) is set when tensors[t] (counts[t] floats) holds a non-finite value; flags_pinned (optional, page-locked) receives a copy
- * behind the launch, for the host to read after its next wait on the stream. */
-int bds_nonfinite_flags(int n_tensors, const float *const *tensors, const int64_t *counts, uint32_t *flags_dev,
-                        uint32_t *flags_pinned, bds_stream_t stream);
-/* The same with a KIND per tensor (kinds [n_tensors], NULL = all 0): the bit says "the tensor's ACTIVATED value would hold a NaN / Inf"
- * for raw parameters whose activation runs inside a kernel (vanilla.py:393-395, checked at :407-412 on the activated tensors):
+ * behind the launch, for the host to read after its next wait on the stream.
+ * kinds ([n_tensors], NULL = all 0): with a KIND the bit says "the tensor's ACTIVATED value would hold a NaN / Inf", for raw
+ * parameters whose activation runs inside a kernel (vanilla.py:393-395, checked at :407-412 on the activated tensors):
  * 0 plain (NaN, +-Inf) | 1 argument of exp (NaN, +Inf, x >= 88.72284: exp overflows; -Inf is fine) | 2 quaternion rows [n/4, 4],
  * 16-byte aligned (NaN / Inf components, or a row whose squared norm is 0 in fp32: 0/0, x/0) | 3 argument of sigmoid (NaN only). */
-int bds_nonfinite_flags_kinds(int n_tensors, const float *const *tensors, const int64_t *counts, const int *kinds, uint32_t *flags_dev,
-                              uint32_t *flags_pinned, bds_stream_t stream);
+int bds_nonfinite_flags(int n_tensors, const float *const *tensors, const int64_t *counts, const int *kinds, uint32_t *flags_dev,
+                        uint32_t *flags_pinned, bds_stream_t stream);
 /* The list-driven projection backward over the visible entries (C = 1; ids, v_records, `accumulate` and row_map as above): the rows of
  * v_means [N,3] v_quats [N,4] v_scales [N,3] v_opacities [N].
  *   flags & BDS_PROJ_ACCUMULATE: ADD to the rows (accumulate = 1 above) instead of storing them.
@@ -483,8 +501,8 @@ int bds_project_view_bwd_list(int flags, int64_t n_list, const uint64_t *n_dev, 
  * grad2d / absgrad2d [N,2], optional: the same rows of a view's PERSISTENT screen-space gradient arrays are cleared as well -- the
  * list-driven projection backward stores the visible rows, so a buffer cleared by the previous visit's list needs no dense fill.
  * The five parameter-gradient pointers may ALL be NULL: only the screen-space arrays are cleared then -- a loop whose optimizer
- * clears the gradients as it consumes them, bds_adam_step_consume.  (Both serve the device-count view; the kernel takes them with a
- * host count as well.) */
+ * clears the gradients as it consumes them (bds_adam_step with consume != 0).  (Both serve the device-count view; the kernel
+ * takes them with a host count as well.) */
 int bds_view_grads_clear_list(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, int K, float *v_means, float *v_quats,
                               float *v_log_scales, float *v_logits, float *v_sh, float *grad2d, float *absgrad2d, bds_stream_t stream);
 /* v_*[ids[s]] += s_*[s]: compact rows (s_means [n_list,3] s_quats [n_list,4] s_log_scales [n_list,3] s_logits [n_list]
@@ -505,21 +523,18 @@ int bds_bilagrid_select(int nlevels, const bds_bilagrid_level_t *levels, const i
 int bds_bilagrid_select_bwd(int nlevels, const bds_bilagrid_level_t *levels, const int32_t *img_idx_dev, float *const *v_sel,
                             int32_t *error_pinned, bds_stream_t stream);
 
-/* The colour transform's backward WITHOUT its last stage, and the compositor's backward that finishes it (one camera, RGB+ED; the
- * fused view, models/trainers/base.py:393-419 + scene_graph.py:86-120,292-294 as one backward).  The last stage of
- * bds_bilagrid_ms_ed_bwd -- guidance route added to the direct route, clamp(max=1) / sky blend / expected-depth backward -- is a
+/* The colour transform's backward WITHOUT its last stage (bds_bilagrid_ms_bwd with defer != 0), and the compositor's backward that
+ * finishes it (one camera, RGB+ED; the fused view, models/trainers/base.py:393-419 + scene_graph.py:86-120,292-294 as one
+ * backward).  The last stage of bds_bilagrid_ms_bwd -- guidance route added to the direct route, clamp(max=1) / sky blend / expected-depth backward -- is a
  * per-pixel function of arrays that exist by then; bds_rasterize_bwd_ms evaluates it for its tile's pixels while it waits for the
  * tile's first records, so v_render [H,W,4] and v_alpha [H,W] are never written and read back and one pass over the image (45 us,
- * 172 MB at 1080p) disappears.  _deferrable: 1 when every level has one grid (gl <= 8) and a factor that is 1 or a power of two
- * dividing H and W (and bit 2 of bds_set_option(7, ..) is clear), else 0 -- use bds_bilagrid_ms_ed_bwd then.  _deferred: v_direct
- * [H,W,4] receives the direct-route gradient (channels 0-2); the grids' gradients are complete on return.  bds_rasterize_bwd_ms:
+ * 172 MB at 1080p) disappears.  bds_bilagrid_ms_bwd_deferrable: 1 when every level has one grid (gl <= 8) and a factor that is 1 or a power of two
+ * dividing H and W (and bit 2 of bds_set_option(7, ..) is clear), else 0 (bad arguments included) -- call with defer = 0 then.  Deferred, the
+ * grids' gradients are complete on return and v_direct is the call's v_in.  bds_rasterize_bwd_ms:
  * bds_rasterize_bwd (M_dev NULL: M_capacity is the host-side count; no split launch) for C = 1, CH = 4, no backgrounds, with the image
  * gradient formed from (levels, ms_ws: the transform's workspace), render [H,W,4] (the compositor's forward output), sky,
  * v_depth / v_alpha_in (may be NULL) and v_direct; writes v_sky [H,W,3] (may be NULL). */
-int bds_bilagrid_ms_ed_bwd_deferrable(int nlevels, const bds_bilagrid_level_t *levels, int H, int W);
-int bds_bilagrid_ms_ed_bwd_deferred(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, const float *render,
-                                    const float *alpha, const float *sky, void *ws, size_t ws_bytes, const float *v_rgb_out,
-                                    float *v_direct, bds_stream_t stream);
+int bds_bilagrid_ms_bwd_deferrable(int nlevels, const bds_bilagrid_level_t *levels, int H, int W);
 int bds_rasterize_bwd_ms(int64_t n_records, int64_t M_capacity, const uint64_t *M_dev, const float *records, int W, int H,
                          int tile_size, int list_tile_size, int tile_w, int tile_h, const int32_t *isect_offsets,
                          const int32_t *flatten, const float *alphas, const float *t_final, const int32_t *last_ids, float *v_records,
@@ -571,33 +586,9 @@ int bds_union_slots(int64_t N, const uint8_t *mask, int64_t capacity, int K, int
                     float *b_quats, float *b_log_scales, float *b_logits, float *b_sh, void *ws, size_t ws_bytes,
                     uint64_t *count_dev, int64_t *count_pinned, bds_stream_t stream);
 
-/* RGB+ED form of the fused image transform: the input is the compositor's 4-channel render [H*W,4] (RGB +
- * accumulated depth, gsplat render_mode "RGB+ED") and its alpha.  Forward additionally writes the expected depth
- * depth [H*W] = render[.,3] / max(alpha, 1e-10) (the normalise inside gsplat's rasterization(); split as in
- * models/trainers/base.py:414-419).  Backward returns v_render [H*W,4] and the TOTAL alpha gradient: colour
- * transform (sky blend) + expected depth + the caller's own v_opacity; v_depth / v_opacity / v_sky may be NULL.
- * Same workspace as bds_bilagrid_ms_fwd/bwd. */
-int bds_bilagrid_ms_ed_fwd(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, const float *render,
-                           const float *alpha, const float *sky, void *ws, size_t ws_bytes, float *rgb_out,
-                           float *depth_out, bds_stream_t stream);
-/* bds_bilagrid_ms_ed_fwd with the training loss of the direct step riding on the same launch (no further pass over the image): the
- * full-resolution kernel also compares the pixel it just produced with target [H*W,3] -- loss_out (slotted as in bds_l1_tv_train) +=
- * mean|rgb_out - target|, v_rgb_out [H*W,3] = sign(rgb_out - target) * v_loss / (3 H W) -- and tv_nlevels extra levels' worth of
- * workgroups add sum_l tv_weights[l] * TV(tv_levels[l].grid) to loss_out and v_loss * its gradient to tv_levels[l].v_grid (atomics;
- * may be NULL).  Same result as bds_bilagrid_ms_ed_fwd followed by bds_l1_tv_train.  (models/trainers/base.py:518-565 rgb term +
- * `losses.affine`, models/modules.py:445,466-472.) */
-int bds_bilagrid_ms_ed_train_fwd(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, const float *render, const float *alpha,
-                                 const float *sky, void *ws, size_t ws_bytes, float *rgb_out, float *depth_out, const float *target,
-                                 int tv_nlevels, const bds_bilagrid_level_t *tv_levels, const float *tv_weights, float v_loss,
-                                 float *loss_out, int loss_slots, float *v_rgb_out, bds_stream_t stream);
-int bds_bilagrid_ms_ed_bwd(int nlevels, const bds_bilagrid_level_t *levels, int H, int W, const float *render,
-                           const float *alpha, const float *sky, void *ws, size_t ws_bytes, const float *v_rgb_out,
-                           const float *v_depth, const float *v_opacity, float *v_render, float *v_alpha, float *v_sky,
-                           bds_stream_t stream);
-
 /* ---- photometric L1 (the step right after the path) ---------------------------------
  * models/trainers/base.py:518-529: mean |a - b| over n floats.  out [1] is ACCUMULATED (caller zero-fills, so that
- * the TV terms of bds_bilagrid_tv_fwd can land in the same scalar); a, b 16-byte aligned.
+ * the TV terms of bds_grid_tv_fwd can land in the same scalar); a, b 16-byte aligned.
  * bwd: v_a = sign(a - b) * v_out / n with v_out a device scalar. */
 int bds_l1_mean_fwd(int64_t n, const float *a, const float *b, float *out, bds_stream_t stream);
 int bds_l1_mean_bwd(int64_t n, const float *a, const float *b, const float *v_out, float *v_a, bds_stream_t stream);
@@ -633,20 +624,17 @@ int bds_pixel_loss_bwd(int64_t P, const float *rgb, const float *pixels, const f
  * torch.optim.Adam as the reference trainer configures it (models/trainers/base.py:201-222: per-group lr / eps /
  * weight_decay, betas (0.9, 0.999), amsgrad off), one streaming pass, in place on param / exp_avg / exp_avg_sq.
  * `step` is the 1-based step count AFTER the increment (torch's state["step"]); the hyper-parameters are doubles (Python
- * floats): 1 - beta and the bias corrections are formed in double and rounded to fp32 once, as torch does. */
-int bds_adam_step(int64_t n, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, double lr, double beta1,
-                  double beta2, double eps, double weight_decay, int64_t step, bds_stream_t stream);
-/* The same, and the gradient is cleared as it is read ("consume and clear"): a training loop whose backward ACCUMULATES into
+ * floats): 1 - beta and the bias corrections are formed in double and rounded to fp32 once, as torch does.
+ * width == 0: a contiguous gradient of n_rows floats (grad_stride is ignored; 16-byte vectors when every array is aligned).
+ * width >= 1: a parameter [n_rows, width] whose gradient is a column range of a wider row block, element (r, c) at
+ * grad[r * grad_stride + c] with grad_stride >= width (the [N,16] row form of the four small per-Gaussian gradients, see
+ * bds_project_view_bwd_list).
+ * consume != 0: the gradient is cleared as it is read ("consume and clear"): a training loop whose backward ACCUMULATES into
  * persistent gradient buffers (dist.FlatGradients / graph_view.FrameGraph) then needs no clearing pass before the next step --
  * what optimizer.zero_grad() (tools/train.py:266) costs the reference as one more pass over every gradient. */
-int bds_adam_step_consume(int64_t n, float *param, float *grad, float *exp_avg, float *exp_avg_sq, double lr, double beta1,
-                          double beta2, double eps, double weight_decay, int64_t step, bds_stream_t stream);
-/* The same update for a parameter [n_rows, width] whose gradient is a column range of a wider row block: element (r, c) at
- * grad[r * grad_stride + c] (the [N,16] row form of the four small per-Gaussian gradients, see bds_project_view_bwd_list);
- * consume != 0 clears the gradient as it is read. */
-int bds_adam_step_rows(int64_t n_rows, int width, int64_t grad_stride, float *param, float *grad, float *exp_avg, float *exp_avg_sq,
-                       double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step, int consume,
-                       bds_stream_t stream);
+int bds_adam_step(int64_t n_rows, int width, int64_t grad_stride, float *param, float *grad, float *exp_avg, float *exp_avg_sq,
+                  double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step, int consume,
+                  bds_stream_t stream);
 
 /* The same update for up to four parameter tensors [N, widths[t]] whose gradients are the column ranges [col0[t], col0[t] + widths[t])
  * of ONE [N,16] row block (64-byte rows; the four small per-Gaussian gradients, see bds_project_view_bwd_list), in one launch that
@@ -655,7 +643,7 @@ int bds_adam_step_rowblock(int64_t N, float *grad_block, int n_parts, float *con
                            float *const *exp_avg_sqs, const int *col0, const int *widths, const double *lrs, const double *beta1s,
                            const double *beta2s, const double *eps, const double *weight_decays, const int64_t *steps, int consume,
                            bds_stream_t stream);
-/* bds_adam_step / _consume / _rows for up to 12 tensors in ONE launch (the trainer's ~10 small groups, models/trainers/base.py:201-226:
+/* bds_adam_step for up to 12 tensors in ONE launch (the trainer's ~10 small groups, models/trainers/base.py:201-226:
  * one launch per tensor is mostly launch gap).  Arrays of n_tensors entries; widths[t] = 0: a contiguous gradient, else element
  * (r, c) of tensor t's gradient at grads[t][r * grad_strides[t] + c] with c < widths[t]; steps[t]: the tensor's own 1-based step.
  * The same arithmetic per element: bit-equal to the single-tensor passes. */

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Where the colour transform's backward spends its time (measurement tooling): bds_bilagrid_ms_ed_bwd at 1920x1080, three levels
+"""Where the colour transform's backward spends its time (measurement tooling): bds_bilagrid_ms_bwd (RGB+ED form) at 1920x1080, three levels
 (grids 2x2x1 / 4x4x2 / 8x8x4, factors 4 / 4 / 2), on a smooth synthetic render, with the ablation bits of option 3
 (1: no y pass, 2: no grid scatter, 4: no guidance route)."""
 import math
@@ -33,11 +33,12 @@ def main():
     rgb, depth = torch.empty(H, W, 3, device=dev), torch.empty(H, W, device=dev)
     nb = lib.bds_bilagrid_ms_workspace_bytes(3, lv, H, W)
     ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-    L.check(lib.bds_bilagrid_ms_ed_fwd(3, lv, H, W, L.ptr(render), L.ptr(alphas), L.ptr(sky), L.ptr(ws), nb, L.ptr(rgb), L.ptr(depth), st), "fwd")
+    L.check(lib.bds_bilagrid_ms_fwd(3, lv, H, W, 4, L.ptr(render), L.ptr(alphas), L.ptr(sky), L.ptr(ws), nb, L.ptr(rgb), L.ptr(depth), None,
+                                    None, 0, None, None, 0.0, None, 0, None, st), "fwd")
 
     def bwd():
-        L.check(lib.bds_bilagrid_ms_ed_bwd(3, lv, H, W, L.ptr(render), L.ptr(alphas), L.ptr(sky), L.ptr(ws), nb, L.ptr(v_rgb), None, None,
-                                           L.ptr(v_render), L.ptr(v_alpha), L.ptr(v_sky), st), "bwd")
+        L.check(lib.bds_bilagrid_ms_bwd(3, lv, H, W, 4, L.ptr(render), L.ptr(alphas), L.ptr(sky), L.ptr(ws), nb, L.ptr(v_rgb), None, None,
+                                        L.ptr(v_render), L.ptr(v_alpha), L.ptr(v_sky), 0, st), "bwd")
 
     for name, mask in (("full", 0), ("full, general guidance gather", 2048), ("full, general x / y pass taps", 4096), ("no y pass", 1), ("no grid scatter", 2), ("no guidance route", 4), ("none of the three", 7)):
         lib.bds_set_option(L.OPT_DEBUG, mask)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Isolated timing of the colour transform's forward with and without the training loss on its launch (measurement tooling):
-bds_bilagrid_ms_ed_fwd + bds_l1_tv_train against bds_bilagrid_ms_ed_train_fwd at 1920x1080, three levels."""
+bds_bilagrid_ms_fwd + bds_l1_tv_train against bds_bilagrid_ms_fwd with a target at 1920x1080, three levels."""
 import ctypes as C
 import math
 import os
@@ -31,16 +31,19 @@ def main():
     nb = lib.bds_bilagrid_ms_workspace_bytes(3, lv, H, W)
     ws = torch.empty(nb, dtype=torch.uint8, device=dev)
 
+    def fwd(*loss_args):       # target .. v_rgb_out
+        L.check(lib.bds_bilagrid_ms_fwd(3, lv, H, W, 4, L.ptr(render), L.ptr(alphas), L.ptr(sky), L.ptr(ws), nb, L.ptr(rgb), L.ptr(depth), None,
+                                        *loss_args, st), "fwd")
+
+    def plain():
+        fwd(None, 0, None, None, 0.0, None, 0, None)
+
     def separate():
-        L.check(lib.bds_bilagrid_ms_ed_fwd(3, lv, H, W, L.ptr(render), L.ptr(alphas), L.ptr(sky), L.ptr(ws), nb, L.ptr(rgb), L.ptr(depth), st), "fwd")
+        plain()
         L.check(lib.bds_l1_tv_train(rgb.numel(), L.ptr(rgb), L.ptr(target), 3, tv, wts, 1.0, L.ptr(loss), L.LOSS_SLOTS, L.ptr(v_rgb), st), "loss")
 
     def fused():
-        L.check(lib.bds_bilagrid_ms_ed_train_fwd(3, lv, H, W, L.ptr(render), L.ptr(alphas), L.ptr(sky), L.ptr(ws), nb, L.ptr(rgb), L.ptr(depth),
-                                                 L.ptr(target), 3, tv, wts, 1.0, L.ptr(loss), L.LOSS_SLOTS, L.ptr(v_rgb), st), "train_fwd")
-
-    def plain():
-        L.check(lib.bds_bilagrid_ms_ed_fwd(3, lv, H, W, L.ptr(render), L.ptr(alphas), L.ptr(sky), L.ptr(ws), nb, L.ptr(rgb), L.ptr(depth), st), "fwd")
+        fwd(L.ptr(target), 3, tv, wts, 1.0, L.ptr(loss), L.LOSS_SLOTS, L.ptr(v_rgb))
 
     for name, fn in (("plain transform", plain), ("transform + loss launch", separate), ("loss on the transform launch", fused)):
         for _ in range(5):

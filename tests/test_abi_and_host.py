@@ -24,7 +24,7 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(bds_[a-z0-9_]+)\s*\(", src)))
 
 
-def test_header_and_library_symbols_match_abi_5(libpath):
+def test_header_and_library_symbols_match_abi_6(libpath):
     names = _declared_symbols()
     assert len(names) >= 19
     h = ctypes.CDLL(libpath)
@@ -37,7 +37,7 @@ def test_header_and_library_symbols_match_abi_5(libpath):
     assert not exported - set(names), f"exported by libbds.so but not declared in include/bds.h: {sorted(exported - set(names))}"
     h.bds_abi_version.restype = ctypes.c_int
     from bilateral_driving_amd import _lib as _L
-    assert h.bds_abi_version() == _L.ABI_VERSION == 5
+    assert h.bds_abi_version() == _L.ABI_VERSION == 6
     h.bds_strerror.restype = ctypes.c_char_p
     assert b"workspace" in h.bds_strerror(-2)
 
@@ -105,6 +105,42 @@ def test_argument_validation_without_gpu(libpath):
     lv[0].gx, lv[0].gy, lv[0].gl, lv[0].factor, lv[0].n_avg = 8, 8, 4, 2, 1
     assert h.bds_bilagrid_ms_workspace_bytes(1, lv, 64, 64) >= 2 * 32 * 32 * 48  # low-res maps + their gradients
     assert h.bds_bilagrid_ms_workspace_bytes(0, lv, 64, 64) == 0
+    # the colour transform's folded entries: `channels` selects the form, and every mix of the forms is refused
+    lv[0].grid = p
+    ms, bufs = (1, lv, 64, 64), (p, 1 << 30)     # nlevels .. W; ws, ws_bytes
+    no_loss = (None, 0, None, None, 0.0, None, 0, None)     # target, tv_nlevels, tv_levels, tv_weights, v_loss, loss_out, loss_slots, v_rgb_out
+    maps = (ctypes.c_void_p * 1)(p)
+    fwd = h.bds_bilagrid_ms_fwd       # .., channels, in, alpha, sky, ws, ws_bytes, rgb_out, depth_out, affine_out, <loss>, stream
+    assert fwd(*ms, 5, p, p, None, *bufs, p, p, None, *no_loss, None) == -1          # channels 5
+    assert fwd(*ms, 3, p, None, None, *bufs, p, p, None, *no_loss, None) == -1       # channels 3 with depth_out
+    assert fwd(*ms, 3, p, None, None, *bufs, p, None, None, p, 0, None, None, 1.0, p, 64, p, None) == -1     # channels 3 with target
+    assert fwd(*ms, 4, p, None, None, *bufs, p, p, None, *no_loss, None) == -1       # channels 4 without alpha
+    assert fwd(*ms, 4, p, p, None, *bufs, p, None, None, *no_loss, None) == -1       # channels 4 without depth_out
+    assert fwd(*ms, 4, p, p, None, *bufs, p, p, maps, *no_loss, None) == -1          # channels 4 with affine_out
+    assert fwd(*ms, 4, p, p, None, *bufs, p, p, None, p, 0, None, None, 1.0, None, 64, p, None) == -1        # target without loss_out
+    assert fwd(*ms, 4, p, p, None, *bufs, p, p, None, p, 0, None, None, 1.0, p, 64, None, None) == -1        # target without v_rgb_out
+    assert fwd(*ms, 4, p, p, None, *bufs, p, p, None, p, 0, None, None, 1.0, p, 48, p, None) == -1           # loss_slots not a power of two
+    assert fwd(*ms, 4, p, p, None, *bufs, p, p, None, p + 4, 0, None, None, 1.0, p, 64, p, None) == -1       # misaligned target
+    bwd = h.bds_bilagrid_ms_bwd       # .., channels, in, alpha, sky, ws, ws_bytes, v_rgb_out, v_depth, v_opacity, v_in, v_alpha, v_sky, defer, stream
+    assert bwd(*ms, 5, p, p, None, *bufs, p, None, None, p, p, None, 0, None) == -1          # channels 5
+    assert bwd(*ms, 3, p, None, None, *bufs, p, p, None, p, None, None, 0, None) == -1       # channels 3 with v_depth
+    assert bwd(*ms, 3, p, None, None, *bufs, p, None, p, p, None, None, 0, None) == -1       # channels 3 with v_opacity
+    assert bwd(*ms, 3, p, None, None, *bufs, p, None, None, p, None, None, 1, None) == -1    # channels 3 with defer
+    assert bwd(*ms, 4, p, None, None, *bufs, p, None, None, p, p, None, 0, None) == -1       # channels 4 without alpha
+    assert bwd(*ms, 4, p, p, None, *bufs, p, None, None, p, None, None, 0, None) == -1       # channels 4 without v_alpha
+    assert bwd(*ms, 4, p, p, None, *bufs, p, None, None, p, p, None, 1, None) == -1          # defer with v_alpha
+    assert bwd(*ms, 4, p, p, p, *bufs, p, None, None, p, None, p, 1, None) == -1             # defer with v_sky
+    assert bwd(*ms, 4, p, p, None, *bufs, p, p, None, p, None, None, 1, None) == -1          # defer with v_depth
+    assert h.bds_bilagrid_ms_bwd_deferrable(0, lv, 64, 64) == 0                              # (the query answers 0, not an error)
+    lv[0].n_avg = 2      # a level averaged over two grids is not deferrable
+    assert h.bds_bilagrid_ms_bwd_deferrable(*ms) == 0
+    assert bwd(*ms, 4, p, p, None, *bufs, p, None, None, p, None, None, 1, None) == -1
+    # Adam's one entry: n_rows, width, grad_stride, param .. exp_avg_sq, lr .. weight_decay, step, consume, stream
+    adam = (p, p, p, p, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1)
+    assert h.bds_adam_step(10, -1, 0, *adam, 0, None) == -1      # width -1
+    assert h.bds_adam_step(10, 4, 3, *adam, 0, None) == -1       # grad_stride < width
+    assert h.bds_adam_step(0, 0, 0, *adam, 1, None) == 0         # empty tensors are fine, contiguous and by rows
+    assert h.bds_adam_step(0, 4, 16, *adam, 0, None) == 0
 
 
 def test_no_cpu_fallback():

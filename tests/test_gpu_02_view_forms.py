@@ -172,11 +172,14 @@ def test_bilagrid_ed_form_equals_rgb_form_plus_depth_normalise(env, H, W, use_sk
     wsb = lib.bds_bilagrid_ms_workspace_bytes(3, lv, H, W)
     ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
     rgb, depth = torch.empty(H, W, 3, device="cuda"), torch.empty(H, W, device="cuda")
-    L.check(lib.bds_bilagrid_ms_ed_fwd(3, lv, H, W, L.ptr(render), L.ptr(alpha), L.ptr(sky), L.ptr(ws), wsb, L.ptr(rgb), L.ptr(depth), st), "ed fwd")
+    no_loss = (None, 0, None, None, 0.0, None, 0, None)     # target .. v_rgb_out
+    L.check(lib.bds_bilagrid_ms_fwd(3, lv, H, W, 4, L.ptr(render), L.ptr(alpha), L.ptr(sky), L.ptr(ws), wsb, L.ptr(rgb), L.ptr(depth), None,
+                                    *no_loss, st), "ed fwd")
     rgb3 = render[..., :3].contiguous()
     ws2 = torch.empty(wsb, dtype=torch.uint8, device="cuda")
     ref = torch.empty(H, W, 3, device="cuda")
-    L.check(lib.bds_bilagrid_ms_fwd(3, lv, H, W, L.ptr(rgb3), L.ptr(alpha), L.ptr(sky), L.ptr(ws2), wsb, L.ptr(ref), None, st), "fwd")
+    L.check(lib.bds_bilagrid_ms_fwd(3, lv, H, W, 3, L.ptr(rgb3), L.ptr(alpha), L.ptr(sky), L.ptr(ws2), wsb, L.ptr(ref), None, None, *no_loss, st),
+            "fwd")
     assert torch.equal(rgb, ref)
     assert torch.equal(depth, render[..., 3] / alpha.clamp(min=1e-10))
     # backward
@@ -186,14 +189,14 @@ def test_bilagrid_ed_form_equals_rgb_form_plus_depth_normalise(env, H, W, use_sk
     lvb = _levels_struct(grids, vg, factors)
     v_render, v_alpha = torch.empty(H, W, 4, device="cuda"), torch.empty(H, W, device="cuda")
     v_sky = torch.empty(H, W, 3, device="cuda") if use_sky else None
-    L.check(lib.bds_bilagrid_ms_ed_bwd(3, lvb, H, W, L.ptr(render), L.ptr(alpha), L.ptr(sky), L.ptr(ws), wsb, L.ptr(v_out), L.ptr(v_depth),
-                                       L.ptr(v_opac), L.ptr(v_render), L.ptr(v_alpha), L.ptr(v_sky), st), "ed bwd")
+    L.check(lib.bds_bilagrid_ms_bwd(3, lvb, H, W, 4, L.ptr(render), L.ptr(alpha), L.ptr(sky), L.ptr(ws), wsb, L.ptr(v_out), L.ptr(v_depth),
+                                    L.ptr(v_opac), L.ptr(v_render), L.ptr(v_alpha), L.ptr(v_sky), 0, st), "ed bwd")
     vg2 = [torch.zeros_like(x) for x in grids]
     lvb2 = _levels_struct(grids, vg2, factors)
     r_rgb, r_alpha = torch.empty(H, W, 3, device="cuda"), torch.zeros(H, W, device="cuda")
     r_sky = torch.empty(H, W, 3, device="cuda") if use_sky else None
-    L.check(lib.bds_bilagrid_ms_bwd(3, lvb2, H, W, L.ptr(rgb3), L.ptr(alpha), L.ptr(sky), L.ptr(ws2), wsb, L.ptr(v_out), L.ptr(r_rgb),
-                                    L.ptr(r_alpha) if use_sky else None, L.ptr(r_sky), st), "bwd")
+    L.check(lib.bds_bilagrid_ms_bwd(3, lvb2, H, W, 3, L.ptr(rgb3), L.ptr(alpha), L.ptr(sky), L.ptr(ws2), wsb, L.ptr(v_out), None, None,
+                                    L.ptr(r_rgb), L.ptr(r_alpha) if use_sky else None, L.ptr(r_sky), 0, st), "bwd")
     ac = alpha.clamp(min=1e-10)
     assert torch.equal(v_render[..., :3], r_rgb)
     assert torch.equal(v_render[..., 3], v_depth / ac)
@@ -267,7 +270,7 @@ def test_fused_view_with_nothing_on_screen(env):
 @pytest.mark.parametrize("W,H,levels,factors", [(320, 192, None, None), (256, 160, [(8, 8, 4), (16, 16, 8)], [2, 1])])
 def test_epilogue_deferred_to_the_compositor_equals_the_three_launch_backward(env, W, H, levels, factors):
     """The colour transform's backward with its last stage (guidance route, clamp / sky blend / expected-depth backward) formed per
-    pixel inside the compositor's backward (bds_bilagrid_ms_ed_bwd_deferred + bds_rasterize_bwd_ms: the one-stream default of the
+    pixel inside the compositor's backward (bds_bilagrid_ms_bwd with defer + bds_rasterize_bwd_ms: the one-stream default of the
     fused view) == the three-launch form (bit 2 of bds_set_option(7, ..)): every gradient, with a loss that also reaches the depth
     and the opacity image (v_depth / v_alpha_in) and a learnable sky.  A pyramid with a full-resolution level included."""
     ops, L = env

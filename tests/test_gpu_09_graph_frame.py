@@ -173,7 +173,7 @@ def test_frame_graph_follows_parameter_updates_and_grows_on_overflow(mods):
 
 
 def test_loss_on_the_transform_launch_equals_the_separate_loss_launch(mods, monkeypatch):
-    """train_view with the L1 + TV loss folded into the colour transform's full-resolution kernel (bds_bilagrid_ms_ed_train_fwd) ==
+    """train_view with the L1 + TV loss folded into the colour transform's full-resolution kernel (bds_bilagrid_ms_fwd with a target) ==
     train_view with the loss as its own launch (bds_l1_tv_train): image bit-equal, loss to fp32 summation order, v_rgb-driven
     gradients to atomics noise, TV gradient in the grids' slices."""
     FV, GV, Hn = mods

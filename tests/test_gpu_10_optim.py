@@ -44,7 +44,7 @@ def test_fused_adam_matches_torch_adam(wd):
 @pytest.mark.parametrize("consume", [False, True])
 def test_fused_adam_reads_gradients_that_are_columns_of_a_row_block(consume):
     """dist.FlatGradients(row_block=True): the gradients of means / quats / log_scales / opacity logits are column ranges of one [N,16]
-    block -- bds_adam_step_rows updates from (and, consuming, clears) them where they lie: the same numbers, bit for bit, as the
+    block -- bds_adam_step with a width updates from (and, consuming, clears) them where they lie: the same numbers, bit for bit, as the
     contiguous pass."""
     from bilateral_driving_amd.dist import FlatGradients
     from bilateral_driving_amd.optim import FusedAdam

@@ -133,7 +133,7 @@ def test_nonfinite_flags_sees_every_element(mods):
     def run():
         ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
         cnts = (ctypes.c_int64 * len(ts))(*[t.numel() for t in ts])
-        L.check(lib.bds_nonfinite_flags(len(ts), ptrs, cnts, flag.data_ptr(), None, L.stream()), "bds_nonfinite_flags")
+        L.check(lib.bds_nonfinite_flags(len(ts), ptrs, cnts, None, flag.data_ptr(), None, L.stream()), "bds_nonfinite_flags")
         return int(flag.item())
 
     assert run() == 0
@@ -150,7 +150,7 @@ def test_nonfinite_flags_sees_every_element(mods):
 
 
 def test_nonfinite_kinds_follow_the_activations(mods):
-    """bds_nonfinite_flags_kinds: the raw one-view node checks the raw parameters, so the bit has to say what the reference's check of
+    """bds_nonfinite_flags with kinds: the raw one-view node checks the raw parameters, so the bit has to say what the reference's check of
     the ACTIVATED tensors would (vanilla.py:393-395,407-412): exp of a log-scale >= 88.72284 is Inf (and of -Inf is 0: fine), a
     zero quaternion normalises to NaN, sigmoid maps +-Inf logits to 0 / 1 (fine) -- each against torch's own activation."""
     import ctypes
@@ -167,7 +167,7 @@ def test_nonfinite_kinds_follow_the_activations(mods):
     def run():
         ptrs = (ctypes.c_void_p * 3)(*[t.data_ptr() for t in ts])
         cnts = (ctypes.c_int64 * 3)(*[t.numel() for t in ts])
-        L.check(lib.bds_nonfinite_flags_kinds(3, ptrs, cnts, (ctypes.c_int * 3)(*kinds), flag.data_ptr(), None, L.stream()), "kinds")
+        L.check(lib.bds_nonfinite_flags(3, ptrs, cnts, (ctypes.c_int * 3)(*kinds), flag.data_ptr(), None, L.stream()), "kinds")
         got = int(flag.item())
         want = sum((1 << i) for i, (t, f) in enumerate(zip(ts, acts)) if not bool(torch.isfinite(f(t)).all()))
         assert got == want, (got, want)
