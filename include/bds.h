@@ -876,6 +876,41 @@ int bds_node_pose_bwd(int64_t N, int F, int I, int cur_frame, const float *means
                       const float *v_world_quats, const float *v_opacities, float *v_means, float *v_quats, float *v_logits,
                       float *v_instances_quats, float *v_instances_trans, void *temp, size_t temp_bytes, bds_stream_t stream);
 
+/* Time transform of the periodic-vibration Gaussians: PeriodicVibrationGaussians.get_gaussians (models/gaussians/pvg.py:374-425) with
+ * get_marginal_t (:81), temporal_means (:65-73), temporal_opacities (:75-78) and velocity / rho (:83-88), as three forward launches and
+ * one backward launch.  Raw parameters, contiguous float32: means [N,3], velocity [N,3], taus [N], betas [N], logits [N] (the [N,1]
+ * columns), log_scales [N,3], quats [N,4], features_dc [N,3], features_rest [N,K-1,3] (may be NULL for K = 1), cam_pos [3].  With
+ * d = tau - cur_time, s_t = exp(beta), a = 2 pi / T (T: ctrl_cfg.cycle_length, a double as in the reference: a is formed in double
+ * and rounded to float32 once, where the Python scalar meets the float32 tensor; cur_time and delta_t arrive rounded the same way):
+ *   marg = exp(-0.5 d^2 / s_t^2); a row is KEPT when marg > 0.05 in float32 (a NaN tau / beta drops it, as the reference's comparison)
+ *   mean' = mean + velocity sin((cur_time - tau) a) / a, + velocity exp(-0.5 s_t / T) delta_t when in_smooth
+ *   opacity = sigmoid(logit) marg, scale = exp(log_scale), quat = q / |q|
+ *   rgb = clamp(SH(degrees_to_use, normalise(mean' - cam_pos)) + 0.5, 0, 1); K = 1 (the class's sh_degree == 0): sigmoid(features_dc)
+ * fwd: the kept rows' outputs COMPACTED in the original order (x[filter_mask]) at the front of out_* (each allocated for N rows;
+ * out_sh_raw [N,3]: the colour before + 0.5 and the clamp -- band 0 itself for K = 1 -- for the backward), filter_mask [N] one byte per
+ * row.  temp (bds_pvg_temp_bytes(N) bytes, 16-byte aligned) starts with uint32 {M, flags, 0, 0}: M = rows kept, flags bit 2 i = a NaN,
+ * bit 2 i + 1 = an Inf among the kept rows of tensor i (means, opacities, rgbs, scales, quats: the order of :419-423); behind it the
+ * exclusive scan of the kept rows per 256-row block, which bwd reads again.  One read of the header gives the host M and the flags.
+ * bwd (M as read from the header; the same scalars, parameters, filter_mask, temp, out_means and out_sh_raw as fwd left them):
+ * v_out_* [M,.] are read by rank; EVERY row of v_means [N,3] v_velocity [N,3] v_taus [N] v_betas [N] v_logits [N] v_log_scales [N,3]
+ * v_quats [N,4] v_features_dc [N,3] v_features_rest [N,K-1,3] is stored, zeros for a dropped row (no memset needed).  The view
+ * direction is detached, the clamp passes the gradient on the closed interval.  No atomics: bit-identical run to run.
+ * BDS_EINVAL before any launch: N < 0 or > INT32_MAX, K not in {1, 4, 9, 16}, (degrees_to_use + 1)^2 > K, T <= 0, a NULL array with
+ * N > 0, a misaligned or short temp.  N = 0 launches nothing. */
+size_t bds_pvg_temp_bytes(int64_t N);
+int bds_pvg_fwd(int64_t N, int K, int degrees_to_use, float cur_time, float delta_t, int in_smooth, double T, const float *means,
+                const float *velocity, const float *taus, const float *betas, const float *logits, const float *log_scales,
+                const float *quats, const float *features_dc, const float *features_rest, const float *cam_pos, float *out_means,
+                float *out_opacities, float *out_rgbs, float *out_scales, float *out_quats, float *out_sh_raw, uint8_t *filter_mask,
+                void *temp, size_t temp_bytes, bds_stream_t stream);
+int bds_pvg_bwd(int64_t N, int64_t M, int K, int degrees_to_use, float cur_time, float delta_t, int in_smooth, double T,
+                const float *velocity, const float *taus, const float *betas, const float *logits, const float *log_scales,
+                const float *quats, const float *cam_pos, const uint8_t *filter_mask, const void *temp, size_t temp_bytes,
+                const float *out_means, const float *out_sh_raw, const float *v_out_means, const float *v_out_opacities,
+                const float *v_out_rgbs, const float *v_out_scales, const float *v_out_quats, float *v_means, float *v_velocity,
+                float *v_taus, float *v_betas, float *v_logits, float *v_log_scales, float *v_quats, float *v_features_dc,
+                float *v_features_rest, bds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
