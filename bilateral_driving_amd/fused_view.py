@@ -416,6 +416,10 @@ def _composite(f: _Front, opac: Tensor, images=None, zero_grad_records: Optional
             L.check(lib.bds_splat_pack_sh(n_vis, f.nvis_dev, L.ptr(f.vis_ids), f.K, f.sh_degree, L.ptr(f.means), L.ptr(f.cam_pos),
                                           L.ptr(f.sh), L.ptr(f.sh_rest), _dp(f.means2d), _dp(f.conics), _dp(f.depths), _dp(opac),
                                           L.ptr(f.radii), L.ptr(rec), L.ptr(f.sh_rgb), *clear, st), "bds_splat_pack_sh")
+        elif f.colors.dim() == 2:   # post-activation colours [N,3] + the depths (rendering._RasterizeView: host-count form only); the
+            #                         dense SH colours of _front_begin are [1,N,4], the only other kind a front carries
+            L.check(lib.bds_splat_pack_rgbd(n_vis, L.ptr(f.vis_ids), L.ptr(f.means2d), L.ptr(f.conics), L.ptr(f.colors), L.ptr(f.depths),
+                                            L.ptr(opac), L.ptr(f.radii), L.ptr(rec), st), "bds_splat_pack_rgbd")
         else:
             L.check(lib.bds_splat_pack(n_vis, f.nvis_dev, 4, L.ptr(f.vis_ids), L.ptr(f.means2d), L.ptr(f.conics), L.ptr(f.colors),
                                        L.ptr(opac), L.ptr(f.radii), L.ptr(rec), *clear, st), "bds_splat_pack")
@@ -427,16 +431,79 @@ def _composite(f: _Front, opac: Tensor, images=None, zero_grad_records: Optional
     return rec, render, alphas, last_ids
 
 
+def _composite_backward(cfg: dict, saved, vis_ids: Tensor, M: int, list_tile: int, absgrad: bool, want_pose: bool, v_render, v_alphas=None,
+                        order: Optional[Tensor] = None, dev_form=None, ms=None, v_means2d_ext: Optional[Tensor] = None):
+    """Backward of ``_composite`` for every one-view node: image-space gradients -> the 64-byte gradient records of the visible
+    Gaussians, in the order of ``vis_ids``.  ``saved``: (rec, flatten, isect_offsets, alphas, last_ids) of the forward; ``order``: the
+    longest-tile-first schedule where the caller has it already.  Host-count form: the records are allocated here, the camera-pose
+    slots of the projection backward behind them with ``want_pose`` (one zero fill for both).  ``dev_form`` = (M_dev, v_rec_all, split): the
+    device-count form -- the list length's device address, the records the forward's pack has cleared, the ``_split`` triple.
+    ``ms`` = (n_grids, lv, bws, render, sky, v_depth, v_opacity, v_sky): the colour transform's deferred epilogue, run by
+    bds_rasterize_bwd_ms (``v_alphas`` is not read).  ``v_means2d_ext``: a gradient sent INTO the means2d output.
+    Returns (v_rec_all, v_rec)."""
+    rec, flatten, isect_offsets, alphas, last_ids = saved
+    lib, st = L.lib(), L.stream()
+    W, H, n_vis = cfg["width"], cfg["height"], vis_ids.numel()
+    M_dev, v_rec_all, split = dev_form if dev_form is not None else (None, None, (0, 0, 0))
+    if dev_form is not None:
+        assert v_rec_all is not None, "the device-count form runs its backward once"
+        assert v_means2d_ext is None, "device-count form: no gradient into info['means2d'] (its visible-id list has no host length)"
+    else:
+        v_rec_all = torch.zeros(max(n_vis, 1) + (L.POSE_GRAD_SLOTS if want_pose else 0), L.GRAD_RECORD_FLOATS, device=rec.device)
+    v_rec = v_rec_all[:max(n_vis, 1)]
+    if order is None:
+        order = ops.bwd_schedule(1, W, H, list_tile, isect_offsets, last_ids)
+    lists = (W, H, TILE, list_tile, math.ceil(W / TILE), math.ceil(H / TILE), L.ptr(isect_offsets), L.ptr(flatten), L.ptr(alphas),
+             _tfinal_ptr(alphas), L.ptr(last_ids))
+    with L.timed("rasterize_bwd"):
+        if ms is not None:
+            n_grids, lv, bws, render, sky, v_depth, v_opacity, v_sky = ms
+            L.check(lib.bds_rasterize_bwd_ms(n_vis, M, M_dev, L.ptr(rec), *lists, L.ptr(v_rec), int(absgrad), L.ptr(order), n_grids, lv,
+                                             L.ptr(bws), bws.numel(), *map(L.ptr, (render, sky, v_depth, v_opacity, v_render, v_sky)), st),
+                    "bds_rasterize_bwd_ms")
+        else:
+            L.check(lib.bds_rasterize_bwd(1, n_vis, M, M_dev, 4, L.ptr(rec), None, *lists, L.ptr(v_render), L.ptr(v_alphas), L.ptr(v_rec),
+                                          int(absgrad), L.ptr(order), *split, st), "bds_rasterize_bwd")
+    if v_means2d_ext is not None and n_vis:   # a loss term on the means2d output itself: add its rows to the records
+        v_rec[:n_vis, 7:9] += v_means2d_ext.reshape(-1, 2).index_select(0, vis_ids.long())
+    return v_rec_all, v_rec
+
+
+def _project_backward(cfg: dict, flags: int, nvis_dev, vis_ids: Tensor, inputs, v_rec: Tensor, outs, g2d: Tensor, ag2d: Optional[Tensor],
+                      v_colors=None, slots=None, row_map=None, grad_always: bool = False) -> None:
+    """Gradient records -> parameter gradients, list-driven over the visible Gaussians.  ``inputs``: the saved (means, quats, scales,
+    opacities, viewmat, K); ``outs``: their four gradients, dense arrays or columns of the gradients' [N,16] row block; ``g2d`` /
+    ``ag2d`` [N,2]: the dense screen-space gradient and its absolute sum (None: not wanted); ``v_colors``: the colour gradient of the
+    ACTIVATED form; ``slots``: camera-pose gradient slots; ``row_map``: a gradient sink's row table.  The tensor the caller holds as
+    means2d (cfg["_means2d_ref"]; trainers/base.py:280-297 read .absgrad / .grad) then gets ``.absgrad`` where there is one, and
+    ``.grad`` when it retains it -- with ``grad_always``, in any case."""
+    with L.timed("project_bwd"):   # (antialiased: record channel 11 is the gradient of opacity * comp)
+        L.check(L.lib().bds_project_view_bwd_list(flags, vis_ids.numel(), nvis_dev, L.ptr(vis_ids), *map(L.ptr, inputs), cfg["width"],
+                                                  cfg["height"], cfg["eps2d"], L.ptr(v_rec), *map(_dp, outs), L.ptr(v_colors), L.ptr(slots),
+                                                  L.ptr(g2d), L.ptr(ag2d), L.ptr(row_map), L.stream()), "bds_project_view_bwd_list")
+    carrier = cfg["_means2d_ref"]() if cfg.get("_means2d_ref") is not None else None
+    if carrier is not None:
+        if ag2d is not None:
+            carrier.absgrad = ag2d.view(1, -1, 2)
+        if grad_always or carrier.retains_grad:
+            carrier.grad = g2d.view(1, -1, 2)
+
+
+def _second_half(steps):
+    """Runs a ``forward_steps`` / ``backward_steps`` generator from its one yield to the end; returns its result."""
+    try:
+        next(steps)
+    except StopIteration as done:
+        return done.value
+    raise AssertionError("the view's step generators yield once")
+
+
 class _FusedView(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg: dict, means, quats, log_scales, logits, sh, sky, viewmat, *grids):
         steps = _FusedView.forward_steps(ctx, cfg, means, quats, log_scales, logits, sh, sky, viewmat, *grids)
         next(steps)                      # Gaussian half: projection, lists, SH, compositor
-        try:
-            next(steps)                  # image half: expected depth, clamp, sky blend, bilateral transform
-        except StopIteration as done:
-            return done.value
-        raise AssertionError("forward_steps yields once")
+        return _second_half(steps)       # image half: expected depth, clamp, sky blend, bilateral transform
 
     @staticmethod
     def forward_steps(ctx, cfg: dict, means, quats, log_scales, logits, sh, sky, viewmat, *grids):
@@ -466,7 +533,7 @@ class _FusedView(torch.autograd.Function):
         # device-count form: the gradient records (+ pose-gradient slots) exist from here on; the record pack clears them
         ctx.dev_counts = None if f.m_dev is None else (f.m_dev, f.nvis_dev)
         want_pose = bool(ctx.needs_input_grad[7])
-        v_rec_all = None
+        v_rec_all = ctx.tail = ctx.tail_pose = None
         ctx.loss_rows = 0
         if f.m_dev is not None:
             # (+ the slotted accumulator of the training loss behind them: the pack's tail clear covers it, no fill launch)
@@ -492,7 +559,7 @@ class _FusedView(torch.autograd.Function):
             sched_buf = _empty((int(lib.bds_rasterize_schedule_ints(1, f.tw, f.th)) + int(lib.bds_rasterize_split_pool_ints(1, f.tw, f.th, sp[1], sp[2], f.M)),),
                                dev, torch.int32)
         ctx.split_ok = sched_buf is not None     # (the long-tile list of a split launch lives behind the schedule words)
-        rec, render, alphas, last_ids = _composite(f, opac, images, v_rec_all, sched_buf, getattr(ctx, "tail", None))
+        rec, render, alphas, last_ids = _composite(f, opac, images, v_rec_all, sched_buf, ctx.tail)
         tiles_wh = (f.tw, f.th)
         sh_rgb, ctx.sh_by_rank = f.sh_rgb, bool(f.sh_by_rank)      # (set by the composite when the pack evaluated the colours)
         ctx.list_tile = f_list_tile = f.list_tile
@@ -561,11 +628,7 @@ class _FusedView(torch.autograd.Function):
     def backward(ctx, v_rgb, v_depth, v_opacity, _v_rgb_g, v_means2d_ext, *_):
         steps = _FusedView.backward_steps(ctx, v_rgb, v_depth, v_opacity, _v_rgb_g, v_means2d_ext)
         next(steps)                      # image half: colour transform + compositor
-        try:
-            next(steps)                  # Gaussian half: SH + projection over the visible rows
-        except StopIteration as done:
-            return done.value
-        raise AssertionError("backward_steps yields once")
+        return _second_half(steps)       # Gaussian half: SH + projection over the visible rows
 
     @staticmethod
     def backward_steps(ctx, v_rgb, v_depth, v_opacity, _v_rgb_g, v_means2d_ext):
@@ -584,7 +647,7 @@ class _FusedView(torch.autograd.Function):
         tw, th = math.ceil(W / TILE), math.ceil(H / TILE)
         # colour transform
         need_g = ctx.needs_input_grad[8:]
-        pre = getattr(ctx, "bwd_pre", None)
+        pre = ctx.bwd_pre
         # grid gradients: one zero fill for all levels; with img_idx the full [n_img, ...] gradient is returned with only that
         # image's slice written (no slice-backward / scatter in the autograd graph)
         # ... or, with grad_arena["grid<i>"] and arena_rows >= 1, ADDED in place to the caller's accumulators (their .grad)
@@ -619,7 +682,8 @@ class _FusedView(torch.autograd.Function):
         # function -- to the compositor's backward wherever the configuration allows it (include/bds.h bds_rasterize_bwd_ms): v_render
         # then holds the direct-route gradient only, v_alphas is not touched, and one launch over the image is gone.
         # (a split launch -- long tiles strip by strip -- keeps those tiles out of the schedule: only bds_rasterize_bwd finds them)
-        split = _split(cfg, ctx.list_tile, tw * th, getattr(ctx, "split_ok", False)) if getattr(ctx, "dev_counts", None) is not None else (0, 0, 0)
+        dev_counts = ctx.dev_counts   # (M effective, visible effective) device addresses: the device-count form, else None
+        split = _split(cfg, ctx.list_tile, tw * th, ctx.split_ok) if dev_counts is not None else (0, 0, 0)
         defer = (_DEFER_EPILOGUE and cfg.get("defer_epilogue", True) and M > 0 and n_vis > 0 and split[0] == 0
                  and bool(lib.bds_bilagrid_ms_bwd_deferrable(len(grids), lv, H, W)))
         with L.timed("bilagrid_bwd"):
@@ -627,38 +691,18 @@ class _FusedView(torch.autograd.Function):
             late = (None, None, v_render, None, None) if defer else (v_depth, v_opacity, v_render, v_alphas, v_sky)
             L.check(lib.bds_bilagrid_ms_bwd(len(grids), lv, H, W, 4, L.ptr(render), L.ptr(alphas), L.ptr(sky), L.ptr(bws), bws.numel(),
                                             L.ptr(v_rgb), *map(L.ptr, late), int(defer), st), "bds_bilagrid_ms_bwd")
-        # compositing: gradient records of the visible Gaussians, in the order of vis_ids (64 bytes each)
-        # (+ the camera-pose gradient slots of the projection backward behind them: one zero fill for both)
         want_pose = bool(ctx.needs_input_grad[7])
-        dev_counts = getattr(ctx, "dev_counts", None)   # (M effective, visible effective) device addresses: the device-count form
+        dev_form = None
         if dev_counts is not None:
-            v_rec_all, ctx.v_rec_all = ctx.v_rec_all, None   # cleared by the forward's record pack
-            assert v_rec_all is not None, "the device-count form runs its backward once"
-            assert v_means2d_ext is None, "device-count form: no gradient into info['means2d'] (its visible-id list has no host length)"
-        else:
-            v_rec_all = torch.zeros(max(n_vis, 1) + (L.POSE_GRAD_SLOTS if want_pose else 0), L.GRAD_RECORD_FLOATS, device=dev,
-                                    dtype=torch.float32)
-        v_rec = v_rec_all[:max(n_vis, 1)]
-        LT = ctx.list_tile
-        order = getattr(ctx, "order", None)
-        if order is None:
-            order = ops.bwd_schedule(1, W, H, LT, isect_offsets, last_ids)
-        with L.timed("rasterize_bwd"):
-            if defer:
-                L.check(lib.bds_rasterize_bwd_ms(n_vis, M, None if dev_counts is None else dev_counts[0], L.ptr(rec), W, H, TILE, LT, tw, th,
-                                                 L.ptr(isect_offsets), L.ptr(flatten), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), L.ptr(v_rec), 1,
-                                                 L.ptr(order), len(grids), lv, L.ptr(bws), bws.numel(), L.ptr(render), L.ptr(sky),
-                                                 L.ptr(v_depth), L.ptr(v_opacity), L.ptr(v_render), L.ptr(v_sky), st), "bds_rasterize_bwd_ms")
-            else:
-                L.check(lib.bds_rasterize_bwd(1, n_vis, M, None if dev_counts is None else dev_counts[0], 4, L.ptr(rec), None, W, H, TILE, LT,
-                                              tw, th, L.ptr(isect_offsets), L.ptr(flatten), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids),
-                                              L.ptr(v_render), L.ptr(v_alphas), L.ptr(v_rec), 1, L.ptr(order), *split, st), "bds_rasterize_bwd")
-        if v_means2d_ext is not None and n_vis:   # a loss term on info["means2d"] itself: add its rows to the records
-            v_rec[:n_vis, 7:9] += v_means2d_ext.reshape(N, 2).index_select(0, vis_ids.long())
+            dev_form, ctx.v_rec_all = (dev_counts[0], ctx.v_rec_all, split), None   # (records cleared by the forward's record pack)
+        v_rec_all, v_rec = _composite_backward(
+            cfg, (rec, flatten, isect_offsets, alphas, last_ids), vis_ids, M, ctx.list_tile, absgrad=True, want_pose=want_pose,
+            v_render=v_render, v_alphas=v_alphas, order=ctx.order, dev_form=dev_form, v_means2d_ext=v_means2d_ext,
+            ms=(len(grids), lv, bws, render, sky, v_depth, v_opacity, v_sky) if defer else None)
         yield
         lib, st = L.lib(), L.stream()    # (the second half may be enqueued on another stream)
         # dense screen-space gradient + its absolute sum for the densification statistics (zeros for culled Gaussians, as gsplat)
-        g2d, ctx.g2d = getattr(ctx, "g2d", None), None
+        g2d, ctx.g2d = ctx.g2d, None
         if g2d is None:
             g2d = torch.zeros(2, N, 2, device=dev, dtype=torch.float32)
         arena = cfg.get("grad_arena") or {}
@@ -686,31 +730,18 @@ class _FusedView(torch.autograd.Function):
 
         v_sh = out_like("sh", sh)
         with L.timed("sh_bwd"):
-            st = L.stream()
             L.check(lib.bds_sh_view_bwd_list(n_vis, None if dev_counts is None else dev_counts[1], L.ptr(vis_ids), K, cfg["sh_degree"],
-                                             L.ptr(means), L.ptr(cam_pos), L.ptr(sh_rgb), int(bool(getattr(ctx, "sh_by_rank", False))),
+                                             L.ptr(means), L.ptr(cam_pos), L.ptr(sh_rgb), int(ctx.sh_by_rank),
                                              L.ptr(v_rec), L.ptr(v_sh), None, L.ptr(row_map), int(rows == 2), st), "bds_sh_view_bwd_list")
-        st = L.stream()
         v_means, v_quats = out_like("means", means), out_like("quats", quats)
         v_ls, v_logits = out_like("log_scales", log_scales), out_like("opacity_logits", opac)
-        Kmat = cfg["K"].contiguous()
-        if dev_counts is not None:
-            tp = getattr(ctx, "tail_pose", None)
-            v_vm_slots = tp.view(L.POSE_GRAD_SLOTS, 4, 4) if (want_pose and tp is not None) else None
-        else:
-            v_vm_slots = (v_rec_all[max(n_vis, 1):max(n_vis, 1) + L.POSE_GRAD_SLOTS].view(L.POSE_GRAD_SLOTS, 4, 4)
-                          if want_pose else None)   # camera-pose gradient (base.py:328-329,399)
-        with L.timed("project_bwd"):
-            flags = (L.PROJ_ACCUMULATE if rows == 2 else 0) | (L.PROJ_ANTIALIASED if cfg.get("antialiased") else 0)
-            L.check(lib.bds_project_view_bwd_list(flags, n_vis, None if dev_counts is None else dev_counts[1], L.ptr(vis_ids), L.ptr(means),
-                                                  L.ptr(quats), L.ptr(scales), L.ptr(opac), L.ptr(viewmat.contiguous()), L.ptr(Kmat), W, H,
-                                                  cfg["eps2d"], L.ptr(v_rec), _dp(v_means), _dp(v_quats), _dp(v_ls), _dp(v_logits), None,
-                                                  L.ptr(v_vm_slots), L.ptr(g2d[0]), L.ptr(g2d[1]), L.ptr(row_map), st),
-                    "bds_project_view_bwd_list")
-        carrier = cfg["_means2d_ref"]() if cfg.get("_means2d_ref") is not None else None
-        if carrier is not None:  # the tensor the caller holds in info["means2d"] (trainers/base.py:282-284 read .absgrad / .grad)
-            carrier.grad = g2d[0:1]
-            carrier.absgrad = g2d[1:2]
+        v_vm_slots = None      # camera-pose gradient (base.py:328-329,399): the slots behind the records, or the caller's tail buffer
+        if want_pose:
+            v_vm_slots = (v_rec_all[v_rec.shape[0]:] if dev_counts is None else ctx.tail_pose).view(L.POSE_GRAD_SLOTS, 4, 4)
+        flags = (L.PROJ_ACCUMULATE if rows == 2 else 0) | (L.PROJ_ANTIALIASED if cfg.get("antialiased") else 0)
+        _project_backward(cfg, flags, None if dev_counts is None else dev_counts[1], vis_ids,
+                          (means, quats, scales, opac, viewmat.contiguous(), cfg["K"].contiguous()), v_rec,
+                          (v_means, v_quats, v_ls, v_logits), g2d=g2d[0], ag2d=g2d[1], slots=v_vm_slots, row_map=row_map, grad_always=True)
         # (defer_pose_sum: the caller sums the slots of all its views in one launch -- graph_view, once per frame)
         v_viewmat = None if (v_vm_slots is None or cfg.get("defer_pose_sum")) else v_vm_slots.sum(0)
         if grids_in_place:
@@ -917,11 +948,7 @@ def train_view(params: Dict[str, Tensor], viewmat: Tensor, K: Tensor, width: int
     def image_half(fsteps):
         """Second half of the forward (colour transform), the L1 + TV loss and its backward with d(loss) = 1 (the TV term's gradient
         is added to the grids' gradient slices with atomics, so it may run next to another view's backward)."""
-        try:
-            next(fsteps)
-            raise AssertionError("forward_steps yields once")
-        except StopIteration as done:
-            (rgb, depth, opacity, rgb_g, means2d, radii, tiles_per_gauss, flatten_ranks, isect_offsets, vis_ids) = done.value
+        (rgb, depth, opacity, rgb_g, means2d, radii, tiles_per_gauss, flatten_ranks, isect_offsets, vis_ids) = _second_half(fsteps)
         cfg["_means2d_ref"] = weakref.ref(means2d)
         info = _Info({"means2d": means2d, "radii": radii, "width": int(width), "height": int(height), "tiles_per_gauss": tiles_per_gauss,
                       "flatten_ranks": flatten_ranks, "visible_ids": vis_ids, "isect_offsets": isect_offsets,
@@ -964,11 +991,7 @@ def train_view(params: Dict[str, Tensor], viewmat: Tensor, K: Tensor, width: int
                 out["loss_slots"] = state.pop("loss_slots")
                 if not lazy_loss:
                     out["loss"] = slots_value(out["loss_slots"])
-            try:
-                next(state["steps"])
-                raise AssertionError("backward_steps yields once")
-            except StopIteration as done:
-                grads = done.value
+            grads = _second_half(state["steps"])
             for p, g in zip(leaves, grads[1:6]):
                 _accumulate(p, g)
             _accumulate(sky, grads[6])

@@ -102,8 +102,9 @@ def _split_materialised(x):
     if isinstance(x, dict):
         return {k: _split_materialised(v) for k, v in x.items()}
     return x
-from .fused_view import _composite, _image_buffers, _lists_begin, _lists_finish, _tfinal_ptr, _view_front
-from .gs_ops import (TILE_SIZE, _f32c, bwd_schedule, fully_fused_projection, isect_tiles, rasterize_to_pixels, spherical_harmonics)
+from .fused_view import (_Front, _composite, _composite_backward, _image_buffers, _lists_begin, _lists_finish, _project_backward,
+                         _view_front)
+from .gs_ops import (TILE_SIZE, _f32c, fully_fused_projection, isect_tiles, rasterize_to_pixels, spherical_harmonics)
 
 
 class _Meta(dict):
@@ -191,20 +192,19 @@ class _RasterizeView(torch.autograd.Function):
                                         L.ptr(viewmat), L.ptr(Kmat), W, H, cfg["eps2d"], cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"],
                                         L.ptr(radii), L.ptr(means2d), L.ptr(depths), L.ptr(conics), None, L.ptr(opac_eff), st), "bds_project_fwd")
         opac_c = opacities.view(1, N) if opac_eff is None else opac_eff
-        lists = _lists_begin(means2d, radii, depths, (L.ptr(conics), L.ptr(opac_c)) if cfg["cull"] else None, W, H, _LIST_TILE)
-        render, alphas, last_ids = _image_buffers(W, H, dev)     # (while the two counts travel to the host)
-        _lists_finish(lists)
-        M, n_vis, vis_ids, ws, flatten, isect_offsets = lists.M, lists.n_vis, lists.vis_ids, lists.ws, lists.flatten, lists.isect_offsets
-        rec = lists.rec_buf[:n_vis]
-        tw, th = math.ceil(W / TILE_SIZE), math.ceil(H / TILE_SIZE)
-        with L.timed("rasterize_fwd"):
-            L.check(lib.bds_splat_pack_rgbd(n_vis, L.ptr(vis_ids), L.ptr(means2d), L.ptr(conics), L.ptr(colors.reshape(N, 3)), L.ptr(depths),
-                                            L.ptr(opac_c), L.ptr(radii), L.ptr(rec), st), "bds_splat_pack_rgbd")
-            L.check(lib.bds_rasterize_fwd(1, n_vis, M, None, 4, L.ptr(rec), None, W, H, TILE_SIZE, _LIST_TILE, tw, th, L.ptr(isect_offsets),
-                                          L.ptr(flatten), L.ptr(render), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), None, 0, 0, 0, st),
-                    "bds_rasterize_fwd")
-        ctx.save_for_backward(means, quats, scales, opacities, viewmat, Kmat, rec, vis_ids, ws, flatten, isect_offsets, render, alphas, last_ids)
-        ctx.cfg, ctx.M = cfg, M
+        s = _lists_begin(means2d, radii, depths, (L.ptr(conics), L.ptr(opac_c)) if cfg["cull"] else None, W, H, _LIST_TILE)
+        images = _image_buffers(W, H, dev)     # (while the two counts travel to the host)
+        _lists_finish(s)
+        f = _Front()         # the lists + what else _composite reads
+        f.flatten, f.vis_ids, f.M, f.n_vis, f.m_dev, f.nvis_dev, f.rec_buf = s.flatten, s.vis_ids, s.M, s.n_vis, s.m_dev, s.nvis_dev, s.rec_buf
+        f.cfg, f.W, f.H, f.list_tile, f.tw, f.th = cfg, W, H, _LIST_TILE, math.ceil(W / TILE_SIZE), math.ceil(H / TILE_SIZE)
+        f.means2d, f.depths, f.conics, f.radii, f.isect_offsets = means2d, depths, conics, radii, s.isect_offsets
+        f.opac = f.opac_row = opac_c
+        f.colors = colors.reshape(N, 3)      # post-activation: the pack adds the depths (bds_splat_pack_rgbd)
+        rec, render, alphas, last_ids = _composite(f, f.opac, images)
+        ctx.save_for_backward(means, quats, scales, opacities, viewmat, Kmat, rec, f.vis_ids, s.ws, f.flatten, f.isect_offsets, render, alphas,
+                              last_ids)
+        ctx.cfg, ctx.M = cfg, f.M
         if cfg["ed"]:      # expected depth: D / clamp(alpha, 1e-10) (gsplat "ED")
             out = torch.empty_like(render)
             L.check(lib.bds_expected_depth_fwd(H * W, L.ptr(render), L.ptr(alphas), L.ptr(out), st), "bds_expected_depth_fwd")
@@ -304,17 +304,14 @@ class _RasterizeRawView(torch.autograd.Function):
 
 
 def _view_backward(ctx, saved, v_out, v_depth, v_alphas, v_means2d_ext, want_pose: bool, widths, flags: int):
-    """The backward both one-view nodes share: expected depth -> compositor -> gradient records of the visible Gaussians (+ a loss on
+    """The backward both one-view nodes share: expected depth -> ``fused_view._composite_backward`` (host-count form, + a loss on
     meta["means2d"]) -> ONE zero fill of the dense outputs, ``widths`` floats per Gaussian (the four parameter gradients first, grad2d |
-    absgrad2d last) -> list-driven projection backward (bds_project_view_bwd_list, ``flags``; ACTIVATED scatters the colour gradient to
-    the fifth output) -> the means2d carrier.  Returns (dense outputs, gradient records, camera-pose slots or None)."""
+    absgrad2d last) -> ``fused_view._project_backward`` (``flags``; ACTIVATED scatters the colour gradient to the fifth output), which
+    gives the means2d carrier .absgrad with cfg["absgrad"] and .grad when it retains it.  Returns (dense outputs, gradient records,
+    camera-pose slots or None)."""
     means, quats, scales, opac, viewmat, Kmat, rec, vis_ids, _ws, flatten, isect_offsets, render, alphas, last_ids = saved[:14]
-    cfg, M = ctx.cfg, ctx.M
-    lib, st = L.lib(), L.stream()
-    dev = means.device
+    cfg, lib, st = ctx.cfg, L.lib(), L.stream()
     W, H, N = cfg["width"], cfg["height"], means.shape[0]
-    n_vis = vis_ids.numel()
-    tw, th = math.ceil(W / TILE_SIZE), math.ceil(H / TILE_SIZE)
     v_render, v_alphas_t = torch.empty_like(render), torch.empty_like(alphas)
     if cfg.get("split"):
         L.check(lib.bds_expected_depth_split_bwd(H * W, int(cfg["ed"]), L.ptr(render), L.ptr(alphas),
@@ -325,34 +322,18 @@ def _view_backward(ctx, saved, v_out, v_depth, v_alphas, v_means2d_ext, want_pos
         L.check(lib.bds_expected_depth_bwd(H * W, cfg["channels"], int(cfg["ed"]), L.ptr(render), L.ptr(alphas),
                                            None if v_out is None else L.ptr(_f32c(v_out)), None if v_alphas is None else L.ptr(_f32c(v_alphas)),
                                            L.ptr(v_render), L.ptr(v_alphas_t), st), "bds_expected_depth_bwd")
-    v_rec_all = torch.zeros(max(n_vis, 1) + (L.POSE_GRAD_SLOTS if want_pose else 0), L.GRAD_RECORD_FLOATS, device=dev)
-    v_rec = v_rec_all[:max(n_vis, 1)]
-    order = bwd_schedule(1, W, H, _LIST_TILE, isect_offsets, last_ids)
-    with L.timed("rasterize_bwd"):
-        L.check(lib.bds_rasterize_bwd(1, n_vis, M, None, 4, L.ptr(rec), None, W, H, TILE_SIZE, _LIST_TILE, tw, th, L.ptr(isect_offsets),
-                                      L.ptr(flatten), L.ptr(alphas), _tfinal_ptr(alphas), L.ptr(last_ids), L.ptr(v_render), L.ptr(v_alphas_t),
-                                      L.ptr(v_rec), int(bool(cfg["absgrad"])), L.ptr(order), 0, 0, 0, st), "bds_rasterize_bwd")
-    if v_means2d_ext is not None and n_vis:   # a loss term on meta["means2d"] itself: add its rows to the records
-        v_rec[:n_vis, 7:9] += v_means2d_ext.reshape(N, 2).index_select(0, vis_ids.long())
-    dense = torch.zeros(N * sum(widths), device=dev)      # ONE zero fill for all dense outputs
+    v_rec_all, v_rec = _composite_backward(cfg, (rec, flatten, isect_offsets, alphas, last_ids), vis_ids, ctx.M, _LIST_TILE,
+                                           absgrad=cfg["absgrad"], want_pose=want_pose, v_render=v_render, v_alphas=v_alphas_t,
+                                           v_means2d_ext=v_means2d_ext)
+    dense = torch.zeros(N * sum(widths), device=means.device)      # ONE zero fill for all dense outputs
     outs, o = [], 0
     for w in widths:
         outs.append(dense[o:o + N * w].view(N, w) if w != 1 else dense[o:o + N])
         o += N * w
-    v_means, v_quats, v_scales, v_opac, g2d, ag2d = *outs[:4], outs[-2], outs[-1]
-    slots = v_rec_all[max(n_vis, 1):].view(L.POSE_GRAD_SLOTS, 4, 4) if want_pose else None
-    with L.timed("project_bwd"):   # (antialiased: record channel 11 is the gradient of opacity * comp)
-        L.check(lib.bds_project_view_bwd_list(flags | (L.PROJ_ANTIALIASED if cfg["aa"] else 0), n_vis, None, L.ptr(vis_ids), L.ptr(means),
-                                              L.ptr(quats), L.ptr(scales), L.ptr(opac), L.ptr(viewmat), L.ptr(Kmat), W, H, cfg["eps2d"],
-                                              L.ptr(v_rec), L.ptr(v_means), L.ptr(v_quats), L.ptr(v_scales), L.ptr(v_opac),
-                                              L.ptr(outs[4]) if flags & L.PROJ_ACTIVATED else None, L.ptr(slots), L.ptr(g2d),
-                                              L.ptr(ag2d) if cfg["absgrad"] else None, None, st), "bds_project_view_bwd_list")
-    carrier = cfg["_means2d_ref"]() if cfg.get("_means2d_ref") is not None else None
-    if carrier is not None:      # the tensor the caller holds in meta["means2d"] (trainers/base.py:280-297 read .absgrad / .grad)
-        if cfg["absgrad"]:
-            carrier.absgrad = ag2d.view(1, N, 2)
-        if carrier.retains_grad:
-            carrier.grad = g2d.view(1, N, 2)
+    slots = v_rec_all[v_rec.shape[0]:].view(L.POSE_GRAD_SLOTS, 4, 4) if want_pose else None
+    _project_backward(cfg, flags | (L.PROJ_ANTIALIASED if cfg["aa"] else 0), None, vis_ids, (means, quats, scales, opac, viewmat, Kmat), v_rec,
+                      outs[:4], g2d=outs[-2], ag2d=outs[-1] if cfg["absgrad"] else None,
+                      v_colors=outs[4] if flags & L.PROJ_ACTIVATED else None, slots=slots)
     return outs, v_rec, slots
 
 
@@ -439,39 +420,36 @@ def rasterization(
             colors.dim() == 4 and colors.shape[:2] == (C, N) and colors.shape[3] == 3), colors.shape
         assert (sh_degree + 1) ** 2 <= colors.shape[-2], colors.shape
 
+    def _meta(radii, means2d, depths, conics, opacities, lists=(None, None, None, None)):     # (lists None: materialised on first access)
+        tiles_per_gauss, isect_ids, flatten_ids, isect_offsets = lists
+        return _Meta({"camera_ids": None, "gaussian_ids": None, "radii": radii, "means2d": means2d, "depths": depths, "conics": conics,
+                      "opacities": opacities, "tile_width": math.ceil(width / float(tile_size)),
+                      "tile_height": math.ceil(height / float(tile_size)), "tiles_per_gauss": tiles_per_gauss, "isect_ids": isect_ids,
+                      "flatten_ids": flatten_ids, "isect_offsets": isect_offsets, "width": width, "height": height,
+                      "tile_size": tile_size, "n_cameras": C, "_cull": _TILE_CULLING})
+
+    def _one_view_cfg(**own):      # what the two one-view nodes' cfg share
+        return dict(width=width, height=height, eps2d=float(eps2d), near_plane=float(near_plane), far_plane=float(far_plane),
+                    radius_clip=float(radius_clip), ed=render_mode == "RGB+ED", channels=3 if render_mode == "RGB" else 4,
+                    absgrad=bool(absgrad), cull=_TILE_CULLING, aa=rasterize_mode == "antialiased", **own)
+
     if raw_ok:
-        cfg = dict(width=width, height=height, eps2d=float(eps2d), near_plane=float(near_plane), far_plane=float(far_plane),
-                   radius_clip=float(radius_clip), ed=render_mode == "RGB+ED", channels=3 if render_mode == "RGB" else 4,
-                   absgrad=bool(absgrad), cull=_TILE_CULLING, sh_degree=src.sh_degree, cam_pos=_f32c(src.cam_pos.detach().reshape(3)),
-                   logits_shape=tuple(src.logits.shape), step=src.step, check_finite=_CHECK_FINITE,
-                   split=_SPLIT_RENDER and render_mode != "RGB", aa=rasterize_mode == "antialiased")
+        cfg = _one_view_cfg(sh_degree=src.sh_degree, cam_pos=_f32c(src.cam_pos.detach().reshape(3)), logits_shape=tuple(src.logits.shape),
+                           step=src.step, check_finite=_CHECK_FINITE, split=_SPLIT_RENDER and render_mode != "RGB")
         out, depth1, alphas, means2d, radii, depths, conics, opac = _RasterizeRawView.apply(
             src.means, src.quats, src.log_scales, src.logits, src.features_dc, src.features_rest, viewmats[0], Ks[0], cfg)
         if depth1 is not None:      # the render as a placeholder over the node's two image outputs (SplitRender)
             out = SplitRender(out[None], depth1[None], first=(out, depth1))
-        cfg["_means2d_ref"] = weakref.ref(means2d)
-        tile_width, tile_height = math.ceil(width / float(tile_size)), math.ceil(height / float(tile_size))
-        meta = _Meta({"camera_ids": None, "gaussian_ids": None, "radii": radii, "means2d": means2d, "depths": depths, "conics": conics,
-                      "opacities": opac.detach()[None, :], "tile_width": tile_width, "tile_height": tile_height,
-                      "tiles_per_gauss": None, "isect_ids": None, "flatten_ids": None, "isect_offsets": None, "width": width,
-                      "height": height, "tile_size": tile_size, "n_cameras": C, "_cull": _TILE_CULLING})
-        return out, alphas, meta
+        cfg["_means2d_ref"] = weakref.ref(means2d)      # the backward attaches .absgrad (and .grad, when retained) to THIS tensor object
+        return out, alphas, _meta(radii, means2d, depths, conics, opac.detach()[None, :])
 
     if (_ONE_VIEW_NODE and C == 1 and N > 0 and sh_degree is None and colors.shape[-1] == 3 and backgrounds is None
             and render_mode in ("RGB", "RGB+ED")):
-        cfg = dict(width=width, height=height, eps2d=float(eps2d), near_plane=float(near_plane), far_plane=float(far_plane),
-                   radius_clip=float(radius_clip), ed=render_mode == "RGB+ED", channels=3 if render_mode == "RGB" else 4,
-                   absgrad=bool(absgrad), cull=_TILE_CULLING, colors_shape=tuple(colors.shape), aa=rasterize_mode == "antialiased")
+        cfg = _one_view_cfg(colors_shape=tuple(colors.shape))
         out, alphas, means2d, radii, depths, conics, opac_eff = _RasterizeView.apply(means, quats, scales, opacities, colors, viewmats[0], Ks[0],
                                                                                      cfg)
-        cfg["_means2d_ref"] = weakref.ref(means2d)      # the backward attaches .absgrad (and .grad, when retained) to THIS tensor object
-        tile_width, tile_height = math.ceil(width / float(tile_size)), math.ceil(height / float(tile_size))
-        meta = _Meta({"camera_ids": None, "gaussian_ids": None, "radii": radii, "means2d": means2d, "depths": depths, "conics": conics,
-                      "opacities": opacities.detach()[None, :] if opac_eff is None else opac_eff, "tile_width": tile_width,
-                      "tile_height": tile_height,
-                      "tiles_per_gauss": None, "isect_ids": None, "flatten_ids": None, "isect_offsets": None, "width": width,
-                      "height": height, "tile_size": tile_size, "n_cameras": C, "_cull": _TILE_CULLING})
-        return out, alphas, meta
+        cfg["_means2d_ref"] = weakref.ref(means2d)
+        return out, alphas, _meta(radii, means2d, depths, conics, opacities.detach()[None, :] if opac_eff is None else opac_eff)
 
     radii, means2d, depths, conics, compensations = fully_fused_projection(
         means, quats, scales, viewmats, Ks, width, height, eps2d=eps2d, near_plane=near_plane, far_plane=far_plane,
@@ -498,8 +476,7 @@ def rasterization(
         if backgrounds is not None:
             backgrounds = torch.zeros(C, 1, device=backgrounds.device)
 
-    tile_width = math.ceil(width / float(tile_size))
-    tile_height = math.ceil(height / float(tile_size))
+    tile_width, tile_height = math.ceil(width / float(tile_size)), math.ceil(height / float(tile_size))
     tiles_per_gauss, isect_ids, flatten_ids, isect_offsets = isect_tiles(means2d, radii, depths, tile_size, tile_width,
                                                                          tile_height, want_isect_ids=False,
                                                                          conics=conics if _TILE_CULLING else None,
@@ -511,24 +488,4 @@ def rasterization(
         render_colors = torch.cat(
             [render_colors[..., :-1], render_colors[..., -1:] / render_alphas.clamp(min=1e-10)], dim=-1)
 
-    meta = _Meta({
-        "camera_ids": None,
-        "gaussian_ids": None,
-        "radii": radii,
-        "means2d": means2d,
-        "depths": depths,
-        "conics": conics,
-        "opacities": opac,
-        "tile_width": tile_width,
-        "tile_height": tile_height,
-        "tiles_per_gauss": tiles_per_gauss,
-        "isect_ids": isect_ids,
-        "flatten_ids": flatten_ids,
-        "isect_offsets": isect_offsets,
-        "width": width,
-        "height": height,
-        "tile_size": tile_size,
-        "n_cameras": C,
-        "_cull": _TILE_CULLING,
-    })
-    return render_colors, render_alphas, meta
+    return render_colors, render_alphas, _meta(radii, means2d, depths, conics, opac, (tiles_per_gauss, isect_ids, flatten_ids, isect_offsets))

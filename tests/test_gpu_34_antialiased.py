@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from oracle import gs_oracle as G
-from tests.util import grad_errors, make_scene
+from tests.util import aa_oracle, grad_errors, make_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -27,42 +27,6 @@ def R():
     _lib.lib()
     import bilateral_driving_amd.rendering as R
     return R
-
-
-def aa_oracle(p, viewmats, Ks, W, H, mode, backgrounds=None, sh_degree=None, near_plane=0.01, probes=None):
-    """float64 (or float32) antialiased rasterization, camera by camera, from the oracle's stages -> render, alphas, unstable, radii,
-    compensations ([C,N] each)."""
-    C = viewmats.shape[0]
-    tw, th = math.ceil(W / 16), math.ceil(H / 16)
-    rs, als, uns, rad, cps = [], [], [], [], []
-    for c in range(C):
-        radii, m2, dep, con, comp = G.project(p["means"], p["quats"], p["scales"], viewmats[c], Ks[c], W, H, near_plane=near_plane,
-                                              calc_compensations=True)
-        if sh_degree is None:
-            col = p["colors"]
-        else:
-            cam_pos = torch.linalg.inv(viewmats[c])[:3, 3]
-            col = G.spherical_harmonics(sh_degree, p["means"] - cam_pos, p["colors"], masks=radii > 0)
-            col = torch.clamp_min(col + 0.5, 0.0)
-        if mode in ("RGB+D", "RGB+ED"):
-            col = torch.cat([col, dep[:, None]], -1)
-        tpg, iids, fids = G.isect_tiles(m2, radii, dep, 16, tw, th)
-        offs = G.isect_offset_encode(iids, tw, th)
-        bg = None if backgrounds is None else torch.cat([backgrounds[c], backgrounds.new_zeros(col.shape[-1] - 3)])
-        probe = None
-        if probes is not None:
-            probe = []
-            probes.append(probe)
-        r, a, _, un = G.rasterize_to_pixels(m2, con, col, p["opacities"] * comp, W, H, 16, offs, fids, bg, return_unstable=True,
-                                            absgrad_probe=probe)
-        if mode == "RGB+ED":
-            r = torch.cat([r[..., :-1], r[..., -1:] / a.clamp(min=1e-10)], -1)
-        rs.append(r)
-        als.append(a)
-        uns.append(un)
-        rad.append(radii)
-        cps.append(comp.detach())
-    return torch.stack(rs), torch.stack(als), torch.stack(uns), torch.stack(rad), torch.stack(cps)
 
 
 def _elem_check(k, got, ref, ref32, near0_rows, radii32_equal):

@@ -37,6 +37,44 @@ def make_scene(N, W, H, seed=0, dtype=torch.float32, device="cpu", fov_deg=70.0,
     return {k: v.to(dtype).to(device) for k, v in out.items()}
 
 
+def aa_oracle(p, viewmats, Ks, W, H, mode, backgrounds=None, sh_degree=None, near_plane=0.01, probes=None):
+    """float64 (or float32) antialiased rasterization, camera by camera, from the oracle's stages -> render, alphas, unstable, radii,
+    compensations ([C,N] each)."""
+    import math
+    from oracle import gs_oracle as _G
+    C = viewmats.shape[0]
+    tw, th = math.ceil(W / 16), math.ceil(H / 16)
+    rs, als, uns, rad, cps = [], [], [], [], []
+    for c in range(C):
+        radii, m2, dep, con, comp = _G.project(p["means"], p["quats"], p["scales"], viewmats[c], Ks[c], W, H, near_plane=near_plane,
+                                              calc_compensations=True)
+        if sh_degree is None:
+            col = p["colors"]
+        else:
+            cam_pos = torch.linalg.inv(viewmats[c])[:3, 3]
+            col = _G.spherical_harmonics(sh_degree, p["means"] - cam_pos, p["colors"], masks=radii > 0)
+            col = torch.clamp_min(col + 0.5, 0.0)
+        if mode in ("RGB+D", "RGB+ED"):
+            col = torch.cat([col, dep[:, None]], -1)
+        tpg, iids, fids = _G.isect_tiles(m2, radii, dep, 16, tw, th)
+        offs = _G.isect_offset_encode(iids, tw, th)
+        bg = None if backgrounds is None else torch.cat([backgrounds[c], backgrounds.new_zeros(col.shape[-1] - 3)])
+        probe = None
+        if probes is not None:
+            probe = []
+            probes.append(probe)
+        r, a, _, un = _G.rasterize_to_pixels(m2, con, col, p["opacities"] * comp, W, H, 16, offs, fids, bg, return_unstable=True,
+                                            absgrad_probe=probe)
+        if mode == "RGB+ED":
+            r = torch.cat([r[..., :-1], r[..., -1:] / a.clamp(min=1e-10)], -1)
+        rs.append(r)
+        als.append(a)
+        uns.append(un)
+        rad.append(radii)
+        cps.append(comp.detach())
+    return torch.stack(rs), torch.stack(als), torch.stack(uns), torch.stack(rad), torch.stack(cps)
+
+
 def grad_errors(got, ref, floor=1e-3):
     """(norm-relative error, largest and 99th-percentile ELEMENT-wise relative error over the elements whose reference magnitude is
     above `floor` x the largest one -- below that a gradient entry is a sum of cancelling terms and its relative error says nothing)."""
