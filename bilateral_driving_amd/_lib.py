@@ -136,6 +136,8 @@ _SIGS = {
     "bds_pvg_temp_bytes": (_sz, [_i64]),
     "bds_pvg_fwd": (_i, [_i64, _i, _i, _fl, _fl, _i, C.c_double] + [_f] * 18 + [_sz, _f]),
     "bds_pvg_bwd": (_i, [_i64, _i64, _i, _i, _fl, _fl, _i, C.c_double] + [_f] * 9 + [_sz] + [_f] * 17),
+    "bds_image_metrics_workspace_bytes": (_sz, [_i, _i]),
+    "bds_image_metrics": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _i, _i, _f, _f, _f, _sz, _f]),
     "bds_opacity_reset": (_i, [_i64, _f, _fl, _f, _f, _f]),
     "bds_cubemap_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f]),
     "bds_cubemap_bwd": (_i, [_i64, _i, _i, _i, _f, _f, _f, _f, _f]),

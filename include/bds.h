@@ -911,6 +911,26 @@ int bds_pvg_bwd(int64_t N, int64_t M, int K, int degrees_to_use, float cur_time,
                 float *v_taus, float *v_betas, float *v_logits, float *v_log_scales, float *v_quats, float *v_features_dc,
                 float *v_features_rest, bds_stream_t stream);
 
+/* Evaluation image metrics of one frame: render_images' scoring (models/video_utils.py:29-44,273-361), i.e. compute_psnr and
+ * skimage.metrics.structural_similarity(data_range=1.0, channel_axis=-1) -- 7x7 uniform window, sample covariance (cov_norm 49/48),
+ * scipy's mode="reflect" borders, C1 = 0.01^2, C2 = 0.03^2, the mean taken over rows / columns 3 .. H-4 / 3 .. W-4 per channel and
+ * then over the channels -- and both under up to four pixel masks, in two launches and without a host wait.  pred, gt: [H,W,3]
+ * float32.  mask0..3: [H,W] or NULL (slot unused); mask_kind 0 = one byte per pixel (uint8 / bool), 1 = float32, non-zero = true as
+ * astype(bool) reads it; bit s of invert_bits scores the pixels where slot s is FALSE (the sky mask, :292).  A slot's PSNR is
+ * compute_psnr over its pixels' three channels, its SSIM the mean of the UNCROPPED map over them (S[mask].mean(), :306).
+ * ssim_map: NULL or [H,W,3] float32, the map of full=True.  out: BDS_IMAGE_METRICS_ROW doubles {psnr, ssim, (psnr, ssim) of slot
+ * 0..3, valid of slot 0..3}: valid = 1.0 when the slot scored at least one pixel, else 0.0 with NaN values; psnr = -10 log10(mse) is
+ * +inf for identical images.  ws: bds_image_metrics_workspace_bytes(H, W) bytes, 16-byte aligned (one row of partial sums per 16x16
+ * tile, added in a fixed order in double: no atomics, bit-identical run to run).  This is NOT the training loss's SSIM (bds_ssim_fwd:
+ * 11x11 Gaussian window, VALID region).  BDS_EINVAL before any launch: H or W < 7 (skimage raises there too) or > 2^19, a NULL pred /
+ * gt / out / ws, an invert bit on a NULL slot, a misaligned pointer; BDS_EWORKSPACE: ws too small (the size query answers 0 for a
+ * refused shape). */
+#define BDS_IMAGE_METRICS_ROW 14
+size_t bds_image_metrics_workspace_bytes(int H, int W);
+int bds_image_metrics(int H, int W, const float *pred, const float *gt, const void *mask0, const void *mask1, const void *mask2,
+                      const void *mask3, int invert_bits, int mask_kind, float *ssim_map, double *out, void *ws, size_t ws_bytes,
+                      bds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
