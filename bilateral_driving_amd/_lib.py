@@ -138,6 +138,10 @@ _SIGS = {
     "bds_pvg_bwd": (_i, [_i64, _i64, _i, _i, _fl, _fl, _i, C.c_double] + [_f] * 9 + [_sz] + [_f] * 17),
     "bds_image_metrics_workspace_bytes": (_sz, [_i, _i]),
     "bds_image_metrics": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _i, _i, _f, _f, _f, _sz, _f]),
+    "bds_geometry_metrics_workspace_bytes": (_sz, [_i, _i]),
+    "bds_geometry_metrics": (_i, [_i, _i] + [_f] * 7 + [_i] + [_f] * 6 + [_sz, _f]),
+    "bds_depth_unproject": (_i, [_i, _i, _f, _f, _i, _f, _f, _f, _f, _f, _sz, _f]),
+    "bds_chamfer_nn": (_i, [_i64, _i64, _f, _f, _i, _f, _f, _f]),
     "bds_opacity_reset": (_i, [_i64, _f, _fl, _f, _f, _f]),
     "bds_cubemap_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f]),
     "bds_cubemap_bwd": (_i, [_i64, _i, _i, _i, _f, _f, _f, _f, _f]),

@@ -13,7 +13,7 @@ boolean-indexed copies, and every value is an ``.item()``.
 * ``MetricAccumulator``: a split's frames into one device buffer, read once by ``results()``: the reference's ``results_dict`` entries
   (``non_zero_mean`` :26-27, :542-552).
 
-LPIPS and the geometry block (Chamfer, depth error) are not covered."""
+LPIPS is not covered; the geometry block (Chamfer, depth error) lives in ``geometry.py``."""
 from __future__ import annotations
 
 import math

@@ -931,6 +931,46 @@ int bds_image_metrics(int H, int W, const float *pred, const float *gt, const vo
                       const void *mask3, int invert_bits, int mask_kind, float *ssim_map, double *out, void *ws, size_t ws_bytes,
                       bds_stream_t stream);
 
+/* Evaluation geometry metrics of one frame: render_images' geometry block (models/video_utils.py:363-536) over
+ * utils/chamfer_distance.py:34-75, without pytorch3d and without a host wait.  pred (the render's expected depth), gt (the lidar depth
+ * map): [H,W] float32.  egocar, mask0..3 (sky, dynamic, human, vehicle): [H,W] or NULL (all false); mask_kind as bds_image_metrics.
+ * K: the row-major 3x3 intrinsics, c2w: the row-major 4x4 camera-to-world, both float32 ON THE DEVICE.
+ *   valid = gt > 0 and not egocar and 0.01 < gt < 80 and 1e-4 < pred < 80; pixel (v,u) with depth z -> ((u-cx) z/fx, (v-cy) z/fy, z, 1)
+ *   through c2w in float32; both clouds use the same valid pixels (n points each, row-major order).
+ *   cham_pred[i]: the SQUARED distance from pred point i to its nearest lidar point, cham_gt the converse (knn_points(norm=2, K=1)
+ *   .dists), from coordinate differences in float32.  A trimmed mean at q is the mean over the k = int(n*q) smallest (k as Python
+ *   forms it; k = 0: NaN).  A class holds the valid pixels of its mask, the background those of none of the four.
+ * row_out: BDS_GEOMETRY_METRICS_ROW doubles (8-byte aligned):
+ *   [0..3]   chamfer, chamfer_99, _97, _95: mean (trimmed mean) of cham_pred + that of cham_gt
+ *   [4..7]   depth_err = sqrt(mean(err^2)), depth_err_rmse_99, _97, _95 over the k smallest |err|, err = pred - gt
+ *   [8]      depth_err_median_squared: the element of rank (n-1)/2 of err^2 (torch's lower median)
+ *   [9..13]  chamfer of sky, dynamic, human, vehicle, background: the two means within the class, summed; NaN for an empty class
+ *   [14]     n;  [15..19] the classes' point counts
+ *   [20..23] mean, _99, _97, _95 of cham_pred;  [24..27] of cham_gt;  [28..31] of |err|
+ * n = 0 gives NaN in every value.  dist_pred, dist_gt: both NULL, or [H*W] float32 whose first n entries receive cham_pred / cham_gt.
+ * ws: bds_geometry_metrics_workspace_bytes(H, W) bytes, 16-byte aligned: the capacity is H*W points (about 57 bytes per pixel); the
+ * launches are sized by it and leave early on the device's counts.  The pair loop takes BDS_GEOMETRY_QUERY_BLOCK queries per
+ * workgroup against LDS tiles of BDS_GEOMETRY_TARGET_TILE targets.  Every sum is taken in double in a fixed order: bit-identical run
+ * to run.  BDS_EINVAL before any launch: H or W < 1 or H*W > 2^24, a NULL pred / gt / K / c2w / row_out / ws, one distance array
+ * without the other, a misaligned pointer, a mask_kind other than 0 / 1; BDS_EWORKSPACE: ws too small (the size query answers 0 for a
+ * refused shape).
+ * bds_depth_unproject: depth_map_to_point_cloud (chamfer_distance.py:54-75).  points [H*W,3]: the first *count rows receive the world
+ * points of the pixels where mask (NULL: every pixel) is non-zero, in row-major pixel order; count: int64 on the device.  Same
+ * workspace size and checks.
+ * bds_chamfer_nn: x [P1,3], y [P2,3] float32 -> dist_x [P1], dist_y [P2]: per point the squared Euclidean distance (norm 2) or the sum
+ * of absolute differences (norm 1) to the nearest point of the other cloud (+inf when that cloud is empty).  BDS_EINVAL: a negative
+ * count or one above INT32_MAX, a norm other than 1 / 2, a NULL or misaligned array of a non-empty cloud. */
+#define BDS_GEOMETRY_METRICS_ROW 32
+#define BDS_GEOMETRY_QUERY_BLOCK 512
+#define BDS_GEOMETRY_TARGET_TILE 512
+size_t bds_geometry_metrics_workspace_bytes(int H, int W);
+int bds_geometry_metrics(int H, int W, const float *pred, const float *gt, const void *egocar, const void *mask0, const void *mask1,
+                         const void *mask2, const void *mask3, int mask_kind, const float *K, const float *c2w, double *row_out,
+                         float *dist_pred, float *dist_gt, void *ws, size_t ws_bytes, bds_stream_t stream);
+int bds_depth_unproject(int H, int W, const float *depth, const void *mask, int mask_kind, const float *K, const float *c2w,
+                        float *points, int64_t *count, void *ws, size_t ws_bytes, bds_stream_t stream);
+int bds_chamfer_nn(int64_t P1, int64_t P2, const float *x, const float *y, int norm, float *dist_x, float *dist_y, bds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
