@@ -142,6 +142,8 @@ _SIGS = {
     "bds_geometry_metrics": (_i, [_i, _i] + [_f] * 7 + [_i] + [_f] * 6 + [_sz, _f]),
     "bds_depth_unproject": (_i, [_i, _i, _f, _f, _i, _f, _f, _f, _f, _f, _sz, _f]),
     "bds_chamfer_nn": (_i, [_i64, _i64, _f, _f, _i, _f, _f, _f]),
+    "bds_knn_workspace_bytes": (_sz, [_i64]),
+    "bds_knn_self": (_i, [_i64, _f, _i, _f, _f, _f, _i, C.c_float, C.c_float, _f, _sz, _f]),
     "bds_opacity_reset": (_i, [_i64, _f, _fl, _f, _f, _f]),
     "bds_cubemap_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f]),
     "bds_cubemap_bwd": (_i, [_i64, _i, _i, _i, _f, _f, _f, _f, _f]),

@@ -17,7 +17,7 @@ background subsets, and reads every value back with ``.item()``.
 
 One deviation: a mask key absent from ``image_infos`` counts as all-false (the reference raises a NameError at line 519 then).  The
 class clouds hold the valid pixels where the mask is non-zero, as ``metrics._mask_kind`` reads masks.  Scene initialisation's K > 1
-neighbour searches are not covered."""
+neighbour searches live in ``init.py``."""
 from __future__ import annotations
 
 import math

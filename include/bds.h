@@ -971,6 +971,49 @@ int bds_depth_unproject(int H, int W, const float *depth, const void *mask, int 
                         float *points, int64_t *count, void *ws, size_t ws_bytes, bds_stream_t stream);
 int bds_chamfer_nn(int64_t P1, int64_t P2, const float *x, const float *y, int norm, float *dist_x, float *dist_y, bds_stream_t stream);
 
+/* Scene initialisation: the exact K nearest neighbours of every point of a cloud among the OTHER points of the same cloud, and the
+ * initial log-scales from them -- k_nearest_sklearn (models/gaussians/basics.py:208-224: a kd-tree on the host over n_neighbors =
+ * k + 1, first column dropped) as create_from_pcd (models/gaussians/vanilla.py:79-105) and the rigid nodes' initialiser
+ * (models/nodes/rigid.py:113-120) call it, without the host.  x: [N,3] float32, every coordinate FINITE (the entry does not check;
+ * a caller must -- bds_nonfinite_flags).  K: 1..BDS_KNN_MAX_K.
+ *   dist [N,K]: the Euclidean distances, ascending, in the rows' original order: sqrt of (dx*dx + dy*dy) + dz*dz from the float32
+ *   coordinate differences, every operation rounded on its own.  idx [N,K] int32 or NULL: the neighbours' rows.  A point is never
+ *   its own neighbour (excluded by row, not by distance: a duplicate of a point is its neighbour at distance 0).  Candidates are
+ *   ordered by (d2, row), so the result does not depend on the order of evaluation: bit-identical run to run.
+ *   log_scales [N,S] or NULL, S 1..3: every column log(min(max(mean of the K distances, clamp_lo), clamp_hi)) -- clamp 0, +inf passes
+ *   the mean through (a mean of 0 gives -inf, as torch.log in vanilla.py:85-92); rigid.py:118 clamps to 0.002, 100.
+ * Method (csrc/knn.hip): a uniform grid (at most max(1, 2 N) cells, chosen on the device) over the cloud's box with at most N / 128
+ * points trimmed beyond each face (two histogram passes; the border cells hold what lies beyond, and exactness does not depend on the
+ * box), a counting sort of 16-byte records by cell, one lane per record walking the rings of cells r = 0..BDS_KNN_RING_MAX around
+ * its own with a conservative
+ * termination test, and an exact brute-force pass (BDS_KNN_QUERY_BLOCK queries per workgroup against LDS tiles of
+ * BDS_KNN_TARGET_TILE records) for the queries the rings leave unresolved.  Eleven launches, no host wait, no allocation.
+ * ws: bds_knn_workspace_bytes(N) bytes (about 28 per point), 16-byte aligned.  It starts with the stats block, BDS_KNN_STATS_WORDS
+ * 32-bit words, valid behind the call: [BDS_KNN_STAT_EDGE] the cell edge (float), [+1] its inverse, [+2] the margin's slack,
+ * [BDS_KNN_STAT_DIMS..+2] the cells per axis (int), [BDS_KNN_STAT_UNRESOLVED] the queries the fallback took (uint),
+ * [BDS_KNN_STAT_LO..+2] / [BDS_KNN_STAT_HI..+2] the grid's box (float), [BDS_KNN_STAT_CELLS] the cells in all (uint),
+ * [BDS_KNN_STAT_CLOUD_LO..+2] / [BDS_KNN_STAT_CLOUD_HI..+2] the cloud's box (float).
+ * BDS_EINVAL before any launch: K outside 1..BDS_KNN_MAX_K; N < K + 1 or N > BDS_KNN_MAX_POINTS; a NULL x, dist or ws; log_scales
+ * with S outside 1..3, clamp_lo > clamp_hi or a NaN clamp; a pointer not aligned to 4 bytes (ws: 16).  BDS_EWORKSPACE: ws too small
+ * (the size query answers 0 for N < 2 or N > BDS_KNN_MAX_POINTS). */
+#define BDS_KNN_MAX_K 8
+#define BDS_KNN_MAX_POINTS 1073741824
+#define BDS_KNN_QUERY_BLOCK 256
+#define BDS_KNN_TARGET_TILE 512
+#define BDS_KNN_RING_MAX 2
+#define BDS_KNN_STATS_WORDS 32
+#define BDS_KNN_STAT_EDGE 0
+#define BDS_KNN_STAT_DIMS 3
+#define BDS_KNN_STAT_UNRESOLVED 6
+#define BDS_KNN_STAT_LO 7
+#define BDS_KNN_STAT_HI 10
+#define BDS_KNN_STAT_CELLS 13
+#define BDS_KNN_STAT_CLOUD_LO 14
+#define BDS_KNN_STAT_CLOUD_HI 17
+size_t bds_knn_workspace_bytes(int64_t N);
+int bds_knn_self(int64_t N, const float *x, int K, float *dist, int32_t *idx, float *log_scales, int S, float clamp_lo, float clamp_hi,
+                 void *ws, size_t ws_bytes, bds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
