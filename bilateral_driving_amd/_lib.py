@@ -144,6 +144,13 @@ _SIGS = {
     "bds_chamfer_nn": (_i, [_i64, _i64, _f, _f, _i, _f, _f, _f]),
     "bds_knn_workspace_bytes": (_sz, [_i64]),
     "bds_knn_self": (_i, [_i64, _f, _i, _f, _f, _f, _i, C.c_float, C.c_float, _f, _sz, _f]),
+    "bds_lidar_project": (_i, [_i, _i, _i, _i64] + [_f] * 9 + [_f]),
+    "bds_lidar_visible": (_i, [_i64, _f, _i, _f, _f, _f, _f]),
+    "bds_lidar_points_in_boxes": (_i, [_i64, _f, _i, _f, _f, _f, _i, _f, _f]),
+    "bds_lidar_boxes_workspace_bytes": (_sz, [_i64]),
+    "bds_lidar_points_in_boxes_count": (_i, [_i64, _f, _i, _f, _f, _f, _i, _f, _f, _sz, _f]),
+    "bds_lidar_points_in_boxes_emit": (_i, [_i64, _f, _i, _f, _f, _f, _f, _i, _f, _sz, _i64, _f, _f, _f]),
+    "bds_lidar_depth_downsample": (_i, [_i, _i, _i, _i, _i, _f, _f, _f]),
     "bds_opacity_reset": (_i, [_i64, _f, _fl, _f, _f, _f]),
     "bds_cubemap_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f]),
     "bds_cubemap_bwd": (_i, [_i64, _i, _i, _i, _f, _f, _f, _f, _f]),

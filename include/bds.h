@@ -1014,6 +1014,61 @@ size_t bds_knn_workspace_bytes(int64_t N);
 int bds_knn_self(int64_t N, const float *x, int K, float *dist, int32_t *idx, float *log_scales, int S, float clamp_lo, float clamp_hi,
                  void *ws, size_t ws_bytes, bds_stream_t stream);
 
+/* Lidar scene preparation: what DrivingDataset makes of the lidar before step 0, and the sparse depth map's downsampler of every
+ * coarse-to-fine step.  points: [N,3] float32, every coordinate FINITE (the entries do not check; a caller must --
+ * bds_nonfinite_flags).  Matrices are row-major float32 ON THE DEVICE.  One thread per point (per pixel / output cell where said); the
+ * per-view and per-box tables go through LDS in chunks of BDS_LIDAR_VIEW_CHUNK / BDS_LIDAR_BOX_CHUNK.  No float atomics anywhere:
+ * every output is bit-identical run to run.  Rows, pixels and records are 32-bit: N, V*H*W, B*H*W and B*Ho*Wo at most 2^31 - 257.
+ *
+ * bds_lidar_project -- project_lidar_pts_on_images (datasets/driving_dataset.py:644-727) for V views of one camera (common W, H).
+ *   lidar2img [V,3,4]: the first three rows of pad(K) @ inverse(c2w) (:681-685).  ranges [V,2] int64: view v takes the rows
+ *   [begin, end) of points (its lidar sweep), clamped to [0, N].  Per point and view: q = M[:, :3] p + M[:, 3] as
+ *   ((m0 x + m1 y) + m2 z) + m3 without fused multiply-add, z = q.z, u = q.x / (z + 1e-6f), v = q.y / (z + 1e-6f); valid iff
+ *   0 <= u < W and 0 <= v < H and z > 0 (:690-698); pixel ((int)v, (int)u) (:704-706).
+ *   winner [V,H,W] int32: per pixel the HIGHEST valid row, -1 where none landed -- what the reference's index_put_ with duplicate
+ *   indices gives on the host (the last write wins) and leaves unspecified on a GPU.  Three passes: an integer atomicMax of the row,
+ *   a per-pixel pass that writes depth [V,H,W] = the winner's z (0 where empty), a per-point pass that writes pix [N] (the linear
+ *   index (v*H + y)*W + x of the point's pixel in the LAST view that sees it, else -1), SETS visible [N] to 1 where pix >= 0 (other
+ *   bytes keep their value: launches accumulate, :714) and, with images [V,H,W,3] and colors [N,3] (both or neither), copies the
+ *   image's pixel to colors for every valid point, winner or not (:717-720; other rows keep their value).
+ *   V = 0 and N = 0: nothing to do.  V > 0, N = 0: winner = -1, depth = 0.
+ * bds_lidar_visible -- check_pts_visibility (:576-603): visible [N] = 1 where the valid test above holds in any of V views, else 0.
+ *   sizes [V,2] int32: (W, H) of each view.  V = 0 writes zeros.
+ * bds_lidar_points_in_boxes* -- the oriented-box test of get_init_objects (:341-354) and filter_pts_in_boxes (:521-536) for B boxes.
+ *   w2o [B,3,4]: the first three rows of inverse(o2w); half [B,3]: o_size / 2; ranges [B,2] int64 or NULL: the rows a box tests (its
+ *   frame's sweep; NULL: every row).  o = w2o [p;1] as above; inside iff -half < o < half on every axis, strictly.  chunk: boxes per
+ *   LDS stage, 1..BDS_LIDAR_BOX_CHUNK (the product passes BDS_LIDAR_BOX_CHUNK; tests pass less to cross stages with few boxes).
+ *   Mask form (bds_lidar_points_in_boxes): inside [N] = 1 where any box holds the point, else 0 (B = 0: zeros).
+ *   Emit form: bds_lidar_points_in_boxes_count writes per point the number of boxes that hold it and scans them (ws:
+ *   bds_lidar_boxes_workspace_bytes(N) bytes, 16-byte aligned) and writes *total (int64, device), the number of records;
+ *   bds_lidar_points_in_boxes_emit, given the SAME arguments and that workspace, writes record r < capacity as rec_ids [r] =
+ *   (instance, frame, row) from ids [B,2] int32 = (instance, frame) and rec_xyz [r] = o, ordered by (row, box): a point inside two
+ *   boxes gives two records.  Records at or past capacity are dropped (the caller reads *total to size the arrays).
+ * bds_lidar_depth_downsample -- sparse_lidar_map_downsampler (datasets/base/pixel_source.py:77-92) for B maps [B,H,W] -> [B,Ho,Wo]:
+ *   output cell (i,j) covers rows [floor(i H / Ho), ceil((i+1) H / Ho)) and columns likewise (F.interpolate(mode="area")); with sum
+ *   over every value of the window in row-major order, cnt the number of values > 1e-3 and kh x kw the window:
+ *   ((sum / kh) / kw) / ((cnt / kh) / kw) where cnt > 0, else 0 -- the reference's order of divisions on the host.  Ho, Wo may exceed H, W (a scale
+ *   factor above 1: the same windows, single pixels or overlapping).
+ * All: 0 for an empty input; BDS_EINVAL before any launch for a negative or too large count, a NULL or misaligned array that the
+ * call would read or write, images without colors or the converse, a chunk outside its range; BDS_EWORKSPACE: ws too small (the size
+ * query answers 0 for N < 1 or too large). */
+#define BDS_LIDAR_VIEW_CHUNK 64
+#define BDS_LIDAR_BOX_CHUNK 128
+int bds_lidar_project(int V, int W, int H, int64_t N, const float *points, const float *lidar2img, const int64_t *ranges,
+                      const float *images, int32_t *winner, float *depth, int32_t *pix, uint8_t *visible, float *colors,
+                      bds_stream_t stream);
+int bds_lidar_visible(int64_t N, const float *points, int V, const float *lidar2img, const int32_t *sizes, uint8_t *visible,
+                      bds_stream_t stream);
+int bds_lidar_points_in_boxes(int64_t N, const float *points, int B, const float *w2o, const float *half, const int64_t *ranges,
+                              int chunk, uint8_t *inside, bds_stream_t stream);
+size_t bds_lidar_boxes_workspace_bytes(int64_t N);
+int bds_lidar_points_in_boxes_count(int64_t N, const float *points, int B, const float *w2o, const float *half, const int64_t *ranges,
+                                    int chunk, int64_t *total, void *ws, size_t ws_bytes, bds_stream_t stream);
+int bds_lidar_points_in_boxes_emit(int64_t N, const float *points, int B, const float *w2o, const float *half, const int64_t *ranges,
+                                   const int32_t *ids, int chunk, const void *ws, size_t ws_bytes, int64_t capacity, int32_t *rec_ids,
+                                   float *rec_xyz, bds_stream_t stream);
+int bds_lidar_depth_downsample(int B, int H, int W, int Ho, int Wo, const float *in, float *out, bds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
