@@ -57,6 +57,7 @@ _SIGS = {
     "bds_project_bwd": (_i, [_i, _i64, _f, _f, _f, _f, _f, _i, _i, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_isect_prepare_workspace_bytes": (_sz, [_i, _i64]),
     "bds_isect_visible_ids_offset": (_sz, [_i, _i64]),
+    "bds_isect_block_counts_offset": (_sz, [_i, _i64]),
     "bds_isect_build_workspace_bytes": (_sz, [_i, _i64, _i64]),
     "bds_isect_prepare": (_i, [_i, _i64, _f, _f, _f, _f, _f, _i, _i, _i, _f, _f, _sz, _i64, _i64, _f, _f, _i, _f]),
     "bds_isect_build": (_i, [_i, _i64, _i64, _i64, _f, _f, _f, _f, _f, _i, _i, _i, _f, _sz, _f, _sz, _f, _f, _f, _f, _i, _i, _f]),
@@ -73,6 +74,7 @@ _SIGS = {
     "bds_rasterize_kernel_name": (_i, [_i, _i, _i, _i, C.c_char_p, _i]),
     "bds_rasterize_bwd_schedule": (_i, [_i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f]),
     "bds_project_view_fwd": (_i, [_i, _i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _f, _f]),
+    "bds_project_view_fwd_kept": (_i, [_i, _i64, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _f, _f, _f]),
     "bds_gaussian_block_bounds": (_i, [_i64, _f, _f, _f, _f]),
     "bds_sh_view_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_sh_view_bwd_list": (_i, [_i64, _f, _f, _i, _i, _f, _f, _f, _i, _f, _f, _f, _f, _i, _f]),

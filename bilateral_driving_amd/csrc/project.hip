@@ -113,6 +113,10 @@ __global__ __launch_bounds__(kProjBlock) void project_bwd_kernel(
 // kAA (rasterize_mode "antialiased", models/trainers/base.py:406): the opacity the tile stage and the compositor read is the EFFECTIVE
 // one, sigmoid(logit) * comp -- in the row form the row's slot 7, in the column form the dense [N] array opac_eff; `opacities` keeps
 // sigmoid(logit), which the backward reads.
+// block_state (with block_bounds; bds_project_view_fwd_kept): one word per 256-row block of THIS set of output buffers, written only by
+// that block's workgroup -- 1 = "the block's rows hold a rejected block's outputs" (the zeros below), 0 = unknown.  A rejected block whose
+// word is 1 stores no row: a persistent buffer already holds exactly those zeros.  The word, not the contents, says so: a block that
+// survived with every row culled one by one holds exp / sigmoid values in scales / opacities.
 template <bool kReduce, bool kAA = false>
 __global__ __launch_bounds__(kProjBlock) void project_view_fwd_kernel(
     int64_t N, const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ log_scales,
@@ -120,7 +124,7 @@ __global__ __launch_bounds__(kProjBlock) void project_view_fwd_kernel(
     float eps2d, float near_plane, float far_plane, float radius_clip, float *__restrict__ scales,
     float *__restrict__ opacities, int32_t *__restrict__ radii, float *__restrict__ means2d, float *__restrict__ depths,
     float *__restrict__ conics, PrepReduceSlots rs, int32_t *__restrict__ tiles_per_gauss, int rows,
-    const float *__restrict__ block_bounds, float *__restrict__ opac_eff = nullptr) {
+    const float *__restrict__ block_bounds, float *__restrict__ opac_eff = nullptr, uint32_t *__restrict__ block_state = nullptr) {
   const int64_t g = (int64_t)blockIdx.x * kProjBlock + threadIdx.x;
   if (kReduce) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *rs.m_total = 0;
@@ -133,7 +137,9 @@ __global__ __launch_bounds__(kProjBlock) void project_view_fwd_kernel(
     const float *bb = block_bounds + (int64_t)blockIdx.x * 8;
     const float lo[3] = {bb[0], bb[1], bb[2]}, hi[3] = {bb[4], bb[5], bb[6]};
     if (!box_may_be_visible(lo, hi, bb[3], load_camera(viewmat, K), W, H, eps2d, near_plane, far_plane)) {
-      if (g < N) {
+      // (workgroup-uniform; every wave reads the word before the barrier below, thread 0 writes it behind that barrier)
+      const bool kept = block_state != nullptr && block_state[blockIdx.x] == 1u;
+      if (g < N && !kept) {
         radii[g] = 0;
         // (dense [N] outputs a later dense consumer may read -- render_classes' opacity x mask: never uninitialised memory)
         scales[g * 3] = 0.f; scales[g * 3 + 1] = 0.f; scales[g * 3 + 2] = 0.f; opacities[g] = 0.f;
@@ -149,6 +155,10 @@ __global__ __launch_bounds__(kProjBlock) void project_view_fwd_kernel(
         if (kReduce && tiles_per_gauss) tiles_per_gauss[g] = 0;
       }
       if (kReduce && threadIdx.x == 0) rs.sums256[blockIdx.x] = 0u;
+      if (block_state != nullptr && !kept) {
+        __syncthreads();
+        if (threadIdx.x == 0) block_state[blockIdx.x] = 1u;
+      }
       return;
     }
   }
@@ -183,9 +193,13 @@ __global__ __launch_bounds__(kProjBlock) void project_view_fwd_kernel(
       if (tiles_per_gauss) tiles_per_gauss[g] = 0;   // (the counting kernel writes the visible entries only)
     }
     const int cnt = __syncthreads_count(radius > 0);
-    if (threadIdx.x == 0) rs.sums256[blockIdx.x] = (uint32_t)cnt;
+    if (threadIdx.x == 0) {
+      rs.sums256[blockIdx.x] = (uint32_t)cnt;
+      if (block_state != nullptr) block_state[blockIdx.x] = 0u;
+    }
     return;
   }
+  if (block_state != nullptr && threadIdx.x == 0) block_state[blockIdx.x] = 0u;   // (a surviving block never reads its word)
   if (g >= N) return;
   float m[3] = {means[g * 3], means[g * 3 + 1], means[g * 3 + 2]};
   float q[4] = {quats[g * 4], quats[g * 4 + 1], quats[g * 4 + 2], quats[g * 4 + 3]};
@@ -444,14 +458,16 @@ static int view_rows(const float *means2d, const float *depths, const float *con
   return BDS_OK;
 }
 
-// The one-view forward (include/bds.h): BDS_PROJ_ANTIALIASED selects kAA, prep_ws kReduce, block_bounds the block skip.
-extern "C" int bds_project_view_fwd(int flags, int64_t N, const float *means, const float *quats, const float *log_scales,
-                                    const float *logits, const float *viewmat, const float *K, int W, int H, float eps2d, float near_plane,
-                                    float far_plane, float radius_clip, float *scales, float *opacities, float *opac_eff, int32_t *radii,
-                                    float *means2d, float *depths, float *conics, int32_t *tiles_per_gauss, void *prep_ws,
-                                    size_t prep_ws_bytes, const float *block_bounds, bds_stream_t stream) {
+// The one-view forward (include/bds.h): BDS_PROJ_ANTIALIASED selects kAA, prep_ws kReduce, block_bounds the block skip, block_state the
+// kept-blocks mode (bds_project_view_fwd_kept only).
+static int project_view_fwd(int flags, int64_t N, const float *means, const float *quats, const float *log_scales, const float *logits,
+                            const float *viewmat, const float *K, int W, int H, float eps2d, float near_plane, float far_plane,
+                            float radius_clip, float *scales, float *opacities, float *opac_eff, int32_t *radii, float *means2d,
+                            float *depths, float *conics, int32_t *tiles_per_gauss, void *prep_ws, size_t prep_ws_bytes,
+                            const float *block_bounds, uint32_t *block_state, bds_stream_t stream) {
   BDS_REQUIRE((flags & ~BDS_PROJ_ANTIALIASED) == 0 && N >= 0 && W > 0 && H > 0);
   BDS_REQUIRE(prep_ws == nullptr || N > 0);
+  BDS_REQUIRE(block_state == nullptr || block_bounds != nullptr);
   if (N == 0) return BDS_OK;
   BDS_REQUIRE(means && quats && log_scales && logits && viewmat && K && scales && opacities && radii && means2d && depths && conics);
   int rows = 0;
@@ -470,12 +486,35 @@ extern "C" int bds_project_view_fwd(int flags, int64_t N, const float *means, co
 #define BDS_VIEW_FWD(R, A)                                                                                                            \
   hipLaunchKernelGGL((project_view_fwd_kernel<R, A>), grid, block, 0, as_stream(stream), N, means, quats, log_scales, logits, viewmat, \
                      K, W, H, eps2d, near_plane, far_plane, radius_clip, scales, opacities, radii, means2d, depths, conics, rs,         \
-                     tiles_per_gauss, rows, block_bounds, opac_eff)
+                     tiles_per_gauss, rows, block_bounds, opac_eff, block_state)
   if (prep_ws) { if (aa) BDS_VIEW_FWD(true, true); else BDS_VIEW_FWD(true, false); }
   else         { if (aa) BDS_VIEW_FWD(false, true); else BDS_VIEW_FWD(false, false); }
 #undef BDS_VIEW_FWD
   BDS_LAUNCH_CHECK();
   return BDS_OK;
+}
+
+extern "C" int bds_project_view_fwd(int flags, int64_t N, const float *means, const float *quats, const float *log_scales,
+                                    const float *logits, const float *viewmat, const float *K, int W, int H, float eps2d, float near_plane,
+                                    float far_plane, float radius_clip, float *scales, float *opacities, float *opac_eff, int32_t *radii,
+                                    float *means2d, float *depths, float *conics, int32_t *tiles_per_gauss, void *prep_ws,
+                                    size_t prep_ws_bytes, const float *block_bounds, bds_stream_t stream) {
+  return project_view_fwd(flags, N, means, quats, log_scales, logits, viewmat, K, W, H, eps2d, near_plane, far_plane, radius_clip, scales,
+                          opacities, opac_eff, radii, means2d, depths, conics, tiles_per_gauss, prep_ws, prep_ws_bytes, block_bounds,
+                          nullptr, stream);
+}
+
+// The same over PERSISTENT outputs (include/bds.h): block_state [cdiv(N, 256)] belongs to this set of output buffers.
+extern "C" int bds_project_view_fwd_kept(int flags, int64_t N, const float *means, const float *quats, const float *log_scales,
+                                         const float *logits, const float *viewmat, const float *K, int W, int H, float eps2d,
+                                         float near_plane, float far_plane, float radius_clip, float *scales, float *opacities,
+                                         float *opac_eff, int32_t *radii, float *means2d, float *depths, float *conics,
+                                         int32_t *tiles_per_gauss, void *prep_ws, size_t prep_ws_bytes, const float *block_bounds,
+                                         uint32_t *block_state, bds_stream_t stream) {
+  BDS_REQUIRE(block_state != nullptr && block_bounds != nullptr);
+  return project_view_fwd(flags, N, means, quats, log_scales, logits, viewmat, K, W, H, eps2d, near_plane, far_plane, radius_clip, scales,
+                          opacities, opac_eff, radii, means2d, depths, conics, tiles_per_gauss, prep_ws, prep_ws_bytes, block_bounds,
+                          block_state, stream);
 }
 
 namespace bds {

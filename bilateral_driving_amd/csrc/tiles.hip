@@ -832,13 +832,26 @@ __device__ __forceinline__ void visible_compact_block(VisCompactSh &sh, int vb, 
   constexpr int kSpan = kCompactSpan;
   uint32_t *lw = sh.lw;
   auto &h = sh.h;
-#pragma unroll
-  for (int t = 0; t < kSpan; t++) h[t][threadIdx.x] = 0;
   uint32_t part = 0;
   // (sums_per_tile = 8: the counts were left per 256-Gaussian workgroup by the one-view projection, bds_project_view_fwd with prep_ws)
   for (int b = threadIdx.x; b < vb * sums_per_tile; b += kScanBlock) part += tile_sums[b];
   uint32_t my_offset;
   block_excl_scan(part, my_offset, lw);   // total of the partial sums = this tile's offset
+  // A tile whose own counts are all zero holds no visible entry (most tiles, with the rows in spatial order): it has taken part in the
+  // offset scan and reads neither radii nor depths, nor touches the histograms.  (Workgroup-uniform: vb and the counts are.)
+  const uint32_t per_sum = (uint32_t)(kScanTile / sums_per_tile);
+  const int n_sums = (int)(((uint32_t)CN + per_sum - 1u) / per_sum);   // (CN < 2^31: the entries check it)
+  uint32_t own = 0;
+  for (int k = 0; k < sums_per_tile; k++) {
+    const int b = vb * sums_per_tile + k;
+    if (b < n_sums) own += tile_sums[b];
+  }
+  if (own == 0) {
+    if (vb == nvb - 1 && threadIdx.x == 0) *n_vis_out = (uint64_t)my_offset;
+    return;
+  }
+#pragma unroll
+  for (int t = 0; t < kSpan; t++) h[t][threadIdx.x] = 0;
   const int64_t base = (int64_t)vb * kScanTile + (int64_t)threadIdx.x * kScanItems;
   bool vis[kScanItems];
   uint32_t s = 0;
@@ -1193,6 +1206,13 @@ extern "C" size_t bds_isect_visible_ids_offset(int C, int64_t N) {
   char *const base = reinterpret_cast<char *>(static_cast<uintptr_t>(4096));   // layout arithmetic only, never dereferenced
   const PrepWs L = prep_layout(base, (int64_t)C * N);
   return static_cast<size_t>(reinterpret_cast<char *>(L.asc) - base);
+}
+
+extern "C" size_t bds_isect_block_counts_offset(int C, int64_t N) {
+  if (C < 1 || N < 0) return 0;
+  char *const base = reinterpret_cast<char *>(static_cast<uintptr_t>(4096));   // layout arithmetic only, never dereferenced
+  const PrepWs L = prep_layout(base, (int64_t)C * N);
+  return static_cast<size_t>(reinterpret_cast<char *>(L.temp) - base);
 }
 
 extern "C" size_t bds_isect_prepare_workspace_bytes(int C, int64_t N) {

@@ -155,6 +155,55 @@ class _Front:
     pass
 
 
+class FrontBuffers:
+    """The projection outputs of ONE view slot as persistent buffers + their kept-blocks state (include/bds.h
+    bds_project_view_fwd_kept): ``state`` [cdiv(N, 256)] int32, 1 = "the block's rows hold a rejected block's zeros".  The owner (a
+    ``graph_view.FrameGraph`` slot) hands the object to every forward of the slot as ``cfg["front_bufs"]``; ``_front_begin`` takes its
+    output tensors from it, always in the same order.  A request that does not match what is there (first call, another N, rows instead
+    of columns) allocates from there on and ZEROES the state -- outside a stream capture only: a capture's private pool may hand a freed
+    block to another view, and then the state would describe memory somebody else writes.  ``reset()`` whenever anything but the slot's
+    own forward may have written the buffers."""
+
+    def __init__(self):
+        self.tensors, self.state, self._i = [], None, 0
+
+    @staticmethod
+    def _not_capturing() -> None:
+        if torch.cuda.is_current_stream_capturing():
+            raise L.BdsError("FrontBuffers: new buffers inside a stream capture (run the slot's forward once outside the capture first)")
+
+    def begin(self):
+        """Start one forward: returns the allocator for its projection outputs."""
+        self._i = 0
+        return self._take
+
+    def _take(self, shape, dev, dtype=torch.float32) -> Tensor:
+        i, self._i = self._i, self._i + 1
+        t = self.tensors[i] if i < len(self.tensors) else None
+        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != dev:
+            self._not_capturing()
+            del self.tensors[i:]
+            t = torch.empty(shape, device=dev, dtype=dtype)
+            self.tensors.append(t)
+            self.state = None
+        return t
+
+    def end(self, N: int) -> Tensor:
+        """All outputs taken: the state that goes with them."""
+        if len(self.tensors) > self._i:      # (fewer outputs than the last call: another form)
+            del self.tensors[self._i:]
+            self.state = None
+        if self.state is None:
+            self._not_capturing()
+            self.state = torch.zeros((N + 255) // 256, device=self.tensors[0].device, dtype=torch.int32)
+        return self.state
+
+    def reset(self) -> None:
+        """The buffers may hold anything again (enqueued on the current stream)."""
+        if self.state is not None:
+            self.state.zero_()
+
+
 class _Lists:
     """The tile stage of one view between ``_lists_begin`` and ``_lists_finish``; attribute bag."""
     pass
@@ -212,8 +261,13 @@ def _front_begin(cfg: dict, means, quats, log_scales, logits, sh, viewmat) -> _F
     means, quats, log_scales, logits, sh = (t.contiguous() for t in (means, quats, log_scales, logits, sh))
     viewmat, Kmat = viewmat.contiguous(), cfg["K"].contiguous()
     # activations (vanilla.py:393-394) + projection (C = 1)
-    scales, opac = _empty((N, 3), dev), _empty((N,), dev)
-    radii = _empty((1, N), dev, torch.int32)
+    # front_bufs (graph_view: a view slot's FrontBuffers): the projection's outputs are PERSISTENT buffers of the slot, and the projection
+    # leaves the rows of a block it rejects alone when they already hold a rejected block's zeros (include/bds.h
+    # bds_project_view_fwd_kept); else fresh buffers per call and the plain entry
+    keep = cfg.get("front_bufs") if N > 0 and cfg.get("block_bounds") is not None else None
+    out_buf = keep.begin() if keep is not None else _empty
+    scales, opac = out_buf((N, 3), dev), out_buf((N,), dev)
+    radii = out_buf((1, N), dev, torch.int32)
     caps = cfg.get("caps")                 # ListCapacity: the device-count form (no host wait in this view)
     in_pack = cfg.get("sh_in_pack", SH_IN_PACK if caps is None else SH_IN_PACK_DEV)
     pack_colours = sh_rest is not None or (in_pack and (K * 3) % 4 == 0 and sh.data_ptr() % 16 == 0)
@@ -222,13 +276,14 @@ def _front_begin(cfg: dict, means, quats, log_scales, logits, sh, viewmat) -> _F
     if pack_colours and _PROJ_ROWS and N > 0:
         # the projection's outputs as the columns of ONE [N,8] block of 32-byte rows (csrc/bds_common.h ProjLayout): the tile stage
         # and the record pack gather one line per visible Gaussian instead of one per array; radii / opacities stay dense as well
-        rows = _empty((N, 8), dev)
+        rows = out_buf((N, 8), dev)
         means2d, depths, conics, opac_row = rows[None, :, 0:2], rows[None, :, 2], rows[None, :, 4:7], rows[:, 7]
     else:
-        means2d, depths, conics, opac_row = _empty((1, N, 2), dev), _empty((1, N), dev), _empty((1, N, 3), dev), opac
+        means2d, depths, conics, opac_row = out_buf((1, N, 2), dev), out_buf((1, N), dev), out_buf((1, N, 3), dev), opac
         if aa:
-            opac_row = opac_eff = _empty((N,), dev)   # (the effective opacities; `opac` keeps sigmoid(logit) for the backward)
-    tiles_per_gauss = _empty((1, N), dev, torch.int32)
+            opac_row = opac_eff = out_buf((N,), dev)   # (the effective opacities; `opac` keeps sigmoid(logit) for the backward)
+    tiles_per_gauss = out_buf((1, N), dev, torch.int32)
+    keep_state = keep.end(N) if keep is not None else None
     ws_bytes = lib.bds_isect_prepare_workspace_bytes(1, N)
     ws = cfg.get("prep_ws")   # a caller-owned prepare workspace (graph_view: the lists and their counts outlive the view)
     if ws is None:
@@ -241,13 +296,17 @@ def _front_begin(cfg: dict, means, quats, log_scales, logits, sh, viewmat) -> _F
         args = (L.PROJ_ANTIALIASED if aa else 0, N, L.ptr(means), L.ptr(quats), L.ptr(log_scales), L.ptr(logits), L.ptr(viewmat),
                 L.ptr(Kmat), W, H, cfg["eps2d"], cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"], L.ptr(scales), L.ptr(opac),
                 L.ptr(opac_eff), L.ptr(radii), _dp(means2d), _dp(depths), _dp(conics))
+        def project(*tile_stage):
+            if keep is None:
+                return lib.bds_project_view_fwd(*args, *tile_stage, L.ptr(bounds), st)
+            return lib.bds_project_view_fwd_kept(*args, *tile_stage, L.ptr(bounds), L.ptr(keep_state), st)
         if caps is not None and N > 0:
-            rc = lib.bds_project_view_fwd(*args, L.ptr(tiles_per_gauss), L.ptr(ws), ws_bytes, L.ptr(bounds), st)
+            rc = project(L.ptr(tiles_per_gauss), L.ptr(ws), ws_bytes)
             pre_reduced = rc == L.BDS_OK
             if rc != L.BDS_ECAPACITY:     # (ECAPACITY: N beyond the short sort path -- the plain projection below)
                 L.check(rc, "bds_project_view_fwd")
         if not pre_reduced:
-            L.check(lib.bds_project_view_fwd(*args, None, None, 0, L.ptr(bounds), st), "bds_project_view_fwd")
+            L.check(project(None, None, 0), "bds_project_view_fwd")
     f = _Front()
     f.list_tile = cfg.get("list_tile", LIST_TILE)
     f.lists = _lists_begin(means2d, radii, depths, (_dp(conics), _dp(opac_row)) if cfg["tile_cull"] else None, W, H, f.list_tile, caps,
@@ -910,6 +969,7 @@ def train_view(params: Dict[str, Tensor], viewmat: Tensor, K: Tensor, width: int
     defer_epilogue = bool(kwargs.pop("defer_epilogue", True))   # (see _DEFER_EPILOGUE)
     split_len, split_cap = kwargs.pop("split_len", None), kwargs.pop("split_cap", None)   # device-count compositors: long tiles strip by strip (_split)
     block_bounds = kwargs.pop("block_bounds", None)    # bds_gaussian_block_bounds of the current parameters (the projection skips whole blocks)
+    front_bufs = kwargs.pop("front_bufs", None)        # FrontBuffers: a view slot's persistent projection outputs + kept-blocks state (needs block_bounds)
     row_catchup = kwargs.pop("row_catchup", None)      # optim.DeferredRowAdam.catchup (device-count form with the SH colours in the pack)
     # the TV term over OTHER tensors than the transform's grids: graph_view's replayable view slices staging copies of ONE image's
     # grids (picked by a device-side index) while the regulariser runs over the full [n_img, ...] parameters (modules.py:445)
@@ -923,7 +983,7 @@ def train_view(params: Dict[str, Tensor], viewmat: Tensor, K: Tensor, width: int
                grad_arena=grad_arena, grad_sink=grad_sink, img_idx=None if img_idx is None else int(img_idx), arena_rows=arena_rows,
                list_tile=int(LIST_TILE if list_tile is None else list_tile), caps=caps, prep_ws=prep_ws, g2d_buf=g2d_buf, tail_buf=tail_buf,
                defer_epilogue=defer_epilogue, split_len=split_len, split_cap=split_cap, block_bounds=block_bounds,
-               defer_pose_sum=defer_pose_sum, row_catchup=row_catchup, antialiased=bool(opts["antialiased"]))
+               front_bufs=front_bufs, defer_pose_sum=defer_pose_sum, row_catchup=row_catchup, antialiased=bool(opts["antialiased"]))
     gs = [g if g.dim() == 5 else g[None] for g in grids]
     if grad_arena is not None and (arena_rows >= 1 or grad_sink is not None):
         # (with a sink the arena names the GRID gradients only: the per-Gaussian rows go to the sink's compact buffers)

@@ -51,9 +51,9 @@ from torch import Tensor
 
 from . import _lib as L
 from .dist import ROW_NAMES, FlatGradients
-from .fused_view import LIST_TILE
+from .fused_view import LIST_TILE, FrontBuffers
 from . import harness as Hn
-from .graph_slots import BLOCK_BOUNDS, GRAD_ROWS, FrameCapacities, ViewGraph, camera_centre as _camera_centre
+from .graph_slots import BLOCK_BOUNDS, BLOCK_KEEP, GRAD_ROWS, FrameCapacities, ViewGraph, camera_centre as _camera_centre
 
 
 class FrameGraph(FrameCapacities):
@@ -154,6 +154,9 @@ class FrameGraph(FrameCapacities):
         self.split_len, self.split_cap = [0] * self.V, [0] * self.V   # per slot: long tiles composited by four waves (graph_slots.calibrate)
         # a bound per 256-row block, refreshed by the begin stage: a view's projection skips the blocks it can not see (densify.spatial_order)
         self._bounds = torch.zeros((self.N + 255) // 256, 8, device=self.dev) if BLOCK_BOUNDS and self.N > 0 else None
+        # per view slot: the projection's outputs as persistent buffers with their kept-blocks state (allocated by the slot's first
+        # forward, the warm-up frame of capture()): a block the slot's camera rejects frame after frame is written once
+        self.front_bufs = [FrontBuffers() for _ in range(self.V)] if BLOCK_KEEP and self._bounds is not None else None
         self.calibrate()
         self.capture()
 
@@ -163,7 +166,8 @@ class FrameGraph(FrameCapacities):
                   sh_degree=self.sh_degree, two_phase=True, lazy_loss=True, split_len=self.split_len[v], split_cap=self.split_cap[v],
                   # two streams: the transform's memory-bound last stage hides behind the other stream's compositor; folded into the
                   # compositor's backward it would lengthen the VALU-bound critical kernel (fused_view._DEFER_EPILOGUE)
-                  defer_epilogue=not self.overlap, block_bounds=self._bounds, row_catchup=self.row_catchup, antialiased=self.antialiased)
+                  defer_epilogue=not self.overlap, block_bounds=self._bounds, row_catchup=self.row_catchup, antialiased=self.antialiased,
+                  front_bufs=None if self.front_bufs is None else self.front_bufs[v])
         if self.fx is not None:     # rows into view v's compact exchange buffer; the dense tail (grids) accumulates in place in .grad
             kw.update(grad_sink=self.fx.static_sink(v), grid_grads=None)
             if self.dynamic:        # the transform's grid gradient -> the slot's staging slices, the TV term -> the parameters' slices
@@ -256,6 +260,8 @@ class FrameGraph(FrameCapacities):
         self.begin_graph = self.begin_graph_rest = None
         self._reprovision = False
         torch.cuda.synchronize()
+        for fb in self.front_bufs or ():     # (a capture starts from "unknown": whatever ran since the last one, the state does not rely on it)
+            fb.reset()
         if self.fx is not None:
             self.fx.static_setup(self._unions)
         self._point_grads_at_flat()

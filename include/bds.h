@@ -143,6 +143,11 @@ size_t bds_isect_prepare_workspace_bytes(int C, int64_t N);
 /* Byte offset, inside the prepare workspace, of the ascending id list of the visible entries (int32 [n_visible], compact mode):
  * a caller that keeps `ws` alive reads the list in place and passes visible_ids = NULL to bds_isect_build (no copy). */
 size_t bds_isect_visible_ids_offset(int C, int64_t N);
+/* Byte offset, inside the prepare workspace, of the visible counts per 256 Gaussians (uint32 [cdiv(N, 256)]) that
+ * bds_project_view_fwd with prep_ws leaves for bds_isect_prepare(..., compact | 2, ...): valid between those two calls.
+ * An inspection hook like bds_isect_counts_offset: nothing in the product calls it; tests/test_gpu_43 reads the counts through it to
+ * show that whole scan tiles were empty. */
+size_t bds_isect_block_counts_offset(int C, int64_t N);
 size_t bds_isect_build_workspace_bytes(int C, int64_t N, int64_t M);
 /* conics [C,N,3] + opacities [C,N] (both or neither): when given, (tile, Gaussian) pairs in which no
  * pixel centre can reach alpha >= 1/255 are dropped ("exact tile culling"): rendered images and
@@ -437,6 +442,20 @@ int bds_project_view_fwd(int flags, int64_t N, const float *means, const float *
                          float radius_clip, float *scales, float *opacities, float *opac_eff, int32_t *radii, float *means2d,
                          float *depths, float *conics, int32_t *tiles_per_gauss, void *prep_ws, size_t prep_ws_bytes,
                          const float *block_bounds, bds_stream_t stream);
+/* The same call over PERSISTENT output buffers ("kept blocks"; block_bounds required): block_state [cdiv(N, 256)] u32 is caller-owned
+ * memory that belongs to ONE set of output buffers (scales .. conics, opac_eff, tiles_per_gauss, in one form: rows or columns, with or
+ * without prep_ws) -- one word per 256-row block, 0 = unknown (a fresh zeroed allocation), 1 = the block's rows hold a rejected block's
+ * outputs.  A rejected block whose word is 1 stores no row (the buffers already hold exactly those zeros); a rejected block whose word is
+ * not 1 stores them and sets the word; a surviving block stores its rows and clears the word.  Every word is read and written by its own
+ * block's workgroup only.  The per-call workspace side (visible counts, cleared tables) is written on every call.  The outputs after a
+ * call are byte for byte those of bds_project_view_fwd.  The state says what the BUFFERS hold, not which camera or parameters wrote
+ * them: zero it whenever the buffers are replaced, or anything but this call (and the tile stage, which writes tiles_per_gauss of
+ * visible rows only) may have written them. */
+int bds_project_view_fwd_kept(int flags, int64_t N, const float *means, const float *quats, const float *log_scales, const float *logits,
+                              const float *viewmat, const float *K, int W, int H, float eps2d, float near_plane, float far_plane,
+                              float radius_clip, float *scales, float *opacities, float *opac_eff, int32_t *radii, float *means2d,
+                              float *depths, float *conics, int32_t *tiles_per_gauss, void *prep_ws, size_t prep_ws_bytes,
+                              const float *block_bounds, uint32_t *block_state, bds_stream_t stream);
 int bds_sh_view_fwd(int64_t N, int K, int degrees_to_use, const float *means, const float *cam_pos, const float *coeffs,
                     const int32_t *radii, const float *depths, float *sh_rgb, float *colors, bds_stream_t stream);
 /* Backward of the one-view forms over the VISIBLE entries only, list-driven (no reference counterpart; the reference's dense
