@@ -10,34 +10,13 @@
 //   count -> device word + page-locked host word (the host looks at it after the fact)
 // HBM-bound byte work: N mask bytes in, 4 N + 4 capacity out, 4 * row_floats per union member zeroed.
 #include "bds_common.h"
+#include "scan.h"
 
 namespace bds {
 
 constexpr int kUnionBlock = 256;
 constexpr int kUnionItems = 16;                       // mask bytes per thread: one 16-byte load
 constexpr int kUnionTile = kUnionBlock * kUnionItems;  // 4096 Gaussians per workgroup
-
-__device__ __forceinline__ uint32_t union_block_scan(uint32_t v, uint32_t &total, uint32_t *lw) {
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const uint32_t t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
-  if (lane == kWave - 1) lw[wv] = inc;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kUnionBlock / kWave; w++) {
-    const uint32_t s = lw[w];
-    if (w < wv) base += s;
-    tot += s;
-  }
-  total = tot;
-  __syncthreads();
-  return base + inc - v;
-}
 
 __global__ __launch_bounds__(kUnionBlock) void union_count_kernel(int64_t N, const uint8_t *__restrict__ mask,
                                                                  uint32_t *__restrict__ tile_sums) {
@@ -56,7 +35,7 @@ __global__ __launch_bounds__(kUnionBlock) void union_count_kernel(int64_t N, con
       if (base + i < N) s += mask[base + i] ? 1u : 0u;
   }
   uint32_t tot;
-  union_block_scan(s, tot, lw);
+  block_excl_scan<kUnionBlock / kWave>(s, tot, lw);
   if (threadIdx.x == 0) tile_sums[blockIdx.x] = tot;
 }
 
@@ -71,7 +50,7 @@ __global__ __launch_bounds__(kUnionBlock) void union_slots_kernel(
   uint32_t part = 0;
   for (int b = threadIdx.x; b < (int)blockIdx.x; b += kUnionBlock) part += tile_sums[b];
   uint32_t my_offset;
-  union_block_scan(part, my_offset, lw);
+  block_excl_scan<kUnionBlock / kWave>(part, my_offset, lw);
   const int64_t base = (int64_t)blockIdx.x * kUnionTile + (int64_t)threadIdx.x * kUnionItems;
   bool in[kUnionItems];
   uint32_t s = 0;
@@ -81,7 +60,7 @@ __global__ __launch_bounds__(kUnionBlock) void union_slots_kernel(
     s += in[i] ? 1u : 0u;
   }
   uint32_t tot;
-  uint32_t slot = union_block_scan(s, tot, lw) + my_offset;
+  uint32_t slot = block_excl_scan<kUnionBlock / kWave>(s, tot, lw) + my_offset;
   if (threadIdx.x == 0) { s_off = my_offset; s_cnt = tot; }
   // running slot of every Gaussian (cumsum(mask) - 1 of the framework formulation: a non-member carries the slot of the last member
   // in front of it, -1 -> 0 clamped), members' ids into the list

@@ -10,7 +10,7 @@
 //             lane also picks the cell edge and the dimensions from the trimmed box and N (at most max(1, 2 N) cells, so the
 //             workspace and the launches depend on N alone) and writes them into the stats block
 //   count     per point its cell; an integer atomic on the cell's count, whose return value is the point's rank inside the cell
-//   scan      one workgroup turns the counts into exclusive offsets (the style of geo_scan_kernel)
+//   scan      one workgroup turns the counts into exclusive offsets (scan.h)
 //   scatter   each point as one 16-byte record {x, y, z, original index} to offset[cell] + rank
 //   query     one lane per record IN CELL ORDER: rings r = 0..BDS_KNN_RING_MAX of cells around the query's, the K best (d2, index)
 //             in registers, the termination test after every ring; a resolved query writes its rows, another appends itself to
@@ -39,11 +39,12 @@
 // cells per lane and stalls the other 63 lanes of its wave meanwhile, the fallback runs them with every lane busy.
 #include "bds_common.h"
 #include "knn_math.h"
+#include "scan.h"
 
 namespace bds {
 
 constexpr int kKnnBlock = 256, kKnnBlockWaves = kKnnBlock / kWave;
-constexpr int kKnnScanBlock = 1024, kKnnScanWaves = kKnnScanBlock / kWave;
+constexpr int kKnnScanBlock = 1024;
 constexpr int kKnnFbThreads = 128, kKnnFbQ = 2;
 constexpr int kKnnQueryBlock = kKnnFbThreads * kKnnFbQ, kKnnTile = 512;
 constexpr int kKnnRingMax = 2;
@@ -236,37 +237,10 @@ __global__ __launch_bounds__(kKnnBlock) void knn_count_kernel(KnnArgs a) {
 
 // counts[0 .. n) -> exclusive offsets, n = cells + 1 (the last count is 0, so offsets[cells] = N)
 __global__ __launch_bounds__(kKnnScanBlock) void knn_scan_kernel(uint32_t *__restrict__ b, const uint32_t *__restrict__ stats, int64_t cell_cap) {
-  __shared__ uint32_t s_w[kKnnScanWaves];
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  int64_t n = (int64_t)stats[kStCells] + 1;
-  n = n < cell_cap ? n : cell_cap;
-  const int64_t chunk = (n + kKnnScanBlock - 1) / kKnnScanBlock;
-  const int64_t lo = (int64_t)tid * chunk < n ? (int64_t)tid * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
-  uint32_t local = 0;
-  for (int64_t i = lo; i < hi; i++) local += b[i];
-  uint32_t v = local;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const uint32_t o = __shfl_up(v, off);
-    if (lane >= off) v += o;
-  }
-  if (lane == kWave - 1) s_w[wave] = v;
-  __syncthreads();
-  if (tid == 0) {
-    uint32_t run = 0;
-    for (int w = 0; w < kKnnScanWaves; w++) {
-      const uint32_t c = s_w[w];
-      s_w[w] = run;
-      run += c;
-    }
-  }
-  __syncthreads();
-  uint32_t run = s_w[wave] + (v - local);
-  for (int64_t i = lo; i < hi; i++) {
-    const uint32_t c = b[i];
-    b[i] = run;
-    run += c;
-  }
+  __shared__ uint32_t lw[kKnnScanBlock / kWave];
+  const int64_t n = (int64_t)stats[kStCells] + 1;
+  uint32_t total;
+  workgroup_scan_in_place<kKnnScanBlock>(b, n < cell_cap ? n : cell_cap, &total, lw);
 }
 
 __global__ __launch_bounds__(kKnnBlock) void knn_scatter_kernel(KnnArgs a) {

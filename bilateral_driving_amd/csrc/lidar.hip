@@ -8,6 +8,7 @@
 // its offsets from a scan of per-point counts, so every output is bit-identical run to run.
 #include "bds_common.h"
 #include "lidar_math.h"
+#include "scan.h"
 
 namespace bds {
 
@@ -143,27 +144,6 @@ struct LidarBoxArgs {
 
 enum { kBoxMask = 0, kBoxCount = 1, kBoxEmit = 2 };
 
-// exclusive scan of one value per thread over the workgroup (kLidarBlock threads); *total receives the workgroup's sum
-__device__ __forceinline__ int lidar_block_scan(int v, int *scratch, int *total) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const int o = __shfl_up(inc, d);
-    if (lane >= d) inc += o;
-  }
-  if (lane == kWave - 1) scratch[wave] = inc;
-  __syncthreads();
-  int before = 0, sum = 0;
-#pragma unroll
-  for (int w = 0; w < kLidarBlock / kWave; w++) {
-    if (w < wave) before += scratch[w];
-    sum += scratch[w];
-  }
-  *total = sum;
-  return before + inc - v;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(kLidarBlock) void lidar_boxes_kernel(LidarBoxArgs a) {
   __shared__ float sm[kLidarBoxChunk][16];      // w2o 12, half 3, -
@@ -180,7 +160,7 @@ __global__ __launch_bounds__(kLidarBlock) void lidar_boxes_kernel(LidarBoxArgs a
   int64_t at = 0;
   if (MODE == kBoxEmit) {
     int total;
-    at = a.block_off[blockIdx.x] + lidar_block_scan(live ? a.counts[i] : 0, scratch, &total);
+    at = a.block_off[blockIdx.x] + block_excl_scan<kLidarBlock / kWave>(live ? a.counts[i] : 0, total, scratch);
   }
   int found = 0;
   for (int b0 = 0; b0 < a.B; b0 += a.chunk) {
@@ -220,33 +200,17 @@ __global__ __launch_bounds__(kLidarBlock) void lidar_boxes_kernel(LidarBoxArgs a
   if (MODE == kBoxCount) {
     if (live) a.counts[i] = found;
     int total;
-    lidar_block_scan(live ? found : 0, scratch, &total);
+    block_excl_scan<kLidarBlock / kWave>(live ? found : 0, total, scratch);
     if (threadIdx.x == 0) a.block_off[blockIdx.x] = total;
   }
 }
 
 // one workgroup: the workgroups' sums -> their exclusive offsets, in place; *total the number of records
 __global__ __launch_bounds__(kLidarScanBlock) void lidar_scan_kernel(int64_t *__restrict__ block_off, int64_t nblk, int64_t *__restrict__ total) {
-  __shared__ int64_t part[kLidarScanBlock];
-  const int64_t per = (nblk + kLidarScanBlock - 1) / kLidarScanBlock;
-  const int64_t s = (int64_t)threadIdx.x * per, e = s + per < nblk ? s + per : nblk;
-  int64_t sum = 0;
-  for (int64_t k = s; k < e; k++) sum += block_off[k];
-  part[threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < kLidarScanBlock; d <<= 1) {
-    const int64_t o = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-    __syncthreads();
-    part[threadIdx.x] += o;
-    __syncthreads();
-  }
-  int64_t run = part[threadIdx.x] - sum;
-  for (int64_t k = s; k < e; k++) {
-    const int64_t c = block_off[k];
-    block_off[k] = run;
-    run += c;
-  }
-  if (threadIdx.x == kLidarScanBlock - 1) *total = part[threadIdx.x];
+  __shared__ int64_t lw[kLidarScanBlock / kWave];
+  int64_t sum;
+  workgroup_scan_in_place<kLidarScanBlock>(block_off, nblk, &sum, lw);
+  if (threadIdx.x == 0) *total = sum;
 }
 
 __global__ __launch_bounds__(kLidarBlock) void lidar_downsample_kernel(int B, int H, int W, int Ho, int Wo, const float *__restrict__ in,

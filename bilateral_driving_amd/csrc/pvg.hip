@@ -3,8 +3,8 @@
 // reference's x[filter_mask]), with the NaN / Inf flags of those tensors.  The per-row math lives in pvg_math.h.
 //   forward, three launches:
 //     count  one thread per row: marg, the keep byte (the bool mask) and the kept rows per 256-row block (ballot + popcount);
-//     scan   one workgroup: exclusive scan of the block counts in place, 1024 counts per pass with a running carry (any number of
-//            blocks); M and the cleared flag word go to the workspace header;
+//     scan   one workgroup: exclusive scan of the block counts in place (any number of blocks: scan.h); M and the cleared flag word
+//            go to the workspace header;
 //     write  one thread per row: rank = block offset + waves in front + mbcnt of the wave's ballot; a kept row computes its outputs
 //            and stores them at its rank, and ORs its NaN / Inf bits into the header (integer, only when a value is not finite).
 //   backward, one launch over the N rows: the rank is formed the same way, the output gradients are read by rank, every row of the
@@ -12,13 +12,12 @@
 // Everything is streamed once: non-temporal loads and stores, as the dense Adam pass (csrc/optim.hip).
 #include "bds_common.h"
 #include "pvg_math.h"
+#include "scan.h"
 
 namespace bds {
 
 constexpr int kPvgBlock = 256;                       // 4 waves
 constexpr int kPvgWaves = kPvgBlock / kWave;
-constexpr int kPvgScanPer = 4;                       // block counts per scan thread and pass
-constexpr int kPvgScanSpan = kPvgBlock * kPvgScanPer;   // 1024 block counts (262 144 rows) per pass
 constexpr int kPvgHeader = 4;                        // workspace words in front of the block table: {M, flags, -, -}
 
 typedef float pvg_f4u __attribute__((ext_vector_type(4), aligned(4)));   // 16 bytes at 4-byte alignment (rows of 3 (K-1) floats)
@@ -32,18 +31,6 @@ __device__ __forceinline__ void pvg_st_n(float *__restrict__ p, const float *v, 
   for (int k = 0; k < n; k++) pvg_st(p + k, v[k]);
 }
 
-// rank of a kept row among the kept rows of its block (every thread of the block calls this: it holds a barrier)
-__device__ __forceinline__ uint32_t pvg_block_rank(bool keep, uint32_t *s_cnt) {
-  const uint64_t b = __ballot(keep);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & (kWave - 1)) == 0) s_cnt[wave] = (uint32_t)__popcll(b);
-  __syncthreads();
-  uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-  for (int w = 0; w < kPvgWaves; w++)
-    if (w < wave) r += s_cnt[w];
-  return r;
-}
-
 __global__ __launch_bounds__(kPvgBlock) void pvg_count_kernel(int64_t N, float cur_time, const float *__restrict__ taus,
                                                              const float *__restrict__ betas, uint8_t *__restrict__ mask,
                                                              uint32_t *__restrict__ counts) {
@@ -54,45 +41,16 @@ __global__ __launch_bounds__(kPvgBlock) void pvg_count_kernel(int64_t N, float c
     keep = pvg_marginal(pvg_ld(taus + p), pvg_ld(betas + p), cur_time) > kPvgKeep;    // (false for NaN)
     mask[p] = keep ? 1 : 0;
   }
-  const uint64_t b = __ballot(keep);
-  if ((threadIdx.x & (kWave - 1)) == 0) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(b);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t c = 0;
-    for (int w = 0; w < kPvgWaves; w++) c += s_cnt[w];
-    counts[blockIdx.x] = c;
-  }
+  const uint32_t total = block_count<1, kPvgWaves>(keep, s_cnt);
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
 // counts[nb] -> exclusive offsets in place; header = {M, 0 (flags), 0, 0}
 __global__ __launch_bounds__(kPvgBlock) void pvg_scan_kernel(int64_t nb, uint32_t *__restrict__ header, uint32_t *__restrict__ counts) {
-  __shared__ uint32_t s[kPvgBlock];
-  const int tid = threadIdx.x;
-  uint32_t carry = 0;
-  for (int64_t base = 0; base < nb; base += kPvgScanSpan) {
-    const int64_t i0 = base + (int64_t)tid * kPvgScanPer;
-    uint32_t v[kPvgScanPer], t = 0;
-    for (int j = 0; j < kPvgScanPer; j++) {
-      v[j] = i0 + j < nb ? counts[i0 + j] : 0u;
-      t += v[j];
-    }
-    s[tid] = t;
-    __syncthreads();
-    for (int off = 1; off < kPvgBlock; off <<= 1) {
-      const uint32_t x = tid >= off ? s[tid - off] : 0u;
-      __syncthreads();
-      s[tid] += x;
-      __syncthreads();
-    }
-    uint32_t e = s[tid] - t + carry;
-    for (int j = 0; j < kPvgScanPer; j++) {
-      if (i0 + j < nb) counts[i0 + j] = e;
-      e += v[j];
-    }
-    carry += s[kPvgBlock - 1];
-    __syncthreads();
-  }
-  if (tid < kPvgHeader) header[tid] = tid == 0 ? carry : 0u;
+  __shared__ uint32_t lw[kPvgWaves];
+  uint32_t M;
+  workgroup_scan_in_place<kPvgBlock>(counts, nb, &M, lw);
+  if (threadIdx.x < kPvgHeader) header[threadIdx.x] = threadIdx.x == 0 ? M : 0u;
 }
 
 // bit 2 i: NaN in tensor i, bit 2 i + 1: Inf in tensor i (i in the order of get_gaussians' dict: means, opacities, rgbs, scales, quats)
@@ -148,7 +106,9 @@ __global__ __launch_bounds__(kPvgBlock, 8) void pvg_write_kernel(int64_t N, int 
   __shared__ uint32_t s_cnt[kPvgWaves];
   const int64_t p = (int64_t)blockIdx.x * kPvgBlock + threadIdx.x;
   const bool keep = p < N && mask[p] != 0;
-  const int64_t r = (int64_t)offsets[blockIdx.x] + pvg_block_rank(keep, s_cnt);
+  uint32_t rank;
+  block_rank<1>(keep, &rank, s_cnt);
+  const int64_t r = (int64_t)offsets[blockIdx.x] + rank;
   if (!keep) return;
   // the means and the colour first, stored before the other parameters are loaded: fewer values live at once (the degree-3 form
   // holds 45 coefficients and 16 bases)
@@ -192,7 +152,9 @@ __global__ __launch_bounds__(kPvgBlock) void pvg_bwd_kernel(int64_t N, int K, Pv
   __shared__ uint32_t s_cnt[kPvgWaves];
   const int64_t p = (int64_t)blockIdx.x * kPvgBlock + threadIdx.x;
   const bool keep = p < N && mask[p] != 0;
-  const int64_t r = (int64_t)offsets[blockIdx.x] + pvg_block_rank(keep, s_cnt);
+  uint32_t rank;
+  block_rank<1>(keep, &rank, s_cnt);
+  const int64_t r = (int64_t)offsets[blockIdx.x] + rank;
   if (p >= N) return;
   float gm[3] = {0.f, 0.f, 0.f}, gv[3] = {0.f, 0.f, 0.f}, gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f}, gc[3] = {0.f, 0.f, 0.f};
   float gt = 0.f, gb = 0.f, gl = 0.f, vc[3] = {0.f, 0.f, 0.f}, B[16];

@@ -19,6 +19,7 @@
 // HBM-bound byte movement: every parameter / state row is read once and written once (+ once per kept child).
 // PINNED by tests/golden/refine_*.npz (the reference's own refinement_after, oracle/gen_golden_refine.py).
 #include "bds_common.h"
+#include "scan.h"
 
 namespace bds {
 
@@ -96,93 +97,42 @@ __global__ __launch_bounds__(kRefBlock) void refine_flags_kernel(int64_t N, Refi
                                                                 const float *__restrict__ logits,
                                                                 const uint8_t *__restrict__ extra_cull, uint8_t *__restrict__ flags,
                                                                 uint32_t *__restrict__ blk) {
-  __shared__ uint32_t wsum[kRefWaves][kChan];
+  __shared__ uint32_t lw[kRefWaves * kChan];
   const int64_t g = (int64_t)blockIdx.x * kRefBlock + threadIdx.x;
   uint8_t f = 0;
   if (g < N) {
     f = refine_classify(g, c, xys_grad_norm, vis_counts, max_2Dsize, log_scales, logits, extra_cull);
     flags[g] = f;
   }
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-#pragma unroll
-  for (int ch = 0; ch < kChan; ch++) {
-    const uint64_t b = __ballot((f >> ch) & 1);
-    if (lane == 0) wsum[wave][ch] = (uint32_t)__popcll(b);
-  }
-  __syncthreads();
-  if (threadIdx.x < kChan) {
-    uint32_t s = 0;
-    for (int w = 0; w < kRefWaves; w++) s += wsum[w][threadIdx.x];
-    blk[(int64_t)blockIdx.x * kChan + threadIdx.x] = s;
-  }
+  const uint32_t total = block_count<kChan, kRefWaves>(f, lw);
+  if (threadIdx.x < kChan) blk[(int64_t)blockIdx.x * kChan + threadIdx.x] = total;
 }
 
-// exclusive scan of the per-workgroup counts (in place) + totals; ONE workgroup of 1024 threads, each owning a contiguous
-// segment of the counts
+// exclusive scan of the per-workgroup counts (in place) + totals; ONE workgroup
 constexpr int kScanThreads = 1024;
 __global__ __launch_bounds__(kScanThreads) void refine_blockscan_kernel(int64_t nb, uint32_t *__restrict__ blk,
                                                                        int64_t *__restrict__ totals) {
-  __shared__ uint32_t part[kScanThreads][kChan];
-  const int t = threadIdx.x;
-  const int64_t seg = (nb + kScanThreads - 1) / kScanThreads;
-  const int64_t lo = t * seg, hi = (lo + seg < nb) ? lo + seg : nb;
-  uint32_t s[kChan] = {0, 0, 0, 0, 0};
-  for (int64_t i = lo; i < hi; i++)
+  __shared__ uint32_t lw[kScanThreads / kWave];
+  uint32_t total[kChan];
+  workgroup_scan_in_place<kScanThreads, kChan>(blk, nb, total, lw);
+  if (threadIdx.x == 0)
 #pragma unroll
-    for (int ch = 0; ch < kChan; ch++) s[ch] += blk[i * kChan + ch];
-#pragma unroll
-  for (int ch = 0; ch < kChan; ch++) part[t][ch] = s[ch];
-  __syncthreads();
-  // Hillis-Steele inclusive scan over the 1024 partial sums
-  for (int d = 1; d < kScanThreads; d <<= 1) {
-    uint32_t add[kChan];
-#pragma unroll
-    for (int ch = 0; ch < kChan; ch++) add[ch] = t >= d ? part[t - d][ch] : 0u;
-    __syncthreads();
-#pragma unroll
-    for (int ch = 0; ch < kChan; ch++) part[t][ch] += add[ch];
-    __syncthreads();
-  }
-  uint32_t run[kChan];
-#pragma unroll
-  for (int ch = 0; ch < kChan; ch++) run[ch] = part[t][ch] - s[ch];  // exclusive prefix of this segment
-  for (int64_t i = lo; i < hi; i++)
-#pragma unroll
-    for (int ch = 0; ch < kChan; ch++) {
-      const uint32_t v = blk[i * kChan + ch];
-      blk[i * kChan + ch] = run[ch];
-      run[ch] += v;
-    }
-  if (t == kScanThreads - 1)
-#pragma unroll
-    for (int ch = 0; ch < kChan; ch++) totals[ch] = (int64_t)part[t][ch];
+    for (int ch = 0; ch < kChan; ch++) totals[ch] = (int64_t)total[ch];
 }
 
 // exclusive ranks per Gaussian: [split, keepO, keepS, keepD]
 __global__ __launch_bounds__(kRefBlock) void refine_ranks_kernel(int64_t N, const uint8_t *__restrict__ flags,
                                                                 const uint32_t *__restrict__ blk, uint32_t *__restrict__ ranks) {
-  __shared__ uint32_t wsum[kRefWaves][4];
+  __shared__ uint32_t lw[kRefWaves * 4];
   const int64_t g = (int64_t)blockIdx.x * kRefBlock + threadIdx.x;
-  const uint8_t f = g < N ? flags[g] : 0;
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  const int chan[4] = {0, 2, 3, 4};
-  uint32_t local[4];
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const uint64_t b = __ballot((f >> chan[k]) & 1);
-    local[k] = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[wave][k] = (uint32_t)__popcll(b);
-  }
-  __syncthreads();
-  if (g >= N) return;
-  uint4 r;
+  const uint32_t f = g < N ? flags[g] : 0;
   uint32_t out[4];
+  block_rank<4>((f & 1u) | (f >> 2 << 1), out, lw);      // channels 0, 2, 3, 4 (kDup's rank is not used)
+  if (g >= N) return;
+  const int chan[4] = {0, 2, 3, 4};
 #pragma unroll
-  for (int k = 0; k < 4; k++) {
-    uint32_t o = blk[(int64_t)blockIdx.x * kChan + chan[k]] + local[k];
-    for (int w = 0; w < wave; w++) o += wsum[w][k];
-    out[k] = o;
-  }
+  for (int k = 0; k < 4; k++) out[k] += blk[(int64_t)blockIdx.x * kChan + chan[k]];
+  uint4 r;
   r.x = out[0]; r.y = out[1]; r.z = out[2]; r.w = out[3];
   reinterpret_cast<uint4 *>(ranks)[g] = r;
 }

@@ -12,6 +12,7 @@
 // A stable sort by tile of a depth-ordered sequence is exactly the (tile, depth, emission) order.
 #include "bds_common.h"
 #include "gs_math.h"
+#include "scan.h"
 
 namespace bds {
 
@@ -21,34 +22,6 @@ namespace bds {
 constexpr int kScanBlock = 256;
 constexpr int kScanItems = 8;
 constexpr int kScanTile = kScanBlock * kScanItems;  // 2048
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-  const int lane = threadIdx.x & (kWave - 1);
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    uint32_t t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-// returns the exclusive prefix of `v` within the block and the block total
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t &total, uint32_t *lds_w /*>= waves+1*/) {
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-  const int nw = blockDim.x / kWave;
-  uint32_t inc = wave_incl_scan(v);
-  if (lane == kWave - 1) lds_w[wv] = inc;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-  for (int w = 0; w < nw; w++) {
-    uint32_t s = lds_w[w];
-    if (w < wv) base += s;
-    tot += s;
-  }
-  total = tot;
-  __syncthreads();
-  return base + inc - v;
-}
 
 __global__ __launch_bounds__(kScanBlock) void scan_reduce_kernel(const uint32_t *__restrict__ in, int64_t n,
                                                                 uint32_t *__restrict__ block_sums) {
