@@ -24,10 +24,9 @@
 // Bound: the FP32 MFMA rate, 2 * 0.51 M flop per point forward, three times that for forward + backward.
 #include "bds_common.h"
 #include "deform_math.h"
+#include "mfma_tile.h"
 
 namespace bds {
-
-typedef float df16 __attribute__((ext_vector_type(16)));
 
 constexpr int kDfW = 256, kDfLayers = 8, kDfSkip = 5;
 constexpr int kDfP = 32;          // points per workgroup
@@ -50,17 +49,6 @@ struct DfNet {
   const float *w[kDfLayers], *b[kDfLayers];
   const float *warp_w, *warp_b, *rot_w, *rot_b, *scale_w, *scale_b;
 };
-
-__device__ __forceinline__ constexpr int df_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-__device__ __forceinline__ df16 df_zero() {
-  df16 z;
-#pragma unroll
-  for (int r = 0; r < 16; r++) z[r] = 0.f;
-  return z;
-}
-
-__device__ __forceinline__ df16 df_mfma(float a, float b, df16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 
 // head row r (0-2 warp, 3-6 rotation, 7-9 scaling) of the padded head tile; NULL for a head that is off and for the padding
 __device__ __forceinline__ const float *df_head_row(const DfNet &net, int r, bool bias) {
@@ -89,7 +77,7 @@ __device__ __forceinline__ void df_encode(float *__restrict__ eT, int64_t base, 
 // acc[o] += sum_k wr[o][k] * B[col][k], k < Kp (a multiple of 16; wr entries past K -- a multiple of 4 -- read as zero).  Lane (col,
 // half) takes k = kc + 8 half + s at step s: 16-byte reads of its weight row (A: row = lane col) and of its point's LDS row (B).
 template <int NO>
-__device__ __forceinline__ void df_gemm_rows(df16 (&acc)[NO], const float *const (&wr)[NO], int K, int Kp, const float *__restrict__ B,
+__device__ __forceinline__ void df_gemm_rows(acc16 (&acc)[NO], const float *const (&wr)[NO], int K, int Kp, const float *__restrict__ B,
                                              int bs, int col, int half) {
   const float *brow = B + col * bs + 8 * half;
   for (int kc = 0; kc < Kp; kc += 16) {
@@ -103,14 +91,14 @@ __device__ __forceinline__ void df_gemm_rows(df16 (&acc)[NO], const float *const
       const float4 a1 = (wr[o] && k + 4 < K) ? *reinterpret_cast<const float4 *>(wr[o] + k + 4) : z;
       const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
 #pragma unroll
-      for (int s = 0; s < 8; s++) acc[o] = df_mfma(a[s], b[s], acc[o]);
+      for (int s = 0; s < 8; s++) acc[o] = mfma(a[s], b[s], acc[o]);
     }
   }
 }
 
 // transposed: acc[o] += sum_n wc[o][n * ldw] * B[col][n], n < 256 (wc = a weight COLUMN, NULL reads zero)
 template <int NO>
-__device__ __forceinline__ void df_gemm_cols(df16 (&acc)[NO], const float *const (&wc)[NO], int ldw, const float *__restrict__ B, int bs,
+__device__ __forceinline__ void df_gemm_cols(acc16 (&acc)[NO], const float *const (&wc)[NO], int ldw, const float *__restrict__ B, int bs,
                                              int col, int half) {
   const float *brow = B + col * bs + 8 * half;
   for (int kc = 0; kc < kDfW; kc += 16) {
@@ -123,13 +111,13 @@ __device__ __forceinline__ void df_gemm_cols(df16 (&acc)[NO], const float *const
 #pragma unroll
       for (int s = 0; s < 8; s++) a[s] = wc[o] ? wc[o][(n + s) * ldw] : 0.f;
 #pragma unroll
-      for (int s = 0; s < 8; s++) acc[o] = df_mfma(a[s], b[s], acc[o]);
+      for (int s = 0; s < 8; s++) acc[o] = mfma(a[s], b[s], acc[o]);
     }
   }
 }
 
-// D tile (rows nb + df_row(r, half), column = point col) -> dst[col * stride + row]: four consecutive rows per register group
-__device__ __forceinline__ void df_store_tile(float *__restrict__ dst, int stride, int nb, int col, int half, const df16 &v) {
+// D tile (rows nb + d_row(r, half), column = point col) -> dst[col * stride + row]: four consecutive rows per register group
+__device__ __forceinline__ void df_store_tile(float *__restrict__ dst, int stride, int nb, int col, int half, const acc16 &v) {
 #pragma unroll
   for (int q = 0; q < 4; q++)
     *reinterpret_cast<float4 *>(dst + (int64_t)col * stride + nb + 8 * q + 4 * half) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
@@ -143,13 +131,13 @@ __device__ __forceinline__ void df_hidden(const DfNet &net, const float *__restr
   using S = DfShape<E>;
   for (int i = 0; i < kDfLayers; i++) {
     const int ldw = i == 0 ? S::K0 : (i == kDfSkip ? S::K0 + kDfW : kDfW);
-    df16 acc[2];
+    acc16 acc[2];
     const float *wr[2];
 #pragma unroll
     for (int o = 0; o < 2; o++) {
       const int nb = 64 * wave + 32 * o;
 #pragma unroll
-      for (int r = 0; r < 16; r++) acc[o][r] = net.b[i][nb + df_row(r, half)];
+      for (int r = 0; r < 16; r++) acc[o][r] = net.b[i][nb + d_row(r, half)];
       wr[o] = net.w[i] + (int64_t)(nb + col) * ldw;
     }
     if (i == 0 || i == kDfSkip) df_gemm_rows<2>(acc, wr, S::K0, S::K0P, eT, S::SE, col, half);
@@ -170,7 +158,7 @@ __device__ __forceinline__ void df_hidden(const DfNet &net, const float *__restr
 #pragma unroll
         for (int r = 0; r < 16; r++) {
           const uint64_t bits = __ballot(acc[o][r] > 0.f);
-          if (col == 0) masks[i * kDfW + nb + df_row(r, half)] = half ? (uint32_t)(bits >> 32) : (uint32_t)bits;
+          if (col == 0) masks[i * kDfW + nb + d_row(r, half)] = half ? (uint32_t)(bits >> 32) : (uint32_t)bits;
         }
       }
     }
@@ -191,10 +179,10 @@ __global__ __launch_bounds__(kDfBlock) void deform_fwd_kernel(int64_t N, const f
   __syncthreads();
   df_hidden<E, false>(net, eT, hT, nullptr, nullptr, 0, 0, wave, col, half);
   if (wave != 0) return;
-  df16 acc[1];
+  acc16 acc[1];
 #pragma unroll
   for (int r = 0; r < 16; r++) {
-    const float *bp = df_head_row(net, df_row(r, half), true);
+    const float *bp = df_head_row(net, d_row(r, half), true);
     acc[0][r] = bp ? *bp : 0.f;
   }
   const float *wr[1] = {df_head_row(net, col, false)};
@@ -203,7 +191,7 @@ __global__ __launch_bounds__(kDfBlock) void deform_fwd_kernel(int64_t N, const f
   if (g >= N) return;
 #pragma unroll
   for (int r = 0; r < 8; r++) {   // rows 0-3 / 8-11 (half 0), 4-7 / 12-15 (half 1)
-    const int row = df_row(r, half);
+    const int row = d_row(r, half);
     if (row < 3) d_xyz[g * 3 + row] = acc[0][r];
     else if (row < 7) { if (rot) rot[g * 4 + row - 3] = acc[0][r]; }
     else if (row < 10) { if (scale) scale[g * 3 + row - 7] = acc[0][r]; }
@@ -262,26 +250,26 @@ __global__ __launch_bounds__(kDfBlock) void deform_bwd_data_kernel(int64_t N, in
 #pragma unroll
   for (int o = 0; o < 2; o++) {
     const int nb = 64 * wave + 32 * o;
-    df16 acc = df_zero();
+    acc16 acc = zero16();
 #pragma unroll
     for (int s = 0; s < 8; s++) {
       const float *hw = df_head_row(net, 8 * half + s, false);
-      acc = df_mfma(hw ? hw[nb + col] : 0.f, gT[col * kDfGS + 8 * half + s], acc);
+      acc = mfma(hw ? hw[nb + col] : 0.f, gT[col * kDfGS + 8 * half + s], acc);
     }
 #pragma unroll
-    for (int r = 0; r < 16; r++) acc[r] = ((masks[(kDfLayers - 1) * kDfW + nb + df_row(r, half)] >> col) & 1u) ? acc[r] : 0.f;
+    for (int r = 0; r < 16; r++) acc[r] = ((masks[(kDfLayers - 1) * kDfW + nb + d_row(r, half)] >> col) & 1u) ? acc[r] : 0.f;
     df_store_tile(hT, kDfSH, nb, col, half, acc);
     df_store_tile(st.dz + (int64_t)(kDfLayers - 1) * C * kDfW + lrow * kDfW, kDfW, nb, col, half, acc);
   }
   __syncthreads();
 
   // layers 7 .. 1: da_{i-1} = W_i^T dz_i (the h columns), dz_{i-1} = da_{i-1} * relu'(a_{i-1}); layer 5 and layer 0 also feed the
-  // encoding rows' gradient dE (rows 32 wave + df_row, K0 valid)
-  df16 dE[1] = {df_zero()};
+  // encoding rows' gradient dE (rows 32 wave + d_row, K0 valid)
+  acc16 dE[1] = {zero16()};
   const int me = 32 * wave + col;
   for (int i = kDfLayers - 1; i >= 1; i--) {
     const int ldw = i == kDfSkip ? S::K0 + kDfW : kDfW, c0 = i == kDfSkip ? S::K0 : 0;
-    df16 acc[2] = {df_zero(), df_zero()};
+    acc16 acc[2] = {zero16(), zero16()};
     const float *wc[2] = {net.w[i] + c0 + 64 * wave + col, net.w[i] + c0 + 64 * wave + 32 + col};
     df_gemm_cols<2>(acc, wc, ldw, hT, kDfSH, col, half);
     if (i == kDfSkip) {
@@ -293,7 +281,7 @@ __global__ __launch_bounds__(kDfBlock) void deform_bwd_data_kernel(int64_t N, in
     for (int o = 0; o < 2; o++) {
       const int nb = 64 * wave + 32 * o;
 #pragma unroll
-      for (int r = 0; r < 16; r++) acc[o][r] = ((masks[(i - 1) * kDfW + nb + df_row(r, half)] >> col) & 1u) ? acc[o][r] : 0.f;
+      for (int r = 0; r < 16; r++) acc[o][r] = ((masks[(i - 1) * kDfW + nb + d_row(r, half)] >> col) & 1u) ? acc[o][r] : 0.f;
       df_store_tile(hT, kDfSH, nb, col, half, acc[o]);
       df_store_tile(st.dz + (int64_t)(i - 1) * C * kDfW + lrow * kDfW, kDfW, nb, col, half, acc[o]);
     }
@@ -366,7 +354,7 @@ __global__ __launch_bounds__(kDfBlock) void deform_wgrad_kernel(DfJobs jobs, int
   const int64_t lda = J.ldz, ldb = m < J.k1 ? J.ld1 : J.ld2;
   const int64_t per = (rows / 32 + kDfSplit - 1) / kDfSplit * 32;
   const int64_t ps = split * per, pe = ps + per < rows ? ps + per : rows;
-  df16 acc = df_zero();
+  acc16 acc = zero16();
   float bsum = 0.f;
   for (int64_t p = ps; p < pe; p += 16) {
     const int64_t pp = p + 8 * half;
@@ -378,13 +366,13 @@ __global__ __launch_bounds__(kDfBlock) void deform_wgrad_kernel(DfJobs jobs, int
     }
 #pragma unroll
     for (int s = 0; s < 8; s++) {
-      acc = df_mfma(a[s], b[s], acc);
+      acc = mfma(a[s], b[s], acc);
       bsum += a[s];
     }
   }
   float *part = partials + ((int64_t)tile * kDfSplit + split) * kDfTileFloats;
 #pragma unroll
-  for (int r = 0; r < 16; r++) part[(nl + df_row(r, half)) * 64 + ml + col] = acc[r];
+  for (int r = 0; r < 16; r++) part[(nl + d_row(r, half)) * 64 + ml + col] = acc[r];
   if (ml == 0) {
     bsum += __shfl_xor(bsum, 32);
     if (half == 0) part[64 * 64 + nl + col] = bsum;

@@ -8,7 +8,7 @@
 // (v_mfma_f32_32x32x2_f32: exact f32, an fmaf chain per output -- no reduced-precision shortcut, parity with the f32 reference):
 //
 //   * activations are kept TRANSPOSED, [neurons x 32 pixels], as MFMA D tiles (lane l: column = pixel l & 31, register r = row
-//     d_row(r, l >> 5)).  The B operand of the instruction is laid out the same way (lane l: B[k = l >> 5][j = l & 31]), and the
+//     d_row(r, l >> 5), mfma_tile.h).  The B operand of the instruction is laid out the same way (lane l: B[k = l >> 5][j = l & 31]), and the
 //     order of the k summation is free, so the D registers of one layer ARE the B operands of the next: step s consumes register
 //     s of the tile, the weights (A operand, read from an LDS image of the [out, in] matrices) follow the same k order.  Nothing
 //     moves between lanes from the feature load to the affine entries.
@@ -20,15 +20,18 @@
 //     gradients accumulate in 128 registers per lane over the whole persistent loop; every wave then writes its partial and a
 //     second kernel sums the partials (deterministic, no atomics).
 //
+// The per-pixel kernels (mlp_head_*) and the whole-image kernels (neural_image_*, the slice folded in) differ in how a tile's
+// features arrive and where their gradient goes; the head itself is one copy: forward mh_layer1_* / mh_layers23 / mh_apply_pixel,
+// backward mh_out_grad / mh_rgb_grad / mh_bwd_layers32 / mh_bwd_layer1 / mh_bwd_features / mh_store_partial.
+//
 // Register dataflow modelled lane by lane and checked against autograd on the CPU: oracle/mfma_dataflow_model.py,
 // tests/test_mlp_head_dataflow.py.  Bound: the FP32 MFMA rate (157 TFLOP/s): 2 * (64 F + 4096 + 2048) flop per pixel forward (the
 // 12-row layer is padded to 32), three times that backward (recompute + data path + weight gradients).
 #include "bds_common.h"
 #include "bilagrid_math.h"
+#include "mfma_tile.h"
 
 namespace bds {
-
-typedef float acc16 __attribute__((ext_vector_type(16)));
 
 constexpr int kMhBlock = 256;  // four waves, one per SIMD
 constexpr int kMhWaves = kMhBlock / kWave;
@@ -38,17 +41,6 @@ constexpr int kMhAff = 12;
 constexpr int kMhWStride = 68;  // row stride of the W2 / W3 images in LDS: 16-byte rows, 16 consecutive rows hit 16 distinct bank groups
 constexpr int kMhTStride = 36;  // row stride of the transposition tiles
 constexpr int kMhBufBig = kMhHid * kMhTStride, kMhBufSmall = 32 * kMhTStride;
-
-__device__ __forceinline__ constexpr int d_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-__device__ __forceinline__ acc16 zero16() {
-  acc16 z;
-#pragma unroll
-  for (int r = 0; r < 16; r++) z[r] = 0.f;
-  return z;
-}
-
-__device__ __forceinline__ acc16 mfma(float a, float b, acc16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 
 // tanh(x) = 1 - 2 / (exp(2x) + 1): saturates correctly at both ends (exp -> inf: 1, exp -> 0: -1), |error| ~ 1e-7
 __device__ __forceinline__ float tanh_fast(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * x) + 1.f); }
@@ -151,6 +143,13 @@ __device__ __forceinline__ void mh_forward_tile(const float *__restrict__ lds, i
   mh_layers23<F>(lds, col, half, h1, h2, aff);
 }
 
+// the 3x4 map applied to the pixel: lo = output channel 0 (half-0 lane) / 1 (half-1 lane), hi = channel 2 (half-0 lane)
+__device__ __forceinline__ void mh_apply_pixel(const acc16 &aff, int half, float c0, float c1, float c2, int residual, float &lo, float &hi) {
+  lo = aff[0] * c0 + aff[1] * c1 + aff[2] * c2 + aff[3];
+  hi = aff[4] * c0 + aff[5] * c1 + aff[6] * c2 + aff[7];
+  if (residual) { lo += half ? c1 : c0; hi += c2; }
+}
+
 template <int F>
 __global__ __launch_bounds__(kMhBlock) void mlp_head_fwd_kernel(int64_t P, const float *__restrict__ feats, const float *__restrict__ rgb,
                                                                const float *__restrict__ w1, const float *__restrict__ w2,
@@ -177,9 +176,8 @@ __global__ __launch_bounds__(kMhBlock) void mlp_head_fwd_kernel(int64_t P, const
     }
     if (out) {
       const float c0 = rgb[pc * 3], c1 = rgb[pc * 3 + 1], c2 = rgb[pc * 3 + 2];
-      float lo = aff[0] * c0 + aff[1] * c1 + aff[2] * c2 + aff[3];
-      float hi = aff[4] * c0 + aff[5] * c1 + aff[6] * c2 + aff[7];
-      if (residual) { lo += half ? c1 : c0; hi += c2; }
+      float lo, hi;
+      mh_apply_pixel(aff, half, c0, c1, c2, residual, lo, hi);
       out[px * 3 + half] = lo;                 // channel 0 (half 0) / 1 (half 1)
       if (half == 0) out[px * 3 + 2] = hi;
     }
@@ -224,6 +222,124 @@ __device__ __forceinline__ void mh_outer(const float *__restrict__ TU, const flo
       g[ob * NV + vb] = acc;
     }
   }
+}
+
+// ---- the backward chain, shared by the per-pixel kernel and the whole-image kernel ------------------------------------------------
+// Gradient of the output pixel (g0, g1, g2; zeros past the end) in the affine tile's layout: this lane's rows take r_lo (entries 0-3)
+// and r_hi (4-7; only the half-0 lane finishes channel 2), o = v_out (x) [rgb; 1]
+__device__ __forceinline__ void mh_out_grad(int half, float c0, float c1, float c2, float g0, float g1, float g2, float &r_lo, float &r_hi,
+                                            float (&o)[8]) {
+  r_lo = half ? g1 : g0; r_hi = half ? 0.f : g2;
+  o[0] = r_lo * c0; o[1] = r_lo * c1; o[2] = r_lo * c2; o[3] = r_lo;
+  o[4] = r_hi * c0; o[5] = r_hi * c1; o[6] = r_hi * c2; o[7] = r_hi;
+}
+
+// sum_r A[r][c] v_out[r]: each half holds part of the rows, one exchange with lane ^ 32 (every lane of the wave must call it)
+__device__ __forceinline__ void mh_rgb_grad(const acc16 &aff, float r_lo, float r_hi, float &p0, float &p1, float &p2) {
+  p0 = aff[0] * r_lo + aff[4] * r_hi; p1 = aff[1] * r_lo + aff[5] * r_hi; p2 = aff[2] * r_lo + aff[6] * r_hi;
+  p0 += __shfl_xor(p0, 32); p1 += __shfl_xor(p1, 32); p2 += __shfl_xor(p2, 32);
+}
+
+// Layers 3 and 2.  t: gradient of the 12 entries in the affine tile's layout (registers 0-7; rows 12-31 are zero); h1 / h2: the
+// recomputed hidden tiles.  On return h2 holds d_z2, h1 holds d_z1 and g3 / g2 have taken the tile's weight gradients.
+// (col, half) are derived here and in mh_bwd_features, not passed in: the compiler simplifies a function's address arithmetic
+// before it inlines it, and only with the ranges of the two in sight (col < 32, half < 2) does it form the transposed weight reads
+// below as it formed them inside the kernels.  With the two passed as plain ints the whole-image backward measured 2.5 % slower at
+// 16x16x8 / 24 features (profiles/NOTES.md).
+template <int F>
+__device__ __forceinline__ void mh_bwd_layers32(const float *__restrict__ lds, float *__restrict__ bufA, float *__restrict__ bufB,
+                                                float *__restrict__ bufS, const float (&t)[8], acc16 (&h1)[2], acc16 (&h2)[2],
+                                                acc16 (&g2)[4], acc16 (&g3)[2]) {
+  using Im = MhImage<F>;
+  const int lane = threadIdx.x % kWave, col = lane & 31, half = lane >> 5;
+  // ---- layer 3: weight gradient (d_aff x h2 over the pixels), then d_h2 = W3^T d_aff and through the tanh
+#pragma unroll
+  for (int r = 0; r < 8; r++) bufS[d_row(r, half) * kMhTStride + col] = t[r];
+  mh_store_tiles<2>(bufA, col, half, h2);
+  mh_wave_fence();
+  mh_outer<1, 2>(bufS, bufA, col, half, g3);
+  mh_wave_fence();
+#pragma unroll
+  for (int o = 0; o < 2; o++) {
+    acc16 acc = zero16();
+#pragma unroll
+    for (int s = 0; s < 8; s++) acc = mfma(lds[Im::off3 + d_row(s, half) * kMhWStride + 32 * o + col], t[s], acc);
+#pragma unroll
+    for (int r = 0; r < 16; r++) h2[o][r] = acc[r] * (1.f - h2[o][r] * h2[o][r]);  // h2 now holds d_z2
+  }
+  // ---- layer 2
+  mh_store_tiles<2>(bufA, col, half, h2);
+  mh_store_tiles<2>(bufB, col, half, h1);
+  mh_wave_fence();
+  mh_outer<2, 2>(bufA, bufB, col, half, g2);
+  mh_wave_fence();
+  acc16 d[2];
+#pragma unroll
+  for (int o = 0; o < 2; o++) {
+    acc16 acc = zero16();
+#pragma unroll
+    for (int b = 0; b < 2; b++)
+#pragma unroll
+      for (int s = 0; s < 16; s++)
+        acc = mfma(lds[Im::off2 + (32 * b + d_row(s, half)) * kMhWStride + 32 * o + col], h2[b][s], acc);
+    d[o] = acc;
+  }
+#pragma unroll
+  for (int o = 0; o < 2; o++)
+#pragma unroll
+    for (int r = 0; r < 16; r++) h1[o][r] = d[o][r] * (1.f - h1[o][r] * h1[o][r]);  // h1 now holds d_z1
+}
+
+// Layer 1's weight gradient.  The caller has stored d_z1 into bufA and its feature rows [F x 32 pixels] into bufS.
+__device__ __forceinline__ void mh_bwd_layer1(const float *__restrict__ bufA, const float *__restrict__ bufS, int col, int half,
+                                              acc16 (&g1)[2]) {
+  mh_wave_fence();
+  mh_outer<2, 1>(bufA, bufS, col, half, g1);
+  mh_wave_fence();
+}
+
+// W1^T d_z1 as a D tile: rows = features d_row(r, half), zero past F
+template <int F>
+__device__ __forceinline__ acc16 mh_bwd_features(const float *__restrict__ lds, const acc16 (&h1)[2]) {
+  using Im = MhImage<F>;
+  const int lane = threadIdx.x % kWave, col = lane & 31, half = lane >> 5;
+  acc16 acc = zero16();
+  const bool live = col < F;
+  const int cc = live ? col : 0;
+#pragma unroll
+  for (int b = 0; b < 2; b++)
+#pragma unroll
+    for (int s = 0; s < 16; s++) {
+      const float w = lds[Im::off1 + (32 * b + d_row(s, half)) * Im::S1 + cc];
+      acc = mfma(live ? w : 0.f, h1[b][s], acc);
+    }
+  return acc;
+}
+
+// this wave's weight-gradient partial, in the matrices' own [out, in] layout, [64, F] | [64, 64] | [12, 64]: register r of tile
+// (ob, vb) is G[32 ob + d_row(r, half)][32 vb + col]
+template <int F>
+__device__ __forceinline__ void mh_store_partial(float *__restrict__ partials, int wave, int col, int half, const acc16 (&g1)[2],
+                                                 const acc16 (&g2)[4], const acc16 (&g3)[2]) {
+  float *part = partials + ((int64_t)blockIdx.x * kMhWaves + wave) * (kMhHid * F + kMhHid * kMhHid + kMhAff * kMhHid);
+#pragma unroll
+  for (int ob = 0; ob < 2; ob++)
+#pragma unroll
+    for (int r = 0; r < 16; r++)
+      if (col < F) part[(32 * ob + d_row(r, half)) * F + col] = g1[ob][r];
+  part += kMhHid * F;
+#pragma unroll
+  for (int ob = 0; ob < 2; ob++)
+#pragma unroll
+    for (int vb = 0; vb < 2; vb++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) part[(32 * ob + d_row(r, half)) * kMhHid + 32 * vb + col] = g2[ob * 2 + vb][r];
+  part += kMhHid * kMhHid;
+#pragma unroll
+  for (int vb = 0; vb < 2; vb++)
+#pragma unroll
+    for (int r = 0; r < 16; r++)
+      if (d_row(r, half) < kMhAff) part[d_row(r, half) * kMhHid + 32 * vb + col] = g3[vb][r];
 }
 
 template <int F>
@@ -272,12 +388,13 @@ __global__ __launch_bounds__(kMhBlock) void mlp_head_bwd_kernel(int64_t P, const
     if (v_out) {
       const float c0 = rgb[pc * 3], c1 = rgb[pc * 3 + 1], c2 = rgb[pc * 3 + 2];
       const float g0 = on ? v_out[pc * 3] : 0.f, gg1 = on ? v_out[pc * 3 + 1] : 0.f, gg2 = on ? v_out[pc * 3 + 2] : 0.f;
-      const float r_lo = half ? gg1 : g0, r_hi = half ? 0.f : gg2;
-      t[0] += r_lo * c0; t[1] += r_lo * c1; t[2] += r_lo * c2; t[3] += r_lo;
-      t[4] += r_hi * c0; t[5] += r_hi * c1; t[6] += r_hi * c2; t[7] += r_hi;
-      if (v_rgb) {  // sum_r A[r][c] v_out[r]: each half holds part of the rows
-        float p0 = aff[0] * r_lo + aff[4] * r_hi, p1 = aff[1] * r_lo + aff[5] * r_hi, p2 = aff[2] * r_lo + aff[6] * r_hi;
-        p0 += __shfl_xor(p0, 32); p1 += __shfl_xor(p1, 32); p2 += __shfl_xor(p2, 32);
+      float r_lo, r_hi, o[8];
+      mh_out_grad(half, c0, c1, c2, g0, gg1, gg2, r_lo, r_hi, o);
+#pragma unroll
+      for (int k = 0; k < 8; k++) t[k] += o[k];
+      if (v_rgb) {
+        float p0, p1, p2;
+        mh_rgb_grad(aff, r_lo, r_hi, p0, p1, p2);
         if (on && half == 0) {
           v_rgb[px * 3] = p0 + (residual ? g0 : 0.f);
           v_rgb[px * 3 + 1] = p1 + (residual ? gg1 : 0.f);
@@ -286,62 +403,14 @@ __global__ __launch_bounds__(kMhBlock) void mlp_head_bwd_kernel(int64_t P, const
       }
     }
 
-    // ---- layer 3: weight gradient (d_aff x h2 over the pixels), then d_h2 = W3^T d_aff and through the tanh
-#pragma unroll
-    for (int r = 0; r < 8; r++) bufS[d_row(r, half) * kMhTStride + col] = t[r];
-    mh_store_tiles<2>(bufA, col, half, h2);
-    mh_wave_fence();
-    mh_outer<1, 2>(bufS, bufA, col, half, g3);
-    mh_wave_fence();
-#pragma unroll
-    for (int o = 0; o < 2; o++) {
-      acc16 acc = zero16();
-#pragma unroll
-      for (int s = 0; s < 8; s++) acc = mfma(lds[Im::off3 + d_row(s, half) * kMhWStride + 32 * o + col], t[s], acc);
-#pragma unroll
-      for (int r = 0; r < 16; r++) h2[o][r] = acc[r] * (1.f - h2[o][r] * h2[o][r]);  // h2 now holds d_z2
-    }
-    // ---- layer 2
-    mh_store_tiles<2>(bufA, col, half, h2);
-    mh_store_tiles<2>(bufB, col, half, h1);
-    mh_wave_fence();
-    mh_outer<2, 2>(bufA, bufB, col, half, g2);
-    mh_wave_fence();
-    {
-      acc16 d[2];
-#pragma unroll
-      for (int o = 0; o < 2; o++) {
-        acc16 acc = zero16();
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-          for (int s = 0; s < 16; s++)
-            acc = mfma(lds[Im::off2 + (32 * b + d_row(s, half)) * kMhWStride + 32 * o + col], h2[b][s], acc);
-        d[o] = acc;
-      }
-#pragma unroll
-      for (int o = 0; o < 2; o++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) h1[o][r] = d[o][r] * (1.f - h1[o][r] * h1[o][r]);  // h1 now holds d_z1
-    }
-    // ---- layer 1
+    mh_bwd_layers32<F>(lds, bufA, bufB, bufS, t, h1, h2, g2, g3);
+    // ---- layer 1: the feature registers go to their rows (k order of the forward: feature half * F/2 + s)
     mh_store_tiles<2>(bufA, col, half, h1);
 #pragma unroll
     for (int s = 0; s < KS1; s++) bufS[(s + KS1 * half) * kMhTStride + col] = x[s];
-    mh_wave_fence();
-    mh_outer<2, 1>(bufA, bufS, col, half, g1);
-    mh_wave_fence();
+    mh_bwd_layer1(bufA, bufS, col, half, g1);
     if (v_feats) {
-      acc16 acc = zero16();
-      const bool live = col < F;
-      const int cc = live ? col : 0;
-#pragma unroll
-      for (int b = 0; b < 2; b++)
-#pragma unroll
-        for (int s = 0; s < 16; s++) {
-          const float w = lds[Im::off1 + (32 * b + d_row(s, half)) * Im::S1 + cc];
-          acc = mfma(live ? w : 0.f, h1[b][s], acc);
-        }
+      const acc16 acc = mh_bwd_features<F>(lds, h1);
       if (on) {  // rows = features d_row(r, half): four consecutive features per register group
         float *dst = v_feats + px * F;
 #pragma unroll
@@ -351,28 +420,7 @@ __global__ __launch_bounds__(kMhBlock) void mlp_head_bwd_kernel(int64_t P, const
       }
     }
   }
-
-  // this wave's weight-gradient partial, in the matrices' own [out, in] layout: register r of tile (ob, vb) is
-  // G[32 ob + d_row(r, half)][32 vb + col]
-  float *part = partials + ((int64_t)blockIdx.x * kMhWaves + wave) * (kMhHid * F + kMhHid * kMhHid + kMhAff * kMhHid);
-#pragma unroll
-  for (int ob = 0; ob < 2; ob++)
-#pragma unroll
-    for (int r = 0; r < 16; r++)
-      if (col < F) part[(32 * ob + d_row(r, half)) * F + col] = g1[ob][r];
-  part += kMhHid * F;
-#pragma unroll
-  for (int ob = 0; ob < 2; ob++)
-#pragma unroll
-    for (int vb = 0; vb < 2; vb++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) part[(32 * ob + d_row(r, half)) * kMhHid + 32 * vb + col] = g2[ob * 2 + vb][r];
-  part += kMhHid * kMhHid;
-#pragma unroll
-  for (int vb = 0; vb < 2; vb++)
-#pragma unroll
-    for (int r = 0; r < 16; r++)
-      if (d_row(r, half) < kMhAff) part[d_row(r, half) * kMhHid + 32 * vb + col] = g3[vb][r];
+  mh_store_partial<F>(partials, wave, col, half, g1, g2, g3);
 }
 
 // sums the waves' partials in a fixed order; the three matrices are contiguous in a partial: [64, F] | [64, 64] | [12, 64].
@@ -650,9 +698,8 @@ __global__ __launch_bounds__(kMhBlock, 2) void neural_image_fwd_kernel(NiParams 
         mh_layer1_tile<F>(lds, col, half, xt, h1);
         mh_layers23<F>(lds, col, half, h1, h2, aff);
         if (!on) continue;
-        float lo = aff[0] * c0 + aff[1] * c1 + aff[2] * c2 + aff[3];
-        float hi = aff[4] * c0 + aff[5] * c1 + aff[6] * c2 + aff[7];
-        if (residual) { lo += half ? c1 : c0; hi += c2; }
+        float lo, hi;
+        mh_apply_pixel(aff, half, c0, c1, c2, residual, lo, hi);
         out[i * 3 + half] = lo;
         if (half == 0) out[i * 3 + 2] = hi;
       }
@@ -716,72 +763,19 @@ __global__ __launch_bounds__(kMhBlock) void neural_image_bwd_kernel(NiParams p, 
         mh_layers23<F>(lds, col, half, h1, h2, aff);
 
         const float g0 = on ? v_out[i * 3] : 0.f, gg1 = on ? v_out[i * 3 + 1] : 0.f, gg2 = on ? v_out[i * 3 + 2] : 0.f;
-        const float r_lo = half ? gg1 : g0, r_hi = half ? 0.f : gg2;
-        float t8[8];
-        t8[0] = r_lo * c0; t8[1] = r_lo * c1; t8[2] = r_lo * c2; t8[3] = r_lo;
-        t8[4] = r_hi * c0; t8[5] = r_hi * c1; t8[6] = r_hi * c2; t8[7] = r_hi;
-        float p0 = aff[0] * r_lo + aff[4] * r_hi, p1 = aff[1] * r_lo + aff[5] * r_hi, p2 = aff[2] * r_lo + aff[6] * r_hi;
-        p0 += __shfl_xor(p0, 32); p1 += __shfl_xor(p1, 32); p2 += __shfl_xor(p2, 32);
+        float r_lo, r_hi, t8[8], p0, p1, p2;
+        mh_out_grad(half, c0, c1, c2, g0, gg1, gg2, r_lo, r_hi, t8);
+        mh_rgb_grad(aff, r_lo, r_hi, p0, p1, p2);
 
-        // ---- layer 3
-#pragma unroll
-        for (int r = 0; r < 8; r++) bufS[d_row(r, half) * kMhTStride + col] = t8[r];
-        mh_store_tiles<2>(bufA, col, half, h2);
-        mh_wave_fence();
-        mh_outer<1, 2>(bufS, bufA, col, half, g3);
-        mh_wave_fence();
-#pragma unroll
-        for (int o = 0; o < 2; o++) {
-          acc16 acc = zero16();
-#pragma unroll
-          for (int s = 0; s < 8; s++) acc = mfma(lds[Im::off3 + d_row(s, half) * kMhWStride + 32 * o + col], t8[s], acc);
-#pragma unroll
-          for (int r = 0; r < 16; r++) h2[o][r] = acc[r] * (1.f - h2[o][r] * h2[o][r]);
-        }
-        // ---- layer 2
-        mh_store_tiles<2>(bufA, col, half, h2);
-        mh_store_tiles<2>(bufB, col, half, h1);
-        mh_wave_fence();
-        mh_outer<2, 2>(bufA, bufB, col, half, g2);
-        mh_wave_fence();
-        {
-          acc16 d[2];
-#pragma unroll
-          for (int o = 0; o < 2; o++) {
-            acc16 acc = zero16();
-#pragma unroll
-            for (int b = 0; b < 2; b++)
-#pragma unroll
-              for (int s = 0; s < 16; s++)
-                acc = mfma(lds[Im::off2 + (32 * b + d_row(s, half)) * kMhWStride + 32 * o + col], h2[b][s], acc);
-            d[o] = acc;
-          }
-#pragma unroll
-          for (int o = 0; o < 2; o++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) h1[o][r] = d[o][r] * (1.f - h1[o][r] * h1[o][r]);
-        }
+        mh_bwd_layers32<F>(lds, bufA, bufB, bufS, t8, h1, h2, g2, g3);
         // ---- layer 1: the feature tile is already in D layout
         mh_store_tiles<2>(bufA, col, half, h1);
         {
           const acc16 xs[1] = {xt};
           mh_store_tiles<1>(bufS, col, half, xs);
         }
-        mh_wave_fence();
-        mh_outer<2, 1>(bufA, bufS, col, half, g1);
-        mh_wave_fence();
-        acc16 dx = zero16();
-        {
-          const bool live = col < F;
-          const int cc = live ? col : 0;
-#pragma unroll
-          for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int s = 0; s < 16; s++) {
-              const float w = lds[Im::off1 + (32 * b + d_row(s, half)) * Im::S1 + cc];
-              dx = mfma(live ? w : 0.f, h1[b][s], dx);
-            }
-        }
+        mh_bwd_layer1(bufA, bufS, col, half, g1);
+        const acc16 dx = mh_bwd_features<F>(lds, h1);
         // ---- the slice: guidance gradient and the region's slot gradient
         const acc16 dz = ni_slice<S>(gimg, lane, half, c, fy, true);
         float vg = 0.f;
@@ -830,25 +824,7 @@ __global__ __launch_bounds__(kMhBlock) void neural_image_bwd_kernel(NiParams p, 
       }
   }
 
-  float *part = partials + ((int64_t)blockIdx.x * kMhWaves + wave) * (kMhHid * F + kMhHid * kMhHid + kMhAff * kMhHid);
-#pragma unroll
-  for (int ob = 0; ob < 2; ob++)
-#pragma unroll
-    for (int r = 0; r < 16; r++)
-      if (col < F) part[(32 * ob + d_row(r, half)) * F + col] = g1[ob][r];
-  part += kMhHid * F;
-#pragma unroll
-  for (int ob = 0; ob < 2; ob++)
-#pragma unroll
-    for (int vb = 0; vb < 2; vb++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) part[(32 * ob + d_row(r, half)) * kMhHid + 32 * vb + col] = g2[ob * 2 + vb][r];
-  part += kMhHid * kMhHid;
-#pragma unroll
-  for (int vb = 0; vb < 2; vb++)
-#pragma unroll
-    for (int r = 0; r < 16; r++)
-      if (d_row(r, half) < kMhAff) part[d_row(r, half) * kMhHid + 32 * vb + col] = g3[vb][r];
+  mh_store_partial<F>(partials, wave, col, half, g1, g2, g3);
 }
 
 inline int mh_grid_fwd(int64_t P) {

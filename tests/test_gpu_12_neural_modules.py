@@ -94,10 +94,12 @@ def _rel(a, b):
 
 
 @pytest.mark.parametrize("F", [8, 16, 24, 32])
-@pytest.mark.parametrize("P,residual", [(1, True), (31, False), (32, True), (1000, True), (70_001, False), (300_017, True)])
+@pytest.mark.parametrize("P,residual", [(1, True), (31, False), (32, True), (1000, True), (70_001, False), (300_017, True),
+                                        (1920, True), (2048, False), (2049, True)])
 def test_fused_head_equals_framework_modules(F, P, residual):
     """Forward (both outputs) and every gradient; sizes below one tile, not a multiple of the 32-pixel tile, and large enough that
-    every wave of the persistent grid owns several tiles and a partial weight gradient."""
+    every wave of the persistent grid owns several tiles and a partial weight gradient.  The last three give 60, 64 and 68 partials:
+    around the 8-deep unroll of the partials' column sum (at 60 only some of its partial lanes take the unrolled body)."""
     from bilateral_driving_amd import mlp_head
     feats, rgb, w1, w2, w3, v_out, v_aff = _head_inputs(P, F, seed=P + F)
     out, aff = mlp_head.transform_and_maps(feats, rgb, w1, w2, w3, residual=residual)
