@@ -153,6 +153,8 @@ _SIGS = {
     "bds_lidar_points_in_boxes_count": (_i, [_i64, _f, _i, _f, _f, _f, _i, _f, _f, _sz, _f]),
     "bds_lidar_points_in_boxes_emit": (_i, [_i64, _f, _i, _f, _f, _f, _f, _i, _f, _sz, _i64, _f, _f, _f]),
     "bds_lidar_depth_downsample": (_i, [_i, _i, _i, _i, _i, _f, _f, _f]),
+    "bds_pseudo_lidar_from_depth": (_i, [_i, _i, _i, _f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f]),
+    "bds_pseudo_lidar_from_points": (_i, [_i64, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f]),
     "bds_opacity_reset": (_i, [_i64, _f, _fl, _f, _f, _f]),
     "bds_cubemap_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f]),
     "bds_cubemap_bwd": (_i, [_i64, _i, _i, _i, _f, _f, _f, _f, _f]),

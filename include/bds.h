@@ -1088,6 +1088,45 @@ int bds_lidar_points_in_boxes_emit(int64_t N, const float *points, int B, const 
                                    float *rec_xyz, bds_stream_t stream);
 int bds_lidar_depth_downsample(int B, int H, int W, int Ho, int Wo, const float *in, float *out, bds_stream_t stream);
 
+/* Pseudo-lidar generation: a rendered depth map (or a cloud) turned into a simulated lidar sweep -- every pixel unprojected, moved
+ * into the lidar's frame, cropped to the sensor's box and binned into an H x W angular map of beams, the occupied beams returned in
+ * beam order.  Where several pixels (rows) fall into one beam the HIGHEST linear pixel index v*Wi + u (the highest row) wins: what
+ * the reference's numpy assignment with duplicate indices gives (the last write).  Two launches per call: an integer atomicMax of
+ * the index into winner [C,H,W] (reset to -1 by the entry, on the stream), then one workgroup per camera that ranks the occupied
+ * cells of the kept rows (row % slice == 0) in cell order and writes, at its rank r < counts[c], the winner's coordinates --
+ * recomputed by the same function, the same bits -- to points [c, r] and, with source != NULL, its index to source [c, r].  Rows at
+ * and past counts[c] are left untouched.  cap = ceil(H / slice) * W rows per camera.  No float atomics: bit-identical run to run.
+ *
+ * beams: BDS_PSEUDO_LIDAR_BEAMS doubles ON THE DEVICE, formed by the caller with the reference's own expressions:
+ *   [0] rad(45), [1] dphi = rad(90 / W), [2] theta0, [3] fov_up, [4] dtheta, [5..10] the crop x0 x1 y0 y1 z0 z1, [11] max_depth.
+ *   The angles are taken in double from the widened float32 coordinates (the reference's numpy part is float64):
+ *   d = sqrt((x x + y y) + z z), r = sqrt(x x + y y), each 1e-6 where 0; column = trunc((rad45 - asin(y / r)) / dphi) clamped to
+ *   [0, W-1] (no point is dropped: beyond +-45 degrees it lands in an edge column).
+ *   mode BDS_PSEUDO_LIDAR_VERTICAL (pto_ang_map_vertical): theta = asin(z / d), kept iff theta0 <= theta <= fov_up (theta0 =
+ *   fov_down, dtheta = (fov_up - fov_down) / H), row = trunc((theta - theta0) / dtheta) clamped to [0, H-1].
+ *   mode BDS_PSEUDO_LIDAR_CLASSIC (pto_ang_map): row = trunc((theta0 - asin(z / d)) / dtheta) clamped, no filter (theta0 = rad(2),
+ *   dtheta = rad(0.4 * 64 / H)).
+ * bds_pseudo_lidar_from_depth -- depth_map_to_lidar_points (generate_lidar/generate_lidar_from_depth.py:95-162) for the C cameras of a
+ *   frame in one call.  depth [C,Hi,Wi]; cams [C,16] float32: fx fy cx cy (after the division by downscale_when_loading) and the
+ *   [3,4] camera-to-lidar matrix inverse(lidar_to_world) @ cam_to_world, formed in double and rounded once (the reference takes two
+ *   float32 products through world coordinates).  Per pixel: valid iff d > 0 && d < max_depth (a NaN is not); xc = ((u - cx) d) / fx,
+ *   yc = ((v - cy) d) / fy, zc = d; p = M [pc;1] as ((m0 x + m1 y) + m2 z) + m3 without fused multiply-add; crop lo <= p < hi.
+ *   points [C,cap,3]; source: the linear pixel.
+ * bds_pseudo_lidar_from_points -- pto_ang_map_vertical (generate_lidar/generate_lidar_from_depth.py:42-92) and pto_ang_map /
+ *   gen_sparse_points (generate_lidar/depth2lidar.py:41-90) for a cloud [N,4] (x, y, z, intensity; FINITE, 16-byte aligned): no
+ *   unprojection and no matrix, the crop applied when crop = 1, the row is the key.  points [cap,4]: the winners' rows, copied;
+ *   winner [H,W], counts [1], source [cap] or NULL.  N = 0 gives counts = 0.
+ * Both: BDS_EINVAL before any launch for H, W or slice below 1, an unknown mode, a NULL or misaligned array that the call would read
+ * or write, C above 65535, or C*Hi*Wi, N, C*H*W or 4*C*cap above 2^31 - 257.  C = 0: nothing to do. */
+#define BDS_PSEUDO_LIDAR_BEAMS 12
+#define BDS_PSEUDO_LIDAR_VERTICAL 0
+#define BDS_PSEUDO_LIDAR_CLASSIC 1
+int bds_pseudo_lidar_from_depth(int C, int Hi, int Wi, const float *depth, const float *cams, const double *beams, int H, int W,
+                                int slice, int mode, int32_t *winner, float *points, int32_t *counts, int32_t *source,
+                                bds_stream_t stream);
+int bds_pseudo_lidar_from_points(int64_t N, const float *cloud, const double *beams, int crop, int H, int W, int slice, int mode,
+                                 int32_t *winner, float *points, int32_t *counts, int32_t *source, bds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
