@@ -132,13 +132,182 @@ static int exclusive_scan_u32(const uint32_t *in, uint32_t *out, int64_t n, uint
 }
 
 // ------------------------------------------------------------------------------------------
-// stable LSD radix pass on (uint32 key, uint32 value), digit of <= 8 bits
+// stable LSD radix passes on uint32 keys (with or without a uint32 value each)
 // ------------------------------------------------------------------------------------------
+// Four forms of one pass, chosen by the host code below:
+//   pairs,     <= 8-bit digit, scanned [digit][workgroup] histogram:  radix_hist_kernel + radix_scatter_lds_kernel
+//   keys only, <= 8-bit digit, the same histogram:                    radix_hist_kernel + radix_scatter_keys_kernel
+//   keys only, 9/10-bit digit, workgroup-major histogram + group rows: radix_hist_wide_kernel + radix_scatter_keys_wide_kernel
+//   pairs,     8-bit digit, workgroup-major + group rows, 1024-entry chunks, no LDS staging: short_hist_kernel + short_scatter_kernel
+// The steps they have in common are the device functions that follow; where the bases come from, whether the output is staged through
+// LDS and what else a kernel fuses stay in the kernels.
 constexpr int kSortBlock = 256;
 constexpr int kSortRounds = 16;
-constexpr int kSortChunk = kSortBlock * kSortRounds;  // 4096 pairs per workgroup
+constexpr int kSortChunk = kSortBlock * kSortRounds;  // 4096 entries per workgroup
 constexpr int kSortWaves = kSortBlock / kWave;
+constexpr int kGroupShift = 6;   // workgroup-major histograms: 64 workgroups per group row
 
+// Chunk histogram: h[kBins] (LDS) = digit counts of the kRounds * 256 keys from `base` on.  Holds barriers.
+template <int kBins, int kRounds>
+__device__ __forceinline__ void chunk_hist(uint32_t *h, const uint32_t *__restrict__ keys, int64_t base, int64_t n, int shift,
+                                           uint32_t mask) {
+  for (int d = threadIdx.x; d < kBins; d += kSortBlock) h[d] = 0;
+  __syncthreads();
+#pragma unroll 4
+  for (int r = 0; r < kRounds; r++) {
+    const int64_t i = base + r * kSortBlock + threadIdx.x;
+    if (i < n) atomicAdd(&h[(keys[i] >> shift) & mask], 1u);
+  }
+  __syncthreads();
+}
+
+// Each wave owns a contiguous 1 / kSortWaves of the workgroup's chunk, kRounds rounds of 64 entries from wbase on: loads them and
+// counts their digits into the wave's row of counters.  A slot past the end holds the key 0xFFFFFFFF.
+template <int kRounds, bool kVals>
+__device__ __forceinline__ void load_and_count(uint32_t *k, uint32_t *v, const uint32_t *__restrict__ keys_in,
+                                               const uint32_t *__restrict__ vals_in, int64_t wbase, int64_t n, int shift, uint32_t mask,
+                                               uint32_t *wrow) {
+  const int lane = threadIdx.x & (kWave - 1);
+#pragma unroll
+  for (int r = 0; r < kRounds; r++) {
+    const int64_t i = wbase + r * kWave + lane;
+    k[r] = 0xFFFFFFFFu;
+    if (kVals) v[r] = 0;
+    if (i < n) {
+      k[r] = keys_in[i];
+      if (kVals) v[r] = vals_in[i];
+      atomicAdd(&wrow[(k[r] >> shift) & mask], 1u);
+    }
+  }
+}
+
+// Digit d's counts per wave -> the position of each wave's first entry of that digit, from `base` on.
+template <int kBins>
+__device__ __forceinline__ void counts_to_positions(uint32_t (&wrun)[kSortWaves][kBins], int d, uint32_t base) {
+#pragma unroll
+  for (int w = 0; w < kSortWaves; w++) {
+    const uint32_t c = wrun[w][d];
+    wrun[w][d] = base;
+    base += c;
+  }
+}
+
+// One ranking round of a wave, no workgroup barrier: the lanes with the same digit find each other by ballot, take the digit's running
+// position from the wave's row and their leader advances it.  Returns the slot of this lane's entry (stable: lanes in order).
+// The read must have landed in every lane before the leader's write: hence the wait and the wave barriers, in this order.
+// kBits: the digit width where the caller has a constant (the bit loop unrolls fully), 0: `bits` at run time.
+template <int kBits = 0>
+__device__ __forceinline__ uint32_t rank_round(uint32_t d, bool on, uint32_t *wrow, int bits = kBits) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  unsigned long long peers = __ballot(on);
+  auto match_bit = [&](int b) {
+    const unsigned long long bal = __ballot((d >> b) & 1u);
+    peers &= ((d >> b) & 1u) ? bal : ~bal;
+  };
+  if constexpr (kBits > 0) {
+#pragma unroll
+    for (int b = 0; b < kBits; b++) match_bit(b);
+  } else {
+    for (int b = 0; b < bits; b++) match_bit(b);
+  }
+  const uint32_t rank = __popcll(peers & lt);
+  uint32_t pos = 0;
+  if (on) pos = wrow[d];
+  __builtin_amdgcn_s_waitcnt(0xc07f);
+  __builtin_amdgcn_wave_barrier();
+  if (on && rank == 0) wrow[d] = pos + __popcll(peers);
+  __builtin_amdgcn_wave_barrier();
+  return pos + rank;
+}
+
+// Bases from a workgroup-major histogram hist[workgroup][bins] and its group rows ghist[group][bins] (the sums of 64 workgroups'
+// rows each), bins = 256 kPer, for the kPer consecutive digits from threadIdx.x * kPer on: their entries in the whole input (total)
+// and in front of workgroup vb (below), from the <= ng group rows and the <= 63 workgroup rows of vb's own group, all L2-resident.
+// kSums independent partial sums over the workgroup rows, so that kSums loads per digit are in flight at a time (a single running sum
+// serialises the L2 latency of every row: that chain was most of short_scatter_kernel's 14 us).  kSums was tuned per caller.
+template <int kPer, int kSums>
+__device__ __forceinline__ void grouped_bases(const uint32_t *__restrict__ hist, const uint32_t *__restrict__ ghist, int vb, int nb,
+                                              uint32_t (&total)[kPer], uint32_t (&below)[kPer]) {
+  constexpr int kBins = kSortBlock * kPer;
+  const int ng = (nb + (1 << kGroupShift) - 1) >> kGroupShift, gb = vb >> kGroupShift;
+#pragma unroll
+  for (int u = 0; u < kPer; u++) { total[u] = 0; below[u] = 0; }
+  const uint32_t *gp = ghist + threadIdx.x * kPer;
+  int g = 0;
+  for (; g + 4 <= ng; g += 4) {   // (independent loads first, then the sums)
+    uint32_t c[4][kPer];
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+      for (int u = 0; u < kPer; u++) c[j][u] = gp[(int64_t)(g + j) * kBins + u];
+#pragma unroll
+    for (int u = 0; u < kPer; u++) {
+      total[u] += (c[0][u] + c[1][u]) + (c[2][u] + c[3][u]);
+      below[u] += (g < gb ? c[0][u] : 0u) + (g + 1 < gb ? c[1][u] : 0u) + (g + 2 < gb ? c[2][u] : 0u) + (g + 3 < gb ? c[3][u] : 0u);
+    }
+  }
+  for (; g < ng; g++) {
+#pragma unroll
+    for (int u = 0; u < kPer; u++) {
+      const uint32_t c = gp[(int64_t)g * kBins + u];
+      total[u] += c;
+      if (g < gb) below[u] += c;
+    }
+  }
+  const uint32_t *hp = hist + ((int64_t)gb << kGroupShift) * kBins + threadIdx.x * kPer;
+  const int nrows = vb - (gb << kGroupShift);
+  uint32_t p[kSums][kPer];
+#pragma unroll
+  for (int j = 0; j < kSums; j++)
+#pragma unroll
+    for (int u = 0; u < kPer; u++) p[j][u] = 0;
+  int r = 0;
+  for (; r + kSums <= nrows; r += kSums) {
+    uint32_t a[kSums][kPer];
+#pragma unroll
+    for (int j = 0; j < kSums; j++)
+#pragma unroll
+      for (int u = 0; u < kPer; u++) a[j][u] = hp[(int64_t)(r + j) * kBins + u];
+#pragma unroll
+    for (int j = 0; j < kSums; j++)
+#pragma unroll
+      for (int u = 0; u < kPer; u++) p[j][u] += a[j][u];
+  }
+  for (; r < nrows; r++) {
+#pragma unroll
+    for (int u = 0; u < kPer; u++) p[0][u] += hp[(int64_t)r * kBins + u];
+  }
+#pragma unroll
+  for (int u = 0; u < kPer; u++) {
+#pragma unroll
+    for (int j = 1; j < kSums; j++) p[0][u] += p[j][u];
+    below[u] += p[0][u];
+  }
+}
+
+// The chunk's entries lie in LDS ordered by digit (lk, with lv where kPairs): consecutive threads write them out, so that a digit's run
+// leaves as whole cache lines (4096 / 2^bits entries at a time) instead of the 8-entry fragments of one wave round.  Entry i of
+// digit d goes to gbase[d] + (i - dstart[d]).  Keys only: with `unpack`, an entry's value is looked up from the low bits of its key.
+template <bool kPairs>
+__device__ __forceinline__ void write_out_ordered(const uint32_t *lk, const uint32_t *lv, int cnt, int shift, uint32_t mask,
+                                                  const uint32_t *gbase, const uint32_t *dstart, uint32_t *__restrict__ keys_out,
+                                                  uint32_t *__restrict__ vals_out, const uint32_t *__restrict__ unpack,
+                                                  uint32_t rank_mask) {
+  for (int i = threadIdx.x; i < cnt; i += kSortBlock) {
+    const uint32_t kk = lk[i];
+    const uint32_t d = (kk >> shift) & mask;
+    const uint32_t g = gbase[d] + ((uint32_t)i - dstart[d]);
+    keys_out[g] = kk;
+    if (kPairs) vals_out[g] = lv[i];
+    else if (unpack) vals_out[g] = unpack[kk & rank_mask];
+  }
+}
+__device__ __forceinline__ int chunk_count(int64_t n, int64_t bbase) {
+  return (int)((n - bbase) < (int64_t)kSortChunk ? (n - bbase) : (int64_t)kSortChunk);
+}
+
+// ---- digits of <= 8 bits, bases from the scanned [digit][workgroup] histogram ----------------------------------------------------
 // n_dev (optional): the element count lives in device memory (a compaction result the host never
 // reads); the launch is sized for the host-side upper bound n_host and surplus workgroups see no elements.
 __global__ __launch_bounds__(kSortBlock) void radix_hist_kernel(const uint32_t *__restrict__ keys, int64_t n_host,
@@ -146,98 +315,52 @@ __global__ __launch_bounds__(kSortBlock) void radix_hist_kernel(const uint32_t *
                                                                uint32_t mask, int nblocks,
                                                                uint32_t *__restrict__ hist /*[256][nblocks]*/) {
   __shared__ uint32_t h[256];
-  const int64_t n = n_dev ? (int64_t)*n_dev : n_host;
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * kSortChunk;
-#pragma unroll 4
-  for (int r = 0; r < kSortRounds; r++) {
-    int64_t i = base + r * kSortBlock + threadIdx.x;
-    if (i < n) atomicAdd(&h[(keys[i] >> shift) & mask], 1u);
-  }
-  __syncthreads();
+  chunk_hist<256, kSortRounds>(h, keys, (int64_t)blockIdx.x * kSortChunk, list_length(n_host, n_dev), shift, mask);
   if (threadIdx.x <= mask) hist[(int64_t)threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
 }
 
-// Scatter with wave-private ranking: each wave owns a contiguous quarter of the workgroup's chunk and ranks it without
-// cross-wave traffic (one LDS histogram + prefix over (wave, digit), then 16 rounds with NO barriers: ballot match).
+// Scatter with wave-private ranking: one LDS histogram + prefix over (wave, digit), then 16 rounds with NO workgroup barriers.
 // Stable: position = scanned block base + elements of earlier waves + earlier rounds of this wave + rank in the round.
-// The workgroup's 4096 pairs are first ordered by digit in LDS and then
-// written out by consecutive threads: a digit's run leaves as whole cache lines (4096 / 2^bits pairs at a time)
-// instead of the 8-pair fragments of one wave round.  Pays on the long tile passes, where the scatter is write-bound.
+// The workgroup's 4096 pairs are first ordered by digit in LDS and then written out in that order (write_out_ordered).  Pays on the
+// long tile passes, where the scatter is write-bound.
 __global__ __launch_bounds__(kSortBlock) void radix_scatter_lds_kernel(
     const uint32_t *__restrict__ keys_in, const uint32_t *__restrict__ vals_in, int64_t n_host,
     const uint64_t *__restrict__ n_dev, int shift, uint32_t mask, int bits, int nblocks,
     const uint32_t *__restrict__ hist_scanned, uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out) {
-  const int64_t n = n_dev ? (int64_t)*n_dev : n_host;
+  const int64_t n = list_length(n_host, n_dev);
   const int64_t bbase = (int64_t)blockIdx.x * kSortChunk;
   if (bbase >= n) return;
   __shared__ uint32_t wrun[kSortWaves][256];  // next LOCAL position per (wave, digit)
   __shared__ uint32_t dstart[256], gbase[256];
   __shared__ uint32_t lw[kSortBlock / kWave + 1];
   __shared__ uint32_t lk[kSortChunk], lv[kSortChunk];
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+  const int tid = threadIdx.x, wv = tid / kWave;
 #pragma unroll
   for (int w = 0; w < kSortWaves; w++) wrun[w][tid] = 0;
   __syncthreads();
-  constexpr int kPerWave = kSortChunk / kSortWaves;
-  const int64_t wbase = bbase + (int64_t)wv * kPerWave;
+  const int64_t wbase = bbase + (int64_t)wv * (kSortChunk / kSortWaves);
   uint32_t k[kSortRounds], v[kSortRounds];
-#pragma unroll
-  for (int r = 0; r < kSortRounds; r++) {
-    const int64_t i = wbase + r * kWave + lane;
-    k[r] = 0xFFFFFFFFu; v[r] = 0;
-    if (i < n) {
-      k[r] = keys_in[i]; v[r] = vals_in[i];
-      atomicAdd(&wrun[wv][(k[r] >> shift) & mask], 1u);
-    }
-  }
+  load_and_count<kSortRounds, true>(k, v, keys_in, vals_in, wbase, n, shift, mask, wrun[wv]);
   __syncthreads();
   {
     uint32_t tot = 0;
 #pragma unroll
     for (int w = 0; w < kSortWaves; w++) tot += wrun[w][tid];
     uint32_t all;
-    uint32_t base = block_excl_scan(tot, all, lw);
+    const uint32_t base = block_excl_scan(tot, all, lw);
     dstart[tid] = base;
     gbase[tid] = tid <= (int)mask ? hist_scanned[(int64_t)tid * nblocks + blockIdx.x] : 0u;
-#pragma unroll
-    for (int w = 0; w < kSortWaves; w++) {
-      const uint32_t c = wrun[w][tid];
-      wrun[w][tid] = base;
-      base += c;
-    }
+    counts_to_positions(wrun, tid, base);
   }
   __syncthreads();
-  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
 #pragma unroll
   for (int r = 0; r < kSortRounds; r++) {
-    const int64_t i = wbase + r * kWave + lane;
-    const bool on = i < n;
-    const uint32_t d = (k[r] >> shift) & mask;
-    unsigned long long peers = __ballot(on);
-    for (int b = 0; b < bits; b++) {
-      const unsigned long long bal = __ballot((d >> b) & 1u);
-      peers &= ((d >> b) & 1u) ? bal : ~bal;
-    }
-    const uint32_t rank = __popcll(peers & lt);
-    uint32_t pos = 0;
-    if (on) pos = wrun[wv][d];
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-    if (on && rank == 0) wrun[wv][d] = pos + __popcll(peers);
-    __builtin_amdgcn_wave_barrier();
-    if (on) { lk[pos + rank] = k[r]; lv[pos + rank] = v[r]; }
+    const bool on = wbase + r * kWave + (tid & (kWave - 1)) < n;
+    const uint32_t slot = rank_round((k[r] >> shift) & mask, on, wrun[wv], bits);
+    if (on) { lk[slot] = k[r]; lv[slot] = v[r]; }
   }
   __syncthreads();
-  const int cnt = (int)((n - bbase) < (int64_t)kSortChunk ? (n - bbase) : (int64_t)kSortChunk);
-  for (int i = tid; i < cnt; i += kSortBlock) {
-    const uint32_t kk = lk[i];
-    const uint32_t d = (kk >> shift) & mask;
-    const uint32_t g = gbase[d] + ((uint32_t)i - dstart[d]);
-    keys_out[g] = kk;
-    vals_out[g] = lv[i];
-  }
+  write_out_ordered<true>(lk, lv, chunk_count(n, bbase), shift, mask, gbase, dstart, keys_out, vals_out, nullptr, 0u);
 }
 
 // Keys-only form of the digit-ordered scatter, for the PACKED tile lists: an entry is one 32-bit word
@@ -255,70 +378,34 @@ __global__ __launch_bounds__(kSortBlock) void radix_scatter_keys_kernel(
   __shared__ uint32_t dstart[256], gbase[256];
   __shared__ uint32_t lw[kSortBlock / kWave + 1];
   __shared__ uint32_t lk[kSortChunk];
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+  const int tid = threadIdx.x, wv = tid / kWave;
 #pragma unroll
   for (int w = 0; w < kSortWaves; w++) wrun[w][tid] = 0;
   __syncthreads();
-  constexpr int kPerWave = kSortChunk / kSortWaves;
-  const int64_t wbase = bbase + (int64_t)wv * kPerWave;
+  const int64_t wbase = bbase + (int64_t)wv * (kSortChunk / kSortWaves);
   uint32_t k[kSortRounds];
-#pragma unroll
-  for (int r = 0; r < kSortRounds; r++) {
-    const int64_t i = wbase + r * kWave + lane;
-    k[r] = 0xFFFFFFFFu;
-    if (i < n) {
-      k[r] = keys_in[i];
-      atomicAdd(&wrun[wv][(k[r] >> shift) & mask], 1u);
-    }
-  }
+  load_and_count<kSortRounds, false>(k, nullptr, keys_in, nullptr, wbase, n, shift, mask, wrun[wv]);
   __syncthreads();
   {
     uint32_t tot = 0;
 #pragma unroll
     for (int w = 0; w < kSortWaves; w++) tot += wrun[w][tid];
     uint32_t all;
-    uint32_t base = block_excl_scan(tot, all, lw);
+    const uint32_t base = block_excl_scan(tot, all, lw);
     dstart[tid] = base;
     gbase[tid] = tid <= (int)mask ? hist_scanned[(int64_t)tid * nblocks + blockIdx.x] : 0u;
-#pragma unroll
-    for (int w = 0; w < kSortWaves; w++) {
-      const uint32_t c = wrun[w][tid];
-      wrun[w][tid] = base;
-      base += c;
-    }
+    counts_to_positions(wrun, tid, base);
   }
   __syncthreads();
-  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
 #pragma unroll
   for (int r = 0; r < kSortRounds; r++) {
-    const int64_t i = wbase + r * kWave + lane;
-    const bool on = i < n;
-    const uint32_t d = (k[r] >> shift) & mask;
-    unsigned long long peers = __ballot(on);
-    for (int b = 0; b < bits; b++) {
-      const unsigned long long bal = __ballot((d >> b) & 1u);
-      peers &= ((d >> b) & 1u) ? bal : ~bal;
-    }
-    const uint32_t rank = __popcll(peers & lt);
-    uint32_t pos = 0;
-    if (on) pos = wrun[wv][d];
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-    if (on && rank == 0) wrun[wv][d] = pos + __popcll(peers);
-    __builtin_amdgcn_wave_barrier();
-    if (on) lk[pos + rank] = k[r];
+    const bool on = wbase + r * kWave + (tid & (kWave - 1)) < n;
+    const uint32_t slot = rank_round((k[r] >> shift) & mask, on, wrun[wv], bits);
+    if (on) lk[slot] = k[r];
   }
   __syncthreads();
-  const int cnt = (int)((n - bbase) < (int64_t)kSortChunk ? (n - bbase) : (int64_t)kSortChunk);
-  for (int i = tid; i < cnt; i += kSortBlock) {
-    const uint32_t kk = lk[i];
-    const uint32_t d = (kk >> shift) & mask;
-    const uint32_t g = gbase[d] + ((uint32_t)i - dstart[d]);
-    keys_out[g] = kk;
-    if (unpack) vals_out[g] = unpack[kk & rank_mask];
-  }
+  write_out_ordered<false>(lk, nullptr, chunk_count(n, bbase), shift, mask, gbase, dstart, keys_out, vals_out, unpack, rank_mask);
 }
-
 
 // ---- wide-digit form of the two kernels above, for the packed tile pass: digits of up to 10 bits (kBins = 512 / 1024) --------
 // With coarse list tiles the whole tile key is 9-10 bits (1080p, 64-px list tiles: 510 lists): ONE stable pass orders the
@@ -327,79 +414,49 @@ __global__ __launch_bounds__(kSortBlock) void radix_scatter_keys_kernel(
 // theirs to a group row (zeroed by the emission kernel in front), and a scatter workgroup derives its bases from <= ng group rows +
 // <= 63 workgroup rows (L2-resident) -- two launches per pass instead of four, which matters most where it runs: next to another
 // stream's compositor every launch of this latency-bound stage waits for wave slots (profiles/NOTES.md, round 4).
-constexpr int kWideGroupShift = 6;
-// (the kernels of the device-count tile stage are thin wrappers around *_block bodies that take their workgroup index and element
-//  count as arguments: the launch shape is not baked into the bodies.  Round 5 ran the same bodies phase by phase inside ONE
-//  persistent launch with device-wide barriers; it lost -- every barrier is an L2 write-back + invalidate per workgroup on this
-//  multi-XCD part -- and was removed again: profiles/NOTES.md)
-template <int kBins>
-struct HistWideSh { uint32_t h[kBins]; };
-template <int kBins>
-__device__ __forceinline__ void radix_hist_wide_block(HistWideSh<kBins> &sh, int vb, const uint32_t *keys, int64_t n, int shift, uint32_t mask,
-                                                      uint32_t *hist /*[nblocks][kBins]*/, uint32_t *ghist /*[ng][kBins], zeroed*/) {
-  const int64_t base = (int64_t)vb * kSortChunk;
-  if (base >= n) return;   // (rows of surplus workgroups are never read)
-  for (int d = threadIdx.x; d < kBins; d += kSortBlock) sh.h[d] = 0;
-  __syncthreads();
-#pragma unroll 4
-  for (int r = 0; r < kSortRounds; r++) {
-    const int64_t i = base + r * kSortBlock + threadIdx.x;
-    if (i < n) atomicAdd(&sh.h[(keys[i] >> shift) & mask], 1u);
-  }
-  __syncthreads();
-  for (int d = threadIdx.x; d < kBins; d += kSortBlock) {
-    const uint32_t c = sh.h[d];
-    hist[(int64_t)vb * kBins + d] = c;
-    if (c) atomicAdd(&ghist[(int64_t)(vb >> kWideGroupShift) * kBins + d], c);
-  }
-}
+// (Round 5 ran the kernels of the device-count tile stage phase by phase inside ONE persistent launch with device-wide barriers; it
+//  lost -- every barrier is an L2 write-back + invalidate per workgroup on this multi-XCD part -- and was removed again:
+//  profiles/NOTES.md)
 template <int kBins>
 __global__ __launch_bounds__(kSortBlock) void radix_hist_wide_kernel(const uint32_t *__restrict__ keys, int64_t n_host,
                                                                     const uint64_t *__restrict__ n_dev, int shift, uint32_t mask,
                                                                     uint32_t *__restrict__ hist /*[nblocks][kBins]*/,
                                                                     uint32_t *__restrict__ ghist /*[ng][kBins], zeroed*/) {
-  __shared__ HistWideSh<kBins> sh;
-  radix_hist_wide_block<kBins>(sh, (int)blockIdx.x, keys, list_length(n_host, n_dev), shift, mask, hist, ghist);
+  __shared__ uint32_t h[kBins];
+  const int64_t n = list_length(n_host, n_dev), base = (int64_t)blockIdx.x * kSortChunk;
+  if (base >= n) return;   // (rows of surplus workgroups are never read)
+  chunk_hist<kBins, kSortRounds>(h, keys, base, n, shift, mask);
+  for (int d = threadIdx.x; d < kBins; d += kSortBlock) {
+    const uint32_t c = h[d];
+    hist[(int64_t)blockIdx.x * kBins + d] = c;
+    if (c) atomicAdd(&ghist[(int64_t)(blockIdx.x >> kGroupShift) * kBins + d], c);
+  }
 }
 
 template <int kBins>
-struct ScatterWideSh {
-  uint32_t wrun[kSortWaves][kBins];
-  uint32_t dstart[kBins], gbase[kBins];
-  uint32_t lw[kSortBlock / kWave + 1];
-  uint32_t lk[kSortChunk];
-};
-template <int kBins>
-__device__ __forceinline__ void radix_scatter_keys_wide_block(
-    ScatterWideSh<kBins> &sh, int vb, const uint32_t *keys_in, int64_t n, int shift, uint32_t mask, int bits, const uint32_t *hist,
-    const uint32_t *ghist, uint32_t *keys_out, const uint32_t *unpack, uint32_t rank_mask, uint32_t *vals_out, int32_t *offsets_out,
+__global__ __launch_bounds__(kSortBlock) void radix_scatter_keys_wide_kernel(
+    const uint32_t *__restrict__ keys_in, int64_t n_host, const uint64_t *__restrict__ n_dev, int shift, uint32_t mask, int bits,
+    const uint32_t *__restrict__ hist, const uint32_t *__restrict__ ghist, uint32_t *__restrict__ keys_out,
+    const uint32_t *__restrict__ unpack, uint32_t rank_mask, uint32_t *__restrict__ vals_out, int32_t *__restrict__ offsets_out,
     int n_offsets) {
   constexpr int kPer = kBins / kSortBlock;   // digits per thread (consecutive: thread t owns [t * kPer, (t + 1) * kPer))
+  const int64_t n = list_length(n_host, n_dev);
+  const int vb = (int)blockIdx.x;
   const int64_t bbase = (int64_t)vb * kSortChunk;
   if (bbase >= n && !(offsets_out && vb == 0)) return;   // (an empty list still owes its per-tile offsets: all zero)
-  auto &wrun = sh.wrun;
-  auto &dstart = sh.dstart;
-  auto &gbase = sh.gbase;
-  auto &lk = sh.lk;
-  uint32_t *lw = sh.lw;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+  __shared__ uint32_t wrun[kSortWaves][kBins];
+  __shared__ uint32_t dstart[kBins], gbase[kBins];
+  __shared__ uint32_t lw[kSortBlock / kWave + 1];
+  __shared__ uint32_t lk[kSortChunk];
+  const int tid = threadIdx.x, wv = tid / kWave;
   for (int d = tid; d < kBins; d += kSortBlock) {
 #pragma unroll
     for (int w = 0; w < kSortWaves; w++) wrun[w][d] = 0;
   }
   __syncthreads();
-  constexpr int kPerWave = kSortChunk / kSortWaves;
-  const int64_t wbase = bbase + (int64_t)wv * kPerWave;
+  const int64_t wbase = bbase + (int64_t)wv * (kSortChunk / kSortWaves);
   uint32_t k[kSortRounds];
-#pragma unroll
-  for (int r = 0; r < kSortRounds; r++) {
-    const int64_t i = wbase + r * kWave + lane;
-    k[r] = 0xFFFFFFFFu;
-    if (i < n) {
-      k[r] = keys_in[i];
-      atomicAdd(&wrun[wv][(k[r] >> shift) & mask], 1u);
-    }
-  }
+  load_and_count<kSortRounds, false>(k, nullptr, keys_in, nullptr, wbase, n, shift, mask, wrun[wv]);
   __syncthreads();
   {
     uint32_t tot[kPer], sum = 0;
@@ -411,41 +468,8 @@ __device__ __forceinline__ void radix_scatter_keys_wide_block(
       for (int w = 0; w < kSortWaves; w++) tot[u] += wrun[w][d];
       sum += tot[u];
     }
-    // this thread's digits in the whole input (gt) and in front of this workgroup (below): group rows, then the <= 63 workgroup rows
-    // of its own group (independent partial sums: several loads in flight)
     uint32_t gt[kPer], below[kPer];
-#pragma unroll
-    for (int u = 0; u < kPer; u++) { gt[u] = 0; below[u] = 0; }
-    {
-      const int nb = (int)((n + kSortChunk - 1) / kSortChunk), ng = (nb + (1 << kWideGroupShift) - 1) >> kWideGroupShift;
-      const int gb = vb >> kWideGroupShift;
-      for (int g = 0; g < ng; g++) {
-        const uint32_t *q = ghist + (int64_t)g * kBins + tid * kPer;
-#pragma unroll
-        for (int u = 0; u < kPer; u++) {
-          const uint32_t c = q[u];
-          gt[u] += c;
-          if (g < gb) below[u] += c;
-        }
-      }
-      const uint32_t *hp = hist + ((int64_t)gb << kWideGroupShift) * kBins + tid * kPer;
-      const int nrows = vb - (gb << kWideGroupShift);
-      uint32_t p0[kPer], p1[kPer], p2[kPer], p3[kPer];
-#pragma unroll
-      for (int u = 0; u < kPer; u++) { p0[u] = 0; p1[u] = 0; p2[u] = 0; p3[u] = 0; }
-      int r = 0;
-      for (; r + 4 <= nrows; r += 4) {
-        const uint32_t *q = hp + (int64_t)r * kBins;
-#pragma unroll
-        for (int u = 0; u < kPer; u++) { p0[u] += q[u]; p1[u] += q[kBins + u]; p2[u] += q[2 * kBins + u]; p3[u] += q[3 * kBins + u]; }
-      }
-      for (; r < nrows; r++) {
-#pragma unroll
-        for (int u = 0; u < kPer; u++) p0[u] += hp[(int64_t)r * kBins + u];
-      }
-#pragma unroll
-      for (int u = 0; u < kPer; u++) below[u] += (p0[u] + p1[u]) + (p2[u] + p3[u]);
-    }
+    grouped_bases<kPer, 4>(hist, ghist, vb, (int)((n + kSortChunk - 1) / kSortChunk), gt, below);
     uint32_t gsum = 0;
 #pragma unroll
     for (int u = 0; u < kPer; u++) gsum += gt[u];
@@ -460,56 +484,19 @@ __device__ __forceinline__ void radix_scatter_keys_wide_block(
       dbase += gt[u];
       // when this pass covers the whole tile key, the first workgroup's bases ARE the per-tile offsets (entries with a smaller key)
       if (offsets_out && vb == 0 && d < n_offsets) offsets_out[d] = (int32_t)gbase[d];
-      uint32_t b2 = base;
-#pragma unroll
-      for (int w = 0; w < kSortWaves; w++) {
-        const uint32_t c = wrun[w][d];
-        wrun[w][d] = b2;
-        b2 += c;
-      }
+      counts_to_positions(wrun, d, base);
       base += tot[u];
     }
   }
   __syncthreads();
-  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
 #pragma unroll
   for (int r = 0; r < kSortRounds; r++) {
-    const int64_t i = wbase + r * kWave + lane;
-    const bool on = i < n;
-    const uint32_t d = (k[r] >> shift) & mask;
-    unsigned long long peers = __ballot(on);
-    for (int b = 0; b < bits; b++) {
-      const unsigned long long bal = __ballot((d >> b) & 1u);
-      peers &= ((d >> b) & 1u) ? bal : ~bal;
-    }
-    const uint32_t rank = __popcll(peers & lt);
-    uint32_t pos = 0;
-    if (on) pos = wrun[wv][d];
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-    if (on && rank == 0) wrun[wv][d] = pos + __popcll(peers);
-    __builtin_amdgcn_wave_barrier();
-    if (on) lk[pos + rank] = k[r];
+    const bool on = wbase + r * kWave + (tid & (kWave - 1)) < n;
+    const uint32_t slot = rank_round((k[r] >> shift) & mask, on, wrun[wv], bits);
+    if (on) lk[slot] = k[r];
   }
   __syncthreads();
-  const int cnt = (int)((n - bbase) < (int64_t)kSortChunk ? (n - bbase) : (int64_t)kSortChunk);
-  for (int i = tid; i < cnt; i += kSortBlock) {
-    const uint32_t kk = lk[i];
-    const uint32_t d = (kk >> shift) & mask;
-    const uint32_t g = gbase[d] + ((uint32_t)i - dstart[d]);
-    keys_out[g] = kk;
-    if (unpack) vals_out[g] = unpack[kk & rank_mask];
-  }
-}
-template <int kBins>
-__global__ __launch_bounds__(kSortBlock) void radix_scatter_keys_wide_kernel(
-    const uint32_t *__restrict__ keys_in, int64_t n_host, const uint64_t *__restrict__ n_dev, int shift, uint32_t mask, int bits,
-    const uint32_t *__restrict__ hist, const uint32_t *__restrict__ ghist, uint32_t *__restrict__ keys_out,
-    const uint32_t *__restrict__ unpack, uint32_t rank_mask, uint32_t *__restrict__ vals_out, int32_t *__restrict__ offsets_out,
-    int n_offsets) {
-  __shared__ ScatterWideSh<kBins> sh;
-  radix_scatter_keys_wide_block<kBins>(sh, (int)blockIdx.x, keys_in, list_length(n_host, n_dev), shift, mask, bits, hist, ghist, keys_out,
-                                       unpack, rank_mask, vals_out, offsets_out, n_offsets);
+  write_out_ordered<false>(lk, nullptr, chunk_count(n, bbase), shift, mask, gbase, dstart, keys_out, vals_out, unpack, rank_mask);
 }
 
 constexpr int kWideBits = 10;   // widest digit of the packed tile pass
@@ -517,14 +504,14 @@ constexpr int kWideBits = 10;   // widest digit of the packed tile pass
 static size_t radix_temp_elems(int64_t n, int max_bins = 256) {
   const int64_t nblocks = cdiv(n > 0 ? n : 1, kSortChunk);
   const size_t h = align_up((size_t)max_bins * nblocks, 4);
-  const size_t group_rows = max_bins > 256 ? (size_t)max_bins * (size_t)cdiv(nblocks, 1 << kWideGroupShift) : 0;   // wide passes
+  const size_t group_rows = max_bins > 256 ? (size_t)max_bins * (size_t)cdiv(nblocks, 1 << kGroupShift) : 0;   // wide passes
   const size_t behind = scan_temp_elems((int64_t)max_bins * nblocks);
   return h + (behind > group_rows ? behind : group_rows);
 }
 
 // uint32 words behind the histogram that the wide pass expects ZERO when it starts (its group rows)
 static size_t radix_wide_group_elems(int64_t n, int bits) {
-  return (size_t)(1 << bits) * (size_t)cdiv(cdiv(n > 0 ? n : 1, kSortChunk), 1 << kWideGroupShift);
+  return (size_t)(1 << bits) * (size_t)cdiv(cdiv(n > 0 ? n : 1, kSortChunk), 1 << kGroupShift);
 }
 
 static int radix_pass(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t *vout, int64_t n, int shift,
@@ -584,35 +571,17 @@ static int radix_pass_keys(const uint32_t *kin, uint32_t *kout, int64_t n, int s
 // ------------------------------------------------------------------------------------------
 // The depth sort of the visible entries is latency-bound (a few hundred thousand keys: every launch costs more
 // than the bytes it moves), so the scan of the [digit][workgroup] histogram is folded away: histograms are stored
-// workgroup-major, every 32 workgroups also add theirs to a group row (256 atomics per workgroup), and a scatter
-// workgroup derives its own bases from <= ng group rows + <= 31 workgroup rows (all L2-resident).
+// workgroup-major, every 64 workgroups also add theirs to a group row (256 atomics per workgroup), and a scatter
+// workgroup derives its own bases from <= ng group rows + <= 63 workgroup rows (all L2-resident).
 // Chunks of 1024 pairs (4 rounds per wave): a few hundred thousand keys then spread over > 256 workgroups.
 // (Measured and dropped: accumulating the NEXT digit's histogram inside the scatter, per output chunk, with global atomics -- the
 // upper bytes of fp32 depths take a handful of values, so a whole chunk hits ONE counter: 14 -> 500 us for the third pass.)
-constexpr int kGroupShift = 6;                      // 64 workgroups per group row
 constexpr int kShortRounds = 4;
 constexpr int kShortChunk = kSortBlock * kShortRounds;   // 1024
 constexpr int kChunkShift = 10;
 static_assert(kShortChunk == (1 << kChunkShift), "chunk shift");
 constexpr int64_t kShortSortMax = (int64_t)kShortChunk * 8192;   // <= 128 group rows
 
-struct ShortHistSh { uint32_t h[256]; };
-__device__ __forceinline__ void short_hist_block(ShortHistSh &sh, int vb, const uint32_t *keys, int64_t n, int shift,
-                                                 uint32_t *hist /*[nblocks][256]*/, uint32_t *ghist /*[ng][256], zeroed*/) {
-  const int64_t base = (int64_t)vb * kShortChunk;
-  if (base >= n) return;  // the launch is sized for the host-side bound
-  sh.h[threadIdx.x] = 0;
-  __syncthreads();
-#pragma unroll 4
-  for (int r = 0; r < kShortRounds; r++) {
-    const int64_t i = base + r * kSortBlock + threadIdx.x;
-    if (i < n) atomicAdd(&sh.h[(keys[i] >> shift) & 255u], 1u);
-  }
-  __syncthreads();
-  const uint32_t c = sh.h[threadIdx.x];
-  hist[(int64_t)vb * 256 + threadIdx.x] = c;
-  if (c) atomicAdd(&ghist[(int64_t)(vb >> kGroupShift) * 256 + threadIdx.x], c);
-}
 // n_cap >= 0: the launch covers n_cap entries only (device-count form: the caller's capacity); a count beyond it is an overflow the
 // host will hear about -- the entries are then left alone altogether (a partial sort would hand garbage positions downstream)
 __device__ __forceinline__ int64_t bounded_count(const uint64_t *n_dev, int64_t n_cap) {
@@ -623,113 +592,48 @@ __global__ __launch_bounds__(kSortBlock) void short_hist_kernel(const uint32_t *
                                                                const uint64_t *__restrict__ n_dev, int64_t n_cap, int shift,
                                                                uint32_t *__restrict__ hist /*[nblocks][256]*/,
                                                                uint32_t *__restrict__ ghist /*[ng][256], zeroed*/) {
-  __shared__ ShortHistSh sh;
-  short_hist_block(sh, (int)blockIdx.x, keys, bounded_count(n_dev, n_cap), shift, hist, ghist);
+  __shared__ uint32_t h[256];
+  const int64_t n = bounded_count(n_dev, n_cap), base = (int64_t)blockIdx.x * kShortChunk;
+  if (base >= n) return;  // the launch is sized for the host-side bound
+  chunk_hist<256, kShortRounds>(h, keys, base, n, shift, 255u);
+  const uint32_t c = h[threadIdx.x];
+  hist[(int64_t)blockIdx.x * 256 + threadIdx.x] = c;
+  if (c) atomicAdd(&ghist[(int64_t)(blockIdx.x >> kGroupShift) * 256 + threadIdx.x], c);
 }
 
-// wave-private ranking as in radix_scatter_lds_kernel; bases from the group / workgroup rows
-struct ShortScatterSh {
-  uint32_t wrun[kSortWaves][256];
-  uint32_t lw[kSortBlock / kWave + 1];
-};
-__device__ __forceinline__ void short_scatter_block(ShortScatterSh &sh, int vb, const uint32_t *keys_in, const uint32_t *vals_in, int64_t n,
-                                                    int shift, const uint32_t *hist, const uint32_t *ghist, uint32_t *keys_out,
-                                                    uint32_t *vals_out) {
-  if ((int64_t)vb * kShortChunk >= n) return;
-  auto &wrun = sh.wrun;
-  uint32_t *lw = sh.lw;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-#pragma unroll
-  for (int w = 0; w < kSortWaves; w++) wrun[w][tid] = 0;
-  // digit `tid`: elements of this digit in front of this workgroup, and in the whole input
-  const int nb = (int)((n + kShortChunk - 1) >> kChunkShift), ng = (nb + (1 << kGroupShift) - 1) >> kGroupShift;
-  const int gb = vb >> kGroupShift;
-  uint32_t below = 0, total = 0;
-  {
-    int g = 0;
-    for (; g + 4 <= ng; g += 4) {   // (independent loads first, then the sums: see the row loop below)
-      const uint32_t *q = ghist + (int64_t)g * 256 + tid;
-      const uint32_t c0 = q[0], c1 = q[256], c2 = q[512], c3 = q[768];
-      total += (c0 + c1) + (c2 + c3);
-      below += (g < gb ? c0 : 0u) + (g + 1 < gb ? c1 : 0u) + (g + 2 < gb ? c2 : 0u) + (g + 3 < gb ? c3 : 0u);
-    }
-    for (; g < ng; g++) {
-      const uint32_t c = ghist[(int64_t)g * 256 + tid];
-      total += c;
-      if (g < gb) below += c;
-    }
-  }
-  {
-    // up to 63 rows of the workgroup-major histogram: EIGHT independent partial sums, so that eight loads are in flight at a time
-    // (a single running sum serialises the L2 latency of every row: that chain was most of this kernel's 14 us)
-    const uint32_t *hp = hist + ((int64_t)gb << kGroupShift) * 256 + tid;
-    const int nrows = vb - (gb << kGroupShift);
-    uint32_t p0 = 0, p1 = 0, p2 = 0, p3 = 0, p4 = 0, p5 = 0, p6 = 0, p7 = 0;
-    int r = 0;
-    for (; r + 8 <= nrows; r += 8) {
-      const uint32_t *q = hp + (int64_t)r * 256;
-      const uint32_t a0 = q[0], a1 = q[256], a2 = q[512], a3 = q[768], a4 = q[1024], a5 = q[1280], a6 = q[1536], a7 = q[1792];
-      p0 += a0; p1 += a1; p2 += a2; p3 += a3; p4 += a4; p5 += a5; p6 += a6; p7 += a7;
-    }
-    for (; r < nrows; r++) p0 += hp[(int64_t)r * 256];
-    below += ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7));
-  }
-  uint32_t all;
-  const uint32_t digit_base = block_excl_scan(total, all, lw);   // (contains the barrier that publishes wrun = 0)
-  constexpr int kPerWave = kShortChunk / kSortWaves;
-  const int64_t wbase = (int64_t)vb * kShortChunk + (int64_t)wv * kPerWave;
-  uint32_t k[kShortRounds], v[kShortRounds];
-#pragma unroll
-  for (int r = 0; r < kShortRounds; r++) {
-    const int64_t i = wbase + r * kWave + lane;
-    k[r] = 0xFFFFFFFFu; v[r] = 0;
-    if (i < n) {
-      k[r] = keys_in[i]; v[r] = vals_in[i];
-      atomicAdd(&wrun[wv][(k[r] >> shift) & 255u], 1u);
-    }
-  }
-  __syncthreads();
-  {
-    uint32_t base = digit_base + below;
-#pragma unroll
-    for (int w = 0; w < kSortWaves; w++) {
-      const uint32_t c = wrun[w][tid];
-      wrun[w][tid] = base;
-      base += c;
-    }
-  }
-  __syncthreads();
-  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-#pragma unroll
-  for (int r = 0; r < kShortRounds; r++) {
-    const int64_t i = wbase + r * kWave + lane;
-    const bool on = i < n;
-    const uint32_t d = (k[r] >> shift) & 255u;
-    unsigned long long peers = __ballot(on);
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-      const unsigned long long bal = __ballot((d >> b) & 1u);
-      peers &= ((d >> b) & 1u) ? bal : ~bal;
-    }
-    const uint32_t rank = __popcll(peers & lt);
-    uint32_t pos = 0;
-    if (on) pos = wrun[wv][d];
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-    if (on && rank == 0) wrun[wv][d] = pos + __popcll(peers);
-    __builtin_amdgcn_wave_barrier();
-    if (on) {
-      keys_out[pos + rank] = k[r];
-      vals_out[pos + rank] = v[r];
-    }
-  }
-}
+// wave-private ranking as in radix_scatter_lds_kernel; bases from the group / workgroup rows; every round's pairs go straight out
 __global__ __launch_bounds__(kSortBlock) void short_scatter_kernel(
     const uint32_t *__restrict__ keys_in, const uint32_t *__restrict__ vals_in, const uint64_t *__restrict__ n_dev, int64_t n_cap,
     int shift, const uint32_t *__restrict__ hist, const uint32_t *__restrict__ ghist, uint32_t *__restrict__ keys_out,
     uint32_t *__restrict__ vals_out) {
-  __shared__ ShortScatterSh sh;
-  short_scatter_block(sh, (int)blockIdx.x, keys_in, vals_in, bounded_count(n_dev, n_cap), shift, hist, ghist, keys_out, vals_out);
+  const int64_t n = bounded_count(n_dev, n_cap);
+  const int vb = (int)blockIdx.x;
+  if ((int64_t)vb * kShortChunk >= n) return;
+  __shared__ uint32_t wrun[kSortWaves][256];
+  __shared__ uint32_t lw[kSortBlock / kWave + 1];
+  const int tid = threadIdx.x, wv = tid / kWave;
+#pragma unroll
+  for (int w = 0; w < kSortWaves; w++) wrun[w][tid] = 0;
+  // digit `tid`: elements of this digit in the whole input, and in front of this workgroup
+  uint32_t total[1], below[1];
+  grouped_bases<1, 8>(hist, ghist, vb, (int)((n + kShortChunk - 1) >> kChunkShift), total, below);
+  uint32_t all;
+  const uint32_t digit_base = block_excl_scan(total[0], all, lw);   // (contains the barrier that publishes wrun = 0)
+  const int64_t wbase = (int64_t)vb * kShortChunk + (int64_t)wv * (kShortChunk / kSortWaves);
+  uint32_t k[kShortRounds], v[kShortRounds];
+  load_and_count<kShortRounds, true>(k, v, keys_in, vals_in, wbase, n, shift, 255u, wrun[wv]);
+  __syncthreads();
+  counts_to_positions(wrun, tid, digit_base + below[0]);
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < kShortRounds; r++) {
+    const bool on = wbase + r * kWave + (tid & (kWave - 1)) < n;
+    const uint32_t slot = rank_round<8>((k[r] >> shift) & 255u, on, wrun[wv]);
+    if (on) {
+      keys_out[slot] = k[r];
+      vals_out[slot] = v[r];
+    }
+  }
 }
 
 // uint32 elements: one workgroup-major histogram + four zero-initialised group tables
@@ -794,17 +698,17 @@ __global__ __launch_bounds__(kScanBlock) void visible_reduce_kernel(int64_t CN, 
 // visible_compact: (depth bits, cam*N+g) of the visible entries in index order; the histogram of the first
 // sort digit is accumulated on the way (a tile's outputs fall into at most kSpan sort chunks).
 constexpr int kCompactSpan = kScanTile / kShortChunk + 1;   // sort chunks a tile's outputs can straddle
-struct VisCompactSh {
-  uint32_t lw[kScanBlock / kWave + 1];
-  uint32_t h[kCompactSpan][256];
-};
-__device__ __forceinline__ void visible_compact_block(VisCompactSh &sh, int vb, int nvb, int64_t CN, const int32_t *radii, const float *depths,
-                                                      const uint32_t *tile_sums, uint32_t *keys, uint32_t *vals, uint32_t *hist,
-                                                      uint32_t *ghist, uint64_t *n_vis_out, uint32_t *asc, int compact, int sums_per_tile,
-                                                      int sd) {
+__global__ __launch_bounds__(kScanBlock) void visible_compact_kernel(int64_t CN, const int32_t *__restrict__ radii,
+                                                                    const float *__restrict__ depths,
+                                                                    const uint32_t *__restrict__ tile_sums,
+                                                                    uint32_t *__restrict__ keys, uint32_t *__restrict__ vals,
+                                                                    uint32_t *__restrict__ hist, uint32_t *__restrict__ ghist,
+                                                                    uint64_t *__restrict__ n_vis_out, uint32_t *__restrict__ asc,
+                                                                    int compact, int sums_per_tile, int sd) {
   constexpr int kSpan = kCompactSpan;
-  uint32_t *lw = sh.lw;
-  auto &h = sh.h;
+  __shared__ uint32_t lw[kScanBlock / kWave + 1];
+  __shared__ uint32_t h[kSpan][256];
+  const int vb = (int)blockIdx.x, nvb = (int)gridDim.x;
   uint32_t part = 0;
   // (sums_per_tile = 8: the counts were left per 256-Gaussian workgroup by the one-view projection, bds_project_view_fwd with prep_ws)
   for (int b = threadIdx.x; b < vb * sums_per_tile; b += kScanBlock) part += tile_sums[b];
@@ -857,17 +761,6 @@ __device__ __forceinline__ void visible_compact_block(VisCompactSh &sh, int vb, 
     }
   }
   if (vb == nvb - 1 && threadIdx.x == 0) *n_vis_out = (uint64_t)my_offset + tot;
-}
-__global__ __launch_bounds__(kScanBlock) void visible_compact_kernel(int64_t CN, const int32_t *__restrict__ radii,
-                                                                    const float *__restrict__ depths,
-                                                                    const uint32_t *__restrict__ tile_sums,
-                                                                    uint32_t *__restrict__ keys, uint32_t *__restrict__ vals,
-                                                                    uint32_t *__restrict__ hist, uint32_t *__restrict__ ghist,
-                                                                    uint64_t *__restrict__ n_vis_out, uint32_t *__restrict__ asc,
-                                                                    int compact, int sums_per_tile, int sd) {
-  __shared__ VisCompactSh sh;
-  visible_compact_block(sh, (int)blockIdx.x, (int)gridDim.x, CN, radii, depths, tile_sums, keys, vals, hist, ghist, n_vis_out, asc, compact,
-                        sums_per_tile, sd);
 }
 
 // ---- row-parallel counting / emission ---------------------------------------------------------------------

@@ -29,6 +29,11 @@ MIN_OCCUPANCY = {
     "mlp_head_fwd_kernelILi24E": 2,
     "neural_image_fwd_kernelILi24ELi8ELi0ELi0E": 2,
     "neural_image_bwd_kernelILi24ELi8ELi0ELi0E": 1,     # 256 VGPRs + the weight / slot gradient accumulators in AGPRs: one wave per SIMD by design
+    "short_scatter_kernelE": 8,                         # tile stage, depth sort of the visible entries (every benchmark shape)
+    "radix_scatter_keys_wide_kernelILi512E": 5,         # ... packed tile sort in one pass, 9-bit key (LDS-bound)
+    "radix_scatter_keys_wide_kernelILi1024E": 3,        # ... 10-bit key (LDS-bound)
+    "radix_scatter_keys_kernelE": 7,                    # ... 8-bit passes of the packed tile sort
+    "radix_scatter_lds_kernelE": 4,                     # ... pairs: unpacked lists, depth sort of long inputs (LDS-bound)
 }
 
 
