@@ -184,6 +184,8 @@ __global__ __launch_bounds__(kOptBlock) void adam_step_multi_kernel(AdamMultiArg
 // of 64-byte rows (bds_common.h GradLayout).  Stepping the four tensors one after the other reads every 64-byte row FOUR times for 3 / 1
 // / 4 / 3 of its floats (512 MB of lines for 88 MB of gradients at 2 M Gaussians: the step was 230 us, 2.7 TB/s nominal); here sixteen
 // lanes take one row, each lane the element of its column's tensor: the block is read (and, consuming, cleared) once.
+// CONTRACT for the columns that belong to no tensor of the launch (another optimizer's tensors, a frozen tensor, a deferred group, the
+// five unused columns 11..15): they are never read into an update and never written -- consuming clears the members' columns only.
 constexpr int kRowParts = 4;
 struct AdamRowBlockArgs {
   float *p[kRowParts], *m[kRowParts], *v[kRowParts];
@@ -194,6 +196,9 @@ struct AdamRowBlockArgs {
 // one thread per ROW: the 64-byte gradient row as four 16-byte loads (a wave reads 4 KB contiguous), then the row's elements of each
 // tensor (consecutive threads, consecutive rows: every tensor's accesses of a wave cover one contiguous span)
 __global__ __launch_bounds__(kOptBlock) void adam_step_rowblock_kernel(int64_t N, float *__restrict__ block, AdamRowBlockArgs A) {
+  unsigned clear_mask = 0u;      // bit c: column c belongs to a tensor of this launch
+  for (int t = 0; t < kRowParts; t++)
+    if (t < A.count) clear_mask |= ((1u << A.width[t]) - 1u) << A.col0[t];
   for (int64_t row = (int64_t)blockIdx.x * kOptBlock + threadIdx.x; row < N; row += (int64_t)gridDim.x * kOptBlock) {
     float4 *g4 = reinterpret_cast<float4 *>(block + row * 16);
     const float4 q0 = g4[0], q1 = g4[1], q2 = g4[2], q3 = g4[3];
@@ -215,8 +220,16 @@ __global__ __launch_bounds__(kOptBlock) void adam_step_rowblock_kernel(int64_t N
       }
     }
     if (A.consume) {
-      const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-      g4[0] = z; g4[1] = z; g4[2] = z; g4[3] = z;
+      // only the MEMBERS' columns are cleared: the other columns of the row may be gradients of tensors that another optimizer (or a
+      // later launch, or a deferred group) still has to read, and the unused columns are nobody's to write -- both are left as they
+      // are.  A 16-byte quarter without a member column is not stored at all; in the others the row's own values go back.
+      const float4 q[4] = {q0, q1, q2, q3};
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const unsigned mq = (clear_mask >> (4 * j)) & 15u;
+        if (mq == 0u) continue;
+        g4[j] = make_float4((mq & 1u) ? 0.f : q[j].x, (mq & 2u) ? 0.f : q[j].y, (mq & 4u) ? 0.f : q[j].z, (mq & 8u) ? 0.f : q[j].w);
+      }
     }
   }
 }
@@ -331,8 +344,10 @@ extern "C" int bds_adam_step_rowblock(int64_t N, float *grad_block, int n_parts,
                                       const int64_t *steps, int consume, bds_stream_t stream) {
   BDS_REQUIRE(N >= 0 && n_parts >= 1 && n_parts <= bds::kRowParts);
   if (N == 0) return BDS_OK;
-  BDS_REQUIRE(grad_block && aligned16(grad_block) && params && exp_avgs && exp_avg_sqs && col0 && widths && lrs && beta1s && beta2s && eps &&
-              weight_decays && steps);
+  // the block's base is the start of a 64-byte row: a base that is only 16-byte aligned would make every row straddle two lines (and
+  // the address arithmetic of a caller that found the block from its columns' addresses would point before the block)
+  BDS_REQUIRE(grad_block && (reinterpret_cast<uintptr_t>(grad_block) & 63u) == 0 && params && exp_avgs && exp_avg_sqs && col0 && widths &&
+              lrs && beta1s && beta2s && eps && weight_decays && steps);
   bds::AdamRowBlockArgs A;
   A.count = n_parts; A.consume = consume;
   unsigned used = 0;

@@ -108,6 +108,9 @@ __global__ __launch_bounds__(kProjBlock) void project_bwd_kernel(
 // scales = exp(log_scales), opacities = sigmoid(logits) (models/gaussians/vanilla.py:393-394) are produced by the
 // projection itself (they are also outputs: the compositor and the backward need them), and the backward returns
 // the gradients of the RAW parameters.  A culled Gaussian reads only its radius and writes zeros.
+// CONTRACT of the dense outputs: radii, means2d, depths, conics (and opac_eff) hold zeros in every culled row; scales and opacities are
+// VALID ONLY WHERE radii > 0 -- a row culled with its whole block (block_bounds) holds zeros there, a row culled on its own exp / sigmoid
+// of its parameters -- so a consumer of all N rows masks them by the radii (fused_view.render_classes does).
 // kReduce: the launch also does the tile stage's first one (visible_reduce_kernel, csrc/tiles.hip): visible Gaussians per workgroup,
 // the sort tables and tiles_per_gauss cleared -- it reads every radius anyway.
 // kAA (rasterize_mode "antialiased", models/trainers/base.py:406): the opacity the tile stage and the compositor read is the EFFECTIVE

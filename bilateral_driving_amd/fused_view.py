@@ -896,10 +896,13 @@ def render_classes(params: Dict[str, Tensor], viewmat: Tensor, K: Tensor, width:
     out: Dict[str, Tensor] = {}
     if include_full:
         out["rgb_gaussians"], out["depth"], out["opacity"] = image(f.opac)
+    # the projection's dense scales / opacities are valid only where radii > 0 (csrc/project.hip project_view_fwd_kernel: a row culled
+    # with its whole block holds zeros, a row culled on its own the activations): a culled row's opacity is never taken from them
+    seen = (f.radii.reshape(-1) > 0).to(f.opac.dtype)
     for name, m in masks.items():
         assert m.shape == (f.N,), (name, tuple(m.shape), f.N)
         base = f.opac_row if f.aa else f.opac      # (antialiased: opacity * comp, as the reference's render_fn(mask) composites it)
-        out[name + "_rgb"], out[name + "_depth"], out[name + "_opacity"] = image(base * m.to(f.opac.dtype))
+        out[name + "_rgb"], out[name + "_depth"], out[name + "_opacity"] = image(base * m.to(f.opac.dtype) * seen)
     return out
 
 

@@ -6,9 +6,29 @@
 (models/gaussians/basics.py:162-206), so it can replace the optimiser without touching the trainer."""
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 
 from . import _lib as L
+
+
+class _Step(NamedTuple):
+    """One tensor of a multi-tensor launch (``FusedAdam._step_multi`` / ``_step_rowblock``)."""
+    p: torch.Tensor
+    grad_ptr: int
+    m: torch.Tensor
+    v: torch.Tensor
+    n: int
+    width: int          # 0: contiguous gradient; >= 1: a column range of a row block
+    grad_stride: int
+    lr: float
+    b1: float
+    b2: float
+    eps: float
+    wd: float
+    step: int
+    grad: torch.Tensor  # the tensor behind grad_ptr: alive until the launch; its storage bounds a row block
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -30,11 +50,12 @@ class FusedAdam(torch.optim.Optimizer):
         import ctypes as C
         n = len(members)
         vp = lambda vals: (C.c_void_p * n)(*vals)
-        dbl = lambda i: (C.c_double * n)(*[b[i] for b in members])
+        dbl = lambda name: (C.c_double * n)(*[getattr(b, name) for b in members])
         L.check(L.lib().bds_adam_step_rowblock(
-            n_rows, base, n, vp([b[0].data_ptr() for b in members]), vp([b[2].data_ptr() for b in members]), vp([b[3].data_ptr() for b in members]),
-            (C.c_int * n)(*[(b[1] - base) // 4 for b in members]), (C.c_int * n)(*[b[5] for b in members]), dbl(7), dbl(8), dbl(9), dbl(10), dbl(11),
-            (C.c_int64 * n)(*[b[12] for b in members]), int(self.consume_grads), L.stream()), "bds_adam_step_rowblock")
+            n_rows, base, n, vp([b.p.data_ptr() for b in members]), vp([b.m.data_ptr() for b in members]), vp([b.v.data_ptr() for b in members]),
+            (C.c_int * n)(*[(b.grad_ptr - base) // 4 for b in members]), (C.c_int * n)(*[b.width for b in members]), dbl("lr"), dbl("b1"),
+            dbl("b2"), dbl("eps"), dbl("wd"), (C.c_int64 * n)(*[b.step for b in members]), int(self.consume_grads), L.stream()),
+            "bds_adam_step_rowblock")
 
     def _step_multi(self, batch) -> None:
         import ctypes as C
@@ -42,12 +63,12 @@ class FusedAdam(torch.optim.Optimizer):
         if n == 0:
             return
         vp = lambda vals: (C.c_void_p * n)(*vals)
-        dbl = lambda i: (C.c_double * n)(*[b[i] for b in batch])
+        dbl = lambda name: (C.c_double * n)(*[getattr(b, name) for b in batch])
         L.check(L.lib().bds_adam_step_multi(
-            n, vp([b[0].data_ptr() for b in batch]), vp([b[1] for b in batch]), vp([b[2].data_ptr() for b in batch]),
-            vp([b[3].data_ptr() for b in batch]), (C.c_int64 * n)(*[b[4] for b in batch]), (C.c_int * n)(*[b[5] for b in batch]),
-            (C.c_int64 * n)(*[b[6] for b in batch]), dbl(7), dbl(8), dbl(9), dbl(10), dbl(11), (C.c_int64 * n)(*[b[12] for b in batch]),
-            int(self.consume_grads), L.stream()), "bds_adam_step_multi")
+            n, vp([b.p.data_ptr() for b in batch]), vp([b.grad_ptr for b in batch]), vp([b.m.data_ptr() for b in batch]),
+            vp([b.v.data_ptr() for b in batch]), (C.c_int64 * n)(*[b.n for b in batch]), (C.c_int * n)(*[b.width for b in batch]),
+            (C.c_int64 * n)(*[b.grad_stride for b in batch]), dbl("lr"), dbl("b1"), dbl("b2"), dbl("eps"), dbl("wd"),
+            (C.c_int64 * n)(*[b.step for b in batch]), int(self.consume_grads), L.stream()), "bds_adam_step_multi")
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -56,7 +77,7 @@ class FusedAdam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         lib, st = L.lib(), L.stream()
-        batch = []      # (p, grad address, m, v, n, width, grad stride, lr, b1, b2, eps, wd, step): tensors stepped by ONE launch
+        batch = []      # _Step entries: the tensors stepped by ONE launch
         for group in self.param_groups:
             b1, b2 = group["betas"]
             if group.get("deferred_rows"):       # (DeferredRowAdam steps these through the views' visible-id lists)
@@ -85,7 +106,7 @@ class FusedAdam(torch.optim.Optimizer):
                     # a column range of a row block (dist.FlatGradients(row_block=True)): read -- and cleared -- where it lies
                     width = 1 if gr.dim() == 1 else int(gr.shape[1])
                     if self.multi_tensor:
-                        batch.append((p, gr.data_ptr(), m, v, p.numel(), width, int(gr.stride(0)), *hyper))
+                        batch.append(_Step(p, gr.data_ptr(), m, v, p.numel(), width, int(gr.stride(0)), *hyper, gr))
                         continue
                     L.check(lib.bds_adam_step(p.shape[0], width, int(gr.stride(0)), L.ptr(p), gr.data_ptr(), L.ptr(m), L.ptr(v), *hyper,
                                               int(self.consume_grads), st), "bds_adam_step")
@@ -93,21 +114,27 @@ class FusedAdam(torch.optim.Optimizer):
                 g = p.grad.contiguous()
                 consume = self.consume_grads and g.data_ptr() == p.grad.data_ptr()     # (clearing a contiguous COPY would clear nothing)
                 if self.multi_tensor and p.numel() <= self.MULTI_MAX_ELEMS and (consume or not self.consume_grads):
-                    batch.append((p, g.data_ptr(), m, v, p.numel(), 0, 0, *hyper))      # (large tensors keep the 16-byte-vector pass)
-                    if g is not p.grad:
-                        batch[-1] = batch[-1] + (g,)     # (keep the contiguous copy alive until the launch)
+                    batch.append(_Step(p, g.data_ptr(), m, v, p.numel(), 0, 0, *hyper, g))      # (large tensors keep the 16-byte-vector pass)
                     continue
                 L.check(lib.bds_adam_step(p.numel(), 0, 0, L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), *hyper, int(consume), st), "bds_adam_step")
                 if self.consume_grads and not consume:
                     p.grad.zero_()
         # tensors whose gradients are column ranges of ONE [N,16] row block (dist.FlatGradients(row_block=True)) step together through
-        # the block, which is then read -- and cleared -- once (bds_adam_step_rowblock) instead of once per tensor
+        # the block, which is then read once (bds_adam_step_rowblock) instead of once per tensor.  The members need not cover the block:
+        # the launch reads and, consuming, clears ITS tensors' columns only -- the columns of a tensor that another optimizer holds,
+        # that is frozen for the step (.grad is None) or that sits in a ``deferred_rows`` group keep their gradients, and the unused
+        # columns are neither read into an update nor written.
         blocks = {}
         for b in batch:
-            if b[5] > 0 and b[5] <= 4 and b[6] == 16 and b[0].dim() >= 1:
-                blocks.setdefault((b[1] & ~63, b[0].shape[0]), []).append(b)
+            if 1 <= b.width <= 4 and b.grad_stride == 16 and b.p.dim() >= 1:
+                base, n_rows = b.grad_ptr & ~63, b.p.shape[0]
+                store = b.grad.untyped_storage()
+                # (the 64-byte row the column lies in starts the block only if the block itself is 64-byte aligned: a row that would
+                #  begin before the gradient's storage, or a last row that would end after it, is no row block -- bds_adam_step_multi)
+                if store.data_ptr() <= base and base + 64 * n_rows <= store.data_ptr() + store.nbytes():
+                    blocks.setdefault((base, n_rows), []).append(b)
         for (base, n_rows), members in blocks.items():
-            if 2 <= len(members) <= 4 and base % 16 == 0:
+            if 2 <= len(members) <= 4:
                 self._step_rowblock(base, n_rows, members)
                 batch = [b for b in batch if not any(b is m for m in members)]
         for k in range(0, len(batch), self.MULTI_MAX_TENSORS):

@@ -154,7 +154,8 @@ def depth_to_lidar(depths: Tensor, intrinsics: Tensor, cam_to_world: Tensor, lid
 def cloud_to_lidar(cloud: Tensor, H: int = 64, W: int = 512, slice: int = 1, mode: str = "classic", crop: Optional[Sequence[float]] = None,
                    fov=(10.0, -30.0), return_source: bool = False):
     """``cloud`` [N,4] (x, y, z, intensity) float32 on the device.  Returns ``points`` [cap,4] -- the winners' rows, copied -- and
-    ``counts`` [1] int32 (and ``source`` [cap] int32, the cloud row of each).  One read-back: the flag of the finiteness check."""
+    ``counts`` [1] int32 (and ``source`` [cap] int32, the cloud row of each) -- as in ``depth_to_lidar``, rows [0, counts[0]) are the
+    occupied beams in beam order, the rows behind them are not written.  One read-back: the flag of the finiteness check."""
     if cloud.dim() != 2 or cloud.shape[1] != 4:
         raise ValueError(f"cloud must be [N,4], got {tuple(cloud.shape)}")
     H, W, slice, cap = _sizes(H, W, slice)

@@ -657,7 +657,10 @@ int bds_adam_step(int64_t n_rows, int width, int64_t grad_stride, float *param, 
 
 /* The same update for up to four parameter tensors [N, widths[t]] whose gradients are the column ranges [col0[t], col0[t] + widths[t])
  * of ONE [N,16] row block (64-byte rows; the four small per-Gaussian gradients, see bds_project_view_bwd_list), in one launch that
- * reads -- and, consuming, clears -- every row once: stepping the four tensors one after the other reads every 64-byte row four times. */
+ * reads -- and, consuming, clears -- every row once: stepping the four tensors one after the other reads every 64-byte row four times.
+ * grad_block is the block's base and must be 64-byte aligned (BDS_EINVAL otherwise).  Columns outside the given ranges -- tensors
+ * that another optimizer steps, a frozen tensor, the unused columns -- are neither read into an update nor written: consuming clears
+ * the given column ranges only. */
 int bds_adam_step_rowblock(int64_t N, float *grad_block, int n_parts, float *const *params, float *const *exp_avgs,
                            float *const *exp_avg_sqs, const int *col0, const int *widths, const double *lrs, const double *beta1s,
                            const double *beta2s, const double *eps, const double *weight_decays, const int64_t *steps, int consume,

@@ -77,6 +77,181 @@ def test_fused_adam_reads_gradients_that_are_columns_of_a_row_block(consume):
         assert torch.equal(oa.state[x]["exp_avg_sq"], ob.state[y]["exp_avg_sq"]) and torch.equal(oa.state[x]["exp_avg"], ob.state[y]["exp_avg"])
 
 
+ROW_NAMES = ["means", "quats", "log_scales", "opacity_logits", "sh"]
+ROW_COLS = {"means": slice(0, 3), "quats": slice(4, 8), "log_scales": slice(8, 11), "opacity_logits": slice(3, 4)}
+
+
+class _RowBlockPair:
+    """The same five parameters twice: ``pa`` with contiguous gradients (the dense run: one ``torch.optim.Adam`` and one contiguous
+    ``FusedAdam``, the run the neighbouring row-block test compares with), ``pb`` with the gradients of the four small tensors as
+    columns of one ``FlatGradients(row_block=True)`` block."""
+
+    def __init__(self, N):
+        from bilateral_driving_amd.dist import FlatGradients
+        self.N = N
+        shapes = [(N, 3), (N, 4), (N, 3), (N,), (N, 16, 3)]
+        make = lambda: [torch.randn(s, generator=torch.Generator().manual_seed(7 + i)).cuda().requires_grad_(True) for i, s in enumerate(shapes)]
+        self.pt, self.pa, self.pb = make(), make(), make()
+        self.flat = FlatGradients(self.pb, sparse_rows=True, row_block=True)
+        self.views = self.flat.arena(ROW_NAMES)
+        self.block = self.flat.flat[:N * 16].view(N, 16)
+        self.gen = torch.Generator().manual_seed(1)
+        self.grads = {}
+
+    def lr(self, i):
+        return 1e-3 * (i + 1)
+
+    def dense(self, consume, skip=()):
+        from bilateral_driving_amd.optim import FusedAdam
+        groups = lambda ps: [{"params": [p], "lr": self.lr(i)} for i, p in enumerate(ps) if ROW_NAMES[i] not in skip]
+        return torch.optim.Adam(groups(self.pt), lr=0.0, eps=1e-15), FusedAdam(groups(self.pa), lr=0.0, eps=1e-15, consume_grads=consume)
+
+    def new_grads(self, frozen=()):
+        """Fresh gradients everywhere; a ``frozen`` tensor has ``.grad = None`` on both sides, but its columns of the block still hold
+        numbers (what an earlier backward left there)."""
+        for i, name in enumerate(ROW_NAMES):
+            gr = (torch.randn(self.pa[i].shape, generator=self.gen) * 0.1).cuda()
+            self.grads[name] = gr
+            self.views[name].copy_(gr)
+            live = name not in frozen
+            self.pt[i].grad = gr.clone() if live else None
+            self.pa[i].grad = gr.clone() if live else None
+            self.pb[i].grad = self.views[name] if live else None
+
+    def columns_hold(self, name):
+        return torch.equal(self.block[:, ROW_COLS[name]].reshape(self.grads[name].shape), self.grads[name])
+
+    def columns_zero(self, name):
+        return float(self.block[:, ROW_COLS[name]].abs().max()) == 0.0
+
+    def assert_equal_dense(self, ot, oa, opts_b, skip=()):
+        """Bit for bit the contiguous FusedAdam (as the neighbouring test); torch.optim.Adam at the bound of the first test of this file
+        (its addcdiv contracts the last multiply-add: not the same bits as the kernel's separate operations)."""
+        for i, name in enumerate(ROW_NAMES):
+            x, y, z = self.pa[i], self.pb[i], self.pt[i]
+            if name in skip:
+                continue
+            ob = next(o for o in opts_b if y in o.state)
+            assert torch.equal(x.detach(), y.detach()), name
+            assert torch.equal(oa.state[x]["exp_avg"], ob.state[y]["exp_avg"]) and torch.equal(oa.state[x]["exp_avg_sq"], ob.state[y]["exp_avg_sq"]), name
+            assert float(ot.state[z]["step"]) == float(ob.state[y]["step"])
+            for a, b in ((z, y), (ot.state[z]["exp_avg"], ob.state[y]["exp_avg"]), (ot.state[z]["exp_avg_sq"], ob.state[y]["exp_avg_sq"])):
+                err = float((a.detach() - b.detach()).abs().max()) / max(float(a.detach().abs().max()), 1e-30)
+                assert err < 2e-6, (name, err)
+
+
+@pytest.mark.parametrize("consume", [False, True])
+@pytest.mark.parametrize("N", [5, 5003])
+def test_row_block_shared_by_two_optimizers(N, consume):
+    """Two FusedAdam instances over ONE row block -- means + quats in the first, log_scales + opacity logits (+ sh) in the second --
+    stepped one after the other: the first launch must not clear (consume) the columns the second has yet to read.  All tensors equal
+    the dense run; after both steps of a consuming pair the block is zero, after the first alone the second's columns hold their
+    gradients."""
+    from bilateral_driving_amd.optim import FusedAdam
+    s = _RowBlockPair(N)
+    ot, oa = s.dense(consume)
+    grp = lambda idx: [{"params": [s.pb[i]], "lr": s.lr(i)} for i in idx]
+    o1 = FusedAdam(grp([0, 1]), lr=0.0, eps=1e-15, consume_grads=consume)
+    o2 = FusedAdam(grp([2, 3, 4]), lr=0.0, eps=1e-15, consume_grads=consume)
+    for it in range(5):
+        s.new_grads()
+        ot.step(); oa.step()
+        o1.step()
+        assert s.columns_hold("log_scales") and s.columns_hold("opacity_logits"), "the first optimizer touched the second's columns"
+        assert (s.columns_zero("means") and s.columns_zero("quats")) if consume else (s.columns_hold("means") and s.columns_hold("quats"))
+        o2.step()
+        if consume:
+            assert float(s.flat.flat.abs().max()) == 0.0
+        else:
+            assert all(s.columns_hold(k) for k in ROW_COLS)
+        assert float(s.block[:, 11:].abs().max()) == 0.0
+    s.assert_equal_dense(ot, oa, (o1, o2))
+
+
+@pytest.mark.parametrize("frozen", ["opacity_logits", "quats"])
+@pytest.mark.parametrize("consume", [False, True])
+@pytest.mark.parametrize("N", [5, 5003])
+def test_row_block_with_a_frozen_tensor_keeps_its_columns(N, consume, frozen):
+    """Three of the four tensors step through the block while the fourth has ``.grad = None`` for a step, as a frozen tensor has: its
+    columns are not touched (``opacity_logits`` shares its 16-byte quarter of the row with the means) and it does not move."""
+    from bilateral_driving_amd.optim import FusedAdam
+    s = _RowBlockPair(N)
+    ot, oa = s.dense(consume)
+    ob = FusedAdam([{"params": [p], "lr": s.lr(i)} for i, p in enumerate(s.pb)], lr=0.0, eps=1e-15, consume_grads=consume)
+    k = ROW_NAMES.index(frozen)
+    for it in range(5):
+        off = it in (1, 3)
+        s.new_grads(frozen=(frozen,) if off else ())
+        before = s.pb[k].detach().clone()
+        ot.step(); oa.step(); ob.step()
+        if off:
+            assert s.columns_hold(frozen), "the columns of a tensor that is no member of the launch were written"
+            assert torch.equal(s.pb[k].detach(), before)
+            s.views[frozen].zero_()                      # (whoever left them there clears them: not this optimizer)
+        if consume:
+            assert float(s.flat.flat.abs().max()) == 0.0
+    s.assert_equal_dense(ot, oa, (ob,))
+
+
+@pytest.mark.parametrize("consume", [False, True])
+@pytest.mark.parametrize("N", [5, 5003])
+def test_row_block_with_a_deferred_group_keeps_its_columns(N, consume):
+    """A group of the same block marked ``deferred_rows`` is not stepped by ``FusedAdam.step`` -- and its columns are left alone."""
+    from bilateral_driving_amd.optim import FusedAdam
+    s = _RowBlockPair(N)
+    ot, oa = s.dense(consume, skip=("log_scales",))
+    ob = FusedAdam([{"params": [p], "lr": s.lr(i), "deferred_rows": ROW_NAMES[i] == "log_scales"} for i, p in enumerate(s.pb)], lr=0.0, eps=1e-15,
+                   consume_grads=consume)
+    start = s.pb[2].detach().clone()
+    for it in range(5):
+        s.new_grads()
+        ot.step(); oa.step(); ob.step()
+        assert s.columns_hold("log_scales") and torch.equal(s.pb[2].detach(), start)
+        assert all(s.columns_zero(k) if consume else s.columns_hold(k) for k in ("means", "quats", "opacity_logits"))
+    s.assert_equal_dense(ot, oa, (ob,), skip=("log_scales",))
+
+
+@pytest.mark.parametrize("consume", [False, True])
+@pytest.mark.parametrize("N", [5, 5003])
+def test_row_block_unused_columns_are_left_as_they_were(N, consume):
+    """THE CONTRACT for the columns 11..15 of the block, which belong to no tensor: the step leaves them as they were -- they are
+    neither read into an update nor written (consuming clears the members' columns only).  Poisoned with NaNs of a known payload
+    before every step: the same bits afterwards, and every tensor equals the dense run."""
+    from bilateral_driving_amd.optim import FusedAdam
+    s = _RowBlockPair(N)
+    ot, oa = s.dense(consume)
+    ob = FusedAdam([{"params": [p], "lr": s.lr(i)} for i, p in enumerate(s.pb)], lr=0.0, eps=1e-15, consume_grads=consume)
+    poison = 0x7FC0BD5A
+    for it in range(5):
+        s.new_grads()
+        s.block[:, 11:].view(torch.int32).fill_(poison)
+        ot.step(); oa.step(); ob.step()
+        assert bool((s.block[:, 11:].view(torch.int32) == poison).all())
+        assert all(s.columns_zero(k) if consume else s.columns_hold(k) for k in ROW_COLS)
+    s.assert_equal_dense(ot, oa, (ob,))
+    for p in s.pb:
+        assert bool(torch.isfinite(p).all())
+
+
+def test_row_block_entry_refuses_a_base_that_is_not_a_row_start():
+    """bds_adam_step_rowblock takes the block's base: 64-byte aligned, or the rows would straddle lines.  Refused before any launch."""
+    import ctypes as C
+    from bilateral_driving_amd import _lib as L
+    N = 4
+    block = torch.zeros(N + 1, 16, device="cuda")
+    p, m, v = (torch.zeros(N, 3, device="cuda") for _ in range(3))
+    one = lambda t, x: (t * 1)(x)
+    args = lambda base: (N, base, 1, one(C.c_void_p, p.data_ptr()), one(C.c_void_p, m.data_ptr()), one(C.c_void_p, v.data_ptr()), one(C.c_int, 0),
+                         one(C.c_int, 3), one(C.c_double, 1e-3), one(C.c_double, 0.9), one(C.c_double, 0.999), one(C.c_double, 1e-15),
+                         one(C.c_double, 0.0), one(C.c_int64, 1), 1, L.stream())
+    assert block.data_ptr() % 64 == 0
+    for off in (16, 32, 48):
+        assert L.lib().bds_adam_step_rowblock(*args(block.data_ptr() + off)) == L.BDS_EINVAL
+    assert L.lib().bds_adam_step_rowblock(*args(block.data_ptr())) == L.BDS_OK
+    torch.cuda.synchronize()
+    assert float(p.abs().max()) == 0.0              # (a zero gradient: m = v = 0, the update is 0 / eps = 0)
+
+
 def test_fused_adam_state_layout_allows_the_reference_surgery():
     """models/gaussians/basics.py:162-206 style: replace a parameter and its state tensors by concatenated ones."""
     from bilateral_driving_amd.optim import FusedAdam
