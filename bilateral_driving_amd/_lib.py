@@ -46,6 +46,7 @@ _SIGS = {
     "bds_strerror": (C.c_char_p, [_i]),
     "bds_set_option": (_i, [_i, _i]),
     "bds_get_option": (_i, [_i]),
+    "bds_reduce12_probe": (_i, [_f, _f, _f, _f]),
     "bds_timer_create": (C.c_void_p, []),
     "bds_timer_destroy": (_i, [_f]),
     "bds_timer_mark": (_i, [_f, _f]),

@@ -26,6 +26,26 @@ extern "C" int bds_set_option(int which, int value) {
 }
 extern "C" int bds_get_option(int which) { return bds::option_get(which); }
 
+// ---- test hook: the 16- and 12-value transpose-reduces on one wave's input (include/bds.h) ----------------------------------
+namespace bds {
+__global__ __launch_bounds__(kWave) void reduce12_probe_kernel(const float *__restrict__ in, float *__restrict__ out16,
+                                                               float *__restrict__ out12) {
+  const int lane = threadIdx.x;
+  float v[16];
+#pragma unroll
+  for (int k = 0; k < 12; k++) v[k] = in[lane * 12 + k];
+  v[12] = v[13] = v[14] = v[15] = 0.f;
+  out16[lane] = butterfly_sum16(v, lane);
+  out12[lane] = butterfly_sum12(v, lane);
+}
+}  // namespace bds
+extern "C" int bds_reduce12_probe(const float *in, float *out16, float *out12, bds_stream_t stream) {
+  BDS_REQUIRE(in && out16 && out12);
+  hipLaunchKernelGGL(bds::reduce12_probe_kernel, dim3(1), dim3(bds::kWave), 0, bds::as_stream(stream), in, out16, out12);
+  BDS_LAUNCH_CHECK();
+  return BDS_OK;
+}
+
 // ---- timing marks that survive graph capture -------------------------------------------------------------------------------
 // An event recorded on a capturing stream with the plain API only orders the capture (it never holds a timestamp); recorded with
 // hipEventRecordExternal it becomes an event-record NODE of the graph and is re-recorded by every replay.  bench.py brackets the

@@ -131,6 +131,37 @@ __device__ __forceinline__ float butterfly_sum16(const float *v, int lane) {
   return w;
 }
 
+// ---- 12-value wave64 transpose-reduce ----------------------------------------------------------
+// The same tree for 12 live values in 27 VALU instructions (6 permlane32_swap + add, 3 permlane16_swap + add, row_ror:8 3 adds +
+// 1 select, half_mirror 2 adds + 1 select, 2 quad-perm adds): the 16-value form padded with four zeros spends three swaps on lanes
+// that carry only the zeros.  Every value goes through the same pairing sequence (lane ^ 32, lane ^ 16, row_ror:8, half_mirror,
+// the quad permutes), so each total is bit-identical to the 16-value form's.  On return lane l holds the wave total of value
+// k(l) = (b2 ? 2 : b3) + 3*((l >> 4) & 1) + 6*(l >> 5), identical in the four lanes of each quad; the quads with b2 & b3 duplicate
+// the b2 & !b3 ones, so the committing lanes are  (l & 3) == 0 && !(b2 & b3):  0, 4, 8, 16, 20, 24, 32, 36, 40, 48, 52, 56.
+__device__ __forceinline__ int butterfly_slot12(int lane) {
+  return ((lane >> 2) & 1 ? 2 : (lane >> 3) & 1) + 3 * ((lane >> 4) & 1) + 6 * (lane >> 5);
+}
+__device__ __forceinline__ bool butterfly_commit12(int lane) { return (lane & 3) == 0 && (lane & 12) != 12; }
+
+__device__ __forceinline__ float butterfly_sum12(const float *v, int lane) {
+  float s[6], t[3];
+#pragma unroll
+  for (int i = 0; i < 6; i++) s[i] = swap_add32(v[i], v[i + 6]);
+#pragma unroll
+  for (int i = 0; i < 3; i++) t[i] = swap_add16(s[i], s[i + 3]);
+  const bool b3 = (lane >> 3) & 1, b2 = (lane >> 2) & 1;
+  float sa = t[0] + dpp_f<0x128, 0xf, false>(t[0]);                  // row_ror:8
+  float sb = t[1] + dpp_f<0x128, 0xf, false>(t[1]);
+  const float u0 = b3 ? sb : sa;
+  const float u1 = t[2] + dpp_f<0x128, 0xf, false>(t[2]);
+  sa = u0 + dpp_f<0x141, 0xf, false>(u0);                            // row_half_mirror
+  sb = u1 + dpp_f<0x141, 0xf, false>(u1);
+  float w = b2 ? sb : sa;
+  w += dpp_f<0xB1, 0xf, false>(w);                                   // quad_perm [1,0,3,2]
+  w += dpp_f<0x4E, 0xf, false>(w);                                   // quad_perm [2,3,0,1]
+  return w;
+}
+
 // Slots of the tile stage's prepare workspace that the ONE-VIEW projection fills when it takes over the stage's first launch (the
 // count of visible Gaussians per 256-Gaussian workgroup, the tables the later launches add into): csrc/tiles.hip prep_reduce_slots.
 struct PrepReduceSlots {

@@ -398,15 +398,15 @@ __device__ __forceinline__ float wave_sum_all(float v) {
 // Neighbouring samples fall into the same grid cell (coarse grids: the whole wave), so per-lane atomics
 // would serialise 20-64 ways on one address.  Instead the wave walks its DISTINCT cells (typically 1-6):
 // for each cell and each of its 8 trilinear corners the 12 channel contributions of the member lanes are
-// summed with the 16-value transpose-reduce (35 VALU ops) and committed by 12 lanes to 12 different
+// summed with the 12-value transpose-reduce (27 VALU ops) and committed by 12 lanes to 12 different
 // addresses -- conflict-free by construction.
 __device__ __forceinline__ void slice_grid_scatter(float *acc, const Cell &c, int gx, int gy, int gl, float scale,
                                                    const float *va, bool active, int nch = 12) {
   const int lane = threadIdx.x & (kWave - 1);
   const int plane = gy * gx, vol = gl * plane;
   const int key = active ? (c.z0 * gy + c.y0) * gx + c.x0 : -1;
-  const int slot = butterfly_slot(lane);
-  const bool committer = ((lane & 3) == 0) && slot < nch;
+  const int slot = butterfly_slot12(lane);
+  const bool committer = butterfly_commit12(lane) && slot < nch;
   unsigned long long remaining = __ballot(active);
   while (remaining) {
     const int leader = __ffsll((long long)remaining) - 1;
@@ -421,11 +421,10 @@ __device__ __forceinline__ void slice_grid_scatter(float *acc, const Cell &c, in
     for (int q = 0; q < 8; q++) {
       const int base = ((q & 4) ? z1 : z0) * plane + ((q & 2) ? y1 : y0) * gx + ((q & 1) ? x1 : x0);
       const float w = member ? ((q & 4) ? c.fz : 1.f - c.fz) * ((q & 2) ? c.fy : 1.f - c.fy) * ((q & 1) ? c.fx : 1.f - c.fx) * scale : 0.f;
-      float v[16];
+      float v[12];
 #pragma unroll
       for (int ch = 0; ch < 12; ch++) v[ch] = w * va[ch];
-      v[12] = v[13] = v[14] = v[15] = 0.f;
-      const float tot = butterfly_sum16(v, lane);
+      const float tot = butterfly_sum12(v, lane);
       if (committer && tot != 0.f) atomicAdd(acc + base + slot * vol, tot);
     }
   }

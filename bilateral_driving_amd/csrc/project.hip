@@ -230,22 +230,20 @@ __global__ __launch_bounds__(kProjBlock) void project_view_fwd_kernel(
   }
 }
 
-// Block reduction of the camera-pose gradient (9 rotation + 3 translation partials per Gaussian): one 16-value
+// Block reduction of the camera-pose gradient (9 rotation + 3 translation partials per Gaussian): one 12-value
 // transpose-reduce per wave, the workgroup's waves summed through LDS, one atomic set per workgroup into one of
 // kPoseSlots replicated [4,4] accumulators (every workgroup on the same 12 addresses serialises in L2: measured +58 us
 // at 7800 workgroups); the caller sums the slots.
 constexpr int kPoseSlots = BDS_POSE_GRAD_SLOTS;
 __device__ __forceinline__ void pose_grad_reduce(const ProjGrad &pg, float (*red)[12], float *__restrict__ v_viewmat_slots) {
   const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-  float v[16];
+  float v[12];
 #pragma unroll
   for (int i = 0; i < 9; i++) v[i] = pg.v_R[i];
 #pragma unroll
   for (int i = 0; i < 3; i++) v[9 + i] = pg.v_t[i];
-  v[12] = v[13] = v[14] = v[15] = 0.f;
-  const float tot = butterfly_sum16(v, lane);
-  const int k = butterfly_slot(lane);
-  if ((lane & 3) == 0 && k < 12) red[wv][k] = tot;
+  const float tot = butterfly_sum12(v, lane);
+  if (butterfly_commit12(lane)) red[wv][butterfly_slot12(lane)] = tot;
   __syncthreads();
   if (threadIdx.x < 12) {
     float t = 0.f;

@@ -664,7 +664,7 @@ __global__ __launch_bounds__(kWave) void rasterize_fwd_split_kernel(
 // ---- backward -----------------------------------------------------------------------------------------------
 // Lane l owns column l % 16 and rows (l / 16) + 4q, q = 0..3.  The four pixels share dx, so the conic / mean gradients
 // need only three per-lane moments of d(loss)/d(sigma) (S0 = sum vs, S1 = sum vs dy, S2 = sum vs dy^2) that are expanded
-// once per (lane, Gaussian); 12 per-lane sums then go through ONE 16-value transpose-reduce and 12 lanes commit them to the
+// once per (lane, Gaussian); 12 per-lane sums then go through ONE 12-value transpose-reduce and 12 lanes commit them to the
 // Gaussian's gradient record.  The list is replayed back to front from the tile's deepest blended entry.
 // kEpi: the image gradient is not read but FORMED per pixel from the colour transform's deferred backward (ed_epilogue.h: direct route +
 // guidance route, clamp / sky blend / expected-depth backward; also writes v_sky) -- the lanes wait for their tile's first records
@@ -726,9 +726,8 @@ __device__ __forceinline__ void rasterize_bwd_wave_body(
   const int tile_bin_final = wave_max_i32(max_bin);
   if (tile_bin_final < start || end <= start) return;   // no pixel of this tile blended anything (last_ids stays 0 then)
   // gradient-record slot this lane commits after the transpose-reduce (one committing lane per quad)
-  const int slot = butterfly_slot(lane);
-  const bool commit = ((lane & 3) == 0) && (slot < 4 ? slot < CH : (slot < 12 && (ABS || (slot != 9 && slot != 10))));
-  float *const tgt = v_rec + slot;
+  const int slot = butterfly_slot12(lane);
+  const bool commit = butterfly_commit12(lane) && (slot < 4 ? slot < CH : (ABS || (slot != 9 && slot != 10)));
   const int nbatch = (end - start + kWave - 1) / kWave;
   const int b0 = (end - 1 - tile_bin_final) / kWave;  // chunks in front of it lie behind every pixel's last Gaussian
   // register prefetch of the next chunk (see the forward kernel)
@@ -829,7 +828,7 @@ __device__ __forceinline__ void rasterize_bwd_wave_body(
       // d(loss)/d(opacity) = sum vm v_alpha = -S0 / opacity (vs = -(opacity vm) v_alpha term by term): no accumulator of its own
       const float go = -S0 * __builtin_amdgcn_rcpf(opac);
       // expand the moments: d sigma / d (a, b, c) = (dx^2 / 2, dx dy, dy^2 / 2); d sigma / d mean = -ln2 * d e / d (dx, dy)
-      float acc[16];
+      float acc[12];
       acc[0] = g0; acc[1] = g1; acc[2] = g2; acc[3] = g3;
       const float dxS0 = dx * S0;
       acc[4] = 0.5f * dx * dxS0;
@@ -839,9 +838,10 @@ __device__ __forceinline__ void rasterize_bwd_wave_body(
       acc[8] = -kLn2 * __builtin_fmaf(A.w, dxS0, two_ec * S1);
       acc[9] = kLn2 * ax; acc[10] = kLn2 * ay;
       acc[11] = go;
-      acc[12] = acc[13] = acc[14] = acc[15] = 0.f;
-      const float tot = butterfly_sum16(acc, lane);
-      if (commit) atomicAdd(tgt + (int64_t)sId[t] * kGradStride, tot);
+      const float tot = butterfly_sum12(acc, lane);
+      // the Gaussian's id is wave-uniform: its record's address is formed in scalar registers, the lane adds its constant slot
+      float *const grec = v_rec + (int64_t)__builtin_amdgcn_readfirstlane(sId[t]) * kGradStride;
+      if (commit) atomicAdd(grec + slot, tot);
     }
   }
 }

@@ -64,6 +64,11 @@ const char *bds_strerror(int code);
 int bds_set_option(int which, int value);
 int bds_get_option(int which);
 
+/* Test hook (one wave, no reference counterpart): the two cross-lane transpose-reduces of csrc/bds_common.h on one input.
+ * in [64][12]: lane l's 12 values; out16 [64] / out12 [64]: what butterfly_sum16 (the values padded with four zeros) and
+ * butterfly_sum12 leave in each lane.  tests/test_gpu_48_reduce12.py compares them with its lane-by-lane model. */
+int bds_reduce12_probe(const float *in, float *out16, float *out12, bds_stream_t stream);
+
 /* Timing marks (measurement plumbing, no reference counterpart): HIP events that are recorded as event-record NODES when the
  * stream is being captured into a hipGraph, so that every replay re-records them and a kernel inside a captured view can be
  * bracketed (bench.py's roofline kernel).  bds_timer_elapsed_ms waits for `stop`; negative = not available. */
