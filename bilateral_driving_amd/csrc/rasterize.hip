@@ -393,18 +393,21 @@ __device__ __forceinline__ void rasterize_fwd_wave_body(
         const float e = splat_exponent(eadx2, ebdx, B.x, A.y - pyc[q]);
         const float ov = B.y * __builtin_amdgcn_exp2f(e);
         const float alpha = clamp_alpha(ov);
-        const bool hit = (T[q] > 0.f) & !((e > 0.f) | (ov < kAlphaMin));   // (bitwise: no short-circuit exec masking)
-        if (kStrip && !__any(hit)) continue;   // no pixel of this 16 x 4 strip blends the Gaussian
+        const bool valid = !((e > 0.f) | (ov < kAlphaMin));   // (bitwise: no short-circuit exec masking)
+        if (kStrip && !__any(valid)) continue;   // no pixel of this 16 x 4 strip reaches the Gaussian
+        // No test of T > 0: a finished pixel (T < 0) has nT = T (1 - alpha) < 0 with 1 - alpha >= 0.001, so `live` is false for it
+        // and the update below hands it -|T| = T back.  A live pixel that this Gaussian would take below the transmittance floor is
+        // finished, not blended: it gets -|T| = -T.
         const float nT = T[q] * (1.f - alpha);
-        const bool stop = hit & (nT <= kTStop);   // this Gaussian would take the pixel below the transmittance floor: finished, not blended
-        const bool blend = hit & !stop;
+        const bool live = nT > kTStop;
+        const bool blend = valid & live;
         const float vis = blend ? alpha * T[q] : 0.f;
         out[q][0] = __builtin_fmaf(B.z, vis, out[q][0]);
         if (CH > 1) out[q][1] = __builtin_fmaf(B.w, vis, out[q][1]);
         if (CH > 2) out[q][2] = __builtin_fmaf(Cc.x, vis, out[q][2]);
         if (CH > 3) out[q][3] = __builtin_fmaf(Cc.y, vis, out[q][3]);
         cur[q] = blend ? pos_t : cur[q];
-        T[q] = stop ? -T[q] : (blend ? nT : T[q]);
+        T[q] = valid ? (live ? nT : -fabsf(T[q])) : T[q];
       }
     };
     // the all-pixels-finished test runs every second entry: an entry blended against a finished tile changes nothing
@@ -746,6 +749,9 @@ __device__ __forceinline__ void rasterize_bwd_wave_body(
     __syncthreads();
     int bs = min(kWave, batch_end + 1 - start);
     int t0 = max(0, batch_end - tile_bin_final);
+    // -1 / opacity of candidate `lane`, once per staged candidate: it rides in the record's radius slot, which only the filter reads
+    // (the entry loop below would otherwise take the reciprocal of a wave-uniform value on 64 lanes for every visited pair)
+    const float nrop = -__builtin_amdgcn_rcpf(pB.y);
     if (kCoarse) {
       // survivors of this chunk (same test as the forward), compacted in replay order; entries behind the tile's deepest blended
       // one are dropped here instead of being skipped through t0
@@ -758,11 +764,12 @@ __device__ __forceinline__ void rasterize_bwd_wave_body(
       if (hit) {
         const int pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
         pC.z = __int_as_float(idx);
+        pC.w = nrop;
         sId[pos] = pg; sA[pos] = pA; sB[pos] = pB; sC[pos] = pC;
       }
     } else if (batch_end - lane >= start) {
       sId[lane] = pg; sA[lane] = pA; sB[lane] = pB;
-      if (CH > 2) sC[lane] = pC;
+      if (CH > 2) { pC.w = nrop; sC[lane] = pC; }
     }
     __syncthreads();
     {
@@ -826,7 +833,9 @@ __device__ __forceinline__ void rasterize_bwd_wave_body(
         }
       }
       // d(loss)/d(opacity) = sum vm v_alpha = -S0 / opacity (vs = -(opacity vm) v_alpha term by term): no accumulator of its own
-      const float go = -S0 * __builtin_amdgcn_rcpf(opac);
+      // (-1 / opacity was taken at staging where the entry's third record word is staged: S0 * (-r) and -S0 * r are the same float.
+      //  The 1- and 2-channel kernels over 16-px lists stage no third word and keep the reciprocal here.)
+      const float go = (CH > 2 || kCoarse) ? S0 * Cc.w : -S0 * __builtin_amdgcn_rcpf(opac);
       // expand the moments: d sigma / d (a, b, c) = (dx^2 / 2, dx dy, dy^2 / 2); d sigma / d mean = -ln2 * d e / d (dx, dy)
       float acc[12];
       acc[0] = g0; acc[1] = g1; acc[2] = g2; acc[3] = g3;
