@@ -156,6 +156,9 @@ _SIGS = {
     "bds_lidar_depth_downsample": (_i, [_i, _i, _i, _i, _i, _f, _f, _f]),
     "bds_pseudo_lidar_from_depth": (_i, [_i, _i, _i, _f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f]),
     "bds_pseudo_lidar_from_points": (_i, [_i64, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f]),
+    "bds_view_fields": (_i, [_i, _i, _i, _f, _f, _i, _fl, _f, _f] + [_f] * 9 + [_f]),
+    "bds_image_resize_aa": (_i, [_i, _i, C.c_double, _f, _f, _f]),
+    "bds_masks_resize_nearest": (_i, [_i, _i, _i, C.c_double, _f, _f, _f]),
     "bds_opacity_reset": (_i, [_i64, _f, _fl, _f, _f, _f]),
     "bds_cubemap_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f]),
     "bds_cubemap_bwd": (_i, [_i64, _i, _i, _i, _f, _f, _f, _f, _f]),

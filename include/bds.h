@@ -1135,6 +1135,40 @@ int bds_pseudo_lidar_from_depth(int C, int Hi, int Wi, const float *depth, const
 int bds_pseudo_lidar_from_points(int64_t N, const float *cloud, const double *beams, int crop, int H, int W, int slice, int mode,
                                  int32_t *winner, float *points, int32_t *counts, int32_t *source, bds_stream_t stream);
 
+/* A view's input preparation: what CameraData.get_image (datasets/base/pixel_source.py:477-657) makes in front of every training step
+ * and every evaluation render, and ScenePixelSource.prepare_novel_view_render_data (:1070-1132) for a novel trajectory.  Pointers +
+ * stream, no allocation, no read-back, one launch each, no atomics: bit-identical run to run.  All math is float32, every operation
+ * rounded on its own (no fused multiply-add); divisions and the square root are correctly rounded.
+ * bds_view_fields -- every per-pixel field of B views (get_rays, pixel_source.py:38-75, and the fills and pixel_coords of :507-630).
+ *   c2w [B,4,4] and intrinsics [n_intrinsics,3,3] (n_intrinsics = 1: one matrix for all views, or B), unscaled; the kernel forms
+ *   fx = K[0][0] scale, fy = K[1][1] scale, cx = K[0][2] scale, cy = K[1][2] scale as ``intrinsics * downscale_factor`` does (:625).
+ *   Per pixel (x = column, y = row): dx = ((x - cx) + 0.5) / fx, dy = ((y - cy) + 0.5) / fy; dir_i = (dx R[i][0] + dy R[i][1]) +
+ *   R[i][2]; n = sqrt((d0 d0 + d1 d1) + d2 d2); viewdirs = dir / (n + 1e-8); origins = c2w[:3,3]; pixel_coords = (float(y) /
+ *   float(H), float(x) / float(W)), row first.  normed_time [B] float32 and ids [B,3] int64 (image, frame, camera) ON THE DEVICE
+ *   are the fills' values.  Outputs, each NULL to skip it, 16-byte aligned: origins, viewdirs [B,H,W,3], direction_norm [B,H,W,1],
+ *   pixel_coords [B,H,W,2], normed_time_out [B,H,W] (needs normed_time), img_idx, frame_idx, cam_id [B,H,W] int64 (need ids),
+ *   intrinsics_out [B,3,3]: intrinsics * scale with [2][2] = 1 (:625-626).  B = 0 or H W = 0: nothing to do.  BDS_EINVAL before the
+ *   launch for a negative size, B above 65535, B H W above 2^31 - 257, a NULL c2w or intrinsics, n_intrinsics neither 1 nor B, a
+ *   scale that is not positive and finite, a misaligned array or a missing fill source.
+ * bds_image_resize_aa -- F.interpolate(mode="bicubic", antialias=True, scale_factor=factor) of an image [H,W,3] (:492-502, without
+ *   its two permutes) into out [floor(H factor), floor(W factor), 3], contiguous.  Per axis: scale = (float)(1 / factor), support =
+ *   2 scale; output i takes the taps [lo, lo + n), c = scale (i + 0.5), lo = max(0, int(c - support + 0.5)), n = min(in, int(c +
+ *   support + 0.5)) - lo, with weights cubic((j + lo - c + 0.5) / scale), Keys' a = -0.5, divided by their sum; width first, then
+ *   height.  1 / BDS_PIXELS_MAX_SCALE <= factor <= 1 (the reference never enlarges; a window of more than 4 * 512 + 3 taps per axis
+ *   does not fit a workgroup's LDS): BDS_EINVAL otherwise.
+ * bds_masks_resize_nearest -- F.interpolate(mode="nearest", scale_factor=factor) of n <= BDS_PIXELS_MAX_MASKS masks [H,W] float32
+ *   (:520-579) into [floor(H factor), floor(W factor)] each, in one launch: source index min(int(floorf(dst * (float)(1 / factor))),
+ *   in - 1) per axis, values copied.  in, out: HOST arrays of n device pointers.  BDS_EINVAL for n above the maximum, a factor
+ *   outside (0, 1] or a NULL pointer. */
+#define BDS_PIXELS_MAX_MASKS 5
+#define BDS_PIXELS_MAX_SCALE 512
+int bds_view_fields(int B, int H, int W, const float *c2w, const float *intrinsics, int n_intrinsics, float scale,
+                    const float *normed_time, const int64_t *ids, float *origins, float *viewdirs, float *direction_norm,
+                    float *pixel_coords, float *normed_time_out, int64_t *img_idx, int64_t *frame_idx, int64_t *cam_id,
+                    float *intrinsics_out, bds_stream_t stream);
+int bds_image_resize_aa(int H, int W, double factor, const float *in, float *out, bds_stream_t stream);
+int bds_masks_resize_nearest(int n, int H, int W, double factor, const float *const *in, float *const *out, bds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
