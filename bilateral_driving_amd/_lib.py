@@ -252,6 +252,15 @@ def ptr(t):
     return t.data_ptr()
 
 
+def f32c(t):
+    """The tensor as contiguous float32 (itself where it already is; None -> None)."""
+    if t is None:
+        return None
+    if t.dtype != torch.float32:
+        t = t.float()
+    return t.contiguous()
+
+
 def stream(device=None):
     return torch.cuda.current_stream(device).cuda_stream
 

@@ -25,14 +25,6 @@ from torch import Tensor
 from . import _lib as L
 
 
-def _f32c(t):
-    if t is None:
-        return None
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
-
-
 def color_affine_transform(affine_mats: Tensor, rgb: Tensor) -> Tensor:
     """affine_mats [..., 3, 4], rgb [..., 3] -> [..., 3]."""
     return torch.matmul(affine_mats[..., :3], rgb.unsqueeze(-1)).squeeze(-1) + affine_mats[..., 3]
@@ -45,7 +37,7 @@ class _TotalVariation(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: Tensor, weight: float):
         L.require_gpu(x)
-        x = _f32c(x)
+        x = L.f32c(x)
         n, c, gl, gy, gx = x.shape
         out = torch.zeros(1, device=x.device, dtype=torch.float32)
         L.check(L.lib().bds_grid_tv_fwd(n, c, gx, gy, gl, L.ptr(x), weight, L.ptr(out), L.stream()), "bds_grid_tv_fwd")
@@ -57,7 +49,7 @@ class _TotalVariation(torch.autograd.Function):
     def backward(ctx, v_out):
         (x,) = ctx.saved_tensors
         n, c, gl, gy, gx = x.shape
-        v = _f32c(v_out.reshape(1))
+        v = L.f32c(v_out.reshape(1))
         v_x = torch.zeros_like(x)
         L.check(L.lib().bds_grid_tv_bwd(n, c, gx, gy, gl, L.ptr(x), ctx.weight, L.ptr(v), L.ptr(v_x), L.stream()),
                 "bds_grid_tv_bwd")
@@ -81,7 +73,7 @@ class _SlicePoints(torch.autograd.Function):
     @staticmethod
     def forward(ctx, grid: Tensor, xy: Tensor, rgb: Tensor):
         L.require_gpu(grid, xy, rgb)
-        grid, xy, rgb = _f32c(grid), _f32c(xy), _f32c(rgb)
+        grid, xy, rgb = L.f32c(grid), L.f32c(xy), L.f32c(rgb)
         P = xy.shape[0]
         nc, gl, gy, gx = grid.shape
         aff = torch.empty(P, nc, device=grid.device, dtype=torch.float32)
@@ -102,7 +94,7 @@ class _SlicePoints(torch.autograd.Function):
                                       "(they come from linspace / pixel indices)")
         P = xy.shape[0]
         nc, gl, gy, gx = grid.shape
-        v_aff = _f32c(v_aff)
+        v_aff = L.f32c(v_aff)
         v_grid = torch.zeros_like(grid) if ctx.needs_input_grad[0] else None
         v_rgb = torch.empty_like(rgb) if ctx.needs_input_grad[2] else None
         if nc == 12:
@@ -120,7 +112,7 @@ class _SliceImage(torch.autograd.Function):
     @staticmethod
     def forward(ctx, grid: Tensor, rgb: Tensor):
         L.require_gpu(grid, rgb)
-        grid, rgb = _f32c(grid), _f32c(rgb)
+        grid, rgb = L.f32c(grid), L.f32c(rgb)
         H, W, _ = rgb.shape
         nc, gl, gy, gx = grid.shape
         out = torch.empty(H, W, nc, device=grid.device, dtype=torch.float32)
@@ -134,7 +126,7 @@ class _SliceImage(torch.autograd.Function):
         grid, rgb = ctx.saved_tensors
         H, W, _ = rgb.shape
         nc, gl, gy, gx = grid.shape
-        v_out = _f32c(v_out)
+        v_out = L.f32c(v_out)
         v_grid = torch.zeros_like(grid) if ctx.needs_input_grad[0] else None
         v_rgb = torch.empty_like(rgb) if ctx.needs_input_grad[1] else None
         L.check(L.lib().bds_bilagrid_slice_feat_image_bwd(H, W, nc, L.ptr(grid), gx, gy, gl, L.ptr(rgb), L.ptr(v_out), L.ptr(v_grid),
@@ -296,8 +288,8 @@ class _BilagridTransform(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb, alpha, sky, factors, want_maps, *grids):
         L.require_gpu(rgb, alpha, sky, *grids)
-        rgb, alpha, sky = _f32c(rgb), _f32c(alpha), _f32c(sky)
-        grids = [_f32c(g) for g in grids]
+        rgb, alpha, sky = L.f32c(rgb), L.f32c(alpha), L.f32c(sky)
+        grids = [L.f32c(g) for g in grids]
         H, W, _ = rgb.shape
         n = len(grids)
         lib = L.lib()
@@ -327,7 +319,7 @@ class _BilagridTransform(torch.autograd.Function):
         need_g = ctx.needs_input_grad[5:]
         v_grids = [torch.zeros_like(g) if need_g[i] else None for i, g in enumerate(grids)]
         lv = _levels_struct(grids, v_grids, ctx.factors)
-        v_out = _f32c(v_out)
+        v_out = L.f32c(v_out)
         v_rgb = torch.empty_like(rgb)
         v_alpha = torch.empty_like(alpha) if sky is not None else None
         v_sky = torch.empty_like(sky) if sky is not None else None

@@ -21,6 +21,7 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from . import _lib as L
+from ._patch import Seam
 
 D_LAYERS, WIDTH, MULTIRES, INPUT_CH = 8, 256, 10, 3
 EMBED_DIMS = (0, 16)
@@ -242,17 +243,15 @@ def _fused_forward(self, x, t, condition=None):
     return deform(self.linear, *heads, x, t, condition)
 
 
+_SEAM = Seam()
+
+
 def install(network_class) -> None:
     """``install(models.modules.ConditionalDeformNetwork)`` (or ``DeformNetwork``): the class's ``forward`` becomes the fused one for
     modules with the supported sizes (others keep the original).  The original stays reachable as
     ``network_class._bds_reference_forward``; ``uninstall`` puts it back."""
-    if getattr(network_class, "_bds_reference_forward", None) is None:
-        network_class._bds_reference_forward = network_class.__dict__.get("forward")
-    network_class.forward = _fused_forward
+    _SEAM.install(network_class, {"forward": _fused_forward}, reference="_bds_reference_forward")
 
 
-def uninstall(network_class) -> None:
-    ref = getattr(network_class, "_bds_reference_forward", None)
-    if ref is not None:
-        network_class.forward = ref
-    network_class._bds_reference_forward = None
+def uninstall(*network_classes) -> None:
+    _SEAM.uninstall(*network_classes)

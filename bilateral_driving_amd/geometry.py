@@ -27,7 +27,8 @@ import torch
 from torch import Tensor
 
 from . import _lib as L
-from .metrics import _mask_kind, non_zero_mean
+from ._patch import Seam
+from .metrics import RowAccumulator, _mask_kind, grown, non_zero_mean
 
 ROW = 32                    # include/bds.h BDS_GEOMETRY_METRICS_ROW
 QUERY_BLOCK = 512           # include/bds.h BDS_GEOMETRY_QUERY_BLOCK: queries per workgroup of the pair loop
@@ -80,10 +81,7 @@ def _masks(masks: list, shape) -> Tuple[list, int]:
 
 
 def _workspace(H: int, W: int, device, ws: Optional[Tensor]) -> Tensor:
-    need = int(L.lib().bds_geometry_metrics_workspace_bytes(H, W))
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
-    return ws
+    return grown(ws, int(L.lib().bds_geometry_metrics_workspace_bytes(H, W)), device)
 
 
 def _launch(pred: Tensor, gt: Tensor, K: Tensor, c2w: Tensor, masks: list, egocar: Optional[Tensor], row: Tensor,
@@ -166,11 +164,18 @@ def chamfer_distance(x: Tensor, y: Tensor, norm: int = 2) -> Tuple[Tensor, Tenso
     return (cx[0] if x.dim() == 2 else cx), (cy[0] if y.dim() == 2 else cy)
 
 
+_SEAM = Seam()
+
+
 def install(module) -> None:
     """Sets ``chamfer_distance`` and ``depth_map_to_point_cloud`` on ``module`` -- the reference's ``utils.chamfer_distance``, which
     ``render_images`` imports from at call time."""
-    module.chamfer_distance = chamfer_distance
-    module.depth_map_to_point_cloud = depth_map_to_point_cloud
+    _SEAM.install(module, {"chamfer_distance": chamfer_distance, "depth_map_to_point_cloud": depth_map_to_point_cloud})
+
+
+def uninstall(*modules) -> None:
+    """Puts back what ``install`` replaced (no module given: on every installed one)."""
+    _SEAM.uninstall(*modules)
 
 
 def _frame_inputs(depth: Tensor, image_infos: Mapping[str, Tensor], cam_infos: Mapping[str, Tensor]):
@@ -199,37 +204,19 @@ def frame_geometry(depth: Tensor, image_infos: Mapping[str, Tensor], cam_infos: 
     return _row_to_dict(row.cpu().tolist())
 
 
-class GeometryAccumulator:
+class GeometryAccumulator(RowAccumulator):
     """The geometry scores of a split: ``add(depth, image_infos, cam_infos)`` writes the next frame's row into a preallocated
     [num_frames, ROW] device buffer (no host wait); ``results()`` reads the buffer once and returns ``results_dict``'s entries
     (video_utils.py:558-573): per key the mean over the frames that produced it, -1 where none did.  Like the reference, a frame
     without a valid point enters the whole-frame means as NaN."""
-
-    def __init__(self, num_frames: int, device=None):
-        """``device``: the GPU every frame lives on (default: the current one).  ``add`` must be called on ONE stream: the frames share
-        a workspace, which the launches of one stream use in order."""
-        dev = torch.device(device if device is not None else "cuda")
-        self.rows = torch.empty(num_frames, ROW, dtype=torch.float64, device=dev)
-        self.count = 0
-        self._ws = None
-        self._stream = None
-
-    def __len__(self) -> int:
-        return self.count
+    ROW, WORKSPACE_BYTES = ROW, "bds_geometry_metrics_workspace_bytes"
 
     @torch.no_grad()
     def add(self, depth: Tensor, image_infos: Mapping[str, Tensor], cam_infos: Mapping[str, Tensor]) -> None:
-        if self.count >= self.rows.shape[0]:
-            raise IndexError(f"GeometryAccumulator holds {self.rows.shape[0]} frames")
+        self._require_room()
         pred, gt, K, c2w, masks, ego = _frame_inputs(depth, image_infos, cam_infos)
-        L.require_gpu(pred, gt, self.rows)           # (one device: the frame's and the buffer's)
-        stream = L.stream()
-        if self._stream is None:
-            self._stream = stream
-        elif stream != self._stream:
-            raise L.BdsError("GeometryAccumulator.add was called on another stream than before: the frames share one workspace")
-        self._ws = _workspace(*pred.shape, pred.device, self._ws)
-        _launch(pred, gt, K, c2w, masks, ego, self.rows[self.count], None, self._ws)
+        row, ws = self._next(*pred.shape, pred, gt)
+        _launch(pred, gt, K, c2w, masks, ego, row, None, ws)
         self.count += 1
 
     def per_frame(self):

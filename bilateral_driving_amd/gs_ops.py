@@ -25,14 +25,6 @@ from . import _lib as L
 TILE_SIZE = 16  # the compositing tile of the gfx950 kernels (gsplat default); lists may be built for any multiple of it
 
 
-def _f32c(t: Optional[Tensor]) -> Optional[Tensor]:
-    if t is None:
-        return None
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
-
-
 # --------------------------------------------------------------------------------------------
 # spherical harmonics
 # --------------------------------------------------------------------------------------------
@@ -40,7 +32,7 @@ class _SphericalHarmonics(torch.autograd.Function):
     @staticmethod
     def forward(ctx, degree: int, dirs: Tensor, coeffs: Tensor, masks: Optional[Tensor]):
         L.require_gpu(dirs, coeffs, masks)
-        dirs, coeffs = _f32c(dirs), _f32c(coeffs)
+        dirs, coeffs = L.f32c(dirs), L.f32c(coeffs)
         n, K = coeffs.shape[0], coeffs.shape[1]
         m8 = None if masks is None else masks.to(torch.uint8).contiguous()
         out = torch.empty(n, 3, device=coeffs.device, dtype=torch.float32)
@@ -54,7 +46,7 @@ class _SphericalHarmonics(torch.autograd.Function):
     def backward(ctx, v_out: Tensor):
         dirs, coeffs, m8 = ctx.saved_tensors
         n, K = coeffs.shape[0], coeffs.shape[1]
-        v_out = _f32c(v_out)
+        v_out = L.f32c(v_out)
         v_coeffs = torch.empty_like(coeffs)
         v_dirs = torch.empty_like(dirs) if ctx.needs_input_grad[1] else None
         with L.timed("sh_bwd"):
@@ -84,7 +76,7 @@ class _Projection(torch.autograd.Function):
     def forward(ctx, means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip,
                 calc_compensations):
         L.require_gpu(means, quats, scales, viewmats, Ks)
-        means, quats, scales, viewmats, Ks = map(_f32c, (means, quats, scales, viewmats, Ks))
+        means, quats, scales, viewmats, Ks = map(L.f32c, (means, quats, scales, viewmats, Ks))
         Cn, N = viewmats.shape[0], means.shape[0]
         dev = means.device
         radii = torch.empty(Cn, N, device=dev, dtype=torch.int32)
@@ -108,7 +100,7 @@ class _Projection(torch.autograd.Function):
         means, quats, scales, viewmats, Ks, radii, conics = ctx.saved_tensors
         width, height, eps2d = ctx.cfg
         Cn, N = viewmats.shape[0], means.shape[0]
-        v_means2d, v_depths, v_conics, v_comps = _f32c(v_means2d), _f32c(v_depths), _f32c(v_conics), _f32c(v_comps)
+        v_means2d, v_depths, v_conics, v_comps = L.f32c(v_means2d), L.f32c(v_depths), L.f32c(v_conics), L.f32c(v_comps)
         v_means = torch.empty_like(means)
         v_quats = torch.empty_like(quats)
         v_scales = torch.empty_like(scales)
@@ -156,11 +148,11 @@ def isect_tiles(means2d: Tensor, radii: Tensor, depths: Tensor, tile_size: int, 
     L.require_gpu(means2d, radii, depths)
     Cn, N = radii.shape
     dev = means2d.device
-    means2d, depths = _f32c(means2d.detach()), _f32c(depths.detach())
+    means2d, depths = L.f32c(means2d.detach()), L.f32c(depths.detach())
     radii = radii.contiguous()
     assert (conics is None) == (opacities is None)
     if conics is not None:
-        conics, opacities = _f32c(conics.detach()), _f32c(opacities.detach())
+        conics, opacities = L.f32c(conics.detach()), L.f32c(opacities.detach())
         assert conics.shape == (Cn, N, 3) and opacities.shape == (Cn, N)
     lib = L.lib()
     tiles_per_gauss = torch.empty(Cn, N, device=dev, dtype=torch.int32)
@@ -215,7 +207,7 @@ class _RasterizeToPixels(torch.autograd.Function):
     def forward(ctx, means2d, conics, colors, opacities, backgrounds, width, height, tile_size, isect_offsets, flatten_ids,
                 absgrad):
         L.require_gpu(means2d, conics, colors, opacities, backgrounds)
-        means2d_c, conics, colors, opacities, backgrounds = map(_f32c, (means2d, conics, colors, opacities, backgrounds))
+        means2d_c, conics, colors, opacities, backgrounds = map(L.f32c, (means2d, conics, colors, opacities, backgrounds))
         Cn, N = means2d_c.shape[0], means2d_c.shape[1]
         CH = colors.shape[-1]
         tw, th = math.ceil(width / TILE_SIZE), math.ceil(height / TILE_SIZE)   # compositing tiles; tile_size = the lists' tile
@@ -247,7 +239,7 @@ class _RasterizeToPixels(torch.autograd.Function):
         Cn, N = means2d.shape[0], means2d.shape[1]
         tw, th = math.ceil(width / TILE_SIZE), math.ceil(height / TILE_SIZE)
         M = flatten_ids.shape[0]
-        v_render, v_alphas = _f32c(v_render), _f32c(v_alphas)
+        v_render, v_alphas = L.f32c(v_render), L.f32c(v_alphas)
         # gradient records (64 bytes per entry, accumulated with atomics): include/bds.h bds_rasterize_bwd
         v_rec = torch.zeros(Cn * N, L.GRAD_RECORD_FLOATS, device=rec.device, dtype=torch.float32)
         order = bwd_schedule(Cn, width, height, tile_size, isect_offsets, last_ids)

@@ -29,6 +29,7 @@ from torch import Tensor
 from torch.nn import Parameter
 
 from . import _lib as L
+from ._patch import Seam
 
 MAX_K = 8                   # include/bds.h BDS_KNN_MAX_K
 MAX_POINTS = 1 << 30        # include/bds.h BDS_KNN_MAX_POINTS
@@ -163,8 +164,7 @@ def create_from_pcd(self, init_means: Tensor, init_colors: Tensor) -> None:
     self._opacities = Parameter(torch.logit(0.1 * torch.ones(N, 1, device=device)))
 
 
-_INSTALLED: Dict[object, object] = {}
-_MISSING = object()
+_SEAM = Seam()
 
 
 def install(*modules) -> None:
@@ -172,19 +172,9 @@ def install(*modules) -> None:
     name at import through ``from models.gaussians.basics import *``, so those are the modules to pass (``basics`` itself changes
     nothing for them)."""
     for m in modules:
-        if m not in _INSTALLED:
-            _INSTALLED[m] = getattr(m, "k_nearest_sklearn", _MISSING)
-        m.k_nearest_sklearn = k_nearest_sklearn
+        _SEAM.install(m, {"k_nearest_sklearn": k_nearest_sklearn})
 
 
 def uninstall(*modules) -> None:
     """Puts back what ``install`` replaced (no module given: on every installed one)."""
-    for m in (modules or tuple(_INSTALLED)):
-        old = _INSTALLED.pop(m, None)
-        if old is None:
-            continue
-        if old is _MISSING:
-            if hasattr(m, "k_nearest_sklearn"):
-                delattr(m, "k_nearest_sklearn")
-        else:
-            m.k_nearest_sklearn = old
+    _SEAM.uninstall(*modules)

@@ -44,6 +44,7 @@ import torch
 from torch import Tensor
 
 from . import _lib as L
+from ._patch import Seam
 
 VIEW_CHUNK = 64             # include/bds.h BDS_LIDAR_VIEW_CHUNK: views per LDS stage
 BOX_CHUNK = 128             # include/bds.h BDS_LIDAR_BOX_CHUNK: boxes per LDS stage
@@ -393,28 +394,17 @@ def filter_pts_in_boxes(dataset, seed_pts: Tensor, valid_instances_dict, seed_co
 
 _METHODS = {"project_lidar_pts_on_images": project_lidar_pts_on_images, "get_init_objects": get_init_objects,
             "filter_pts_in_boxes": filter_pts_in_boxes, "check_pts_visibility": check_pts_visibility}
-_INSTALLED: Dict[object, Dict[str, object]] = {}
-_MISSING = object()
+_SEAM = Seam()
 
 
 def install(dataset_class=None, pixel_source_module=None) -> None:
     """Sets the four methods on ``dataset_class`` (the reference's ``DrivingDataset``) and ``sparse_lidar_map_downsampler`` on
     ``pixel_source_module`` (``datasets.base.pixel_source``, whose ``get_image`` looks the name up at call time)."""
     for target, names in ((dataset_class, _METHODS), (pixel_source_module, {"sparse_lidar_map_downsampler": sparse_lidar_map_downsampler})):
-        if target is None:
-            continue
-        former = _INSTALLED.setdefault(target, {})
-        for name, fn in names.items():
-            former.setdefault(name, target.__dict__.get(name, _MISSING))
-            setattr(target, name, fn)
+        if target is not None:
+            _SEAM.install(target, names)
 
 
 def uninstall(*targets) -> None:
     """Puts back what ``install`` replaced (no target given: on every installed one)."""
-    for target in (targets or tuple(_INSTALLED)):
-        for name, old in _INSTALLED.pop(target, {}).items():
-            if old is _MISSING:
-                if name in target.__dict__:
-                    delattr(target, name)
-            else:
-                setattr(target, name, old)
+    _SEAM.uninstall(*targets)

@@ -28,6 +28,7 @@ from typing import Callable, Dict, List, Mapping, Optional, Tuple
 import torch
 from torch import Tensor
 
+from ._patch import Seam
 from .gs_ops import spherical_harmonics
 from .rendering import rasterization
 
@@ -145,22 +146,18 @@ def get_gaussians_lazy(self, cam: dataclass_camera) -> Dict[str, Tensor]:
                 _rgbs=LazyField(src, "_rgbs", (N, 3)), _scales=LazyField(src, "_scales", (N, 3)), _quats=LazyField(src, "_quats", (N, 4)))
 
 
+_SEAM = Seam()
+
+
 def install(gaussian_class) -> None:
     """``install(VanillaGaussians)``: the class's ``get_gaussians`` becomes ``get_gaussians_lazy`` (the reference's file is not
     touched; the same mechanism as assigning ``densify.refinement_after``).  The original stays reachable as
     ``gaussian_class._bds_reference_get_gaussians``; ``uninstall`` puts it back."""
-    if getattr(gaussian_class, "_bds_reference_get_gaussians", None) is None:
-        gaussian_class._bds_reference_get_gaussians = gaussian_class.__dict__.get("get_gaussians")
-    gaussian_class.get_gaussians = get_gaussians_lazy
+    _SEAM.install(gaussian_class, {"get_gaussians": get_gaussians_lazy}, reference="_bds_reference_get_gaussians")
 
 
-def uninstall(gaussian_class) -> None:
-    ref = getattr(gaussian_class, "_bds_reference_get_gaussians", None)
-    if ref is not None:
-        gaussian_class.get_gaussians = ref
-    elif "get_gaussians" in gaussian_class.__dict__:
-        del gaussian_class.get_gaussians
-    gaussian_class._bds_reference_get_gaussians = None
+def uninstall(*gaussian_classes) -> None:
+    _SEAM.uninstall(*gaussian_classes)
 
 
 def collect_gaussians(models: Mapping[str, object], gaussian_classes: Mapping[str, int], cam: dataclass_camera,

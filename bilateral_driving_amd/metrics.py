@@ -44,6 +44,13 @@ def _mask_kind(m: Tensor) -> int:
     return 1 if m.dtype == torch.float32 else (0 if m.dtype in (torch.bool, torch.uint8) else -1)
 
 
+def grown(ws: Optional[Tensor], need: int, device) -> Tensor:
+    """``ws`` where it holds ``need`` bytes, else a new uint8 buffer that does (never empty: the entries take no NULL workspace)."""
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+    return ws
+
+
 def _launch(rgb: Tensor, gt: Tensor, masks: list, invert_bits: int, row: Tensor, ssim_map: Optional[Tensor],
             ws: Optional[Tensor] = None) -> None:
     """``masks``: up to four [H,W] tensors or None per slot; ``row``: [ROW] float64, contiguous."""
@@ -59,9 +66,7 @@ def _launch(rgb: Tensor, gt: Tensor, masks: list, invert_bits: int, row: Tensor,
     held = [None if m is None else m.detach().contiguous() for m in masks]      # (alive until the launches are enqueued)
     ptrs = [L.ptr(m) for m in held] + [None] * (SLOTS - len(held))
     lib = L.lib()
-    nbytes = int(lib.bds_image_metrics_workspace_bytes(H, W))
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=rgb.device)
+    ws = grown(ws, int(lib.bds_image_metrics_workspace_bytes(H, W)), rgb.device)
     L.check(lib.bds_image_metrics(H, W, L.ptr(rgb), L.ptr(gt), *ptrs, invert_bits, kinds.pop() if kinds else 0, L.ptr(ssim_map),
                                   L.ptr(row), L.ptr(ws), ws.numel(), L.stream()), "bds_image_metrics")
 
@@ -156,44 +161,62 @@ def non_zero_mean(x) -> float:
     return sum(x) / len(x) if len(x) > 0 else -1        # video_utils.py:26-27
 
 
-class MetricAccumulator:
-    """The scores of a split: ``add(rgb, image_infos)`` writes the next frame's row into a preallocated [num_frames, ROW] device
-    buffer (no host wait); ``results()`` reads the buffer once and returns ``results_dict``'s entries (video_utils.py:542-552): per
-    key the mean over the frames that produced it, -1 where none did."""
+class RowAccumulator:
+    """What ``MetricAccumulator`` and ``geometry.GeometryAccumulator`` share: a preallocated [num_frames, ROW] float64 device buffer
+    with one row per frame, and one grow-only workspace for the frames' launches."""
+    ROW = 0                     # floats per frame
+    WORKSPACE_BYTES = ""        # the C entry that sizes the workspace of an [H,W] frame
 
     def __init__(self, num_frames: int, device=None):
         """``device``: the GPU every frame lives on (default: the current one).  ``add`` must be called on ONE stream: the frames share
         a workspace, which the launches of one stream use in order."""
         dev = torch.device(device if device is not None else "cuda")
-        self.rows = torch.empty(num_frames, ROW, dtype=torch.float64, device=dev)
-        self.present = []        # per frame: which mask keys image_infos had (host knowledge, no read-back)
+        self.rows = torch.empty(num_frames, self.ROW, dtype=torch.float64, device=dev)
+        self.count = 0
         self._ws = None
         self._stream = None
 
     def __len__(self) -> int:
-        return len(self.present)
+        return self.count
 
-    @torch.no_grad()
-    def add(self, rgb: Tensor, image_infos: Mapping[str, Tensor]) -> None:
-        i = len(self.present)
-        if i >= self.rows.shape[0]:
-            raise IndexError(f"MetricAccumulator holds {self.rows.shape[0]} frames")
-        rgb, gt, masks, bits = _frame_inputs(rgb, image_infos)
-        L.require_gpu(rgb, gt, self.rows)           # (one device: the frame's and the buffer's)
+    def _require_room(self) -> None:
+        if self.count >= self.rows.shape[0]:
+            raise IndexError(f"{type(self).__name__} holds {self.rows.shape[0]} frames")
+
+    def _next(self, H: int, W: int, *frame: Tensor):
+        """(the row of the next frame, the workspace) for a launch over the [H,W] tensors ``frame``; the caller counts the frame."""
+        L.require_gpu(*frame, self.rows)           # (one device: the frame's and the buffer's)
         stream = L.stream()
         if self._stream is None:
             self._stream = stream
         elif stream != self._stream:
-            raise L.BdsError("MetricAccumulator.add was called on another stream than before: the frames share one workspace")
-        need = int(L.lib().bds_image_metrics_workspace_bytes(*rgb.shape[:2]))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(max(need, 16), dtype=torch.uint8, device=rgb.device)
-        _launch(rgb, gt, masks, bits, self.rows[i], None, self._ws)
+            raise L.BdsError(f"{type(self).__name__}.add was called on another stream than before: the frames share one workspace")
+        self._ws = grown(self._ws, int(getattr(L.lib(), self.WORKSPACE_BYTES)(H, W)), frame[0].device)
+        return self.rows[self.count], self._ws
+
+
+class MetricAccumulator(RowAccumulator):
+    """The scores of a split: ``add(rgb, image_infos)`` writes the next frame's row into a preallocated [num_frames, ROW] device
+    buffer (no host wait); ``results()`` reads the buffer once and returns ``results_dict``'s entries (video_utils.py:542-552): per
+    key the mean over the frames that produced it, -1 where none did."""
+    ROW, WORKSPACE_BYTES = ROW, "bds_image_metrics_workspace_bytes"
+
+    def __init__(self, num_frames: int, device=None):
+        super().__init__(num_frames, device)
+        self.present = []        # per frame: which mask keys image_infos had (host knowledge, no read-back)
+
+    @torch.no_grad()
+    def add(self, rgb: Tensor, image_infos: Mapping[str, Tensor]) -> None:
+        self._require_room()
+        rgb, gt, masks, bits = _frame_inputs(rgb, image_infos)
+        row, ws = self._next(*rgb.shape[:2], rgb, gt)
+        _launch(rgb, gt, masks, bits, row, None, ws)
         self.present.append([m is not None for m in masks])
+        self.count += 1
 
     def per_frame(self):
         """[{key: float}] of the frames added so far, the keys ``frame_metrics`` gives (one read-back)."""
-        vals = self.rows[:len(self.present)].cpu().tolist()
+        vals = self.rows[:self.count].cpu().tolist()
         return [_row_to_dict(v, p) for v, p in zip(vals, self.present)]
 
     def results(self) -> Dict[str, float]:

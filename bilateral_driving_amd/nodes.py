@@ -19,6 +19,7 @@ from torch import Tensor
 
 from . import _lib as L
 from . import gs_ops
+from ._patch import Seam
 
 GS_KEYS = ("_means", "_opacities", "_rgbs", "_scales", "_quats")   # the order of get_gaussians' dict and of its NaN / Inf check
 
@@ -84,10 +85,6 @@ def framework_transform(means: Tensor, quats: Tensor, logits: Tensor, point_ids:
     return world_means, world_quats, opacities
 
 
-def _f32c(t: Tensor) -> Tensor:
-    return t.detach().contiguous().float()
-
-
 class _PoseTransform(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, quats, logits, instances_quats, instances_trans, point_ids, instances_fv, cur_frame, interpolate, bad_ids):
@@ -97,8 +94,8 @@ class _PoseTransform(torch.autograd.Function):
         if point_ids.dtype != torch.int64 or point_ids.numel() != N:
             raise L.BdsError(f"point_ids must be int64 [N,1] with N = {N} (got {point_ids.dtype} {tuple(point_ids.shape)})")
         assert quats.shape == (N, 4) and logits.numel() == N and instances_quats.shape == (F, I, 4) and instances_trans.shape == (F, I, 3)
-        m, q, lg = _f32c(means), _f32c(quats), _f32c(logits).reshape(N)
-        iq, it = _f32c(instances_quats), _f32c(instances_trans)
+        m, q, lg, iq, it = (L.f32c(t.detach()) for t in (means, quats, logits, instances_quats, instances_trans))
+        lg = lg.reshape(N)
         ids = point_ids.detach().reshape(N).contiguous()
         fv = instances_fv.detach().contiguous().to(torch.bool).view(torch.uint8)
         dev = means.device
@@ -217,17 +214,16 @@ def deformable_get_gaussians(self, cam) -> dict:
     return gs
 
 
+_SEAM = Seam()
+
+
 def install(node_class) -> None:
     """``install(models.nodes.RigidNodes)`` / ``install(models.nodes.DeformableNodes)``: the class's ``get_gaussians`` becomes the fused
     one (a class with ``get_deformation`` gets the deformable form).  The original stays reachable as
     ``node_class._bds_reference_get_gaussians``; ``uninstall`` puts it back."""
-    if node_class.__dict__.get("_bds_reference_get_gaussians") is None:
-        node_class._bds_reference_get_gaussians = node_class.__dict__.get("get_gaussians", getattr(node_class, "get_gaussians"))
-    node_class.get_gaussians = deformable_get_gaussians if hasattr(node_class, "get_deformation") else rigid_get_gaussians
+    fn = deformable_get_gaussians if hasattr(node_class, "get_deformation") else rigid_get_gaussians
+    _SEAM.install(node_class, {"get_gaussians": fn}, reference="_bds_reference_get_gaussians")
 
 
-def uninstall(node_class) -> None:
-    ref = node_class.__dict__.get("_bds_reference_get_gaussians")
-    if ref is not None:
-        node_class.get_gaussians = ref
-    node_class._bds_reference_get_gaussians = None
+def uninstall(*node_classes) -> None:
+    _SEAM.uninstall(*node_classes)

@@ -39,6 +39,7 @@ from torch import Tensor
 
 from . import _lib as L
 from . import lidar
+from ._patch import MISSING, Seam
 
 MAX_MASKS = 5               # include/bds.h BDS_PIXELS_MAX_MASKS
 MAX_VIEWS = 65535           # include/bds.h: the launch's second grid dimension
@@ -272,8 +273,7 @@ def prepare_novel_view_render_data(self, dataset_type: str, traj: Tensor) -> lis
             for i in range(N)]
 
 
-_INSTALLED: Dict[object, Dict[str, object]] = {}
-_MISSING = object()
+_SEAM = Seam()
 
 
 def _on_device(obj) -> bool:
@@ -285,11 +285,12 @@ def _on_device(obj) -> bool:
     return isinstance(t, Tensor) and t.is_cuda
 
 
-def _dispatch(fn, target, name, own):
-    """``fn`` for an object on the device; for one on the CPU the method that ``target`` had: its own (``own``), else the inherited one."""
+def _dispatch(fn, target, name):
+    """``fn`` for an object on the device; for one on the CPU the method that ``target`` had: its own, else the inherited one."""
     def method(self, *args, **kwargs):
         if not _on_device(self):
-            if own is not _MISSING:
+            own = _SEAM.former(target, name)
+            if own is not MISSING:
                 return own(self, *args, **kwargs)
             inherited = getattr(super(target, self), name, None)
             if inherited is not None:
@@ -307,17 +308,9 @@ def install(camera_data_class=None, scene_pixel_source_class=None) -> None:
                              (scene_pixel_source_class, "prepare_novel_view_render_data", prepare_novel_view_render_data)):
         if target is None:
             continue
-        former = _INSTALLED.setdefault(target, {})
-        former.setdefault(name, target.__dict__.get(name, _MISSING))
-        setattr(target, name, _dispatch(fn, target, name, former[name]))
+        _SEAM.install(target, {name: _dispatch(fn, target, name)})
 
 
 def uninstall(*targets) -> None:
     """Puts back what ``install`` replaced (no target given: on every installed one)."""
-    for target in (targets or tuple(_INSTALLED)):
-        for name, old in _INSTALLED.pop(target, {}).items():
-            if old is _MISSING:
-                if name in target.__dict__:
-                    delattr(target, name)
-            else:
-                setattr(target, name, old)
+    _SEAM.uninstall(*targets)

@@ -34,13 +34,14 @@ Not covered: ``save_ply``, ``pto_rec_map``, ``gen_sparse_points_all``, the radar
 from __future__ import annotations
 
 import math
-from typing import Dict, Optional, Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
 from torch import Tensor
 
 from . import _lib as L
+from ._patch import Seam
 from .lidar import MAX_ROWS, _cloud as _finite_on_device
 
 VERTICAL, CLASSIC = 0, 1      # include/bds.h BDS_PSEUDO_LIDAR_VERTICAL / _CLASSIC
@@ -223,26 +224,16 @@ def gen_sparse_points(pl_data_path, args):
 
 _FUNCTIONS = {"depth_map_to_lidar_points": depth_map_to_lidar_points, "pto_ang_map": pto_ang_map,
               "pto_ang_map_vertical": pto_ang_map_vertical, "gen_sparse_points": gen_sparse_points}
-_INSTALLED: Dict[object, Dict[str, object]] = {}
-_MISSING = object()
+_SEAM = Seam()
 
 
 def install(module) -> None:
     """Sets the functions on ``module``: those of the four names that it defines (``generate_lidar.generate_lidar_from_depth`` has
     three, ``generate_lidar.depth2lidar`` two), or all four on a module that defines none."""
     names = [n for n in _FUNCTIONS if n in module.__dict__] or list(_FUNCTIONS)
-    former = _INSTALLED.setdefault(module, {})
-    for name in names:
-        former.setdefault(name, module.__dict__.get(name, _MISSING))
-        setattr(module, name, _FUNCTIONS[name])
+    _SEAM.install(module, {name: _FUNCTIONS[name] for name in names})
 
 
 def uninstall(*modules) -> None:
     """Puts back what ``install`` replaced (no module given: on every installed one)."""
-    for module in (modules or tuple(_INSTALLED)):
-        for name, old in _INSTALLED.pop(module, {}).items():
-            if old is _MISSING:
-                if name in module.__dict__:
-                    delattr(module, name)
-            else:
-                setattr(module, name, old)
+    _SEAM.uninstall(*modules)

@@ -21,6 +21,7 @@ import torch
 from torch import Tensor
 
 from . import _lib as L
+from ._patch import Seam
 
 GS_KEYS = ("_means", "_opacities", "_rgbs", "_scales", "_quats")   # the order of get_gaussians' dict and of its NaN / Inf check
 KEEP = 0.05                                                        # pvg.py:389
@@ -69,10 +70,6 @@ def framework_transform(means: Tensor, velocity: Tensor, taus: Tensor, betas: Te
     return out_means, opacities, rgbs, scales, out_quats, mask
 
 
-def _f32c(t: Tensor) -> Tensor:
-    return t.detach().contiguous().float()
-
-
 class _TimeTransform(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, velocity, taus, betas, logits, log_scales, quats, features_dc, features_rest, cam_pos, cfg, info):
@@ -83,9 +80,9 @@ class _TimeTransform(torch.autograd.Function):
         assert velocity.shape == (N, 3) and taus.numel() == N and betas.numel() == N and logits.numel() == N
         assert log_scales.shape == (N, 3) and quats.shape == (N, 4) and features_dc.shape == (N, 3) and features_rest.shape == (N, K - 1, 3)
         dev = means.device
-        m, v, ta, be, lg, ls, q, dc, rest = (_f32c(x) for x in (means, velocity, taus, betas, logits, log_scales, quats, features_dc,
-                                                                 features_rest))
-        cam = _f32c(cam_pos).reshape(-1)[:3].contiguous()
+        m, v, ta, be, lg, ls, q, dc, rest = (L.f32c(x.detach()) for x in (means, velocity, taus, betas, logits, log_scales, quats,
+                                                                          features_dc, features_rest))
+        cam = L.f32c(cam_pos.detach()).reshape(-1)[:3].contiguous()
         o_m, o_o, o_c, o_s, o_q, raw = (torch.empty(N, w, device=dev) for w in (3, 1, 3, 3, 4, 3))
         mask = torch.empty(N, dtype=torch.bool, device=dev)
         nbytes = int(L.lib().bds_pvg_temp_bytes(N))
@@ -177,16 +174,14 @@ def pvg_get_gaussians(self, cam) -> dict:
     return gs
 
 
+_SEAM = Seam()
+
+
 def install(cls) -> None:
     """``install(models.gaussians.pvg.PeriodicVibrationGaussians)``: the class's ``get_gaussians`` becomes the fused one.  The original
     stays reachable as ``cls._bds_reference_get_gaussians``; ``uninstall`` puts it back."""
-    if cls.__dict__.get("_bds_reference_get_gaussians") is None:
-        cls._bds_reference_get_gaussians = cls.__dict__.get("get_gaussians", getattr(cls, "get_gaussians"))
-    cls.get_gaussians = pvg_get_gaussians
+    _SEAM.install(cls, {"get_gaussians": pvg_get_gaussians}, reference="_bds_reference_get_gaussians")
 
 
-def uninstall(cls) -> None:
-    ref = cls.__dict__.get("_bds_reference_get_gaussians")
-    if ref is not None:
-        cls.get_gaussians = ref
-    cls._bds_reference_get_gaussians = None
+def uninstall(*classes) -> None:
+    _SEAM.uninstall(*classes)

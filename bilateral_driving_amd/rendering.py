@@ -104,7 +104,7 @@ def _split_materialised(x):
     return x
 from .fused_view import (_Front, _composite, _composite_backward, _image_buffers, _lists_begin, _lists_finish, _project_backward,
                          _view_front)
-from .gs_ops import (TILE_SIZE, _f32c, fully_fused_projection, isect_tiles, rasterize_to_pixels, spherical_harmonics)
+from .gs_ops import (TILE_SIZE, fully_fused_projection, isect_tiles, rasterize_to_pixels, spherical_harmonics)
 
 
 class _Meta(dict):
@@ -180,7 +180,7 @@ class _RasterizeView(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, quats, scales, opacities, colors, viewmat, Kmat, cfg):
         L.require_gpu(means, quats, scales, opacities, colors, viewmat, Kmat)
-        means, quats, scales, opacities, colors, viewmat, Kmat = map(_f32c, (means, quats, scales, opacities, colors, viewmat, Kmat))
+        means, quats, scales, opacities, colors, viewmat, Kmat = map(L.f32c, (means, quats, scales, opacities, colors, viewmat, Kmat))
         lib, st = L.lib(), L.stream()
         dev = means.device
         W, H, N = cfg["width"], cfg["height"], means.shape[0]
@@ -241,7 +241,7 @@ class _RasterizeRawView(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, quats, log_scales, logits, dc, rest, viewmat, Kmat, cfg):
         L.require_gpu(means, quats, log_scales, logits, dc, rest, viewmat, Kmat)
-        means, quats, log_scales, logits, dc, rest, viewmat, Kmat = map(_f32c, (means, quats, log_scales, logits, dc, rest, viewmat, Kmat))
+        means, quats, log_scales, logits, dc, rest, viewmat, Kmat = map(L.f32c, (means, quats, log_scales, logits, dc, rest, viewmat, Kmat))
         lib, st = L.lib(), L.stream()
         dev = means.device
         W, H, N = cfg["width"], cfg["height"], means.shape[0]
@@ -315,12 +315,12 @@ def _view_backward(ctx, saved, v_out, v_depth, v_alphas, v_means2d_ext, want_pos
     v_render, v_alphas_t = torch.empty_like(render), torch.empty_like(alphas)
     if cfg.get("split"):
         L.check(lib.bds_expected_depth_split_bwd(H * W, int(cfg["ed"]), L.ptr(render), L.ptr(alphas),
-                                                 None if v_out is None else L.ptr(_f32c(v_out)), None if v_depth is None else L.ptr(_f32c(v_depth)),
-                                                 None if v_alphas is None else L.ptr(_f32c(v_alphas)), L.ptr(v_render), L.ptr(v_alphas_t), st),
+                                                 None if v_out is None else L.ptr(L.f32c(v_out)), None if v_depth is None else L.ptr(L.f32c(v_depth)),
+                                                 None if v_alphas is None else L.ptr(L.f32c(v_alphas)), L.ptr(v_render), L.ptr(v_alphas_t), st),
                 "bds_expected_depth_split_bwd")
     else:
         L.check(lib.bds_expected_depth_bwd(H * W, cfg["channels"], int(cfg["ed"]), L.ptr(render), L.ptr(alphas),
-                                           None if v_out is None else L.ptr(_f32c(v_out)), None if v_alphas is None else L.ptr(_f32c(v_alphas)),
+                                           None if v_out is None else L.ptr(L.f32c(v_out)), None if v_alphas is None else L.ptr(L.f32c(v_alphas)),
                                            L.ptr(v_render), L.ptr(v_alphas_t), st), "bds_expected_depth_bwd")
     v_rec_all, v_rec = _composite_backward(cfg, (rec, flatten, isect_offsets, alphas, last_ids), vis_ids, ctx.M, _LIST_TILE,
                                            absgrad=cfg["absgrad"], want_pose=want_pose, v_render=v_render, v_alphas=v_alphas_t,
@@ -434,7 +434,7 @@ def rasterization(
                     absgrad=bool(absgrad), cull=_TILE_CULLING, aa=rasterize_mode == "antialiased", **own)
 
     if raw_ok:
-        cfg = _one_view_cfg(sh_degree=src.sh_degree, cam_pos=_f32c(src.cam_pos.detach().reshape(3)), logits_shape=tuple(src.logits.shape),
+        cfg = _one_view_cfg(sh_degree=src.sh_degree, cam_pos=L.f32c(src.cam_pos.detach().reshape(3)), logits_shape=tuple(src.logits.shape),
                            step=src.step, check_finite=_CHECK_FINITE, split=_SPLIT_RENDER and render_mode != "RGB")
         out, depth1, alphas, means2d, radii, depths, conics, opac = _RasterizeRawView.apply(
             src.means, src.quats, src.log_scales, src.logits, src.features_dc, src.features_rest, viewmats[0], Ks[0], cfg)

@@ -9,6 +9,8 @@ import sys
 import pytest
 import torch
 
+from tests.util import declared_signatures, header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -19,9 +21,7 @@ def libpath():
 
 
 def _declared_symbols():
-    src = open(os.path.join(ROOT, "include", "bds.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(bds_[a-z0-9_]+)\s*\(", src)))
+    return sorted(set(re.findall(r"\b(bds_[a-z0-9_]+)\s*\(", header())))
 
 
 def test_header_and_library_symbols_match_abi_6(libpath):
@@ -46,6 +46,25 @@ def test_binding_table_matches_header(libpath):
     from bilateral_driving_amd import _lib
     assert sorted(_lib.EXPORTS) == _declared_symbols()
     _lib.lib()  # sets argtypes for every symbol; raises if one is missing
+
+
+def test_every_binding_signature_matches_the_header(libpath):
+    """Every entry of the hand-written table against include/bds.h: result and scalar arguments exactly; a pointer or a
+    ``bds_stream_t`` of the header is any ctypes pointer type (device addresses go as ``c_void_p``, host arrays as ``POINTER(...)``)."""
+    from bilateral_driving_amd import _lib
+
+    def is_pointer(t):
+        return t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer)
+    decl, lib = declared_signatures(), _lib.lib()
+    assert sorted(decl) == sorted(_lib._SIGS) and len(decl) >= 127
+    for name, (res, argtypes) in _lib._SIGS.items():
+        ret, args = decl[name]
+        assert res is ret, (name, res, ret)
+        assert len(argtypes) == len(args), (name, len(argtypes), len(args))
+        for i, (got, want) in enumerate(zip(argtypes, args)):
+            assert is_pointer(got) if want is ctypes.c_void_p else got is want, (name, i, got, want)
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == list(argtypes), name
 
 
 def test_library_is_gfx950_only(libpath):

@@ -2,15 +2,13 @@
 (csrc/gs_math.h project_one / project_one_vjp(..., v_comp, comp_out)) run on the host in float32 through tests/hostmath_aa_shim.hip,
 against float64 autograd through oracle.gs_oracle.project(..., calc_compensations=True) with the compensation in the loss.  No GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import gs_oracle as G
-from tests.util import ROOT, fptr, hostmath, make_scene
+from tests.util import build_shim, fptr, hostmath, make_scene
 
 F64 = torch.float64
 EPS2D = 0.3
@@ -18,14 +16,7 @@ EPS2D = 0.3
 
 @pytest.fixture(scope="module")
 def hm():
-    src = os.path.join(ROOT, "tests", "hostmath_aa_shim.hip")
-    bdir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(bdir, exist_ok=True)
-    so = os.path.join(bdir, "libhostmath_aa.so")
-    deps = [src, os.path.join(ROOT, "bilateral_driving_amd", "csrc", "gs_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", src, "-o", so])
-    return C.CDLL(so)
+    return build_shim("aa")
 
 
 def _scene(kind, seed, W, H):

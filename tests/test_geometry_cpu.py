@@ -13,9 +13,7 @@ next power of ten, 1e-6.  With a camera 10^3 m from the origin (case "far") the 
 to 1.9e-3 on the distances, and the shim's equals it."""
 import ctypes
 import math
-import os
 import re
-import subprocess
 import types
 
 import numpy as np
@@ -23,10 +21,8 @@ import pytest
 import torch
 
 from bilateral_driving_amd import _lib as L
-from bilateral_driving_amd import build as B
 from tests import geometry_ref64 as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.util import build_shim, declared_signatures, header, kernel_resources, short_name
 
 
 # ---- the restatement against known answers -------------------------------------------------------------------------------------------
@@ -76,11 +72,8 @@ def test_validity_edges_and_classes_of_the_restatement():
 
 # ---- the device math on the host ----------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("geometry_shim") / "geometry_shim.so")
-    subprocess.check_call([B._hipcc(), f"--offload-arch={B.ARCH}", "-O2", "-std=c++17", "-fPIC", "-shared",
-                           os.path.join(ROOT, "tests", "hostmath_geometry_shim.hip"), "-o", so])
-    h = ctypes.CDLL(so)
+def shim():
+    h = build_shim("geometry")
     vp = ctypes.c_void_p
     h.hm_geo_unproject.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_float, vp, vp, vp]
     h.hm_geo_trim_count.argtypes = [ctypes.c_longlong, ctypes.c_int]
@@ -189,21 +182,8 @@ def test_host_math_frame_matches_float64_within_the_bound(shim):
 
 # ---- resources, signatures and argument validation ------------------------------------------------------------------------------------
 def test_geometry_kernel_resources():
-    cmd = [B._hipcc(), f"--offload-arch={B.ARCH}", *B.FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c",
-           os.path.join(B.CSRC, "geometry.hip"), "-o", os.devnull]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-2000:]
-    res, cur = {}, None
-    for line in r.stdout.splitlines():
-        m = re.search(r"Function Name: _ZN3bds\d+(\w+?kernel)", line)
-        if m:
-            cur = m.group(1) + ("<1>" if "ILi1E" in line else "")
-            res[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur:
-            res[cur][m.group(1).strip()] = int(m.group(2))
-    want = ("geo_flag_kernel", "geo_scan_kernel", "geo_scatter_kernel", "geo_nn_kernel", "geo_nn_kernel<1>", "geo_select_kernel",
+    res = {short_name(k): v for k, v in kernel_resources("geometry.hip").items()}
+    want = ("geo_flag_kernel", "geo_scan_kernel", "geo_scatter_kernel", "geo_nn_kernel<1>", "geo_nn_kernel<2>", "geo_select_kernel",
             "geo_finish_kernel")
     assert sorted(res) == sorted(want), list(res)
     for k in want:
@@ -214,20 +194,13 @@ def test_geometry_kernel_resources():
 
 
 def test_entries_resolve_with_the_declared_signatures():
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "bds.h")).read(), flags=re.S)
-    decl = {m.group(2): (m.group(1).strip(), [a.strip() for a in m.group(3).split(",")])
-            for m in re.finditer(r"\n(size_t|int)\s+(bds_geometry_metrics\w*|bds_depth_unproject|bds_chamfer_nn)\s*\(([^)]*)\)\s*;", hdr)}
+    hdr = header()
+    decl = {k: v for k, v in declared_signatures().items() if re.fullmatch(r"bds_geometry_metrics\w*|bds_depth_unproject|bds_chamfer_nn", k)}
     assert sorted(decl) == ["bds_chamfer_nn", "bds_depth_unproject", "bds_geometry_metrics", "bds_geometry_metrics_workspace_bytes"]
-
-    def ctype(a):
-        if "*" in a or a.startswith("bds_stream_t"):
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64}[a.split()[0]]
     lib = L.lib()
     for name, (ret, args) in decl.items():
-        res, argtypes = L._SIGS[name]
-        assert res is {"int": ctypes.c_int, "size_t": ctypes.c_size_t}[ret] and list(argtypes) == [ctype(a) for a in args], name
-        assert getattr(lib, name).argtypes == argtypes
+        assert L._SIGS[name] == (ret, args) and ret in (ctypes.c_int, ctypes.c_size_t), name
+        assert getattr(lib, name).argtypes == args, name
     from bilateral_driving_amd import geometry
     for macro, value in (("BDS_GEOMETRY_METRICS_ROW", geometry.ROW), ("BDS_GEOMETRY_QUERY_BLOCK", geometry.QUERY_BLOCK),
                          ("BDS_GEOMETRY_TARGET_TILE", geometry.TARGET_TILE)):

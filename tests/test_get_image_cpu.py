@@ -10,7 +10,6 @@ the same inputs, at least 1e-6; each test prints the figures."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,6 +18,7 @@ import torch
 from bilateral_driving_amd import _lib as L
 from bilateral_driving_amd import build as B
 from tests import get_image_ref64 as R
+from tests.util import build_shim, declared_signatures, header, kernel_resources, short_name
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXACT_INFO = ("pixel_coords", "origins", "normed_time", "img_idx", "frame_idx", "lidar_depth_map") + R.MASK_KEYS
@@ -81,11 +81,8 @@ def test_restatement_equals_the_references_novel_views():
 
 # ---- the device math on the host ----------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("pixels_shim") / "pixels_shim.so")
-    subprocess.check_call([B._hipcc(), f"--offload-arch={B.ARCH}", "-O2", "-std=c++17", "-fPIC", "-shared",
-                           os.path.join(ROOT, "tests", "hostmath_pixels_shim.hip"), "-o", so])
-    h = ctypes.CDLL(so)
+def shim():
+    h = build_shim("pixels")
     vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
     h.hm_px_view.argtypes = [vp, vp, ctypes.c_float, ci, ci, vp, vp, vp, vp, vp]
     h.hm_px_view.restype = None
@@ -225,20 +222,7 @@ def test_windows_equal_torchs_at_awkward_factors(shim, factor):
 # ---- resources, signatures and argument validation ------------------------------------------------------------------------------------
 def test_pixels_kernel_resources():
     assert "pixels.hip" in B.SOURCES
-    cmd = [B._hipcc(), f"--offload-arch={B.ARCH}", *B.FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c",
-           os.path.join(B.CSRC, "pixels.hip"), "-o", os.devnull]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-2000:]
-    res, cur = {}, None
-    for line in r.stdout.splitlines():
-        m = re.search(r"Function Name: _ZN3bds\d+(\w+?kernel)", line)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur:
-            res[cur][m.group(1).strip()] = int(m.group(2))
+    res = {short_name(k): v for k, v in kernel_resources("pixels.hip").items()}
     want = ["view_fields_kernel", "image_resize_aa_kernel", "masks_resize_nearest_kernel"]
     assert sorted(res) == sorted(want), list(res)
     for k in want:
@@ -251,20 +235,13 @@ def test_pixels_kernel_resources():
 
 def test_entries_resolve_with_the_declared_signatures():
     full = open(os.path.join(ROOT, "include", "bds.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", full, flags=re.S)
-    decl = {m.group(2): (m.group(1).strip(), [a.strip() for a in m.group(3).split(",")])
-            for m in re.finditer(r"\n(size_t|int)\s+(bds_view_fields|bds_image_resize_aa|bds_masks_resize_nearest)\s*\(([^)]*)\)\s*;", hdr)}
+    hdr = header()
+    decl = {k: v for k, v in declared_signatures().items() if re.fullmatch(r"bds_view_fields|bds_image_resize_aa|bds_masks_resize_nearest", k)}
     assert sorted(decl) == ["bds_image_resize_aa", "bds_masks_resize_nearest", "bds_view_fields"]
-
-    def ctype(a):
-        if "*" in a or a.startswith("bds_stream_t"):
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double}[a.split()[0]]
     lib = L.lib()
     for name, (ret, args) in decl.items():
-        res, argtypes = L._SIGS[name]
-        assert res is ctypes.c_int and ret == "int" and list(argtypes) == [ctype(a) for a in args], name
-        assert getattr(lib, name).argtypes == argtypes
+        assert L._SIGS[name] == (ret, args) and ret in (ctypes.c_int, ctypes.c_size_t), name
+        assert getattr(lib, name).argtypes == args, name
     P = module()
     assert f"#define BDS_PIXELS_MAX_MASKS {P.MAX_MASKS}\n" in hdr and P.MAX_MASKS == 5
     assert f"#define BDS_PIXELS_MAX_SCALE {P.MAX_SCALE}\n" in hdr

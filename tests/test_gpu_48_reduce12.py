@@ -17,7 +17,7 @@ import torch
 from oracle import bilagrid_oracle as BO
 from oracle import gs_oracle as G
 from tests import reduce12_model as M
-from tests.util import make_scene
+from tests.util import kernel_resources, make_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -319,7 +319,7 @@ def test_pyramid_general_path_grid_gradient_channels_against_oracle(env, cells, 
 # ---- resource report -------------------------------------------------------------------------------------------------------------
 def test_backward_compositors_keep_their_registers():
     from tests import test_kernel_resources as R
-    rep = R.report("rasterize.hip")
+    rep = kernel_resources("rasterize.hip")
     pins = {k: v for k, v in R.MIN_OCCUPANCY.items() if k.startswith("rasterize_bwd")}
     assert len(pins) == 2
     pins["rasterize_fwd_wave_kernelILi4ELb1ELb1E"] = R.MIN_OCCUPANCY["rasterize_fwd_wave_kernelILi4ELb1ELb1E"]

@@ -1,14 +1,11 @@
 """Register budget of the hot kernels, read from hipcc's own resource report (-Rpass-analysis=kernel-resource-usage) with the product's
 build flags: no kernel may spill to scratch, and the kernels whose speed depends on how many waves fit a SIMD keep the occupancy they
 were tuned at.  Cross-compiles for gfx950, needs no GPU."""
-import os
-import re
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-from bilateral_driving_amd import build as B
+from tests.util import kernel_resources
 
 FILES = ["rasterize.hip", "tiles.hip", "bilagrid.hip", "bilagrid_cells.hip", "bilagrid_tile.hip", "sh.hip", "project.hip", "mlp_head.hip", "loss.hip", "refine.hip"]
 # scratch allowed (bytes / lane): a shape no shipped config uses
@@ -37,28 +34,10 @@ MIN_OCCUPANCY = {
 }
 
 
-def report(src):
-    cmd = [B._hipcc(), f"--offload-arch={B.ARCH}", *B.FLAGS, *B.EXTRA_FLAGS.get(src, []), "-Rpass-analysis=kernel-resource-usage", "-c",
-           os.path.join(B.CSRC, src), "-o", os.devnull]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-2000:]
-    out, cur = {}, None
-    for line in r.stdout.splitlines():
-        m = re.search(r"Function Name: _ZN3bds\d+(\S+)", line)
-        if m:
-            cur = m.group(1)
-            out[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur:
-            out[cur][m.group(1).strip()] = int(m.group(2))
-    return out
-
-
 @pytest.fixture(scope="module")
 def kernels():
     with ThreadPoolExecutor(max_workers=8) as ex:
-        reps = list(ex.map(report, FILES))
+        reps = list(ex.map(kernel_resources, FILES))
     merged = {}
     for r in reps:
         merged.update(r)

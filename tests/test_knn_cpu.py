@@ -16,9 +16,7 @@ logarithm may add: logf is specified to 1 ulp, one float32 ulp of a log-scale of
 device's logf is about 1.5 ulp off at its worst on these values, inside the floor)."""
 import ctypes
 import math
-import os
 import re
-import subprocess
 import types
 
 import numpy as np
@@ -26,10 +24,9 @@ import pytest
 import torch
 
 from bilateral_driving_amd import _lib as L
-from bilateral_driving_amd import build as B
 from tests import knn_ref64 as R
+from tests.util import build_shim, declared_signatures, header, kernel_resources, short_name
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIST_RTOL = 1e-6
 SCALE_FLOOR = 1e-6
 RIGID_CLAMP = (0.002, 100.0)
@@ -92,11 +89,8 @@ def test_known_answers_of_the_restatement():
 
 # ---- the device math on the host ----------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("knn_shim") / "knn_shim.so")
-    subprocess.check_call([B._hipcc(), f"--offload-arch={B.ARCH}", "-O2", "-std=c++17", "-fPIC", "-shared",
-                           os.path.join(ROOT, "tests", "hostmath_knn_shim.hip"), "-o", so])
-    h = ctypes.CDLL(so)
+def shim():
+    h = build_shim("knn")
     vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     h.hm_knn_pair.argtypes = [vp, vp]
     h.hm_knn_pair.restype = cf
@@ -273,20 +267,7 @@ def test_host_scale_epilogue_is_within_the_bound(shim, clamp):
 
 # ---- resources, signatures and argument validation ------------------------------------------------------------------------------------
 def test_knn_kernel_resources():
-    cmd = [B._hipcc(), f"--offload-arch={B.ARCH}", *B.FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c",
-           os.path.join(B.CSRC, "knn.hip"), "-o", os.devnull]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-2000:]
-    res, cur = {}, None
-    for line in r.stdout.splitlines():
-        m = re.search(r"Function Name: _ZN3bds\d+(\w+?kernel)(?:ILi(\d)E)?", line)
-        if m:
-            cur = m.group(1) + (f"<{m.group(2)}>" if m.group(2) else "")
-            res[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur:
-            res[cur][m.group(1).strip()] = int(m.group(2))
+    res = {short_name(k): v for k, v in kernel_resources("knn.hip").items()}
     want = ["knn_clear_kernel", "knn_bounds_kernel", "knn_hist_kernel", "knn_trim_kernel", "knn_count_kernel", "knn_scan_kernel",
             "knn_scatter_kernel"]
     want += [f"knn_{w}_kernel<{k}>" for w in ("query", "fallback") for k in range(1, 9)]
@@ -301,20 +282,13 @@ def test_knn_kernel_resources():
 
 
 def test_entries_resolve_with_the_declared_signatures():
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "bds.h")).read(), flags=re.S)
-    decl = {m.group(2): (m.group(1).strip(), [a.strip() for a in m.group(3).split(",")])
-            for m in re.finditer(r"\n(size_t|int)\s+(bds_knn\w*)\s*\(([^)]*)\)\s*;", hdr)}
+    hdr = header()
+    decl = {k: v for k, v in declared_signatures().items() if re.fullmatch(r"bds_knn\w*", k)}
     assert sorted(decl) == ["bds_knn_self", "bds_knn_workspace_bytes"]
-
-    def ctype(a):
-        if "*" in a or a.startswith("bds_stream_t"):
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64, "float": ctypes.c_float}[a.split()[0]]
     lib = L.lib()
     for name, (ret, args) in decl.items():
-        res, argtypes = L._SIGS[name]
-        assert res is {"int": ctypes.c_int, "size_t": ctypes.c_size_t}[ret] and list(argtypes) == [ctype(a) for a in args], name
-        assert getattr(lib, name).argtypes == argtypes
+        assert L._SIGS[name] == (ret, args) and ret in (ctypes.c_int, ctypes.c_size_t), name
+        assert getattr(lib, name).argtypes == args, name
     from bilateral_driving_amd import init
     for macro, value in (("BDS_KNN_MAX_K", init.MAX_K), ("BDS_KNN_MAX_POINTS", init.MAX_POINTS), ("BDS_KNN_QUERY_BLOCK", init.QUERY_BLOCK),
                          ("BDS_KNN_TARGET_TILE", init.TARGET_TILE), ("BDS_KNN_RING_MAX", init.RING_MAX),

@@ -17,7 +17,6 @@ was asked for, and so also passes on a tree without the feature (the module stil
 import ctypes
 import os
 import re
-import subprocess
 import types
 
 import numpy as np
@@ -27,6 +26,7 @@ import torch
 from bilateral_driving_amd import _lib as L
 from bilateral_driving_amd import build as B
 from tests import lidar_ref64 as R
+from tests.util import build_shim, declared_signatures, header, kernel_resources, short_name
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("shared", "sparse")
@@ -130,11 +130,8 @@ def test_every_random_seed_stays_within_the_cap_for_the_restatement_alone():
 
 # ---- the device math on the host ----------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("lidar_shim") / "lidar_shim.so")
-    subprocess.check_call([B._hipcc(), f"--offload-arch={B.ARCH}", "-O2", "-std=c++17", "-fPIC", "-shared",
-                           os.path.join(ROOT, "tests", "hostmath_lidar_shim.hip"), "-o", so])
-    h = ctypes.CDLL(so)
+def shim():
+    h = build_shim("lidar")
     vp, ci, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
     h.hm_lidar_project.argtypes = [vp, vp, ci, ci, vp, vp, vp]
     h.hm_lidar_views.argtypes = [ci, ci, ci, ll] + [vp] * 9
@@ -281,21 +278,7 @@ def test_host_downsampler_takes_a_scale_factor_above_one_as_torch_does(shim):
 
 # ---- resources, signatures and argument validation ------------------------------------------------------------------------------------
 def test_lidar_kernel_resources():
-    cmd = [B._hipcc(), f"--offload-arch={B.ARCH}", *B.FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c",
-           os.path.join(B.CSRC, "lidar.hip"), "-o", os.devnull]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-2000:]
-    res, cur = {}, None
-    for line in r.stdout.splitlines():
-        m = re.search(r"Function Name: _ZN3bds\d+(\w+?kernel)(?:ILb(\d)E|ILi(\d)E)?", line)
-        if m:
-            t = m.group(2) if m.group(2) is not None else m.group(3)
-            cur = m.group(1) + (f"<{t}>" if t is not None else "")
-            res[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur:
-            res[cur][m.group(1).strip()] = int(m.group(2))
+    res = {short_name(k): v for k, v in kernel_resources("lidar.hip").items()}
     want = ["lidar_points_kernel<0>", "lidar_points_kernel<1>", "lidar_resolve_kernel", "lidar_visible_kernel", "lidar_boxes_kernel<0>",
             "lidar_boxes_kernel<1>", "lidar_boxes_kernel<2>", "lidar_scan_kernel", "lidar_downsample_kernel"]
     assert sorted(res) == sorted(want), list(res)
@@ -310,21 +293,14 @@ def test_lidar_kernel_resources():
 
 
 def test_entries_resolve_with_the_declared_signatures():
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "bds.h")).read(), flags=re.S)
-    decl = {m.group(2): (m.group(1).strip(), [a.strip() for a in m.group(3).split(",")])
-            for m in re.finditer(r"\n(size_t|int)\s+(bds_lidar\w*)\s*\(([^)]*)\)\s*;", hdr)}
+    hdr = header()
+    decl = {k: v for k, v in declared_signatures().items() if re.fullmatch(r"bds_lidar\w*", k)}
     assert sorted(decl) == ["bds_lidar_boxes_workspace_bytes", "bds_lidar_depth_downsample", "bds_lidar_points_in_boxes",
                             "bds_lidar_points_in_boxes_count", "bds_lidar_points_in_boxes_emit", "bds_lidar_project", "bds_lidar_visible"]
-
-    def ctype(a):
-        if "*" in a or a.startswith("bds_stream_t"):
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64, "float": ctypes.c_float}[a.split()[0]]
     lib = L.lib()
     for name, (ret, args) in decl.items():
-        res, argtypes = L._SIGS[name]
-        assert res is {"int": ctypes.c_int, "size_t": ctypes.c_size_t}[ret] and list(argtypes) == [ctype(a) for a in args], name
-        assert getattr(lib, name).argtypes == argtypes
+        assert L._SIGS[name] == (ret, args) and ret in (ctypes.c_int, ctypes.c_size_t), name
+        assert getattr(lib, name).argtypes == args, name
     from bilateral_driving_amd import lidar
     for macro, value in (("BDS_LIDAR_VIEW_CHUNK", lidar.VIEW_CHUNK), ("BDS_LIDAR_BOX_CHUNK", lidar.BOX_CHUNK)):
         assert f"#define {macro} {value}\n" in hdr, macro

@@ -7,19 +7,16 @@ Measured over the 21 cases (printed by the test): the float32 restatement's wors
 uxx - ux ux cancels), the shim's 3.0e-8 everywhere -- it takes the window sums in double and rounds S once."""
 import ctypes
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from bilateral_driving_amd import _lib as L
-from bilateral_driving_amd import build as B
 from tests import metrics_ref64 as R
+from tests.util import build_shim, declared_signatures, header, kernel_resources
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C1, C2 = 0.01 ** 2, 0.03 ** 2
 
 
@@ -62,11 +59,8 @@ def test_masked_values_are_the_uncropped_mean_and_the_mask_psnr():
 
 # ---- the device math on the host ----------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("metrics_shim") / "metrics_shim.so")
-    subprocess.check_call([B._hipcc(), f"--offload-arch={B.ARCH}", "-O2", "-std=c++17", "-fPIC", "-shared",
-                           os.path.join(ROOT, "tests", "hostmath_metrics_shim.hip"), "-o", so])
-    h = ctypes.CDLL(so)
+def shim():
+    h = build_shim("metrics")
     h.hm_metrics_map.argtypes = [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3
     h.hm_metrics_reflect.argtypes = [ctypes.c_int] * 2
     h.hm_metrics_psnr.argtypes = [ctypes.c_double] * 2
@@ -99,20 +93,7 @@ def test_host_math_map_matches_float64_everywhere(shim):
 
 # ---- resources, signatures and argument validation ------------------------------------------------------------------------------------
 def test_metrics_kernel_resources():
-    cmd = [B._hipcc(), f"--offload-arch={B.ARCH}", *B.FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c",
-           os.path.join(B.CSRC, "metrics.hip"), "-o", os.devnull]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-2000:]
-    res, cur = {}, None
-    for line in r.stdout.splitlines():
-        m = re.search(r"Function Name: _ZN3bds\d+(\S+)", line)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur:
-            res[cur][m.group(1).strip()] = int(m.group(2))
+    res = kernel_resources("metrics.hip")
     for prefix in ("metrics_tile_kernel", "metrics_reduce_kernel"):
         ks = [k for k in res if k.startswith(prefix)]
         assert len(ks) == 1, (prefix, list(res))
@@ -122,18 +103,13 @@ def test_metrics_kernel_resources():
 
 
 def test_entries_resolve_with_the_declared_signatures():
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "bds.h")).read(), flags=re.S)
-    decl = {m.group(2): (m.group(1).strip(), [a.strip() for a in m.group(3).split(",")])
-            for m in re.finditer(r"\n(size_t|int)\s+(bds_image_metrics\w*)\s*\(([^)]*)\)\s*;", hdr)}
+    hdr = header()
+    decl = {k: v for k, v in declared_signatures().items() if re.fullmatch(r"bds_image_metrics\w*", k)}
     assert sorted(decl) == ["bds_image_metrics", "bds_image_metrics_workspace_bytes"]
-
-    def ctype(a):
-        return ctypes.c_void_p if "*" in a or a.startswith("bds_stream_t") else {"int": ctypes.c_int, "size_t": ctypes.c_size_t}[a.split()[0]]
     lib = L.lib()
     for name, (ret, args) in decl.items():
-        res, argtypes = L._SIGS[name]
-        assert res is {"int": ctypes.c_int, "size_t": ctypes.c_size_t}[ret] and list(argtypes) == [ctype(a) for a in args], name
-        assert getattr(lib, name).argtypes == argtypes
+        assert L._SIGS[name] == (ret, args) and ret in (ctypes.c_int, ctypes.c_size_t), name
+        assert getattr(lib, name).argtypes == args, name
     assert "BDS_IMAGE_METRICS_ROW 14" in hdr
     from bilateral_driving_amd import metrics
     assert metrics.ROW == 14 and lib.bds_abi_version() == L.ABI_VERSION == 6

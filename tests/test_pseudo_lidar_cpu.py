@@ -15,7 +15,6 @@ One test here needs nothing of the product: the check that every random seed sta
 import ctypes
 import os
 import re
-import subprocess
 import types
 
 import numpy as np
@@ -25,6 +24,7 @@ import torch
 from bilateral_driving_amd import _lib as L
 from bilateral_driving_amd import build as B
 from tests import pseudo_lidar_ref64 as R
+from tests.util import build_shim, declared_signatures, header, kernel_resources, short_name
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEPTH_NAMES = tuple(R.GOLDEN_DEPTH)
@@ -93,11 +93,8 @@ def test_every_random_seed_stays_within_the_caps_for_the_restatement_alone():
 
 # ---- the device math on the host ----------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("pseudo_lidar_shim") / "pseudo_lidar_shim.so")
-    subprocess.check_call([B._hipcc(), f"--offload-arch={B.ARCH}", "-O2", "-std=c++17", "-fPIC", "-shared",
-                           os.path.join(ROOT, "tests", "hostmath_pseudo_lidar_shim.hip"), "-o", so])
-    h = ctypes.CDLL(so)
+def shim():
+    h = build_shim("pseudo_lidar")
     vp, ci, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
     h.hm_pl_pixel.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.c_float, vp]
     h.hm_pl_point.argtypes = [vp, ci, ci, ci, ci, vp]
@@ -238,20 +235,7 @@ def test_host_known_answers(shim):
 # ---- resources, signatures and argument validation ------------------------------------------------------------------------------------
 def test_pseudo_lidar_kernel_resources():
     assert "pseudo_lidar.hip" in B.SOURCES
-    cmd = [B._hipcc(), f"--offload-arch={B.ARCH}", *B.FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c",
-           os.path.join(B.CSRC, "pseudo_lidar.hip"), "-o", os.devnull]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-2000:]
-    res, cur = {}, None
-    for line in r.stdout.splitlines():
-        m = re.search(r"Function Name: _ZN3bds\d+(\w+?kernel)(?:ILb(\d)E)?", line)
-        if m:
-            cur = m.group(1) + (f"<{m.group(2)}>" if m.group(2) is not None else "")
-            res[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur:
-            res[cur][m.group(1).strip()] = int(m.group(2))
+    res = {short_name(k): v for k, v in kernel_resources("pseudo_lidar.hip").items()}
     want = ["pseudo_lidar_bin_kernel<0>", "pseudo_lidar_bin_kernel<1>", "pseudo_lidar_emit_kernel<0>", "pseudo_lidar_emit_kernel<1>"]
     assert sorted(res) == sorted(want), list(res)
     for k in want:
@@ -265,20 +249,13 @@ def test_pseudo_lidar_kernel_resources():
 
 def test_entries_resolve_with_the_declared_signatures():
     full = open(os.path.join(ROOT, "include", "bds.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", full, flags=re.S)
-    decl = {m.group(2): (m.group(1).strip(), [a.strip() for a in m.group(3).split(",")])
-            for m in re.finditer(r"\n(size_t|int)\s+(bds_pseudo_lidar\w*)\s*\(([^)]*)\)\s*;", hdr)}
+    hdr = header()
+    decl = {k: v for k, v in declared_signatures().items() if re.fullmatch(r"bds_pseudo_lidar\w*", k)}
     assert sorted(decl) == ["bds_pseudo_lidar_from_depth", "bds_pseudo_lidar_from_points"]
-
-    def ctype(a):
-        if "*" in a or a.startswith("bds_stream_t"):
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64}[a.split()[0]]
     lib = L.lib()
     for name, (ret, args) in decl.items():
-        res, argtypes = L._SIGS[name]
-        assert res is ctypes.c_int and ret == "int" and list(argtypes) == [ctype(a) for a in args], name
-        assert getattr(lib, name).argtypes == argtypes
+        assert L._SIGS[name] == (ret, args) and ret in (ctypes.c_int, ctypes.c_size_t), name
+        assert getattr(lib, name).argtypes == args, name
     P = module()
     for macro, value in (("BDS_PSEUDO_LIDAR_BEAMS", P.BEAMS), ("BDS_PSEUDO_LIDAR_VERTICAL", P.VERTICAL), ("BDS_PSEUDO_LIDAR_CLASSIC", P.CLASSIC)):
         assert f"#define {macro} {value}\n" in hdr, macro

@@ -8,17 +8,15 @@ Measured on the 4000 shim rows (printed by the test): float32 framework ops agai
 gradient), so the shim is allowed 2.2e-5 and 1.7e-5; it measures 5.7e-6 and 4.4e-6."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from bilateral_driving_amd import _lib as L
-from bilateral_driving_amd import build as B
 from bilateral_driving_amd import pvg
 from tests.pvg_ref64 import BAND, OUTS, RAW, SETTINGS, T, marg64, measured_bound, random_rows, run_framework, scaled_err, settle_clamp
+from tests.util import build_shim, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "pvg_time.npz")
@@ -66,11 +64,8 @@ def test_cpu_tensors_raise():
 
 # ---- the device math on the host ----------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("pvg_shim") / "pvg_shim.so")
-    subprocess.check_call([B._hipcc(), f"--offload-arch={B.ARCH}", "-O2", "-std=c++17", "-fPIC", "-shared",
-                           os.path.join(ROOT, "tests", "hostmath_pvg_shim.hip"), "-o", so])
-    h = ctypes.CDLL(so)
+def shim():
+    h = build_shim("pvg")
     vp, ci, cf, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double
     h.hm_pvg_fwd.argtypes = [ci, ci, ci, cf, cf, ci, cd] + [vp] * 15
     h.hm_pvg_bwd.argtypes = [ci, cf, cf, ci, cd] + [vp] * 16
@@ -115,20 +110,7 @@ def test_host_math_matches_float64_autograd(shim, rows, setting):
 
 # ---- resources and argument validation ---------------------------------------------------------------------------------------------
 def test_pvg_kernel_resources():
-    cmd = [B._hipcc(), f"--offload-arch={B.ARCH}", *B.FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c",
-           os.path.join(B.CSRC, "pvg.hip"), "-o", os.devnull]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-2000:]
-    res, cur = {}, None
-    for line in r.stdout.splitlines():
-        m = re.search(r"Function Name: _ZN3bds\d+(\S+)", line)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur:
-            res[cur][m.group(1).strip()] = int(m.group(2))
+    res = kernel_resources("pvg.hip")
     # (count, scan: one instance each; write, backward: one per colour mode 0..3 and the sigmoid form)
     for prefix, (n, occ) in {"pvg_count_kernel": (1, 8), "pvg_scan_kernel": (1, 8), "pvg_write_kernel": (5, 8), "pvg_bwd_kernel": (5, 7)}.items():
         ks = [k for k in res if k.startswith(prefix)]

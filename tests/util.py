@@ -1,10 +1,15 @@
-"""Shared helpers for the tests (synthetic scenes, error metrics, host-math shim loader)."""
+"""Shared helpers for the tests: synthetic scenes, error metrics, the host-math shim loader, hipcc's kernel resource report and the
+header's declarations."""
 import ctypes
+import functools
 import os
+import re
 import subprocess
 
 import numpy as np
 import torch
+
+from bilateral_driving_amd import build as B
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -92,25 +97,77 @@ def rel_err(a, b):
     return float((a.detach() - b.detach()).abs().max() / b.detach().abs().max().clamp(min=1e-12))
 
 
-_HM = None
-
-
-def hostmath():
-    """Build (hipcc, host side only) and load the test-only shim around the kernels' HD math."""
-    global _HM
-    if _HM is not None:
-        return _HM
-    src = os.path.join(ROOT, "tests", "hostmath_shim.hip")
-    bdir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(bdir, exist_ok=True)
-    so = os.path.join(bdir, "libhostmath.so")
-    deps = [src, os.path.join(ROOT, "bilateral_driving_amd", "csrc", "gs_math.h"),
-            os.path.join(ROOT, "bilateral_driving_amd", "csrc", "bilagrid_math.h")]
+def build_shim(stem=""):
+    """Build (hipcc, host side only) and load tests/hostmath_<stem>_shim.hip, a test-only shim around the kernels' HD math; rebuilt
+    when the shim or one of the kernels' headers is newer than the library."""
+    name = f"hostmath_{stem}_shim" if stem else "hostmath_shim"
+    src = os.path.join(ROOT, "tests", name + ".hip")
+    so = os.path.join(ROOT, "tests", "_build", f"lib{name}.so")
+    os.makedirs(os.path.dirname(so), exist_ok=True)
+    deps = [src] + [os.path.join(B.CSRC, f) for f in os.listdir(B.CSRC) if f.endswith(".h")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        hipcc = "/opt/rocm/bin/hipcc"
-        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", src, "-o", so])
-    _HM = ctypes.CDLL(so)
-    return _HM
+        tmp = f"{so}.{os.getpid()}.tmp"
+        subprocess.check_call([B._hipcc(), f"--offload-arch={B.ARCH}", "-O2", "-std=c++17", "-fPIC", "-shared", src, "-o", tmp])
+        os.replace(tmp, so)
+    return ctypes.CDLL(so)
+
+
+@functools.lru_cache(maxsize=None)
+def hostmath():
+    """The shim around the projection's and the bilateral grid's HD math (tests/hostmath_shim.hip)."""
+    return build_shim()
+
+
+@functools.lru_cache(maxsize=None)
+def kernel_resources(src):
+    """hipcc's resource report (-Rpass-analysis=kernel-resource-usage) of csrc/<src> under the product's build flags:
+    {mangled kernel name after _ZN3bds<digits>: {remark: int}}.  Cross-compiles, needs no GPU; one compile per file and session."""
+    cmd = [B._hipcc(), f"--offload-arch={B.ARCH}", *B.FLAGS, *B.EXTRA_FLAGS.get(src, []), "-Rpass-analysis=kernel-resource-usage", "-c",
+           os.path.join(B.CSRC, src), "-o", os.devnull]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout[-2000:]
+    out, cur = {}, None
+    for line in r.stdout.splitlines():
+        m = re.search(r"Function Name: _ZN3bds\d+(\S+)", line)
+        if m:
+            cur = m.group(1)
+            out[cur] = {}
+            continue
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
+        if m and cur:
+            out[cur][m.group(1).strip()] = int(m.group(2))
+    return out
+
+
+def short_name(mangled):
+    """``lidar_boxes_kernelILi2EEvl...`` -> ``lidar_boxes_kernel<2>``: the kernel's name with its first template argument where that
+    is a bool or a one-digit int, without its parameter types."""
+    m = re.match(r"(\w+?kernel)(?:IL[bi](\d)E)?", mangled)
+    return m.group(1) + (f"<{m.group(2)}>" if m.group(2) is not None else "")
+
+
+_SCALARS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+@functools.lru_cache(maxsize=None)
+def header():
+    """include/bds.h without its comments."""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "bds.h")).read(), flags=re.S)
+
+
+@functools.lru_cache(maxsize=None)
+def declared_signatures():
+    """{entry: (return ctype, [argument ctypes])} of every function include/bds.h declares.  Scalars are their ctypes type; every
+    pointer and ``bds_stream_t`` is ``c_void_p`` (a ``const char *`` result: ``c_char_p``)."""
+    def ctype(a):
+        if "*" in a or a.startswith("bds_stream_t"):
+            return ctypes.c_void_p
+        return _SCALARS[a.split()[0]]
+    out = {}
+    for m in re.finditer(r"\n((?:const\s+)?\w+\s*\*?)\s*(bds_\w+)\s*\(([^)]*)\)\s*;", header()):
+        ret, args = " ".join(m.group(1).split()), [a.strip() for a in m.group(3).split(",")]
+        out[m.group(2)] = (ctypes.c_char_p if ret == "const char *" else ctype(ret), [] if args == ["void"] else [ctype(a) for a in args])
+    return out
 
 
 def fptr(a):
