@@ -92,6 +92,12 @@ __device__ __forceinline__ float wave_sum_to_lane63(float v) {
   v += dpp_f<0x143, 0xc, false>(v);  // row_bcast:31 into rows 2,3 -> lane 63 holds the wave sum
   return v;
 }
+// wave64 sum that leaves the total in EVERY lane (xor butterfly: another summation order than the DPP form above)
+__device__ __forceinline__ float wave_sum_all(float v) {
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 
 // ---- 16-value wave64 transpose-reduce ----------------------------------------------------------
 // Sums 16 per-lane values over the 64 lanes in 35 VALU instructions (vs 16 x 6 for one-at-a-time

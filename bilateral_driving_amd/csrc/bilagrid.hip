@@ -20,43 +20,16 @@
 namespace bds {
 
 // ---- A: per-level low-resolution slice -------------------------------------------------------
-// trilinear sample of the 12 channels from a CELL-MAJOR copy of the grid ([cell][12] as three float4): the arithmetic (and its
-// order) is slice_sample's, the eight taps are three 16-byte reads each instead of twelve scalar gathers
-__device__ __forceinline__ void slice_sample_cells(const float4 *__restrict__ cells, int gx, int gy, const Cell &c, float *out12) {
+// trilinear sample of the 12 channels (kOut) and / or its d/d(iz) (kDz) from a CELL-MAJOR copy of the grid ([cell][12] as three
+// float4): the eight taps are three 16-byte reads each instead of twelve scalar gathers
+template <bool kOut, bool kDz>
+__device__ __forceinline__ void slice_cells(const float4 *__restrict__ cells, int gx, int gy, const Cell &c, float *out12, float *dz12) {
   const int plane = gy * gx;
   const int o00 = c.y0 * gx + c.x0, o01 = c.y0 * gx + c.x1, o10 = c.y1 * gx + c.x0, o11 = c.y1 * gx + c.x1;
-  const float w00 = (1.f - c.fy) * (1.f - c.fx), w01 = (1.f - c.fy) * c.fx, w10 = c.fy * (1.f - c.fx), w11 = c.fy * c.fx;
-  const float4 *g0 = cells + (int64_t)c.z0 * plane * 3, *g1 = cells + (int64_t)c.z1 * plane * 3;
-#pragma unroll
-  for (int q = 0; q < 3; q++) {
-    const float4 a00 = g0[o00 * 3 + q], a01 = g0[o01 * 3 + q], a10 = g0[o10 * 3 + q], a11 = g0[o11 * 3 + q];
-    const float4 b00 = g1[o00 * 3 + q], b01 = g1[o01 * 3 + q], b10 = g1[o10 * 3 + q], b11 = g1[o11 * 3 + q];
-    const float ax = a00.x * w00 + a01.x * w01 + a10.x * w10 + a11.x * w11, bx = b00.x * w00 + b01.x * w01 + b10.x * w10 + b11.x * w11;
-    const float ay = a00.y * w00 + a01.y * w01 + a10.y * w10 + a11.y * w11, by = b00.y * w00 + b01.y * w01 + b10.y * w10 + b11.y * w11;
-    const float az = a00.z * w00 + a01.z * w01 + a10.z * w10 + a11.z * w11, bz = b00.z * w00 + b01.z * w01 + b10.z * w10 + b11.z * w11;
-    const float aw = a00.w * w00 + a01.w * w01 + a10.w * w10 + a11.w * w11, bw = b00.w * w00 + b01.w * w01 + b10.w * w10 + b11.w * w11;
-    out12[q * 4 + 0] = ax * (1.f - c.fz) + bx * c.fz;
-    out12[q * 4 + 1] = ay * (1.f - c.fz) + by * c.fz;
-    out12[q * 4 + 2] = az * (1.f - c.fz) + bz * c.fz;
-    out12[q * 4 + 3] = aw * (1.f - c.fz) + bw * c.fz;
-  }
-}
-
-// d(slice)/d(iz) of the 12 channels from the cell-major copy (slice_sample's dz: upper plane minus lower plane)
-__device__ __forceinline__ void slice_dz_cells(const float4 *__restrict__ cells, int gx, int gy, const Cell &c, float *dz12) {
-  const int plane = gy * gx;
-  const int o00 = c.y0 * gx + c.x0, o01 = c.y0 * gx + c.x1, o10 = c.y1 * gx + c.x0, o11 = c.y1 * gx + c.x1;
-  const float w00 = (1.f - c.fy) * (1.f - c.fx), w01 = (1.f - c.fy) * c.fx, w10 = c.fy * (1.f - c.fx), w11 = c.fy * c.fx;
-  const float4 *g0 = cells + (int64_t)c.z0 * plane * 3, *g1 = cells + (int64_t)c.z1 * plane * 3;
-#pragma unroll
-  for (int q = 0; q < 3; q++) {
-    const float4 a00 = g0[o00 * 3 + q], a01 = g0[o01 * 3 + q], a10 = g0[o10 * 3 + q], a11 = g0[o11 * 3 + q];
-    const float4 b00 = g1[o00 * 3 + q], b01 = g1[o01 * 3 + q], b10 = g1[o10 * 3 + q], b11 = g1[o11 * 3 + q];
-    dz12[q * 4 + 0] = (b00.x * w00 + b01.x * w01 + b10.x * w10 + b11.x * w11) - (a00.x * w00 + a01.x * w01 + a10.x * w10 + a11.x * w11);
-    dz12[q * 4 + 1] = (b00.y * w00 + b01.y * w01 + b10.y * w10 + b11.y * w11) - (a00.y * w00 + a01.y * w01 + a10.y * w10 + a11.y * w11);
-    dz12[q * 4 + 2] = (b00.z * w00 + b01.z * w01 + b10.z * w10 + b11.z * w11) - (a00.z * w00 + a01.z * w01 + a10.z * w10 + a11.z * w11);
-    dz12[q * 4 + 3] = (b00.w * w00 + b01.w * w01 + b10.w * w10 + b11.w * w11) - (a00.w * w00 + a01.w * w01 + a10.w * w10 + a11.w * w11);
-  }
+  float w00, w01, w10, w11;
+  corner_weights(c.fx, c.fy, w00, w01, w10, w11);
+  trilinear12<kOut, kDz>(cells + (int64_t)c.z0 * plane * 3, cells + (int64_t)c.z1 * plane * 3, o00 * 3, o01 * 3, o10 * 3, o11 * 3, w00, w01,
+                         w10, w11, c.fz, out12, dz12);
 }
 
 // kLds: the level's grid(s) (n_avg * 12*gl*gy*gx floats) are staged cell-major in the workgroup's LDS once, and the workgroup then
@@ -95,7 +68,7 @@ __global__ __launch_bounds__(kBgBlock) void ms_lowres_fwd_kernel(MsParams p, Lev
     for (int k = 0; k < 12; k++) acc[k] = 0.f;
     for (int n = 0; n < L.n_avg; n++) {
       float a[12];
-      if (kLds) slice_sample_cells(reinterpret_cast<const float4 *>(lds_grid) + (int64_t)n * vol * 3, L.gx, L.gy, c, a);
+      if (kLds) slice_cells<true, false>(reinterpret_cast<const float4 *>(lds_grid) + (int64_t)n * vol * 3, L.gx, L.gy, c, a, nullptr);
       else slice_sample(L.grid + (int64_t)n * gsz, L.gx, L.gy, L.gl, c, a, nullptr);
 #pragma unroll
       for (int k = 0; k < 12; k++) acc[k] += a[k];
@@ -146,11 +119,7 @@ __device__ __forceinline__ void upsample_affine(const LevelDev &L, int H, int W,
 template <int NL, bool kTrain>  // NL >= p.nlevels: bounds the static unrolling (registers) of the level loop
 __global__ __launch_bounds__(kBgBlock) void ms_apply_fwd_kernel(MsParams p, float *__restrict__ out, TrainLoss tl) {
   __shared__ float red[kBgBlock / kWave];
-  if (kTrain && (int)blockIdx.x >= tl.pix_blocks) {   // the TV term of the loss: one grid element per thread
-    const float t = block_sum_to_thread0(tv_train_element(tl.T, (int)blockIdx.x - tl.pix_blocks, tl.v_loss), red);
-    if (threadIdx.x == 0 && t != 0.f) atomicAdd(tl.loss + (size_t)(blockIdx.x & (tl.loss_slots - 1)) * kLossSlotStride, t);
-    return;
-  }
+  if (train_tv_workgroup<kTrain>(tl, red)) return;
   // each XCD works on one contiguous band of the image: the rows of the low-res maps that 2f consecutive pixel rows share are then
   // fetched into ONE private L2 (measured before: 236 MB of fabric traffic for 136 MB of distinct data)
   const int pix = xcd_contiguous((int)blockIdx.x, kTrain ? tl.pix_blocks : (int)gridDim.x) * kBgBlock + (int)threadIdx.x;
@@ -174,22 +143,9 @@ __global__ __launch_bounds__(kBgBlock) void ms_apply_fwd_kernel(MsParams p, floa
         apply_affine(A, r, g, b);
       }
     }
-    const int p3 = times3(pix);
-    out[p3] = r; out[p3 + 1] = g; out[p3 + 2] = b;
-    if (p.depth_out) p.depth_out[pix] = p.rgb[(pix << 2) + 3] / fmaxf(p.alpha[pix], 1e-10f);
-    if (kTrain) {   // photometric L1 of the pixel just produced + its gradient (torch: sign(0) = 0)
-      const float gs = tl.v_loss * tl.inv_n;
-      const float d0 = r - tl.target[p3], d1 = g - tl.target[p3 + 1], d2 = b - tl.target[p3 + 2];
-      l1 = fabsf(d0) + fabsf(d1) + fabsf(d2);
-      tl.v_out[p3] = d0 > 0.f ? gs : (d0 < 0.f ? -gs : 0.f);
-      tl.v_out[p3 + 1] = d1 > 0.f ? gs : (d1 < 0.f ? -gs : 0.f);
-      tl.v_out[p3 + 2] = d2 > 0.f ? gs : (d2 < 0.f ? -gs : 0.f);
-    }
+    l1 = emit_pixel<kTrain>(p, tl, out, pix, r, g, b);
   }
-  if (kTrain) {
-    const float t = block_sum_to_thread0(l1, red);
-    if (threadIdx.x == 0 && t != 0.f) atomicAdd(tl.loss + (size_t)(blockIdx.x & (tl.loss_slots - 1)) * kLossSlotStride, t * tl.inv_n);
-  }
+  if (kTrain) l1_commit(tl, l1, red);
 }
 
 // ---- C: full-resolution backward: direct route + per-level (P, Q) ------------------------------------
@@ -387,13 +343,6 @@ __global__ __launch_bounds__(kBgBlock) void ms_apply_bwd_x_kernel(MsParams p, co
   }
 }
 
-// wave64 sum leaving the result in every lane (used only on wave-uniform-address grid updates)
-__device__ __forceinline__ float wave_sum_all(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // Scatter the slice gradient of a wave's 64 samples into the grid-gradient accumulator (LDS or global).
 // Neighbouring samples fall into the same grid cell (coarse grids: the whole wave), so per-lane atomics
 // would serialise 20-64 ways on one address.  Instead the wave walks its DISTINCT cells (typically 1-6):
@@ -523,7 +472,7 @@ __global__ __launch_bounds__(kBgBlock) void ms_lowres_bwd_kernel(MsParams p, Lev
     if (L.v_grid && !(dbg & 2)) slice_grid_scatter(acc + n * gsz, c, L.gx, L.gy, L.gl, inv_n, va, active);
     if (active && c.z_interior && !(dbg & 4)) {
       float a12[12], dz[12];
-      if (cells) slice_dz_cells(reinterpret_cast<const float4 *>(lds_cells) + (int64_t)n * vol * 3, L.gx, L.gy, c, dz);
+      if (cells) slice_cells<false, true>(reinterpret_cast<const float4 *>(lds_cells) + (int64_t)n * vol * 3, L.gx, L.gy, c, nullptr, dz);
       else slice_sample(L.grid + (int64_t)n * gsz, L.gx, L.gy, L.gl, c, a12, dz);
 #pragma unroll
       for (int ch = 0; ch < 12; ch++) v_iz += va[ch] * dz[ch] * inv_n;
@@ -603,14 +552,8 @@ __global__ __launch_bounds__(kBgBlock) void ms_guidance_blend_bwd_kernel(MsParam
     if (l >= p.nlevels) break;
     const LevelDev &L = p.lv[l];
     if (L.Hd == p.H && L.Wd == p.W) { vg += L.vg[pix]; continue; }
-    if (L.dn_shift > 0 && !(dbg & 2048)) {
-      // power-of-two factor f dividing the image: low-res pixel (i, j) was sampled at f (i + 1/2) - 1/2, i.e. from the two central
-      // rows / columns of its f x f block with weights 1/2, 1/2 -- a pixel receives 1/4 of ONE low-res value or nothing (the same
-      // single term, the same product, as the general gather below: bit-identical, ~10 instructions instead of ~200)
-      const int f = 1 << L.dn_shift, h = f >> 1;
-      const int fy = y & (f - 1), fx = x & (f - 1);
-      if ((fy == h - 1 || fy == h) && (fx == h - 1 || fx == h))
-        vg += (0.5f * 0.5f) * L.vg[row_major(y >> L.dn_shift, L.Wd, x >> L.dn_shift)];
+    if (L.dn_shift > 0 && !(dbg & 2048)) {   // (the same single term, the same product, as the general gather below: bit-identical)
+      guidance_tap_pow2(vg, L.vg, L.Wd, L.dn_shift, y, x);
       continue;
     }
     int ilo, ihi, jlo, jhi;
@@ -650,30 +593,9 @@ __global__ __launch_bounds__(kBgBlock) void ms_guidance_blend_bwd_kernel(MsParam
       }
     }
   }
-  const int cs = p.cs;
-  const int oc = cs == 4 ? pix << 2 : times3(pix), p3 = times3(pix);
-  float v[3] = {v_in[oc] + vg * kGrayR, v_in[oc + 1] + vg * kGrayG, v_in[oc + 2] + vg * kGrayB};
-  float va = 0.f;
-  if (p.sky) {
-    const float k = 1.f - p.alpha[pix];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      va -= v[c] * p.sky[p3 + c];
-      if (v_sky) v_sky[p3 + c] = v[c] * k;
-      v[c] = p.rgb[oc + c] <= 1.f ? v[c] : 0.f;  // torch.clamp(max=1) passes gradient at x <= 1
-    }
-  }
-  v_in[oc] = v[0]; v_in[oc + 1] = v[1]; v_in[oc + 2] = v[2];
-  if (cs == 4) {  // RGB+ED form: depth = D / clamp(alpha, min=1e-10); plus the caller's own alpha gradient
-    const float a = p.alpha[pix], ac = fmaxf(a, 1e-10f);
-    const float vd = p.v_depth ? p.v_depth[pix] : 0.f;
-    v_in[(pix << 2) + 3] = vd / ac;
-    if (p.v_alpha_in) va += p.v_alpha_in[pix];
-    if (a >= 1e-10f) va -= p.rgb[(pix << 2) + 3] * vd / (ac * ac);  // clamp(min) passes the gradient where alpha >= 1e-10
-    if (v_alpha) v_alpha[pix] = va;
-  } else if (p.sky && v_alpha) {
-    v_alpha[pix] = va;
-  }
+  const int oc = p.cs == 4 ? pix << 2 : times3(pix);
+  const float v[3] = {v_in[oc] + vg * kGrayR, v_in[oc + 1] + vg * kGrayG, v_in[oc + 2] + vg * kGrayB};
+  input_backward_store(p, pix, oc, v, v_in, v_alpha, v_sky);
 }
 
 // ---- generic point slice (BilateralGrid.forward on arbitrary points) ------------------------------
@@ -1489,25 +1411,18 @@ __global__ __launch_bounds__(kBgBlock) void l1_tv_train_kernel(TvLevels L, int t
       const float4 p = a4[i], q = b4[i];
       const float d0 = p.x - q.x, d1 = p.y - q.y, d2 = p.z - q.z, d3 = p.w - q.w;
       s += fabsf(d0) + fabsf(d1) + fabsf(d2) + fabsf(d3);
-      v_a4[i] = make_float4(d0 > 0.f ? gs : (d0 < 0.f ? -gs : 0.f), d1 > 0.f ? gs : (d1 < 0.f ? -gs : 0.f),
-                            d2 > 0.f ? gs : (d2 < 0.f ? -gs : 0.f), d3 > 0.f ? gs : (d3 < 0.f ? -gs : 0.f));   // torch: sign(0) = 0
+      v_a4[i] = make_float4(sign_scaled(d0, gs), sign_scaled(d1, gs), sign_scaled(d2, gs), sign_scaled(d3, gs));
     }
     if (bid == 0 && threadIdx.x < n - n4 * 4) {   // tail (n not a multiple of 4)
       const int64_t i = n4 * 4 + threadIdx.x;
       const float d = a[i] - b[i];
       s += fabsf(d);
-      v_a[i] = d > 0.f ? gs : (d < 0.f ? -gs : 0.f);
+      v_a[i] = sign_scaled(d, gs);
     }
     acc = s * inv_n;
   }
-  acc = wave_sum_all(acc);
-  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int w = 0; w < kBgBlock / kWave; w++) t += red[w];
-    if (t != 0.f) atomicAdd(loss_out + (size_t)(blockIdx.x & (loss_slots - 1)) * kLossSlotStride, t);
-  }
+  const float t = block_sum_to_thread0(acc, red);
+  if (threadIdx.x == 0 && t != 0.f) atomicAdd(loss_out + (size_t)(blockIdx.x & (loss_slots - 1)) * kLossSlotStride, t);
 }
 
 static int tv_levels_fill(TvLevels &T, int nlevels, const bds_bilagrid_level_t *lv, const float *weights, bool bwd, int cap) {

@@ -114,7 +114,7 @@ __device__ __forceinline__ PixCell pix_cell(const LevelDev &L, int i, int j, flo
   float fx, fy;
   axis_cell(linspace01_s(j, L.Wd, L.lin_x), L.gx, x0, fx);
   axis_cell(linspace01_s(i, L.Hd, L.lin_y), L.gy, y0, fy);
-  c.w00 = (1.f - fy) * (1.f - fx); c.w01 = (1.f - fy) * fx; c.w10 = fy * (1.f - fx); c.w11 = fy * fx;
+  corner_weights(fx, fy, c.w00, c.w01, c.w10, c.w11);
   const float iz = guide_coord(gray, L.gl, c.z_interior);
   const float z0 = floorf(iz);
   c.fz = iz - z0;
@@ -122,32 +122,12 @@ __device__ __forceinline__ PixCell pix_cell(const LevelDev &L, int i, int j, flo
   c.z1 = c.z0 + 1 < L.gl ? c.z0 + 1 : L.gl - 1;
   return c;
 }
-// a 16-byte LDS read the compiler may not narrow: where a component of the result is unused it splits the access into ds_read_b96 +
-// ds_read2_b32 (8 + 4 LDS cycles instead of 4: measured as the first cost of the backward, which is bound by the LDS pipeline)
-__device__ __forceinline__ float4 lds_read4(const float4 *p) {
-  float4 v = *p;
-  asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
-  return v;
-}
-// trilinear sample of the 12 channels from the staged nodes (slice_sample's arithmetic and order); dz12: upper minus lower plane
+// trilinear sample of the 12 channels from the job's staged nodes [z][corner][12]; dz12: upper minus lower plane
 template <bool kDz>
 __device__ __forceinline__ void slice_nodes(const float *__restrict__ nodes, const PixCell &c, float *out12, float *dz12) {
-  const float4 *n0 = reinterpret_cast<const float4 *>(nodes + c.z0 * kNodeStride);
-  const float4 *n1 = reinterpret_cast<const float4 *>(nodes + c.z1 * kNodeStride);
-#pragma unroll
-  for (int q = 0; q < 3; q++) {
-    const float4 a00 = lds_read4(n0 + q), a01 = lds_read4(n0 + 3 + q), a10 = lds_read4(n0 + 6 + q), a11 = lds_read4(n0 + 9 + q);
-    const float4 b00 = lds_read4(n1 + q), b01 = lds_read4(n1 + 3 + q), b10 = lds_read4(n1 + 6 + q), b11 = lds_read4(n1 + 9 + q);
-    const float ax = a00.x * c.w00 + a01.x * c.w01 + a10.x * c.w10 + a11.x * c.w11, bx = b00.x * c.w00 + b01.x * c.w01 + b10.x * c.w10 + b11.x * c.w11;
-    const float ay = a00.y * c.w00 + a01.y * c.w01 + a10.y * c.w10 + a11.y * c.w11, by = b00.y * c.w00 + b01.y * c.w01 + b10.y * c.w10 + b11.y * c.w11;
-    const float az = a00.z * c.w00 + a01.z * c.w01 + a10.z * c.w10 + a11.z * c.w11, bz = b00.z * c.w00 + b01.z * c.w01 + b10.z * c.w10 + b11.z * c.w11;
-    const float aw = a00.w * c.w00 + a01.w * c.w01 + a10.w * c.w10 + a11.w * c.w11, bw = b00.w * c.w00 + b01.w * c.w01 + b10.w * c.w10 + b11.w * c.w11;
-    out12[q * 4 + 0] = ax * (1.f - c.fz) + bx * c.fz;
-    out12[q * 4 + 1] = ay * (1.f - c.fz) + by * c.fz;
-    out12[q * 4 + 2] = az * (1.f - c.fz) + bz * c.fz;
-    out12[q * 4 + 3] = aw * (1.f - c.fz) + bw * c.fz;
-    if (kDz) { dz12[q * 4 + 0] = bx - ax; dz12[q * 4 + 1] = by - ay; dz12[q * 4 + 2] = bz - az; dz12[q * 4 + 3] = bw - aw; }
-  }
+  trilinear12<true, kDz, LoadLds16>(reinterpret_cast<const float4 *>(nodes + c.z0 * kNodeStride),
+                                    reinterpret_cast<const float4 *>(nodes + c.z1 * kNodeStride), 0, 3, 6, 9, c.w00, c.w01, c.w10, c.w11, c.fz,
+                                    out12, dz12);
 }
 
 // the job's pixels, 256 at a time: thread t takes pixel base + t of the row-major rectangle
@@ -174,11 +154,7 @@ __global__ __launch_bounds__(kBgBlock) void cell_fwd_kernel(MsParams p, CellSche
   __shared__ __attribute__((aligned(16))) float nodes[kCellMaxGl * kNodeStride];
   __shared__ float red[kCellWaves];
   __shared__ int bounds[4];
-  if (kTrain && (int)blockIdx.x >= tl.pix_blocks) {   // the TV term of the loss: one grid element per thread
-    const float t = block_sum_to_thread0(tv_train_element(tl.T, (int)blockIdx.x - tl.pix_blocks, tl.v_loss), red);
-    if (threadIdx.x == 0 && t != 0.f) atomicAdd(tl.loss + (size_t)(blockIdx.x & (tl.loss_slots - 1)) * kLossSlotStride, t);
-    return;
-  }
+  if (train_tv_workgroup<kTrain>(tl, red)) return;
   CellJob J;
   const bool any = cell_job(p, sc, (int)blockIdx.x, J, bounds, nodes);
   if (!any && !kTrain) return;
@@ -207,28 +183,16 @@ __global__ __launch_bounds__(kBgBlock) void cell_fwd_kernel(MsParams p, CellSche
       L.lg[idx] = gray;
     } else {
       apply_affine(A, r, g, b);
-      const int p3 = times3(idx);
-      out[p3] = r; out[p3 + 1] = g; out[p3 + 2] = b;
-      if (p.depth_out) p.depth_out[idx] = p.rgb[(idx << 2) + 3] / fmaxf(p.alpha[idx], 1e-10f);
-      if (kTrain) {   // photometric L1 of the pixel just produced + its gradient (torch: sign(0) = 0)
-        const float gs = tl.v_loss * tl.inv_n;
-        const float d0 = r - tl.target[p3], d1 = g - tl.target[p3 + 1], d2 = b - tl.target[p3 + 2];
-        l1 += fabsf(d0) + fabsf(d1) + fabsf(d2);
-        tl.v_out[p3] = d0 > 0.f ? gs : (d0 < 0.f ? -gs : 0.f);
-        tl.v_out[p3 + 1] = d1 > 0.f ? gs : (d1 < 0.f ? -gs : 0.f);
-        tl.v_out[p3 + 2] = d2 > 0.f ? gs : (d2 < 0.f ? -gs : 0.f);
-      }
+      l1 += emit_pixel<kTrain>(p, tl, out, idx, r, g, b);
     }
   }
-  if (kTrain) {
-    const float t = block_sum_to_thread0(l1, red);
-    if (threadIdx.x == 0 && t != 0.f) atomicAdd(tl.loss + (size_t)(blockIdx.x & (tl.loss_slots - 1)) * kLossSlotStride, t * tl.inv_n);
-  }
+  if (kTrain) l1_commit(tl, l1, red);
 }
 
 // ---- backward -------------------------------------------------------------------------------------------------------------------
 // d(loss)/d(lo) of a low-res pixel of an up-sampled level: y pass of the up-sampler's adjoint over the x-reduced rows R (the x pass
-// ran in the full-resolution kernel, csrc/bilagrid.hip ms_apply_bwd_x_kernel); arithmetic and order of ms_lowres_bwd_kernel
+// ran in the full-resolution kernel, csrc/bilagrid.hip ms_apply_bwd_x_kernel).  (ms_lowres_bwd_kernel keeps this loop in a form of its
+// own: ablation switches and an unroll factor per instance.)
 __device__ __forceinline__ void adjoint_y(const MsParams &p, const LevelDev &L, int i, int j, float *va) {
   int ylo, yhi;
   // power-of-two factor f dividing the image, interior row: exactly the 2 f rows f i - f/2 .. f i + 3f/2 - 1 with the tent weights
@@ -312,30 +276,9 @@ __global__ __launch_bounds__(kBgBlock) void cell_bwd_kernel(MsParams p, CellSche
         }
         const float vgr = c.z_interior ? v_iz * (float)(gl - 1) : 0.f;
         // direct route (A^T v_out) + guidance route, then the clamp / sky blend / expected-depth backward in front of the transform
-        float v[3] = {A[0] * q0 + A[4] * q1 + A[8] * q2 + vgr * kGrayR, A[1] * q0 + A[5] * q1 + A[9] * q2 + vgr * kGrayG,
+        const float v[3] = {A[0] * q0 + A[4] * q1 + A[8] * q2 + vgr * kGrayR, A[1] * q0 + A[5] * q1 + A[9] * q2 + vgr * kGrayG,
                       A[2] * q0 + A[6] * q1 + A[10] * q2 + vgr * kGrayB};
-        const int cs = p.cs, oc = cs == 4 ? idx << 2 : p3;
-        float vaa = 0.f;
-        if (p.sky) {
-          const float k = 1.f - p.alpha[idx];
-#pragma unroll
-          for (int cc = 0; cc < 3; cc++) {
-            vaa -= v[cc] * p.sky[p3 + cc];
-            if (v_sky) v_sky[p3 + cc] = v[cc] * k;
-            v[cc] = p.rgb[oc + cc] <= 1.f ? v[cc] : 0.f;   // torch.clamp(max=1) passes gradient at x <= 1
-          }
-        }
-        v_in[oc] = v[0]; v_in[oc + 1] = v[1]; v_in[oc + 2] = v[2];
-        if (cs == 4) {   // RGB+ED form: depth = D / clamp(alpha, min=1e-10); plus the caller's own alpha gradient
-          const float a = p.alpha[idx], ac = fmaxf(a, 1e-10f);
-          const float vd = p.v_depth ? p.v_depth[idx] : 0.f;
-          v_in[(idx << 2) + 3] = vd / ac;
-          if (p.v_alpha_in) vaa += p.v_alpha_in[idx];
-          if (a >= 1e-10f) vaa -= p.rgb[(idx << 2) + 3] * vd / (ac * ac);
-          if (v_alpha) v_alpha[idx] = vaa;
-        } else if (p.sky && v_alpha) {
-          v_alpha[idx] = vaa;
-        }
+        input_backward_store(p, idx, p.cs == 4 ? idx << 2 : p3, v, v_in, v_alpha, v_sky);
       } else {
         if (L.Hd == p.H && L.Wd == p.W) {   // a level without up-sampling inside a pyramid: the full-resolution kernel left P, Q
           const float *P = L.P + times3(idx), *Q = L.Q + times3(idx);

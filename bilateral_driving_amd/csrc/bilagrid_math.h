@@ -104,26 +104,19 @@ BDS_HD Cell slice_cell(float x01, float y01, float gray, int gx, int gy, int gl)
   return c;
 }
 
-// trilinear sample of the 12 channels of grid [12, L, gy, gx]; optionally d(out)/d(iz)
-BDS_HD void slice_sample(const float *grid, int gx, int gy, int gl, const Cell &c, float *out12, float *dz12) {
-  const int plane = gy * gx, vol = gl * plane;
-  const int o00 = c.y0 * gx + c.x0, o01 = c.y0 * gx + c.x1, o10 = c.y1 * gx + c.x0, o11 = c.y1 * gx + c.x1;
-  const float w00 = (1.f - c.fy) * (1.f - c.fx), w01 = (1.f - c.fy) * c.fx, w10 = c.fy * (1.f - c.fx), w11 = c.fy * c.fx;
-  for (int ch = 0; ch < 12; ch++) {
-    const float *g0 = grid + ch * vol + c.z0 * plane;
-    const float *g1 = grid + ch * vol + c.z1 * plane;
-    const float a = g0[o00] * w00 + g0[o01] * w01 + g0[o10] * w10 + g0[o11] * w11;
-    const float b = g1[o00] * w00 + g1[o01] * w01 + g1[o10] * w10 + g1[o11] * w11;
-    out12[ch] = a * (1.f - c.fz) + b * c.fz;
-    if (dz12) dz12[ch] = b - a;
-  }
+// the four in-plane corner weights of a cell: (y0, x0), (y0, x1), (y1, x0), (y1, x1)
+BDS_HD void corner_weights(float fx, float fy, float &w00, float &w01, float &w10, float &w11) {
+  w00 = (1.f - fy) * (1.f - fx); w01 = (1.f - fy) * fx; w10 = fy * (1.f - fx); w11 = fy * fx;
 }
 
-// the same for a run of `nch` <= 12 channels starting at `grid` (feature grids: any channel count, 12 at a time)
+// trilinear sample of a run of `nch` <= 12 channels of grid [., L, gy, gx] starting at `grid` (feature grids: any channel count, 12
+// at a time; the channels past nch come out 0); optionally d(out)/d(iz).  The staged forms (bilagrid_ms.h trilinear12) keep this
+// order: four corner products per plane, then a (1 - fz) + b fz, and dz = b - a.
 BDS_HD void slice_sample_n(const float *grid, int gx, int gy, int gl, const Cell &c, int nch, float *out, float *dz) {
   const int plane = gy * gx, vol = gl * plane;
   const int o00 = c.y0 * gx + c.x0, o01 = c.y0 * gx + c.x1, o10 = c.y1 * gx + c.x0, o11 = c.y1 * gx + c.x1;
-  const float w00 = (1.f - c.fy) * (1.f - c.fx), w01 = (1.f - c.fy) * c.fx, w10 = c.fy * (1.f - c.fx), w11 = c.fy * c.fx;
+  float w00, w01, w10, w11;
+  corner_weights(c.fx, c.fy, w00, w01, w10, w11);
   for (int ch = 0; ch < 12; ch++) {
     if (ch >= nch) { out[ch] = 0.f; if (dz) dz[ch] = 0.f; continue; }
     const float *g0 = grid + ch * vol + c.z0 * plane;
@@ -134,6 +127,10 @@ BDS_HD void slice_sample_n(const float *grid, int gx, int gy, int gl, const Cell
     if (dz) dz[ch] = b - a;
   }
 }
+// the 12 channels of the colour transform's grid [12, L, gy, gx]
+BDS_HD void slice_sample(const float *grid, int gx, int gy, int gl, const Cell &c, float *out12, float *dz12) {
+  slice_sample_n(grid, gx, gy, gl, c, 12, out12, dz12);
+}
 
 // p <- A[:, :3] p + A[:, 3]   (A row-major 3x4 in a12)
 BDS_HD void apply_affine(const float *a12, float &r, float &g, float &b) {
@@ -142,5 +139,46 @@ BDS_HD void apply_affine(const float *a12, float &r, float &g, float &b) {
   const float nb = a12[8] * r + a12[9] * g + a12[10] * b + a12[11];
   r = nr; g = ng; b = nb;
 }
+
+// ---- the pixel formulas in front of / behind the transform (models/trainers/base.py:409-419, trainers/scene_graph.py:292-294) ----
+constexpr float kAlphaFloor = 1e-10f;
+
+// expected depth of gsplat's "ED" modes: D / clamp(alpha, min=1e-10)
+BDS_HD float expected_depth(float D, float alpha) { return D / fmaxf(alpha, kAlphaFloor); }
+
+// its backward for a depth gradient vd: the gradient of D, and the term to SUBTRACT from the gradient of alpha (clamp(min) passes
+// the gradient where alpha >= 1e-10: 0 below)
+struct EdGrad {
+  float v_D, alpha_sub;
+};
+BDS_HD EdGrad expected_depth_backward(float D, float alpha, float vd) {
+  const float ac = fmaxf(alpha, kAlphaFloor);
+  EdGrad g;
+  g.v_D = vd / ac;
+  g.alpha_sub = alpha >= kAlphaFloor ? D * vd / (ac * ac) : 0.f;
+  return g;
+}
+
+// backward of  clamp(colour, max=1) + sky (1 - alpha)  for a gradient v[3] of the blend: the gradient of the colour (torch.clamp(max)
+// passes it at x <= 1), of the sky, and the term to ADD to the gradient of alpha
+struct SkyGrad {
+  float v[3], v_sky[3], alpha_add;
+};
+BDS_HD SkyGrad sky_clamp_backward(const float *v, const float *colour_before_clamp, float alpha, const float *sky) {
+  SkyGrad g;
+  const float k = 1.f - alpha;
+  float va = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    va -= v[c] * sky[c];
+    g.v_sky[c] = v[c] * k;
+    g.v[c] = colour_before_clamp[c] <= 1.f ? v[c] : 0.f;
+  }
+  g.alpha_add = va;
+  return g;
+}
+
+// gs * sign(d), the gradient of gs |d| with torch's sign(0) = 0 (+0 whatever the signs; a NaN d gives 0 too)
+BDS_HD float sign_scaled(float d, float gs) { return d > 0.f ? gs : (d < 0.f ? -gs : 0.f); }
 
 }  // namespace bds

@@ -1,5 +1,6 @@
 // Shared by the bilateral-grid translation units (csrc/bilagrid.hip: general kernels + host side; csrc/bilagrid_cells.hip: the
-// cell-aligned kernels): launch parameter blocks, index helpers, the input-colour prologue (clamp + sky blend) and the loss epilogue.
+// cell-aligned kernels; csrc/bilagrid_tile.hip: the one-pass forward): launch parameter blocks, index helpers, the input-colour prologue
+// (clamp + sky blend) with its backward, the forward kernels' pixel / loss epilogue and the staged trilinear sample.
 #pragma once
 #include "bds_common.h"
 #include "bilagrid_math.h"
@@ -81,6 +82,32 @@ __device__ __forceinline__ void load_input(const MsParams &p, int y, int x, floa
   }
 }
 
+// backward of load_input and of the expected depth next to it (RGB+ED form: cs == 4) at pixel `pix`, for the gradient v[3] of the
+// transform's input colour: the final v_in (cs floats per pixel, at `oc`), and v_sky / v_alpha where the caller has them
+__device__ __forceinline__ void input_backward_store(const MsParams &p, int pix, int oc, const float *v, float *__restrict__ v_in,
+                                                     float *__restrict__ v_alpha, float *__restrict__ v_sky) {
+  const int p3 = times3(pix);
+  float vc[3] = {v[0], v[1], v[2]};
+  float va = 0.f;
+  if (p.sky) {
+    const float colour[3] = {p.rgb[oc], p.rgb[oc + 1], p.rgb[oc + 2]}, sky[3] = {p.sky[p3], p.sky[p3 + 1], p.sky[p3 + 2]};
+    const SkyGrad g = sky_clamp_backward(v, colour, p.alpha[pix], sky);
+    if (v_sky) { v_sky[p3] = g.v_sky[0]; v_sky[p3 + 1] = g.v_sky[1]; v_sky[p3 + 2] = g.v_sky[2]; }
+    vc[0] = g.v[0]; vc[1] = g.v[1]; vc[2] = g.v[2];
+    va = g.alpha_add;
+  }
+  v_in[oc] = vc[0]; v_in[oc + 1] = vc[1]; v_in[oc + 2] = vc[2];
+  if (p.cs == 4) {   // plus the caller's own alpha gradient
+    const EdGrad e = expected_depth_backward(p.rgb[(pix << 2) + 3], p.alpha[pix], p.v_depth ? p.v_depth[pix] : 0.f);
+    v_in[(pix << 2) + 3] = e.v_D;
+    if (p.v_alpha_in) va += p.v_alpha_in[pix];
+    va -= e.alpha_sub;
+    if (v_alpha) v_alpha[pix] = va;
+  } else if (p.sky && v_alpha) {
+    v_alpha[pix] = va;
+  }
+}
+
 __device__ __forceinline__ void lowres_colour(const MsParams &p, const Tap &ty, const Tap &tx, float &r, float &g, float &b) {
   float r00, g00, b00, r01, g01, b01, r10, g10, b10, r11, g11, b11;
   load_input(p, ty.i0, tx.i0, r00, g00, b00);
@@ -144,8 +171,7 @@ struct TrainLoss {
 };
 
 __device__ __forceinline__ float block_sum_to_thread0(float acc, float *red /* [kBgBlock / kWave] shared */) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  acc = wave_sum_all(acc);
   if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = acc;
   __syncthreads();
   float t = 0.f;
@@ -154,6 +180,70 @@ __device__ __forceinline__ float block_sum_to_thread0(float acc, float *red /* [
   return t;
 }
 
+// ---- the loss epilogue of the three full-resolution forward kernels, in three pieces -----------------------------------------------
+// thread 0's block sum `t` into the workgroup's loss slot
+__device__ __forceinline__ void loss_commit(const TrainLoss &tl, float t) {
+  if (threadIdx.x == 0 && t != 0.f) atomicAdd(tl.loss + (size_t)(blockIdx.x & (tl.loss_slots - 1)) * kLossSlotStride, t);
+}
+// the workgroups behind the pixel workgroups own the TV term of the loss, one grid element per thread: true = this was one of them
+template <bool kTrain>
+__device__ __forceinline__ bool train_tv_workgroup(const TrainLoss &tl, float *red) {
+  if (!kTrain || (int)blockIdx.x < tl.pix_blocks) return false;
+  loss_commit(tl, block_sum_to_thread0(tv_train_element(tl.T, (int)blockIdx.x - tl.pix_blocks, tl.v_loss), red));
+  return true;
+}
+// pixel `pix` leaves the transform as (r, g, b): store it, the expected depth next to it (RGB+ED form) and, training, the gradient
+// of the photometric L1 against the target; returns the pixel's L1
+template <bool kTrain>
+__device__ __forceinline__ float emit_pixel(const MsParams &p, const TrainLoss &tl, float *__restrict__ out, int pix, float r, float g,
+                                            float b) {
+  const int p3 = times3(pix);
+  out[p3] = r; out[p3 + 1] = g; out[p3 + 2] = b;
+  if (p.depth_out) p.depth_out[pix] = expected_depth(p.rgb[(pix << 2) + 3], p.alpha[pix]);
+  if (!kTrain) return 0.f;
+  const float gs = tl.v_loss * tl.inv_n;
+  const float d0 = r - tl.target[p3], d1 = g - tl.target[p3 + 1], d2 = b - tl.target[p3 + 2];
+  tl.v_out[p3] = sign_scaled(d0, gs); tl.v_out[p3 + 1] = sign_scaled(d1, gs); tl.v_out[p3 + 2] = sign_scaled(d2, gs);
+  return fabsf(d0) + fabsf(d1) + fabsf(d2);
+}
+// the workgroup's L1 sum into its loss slot (contains a barrier: every thread of the workgroup calls it)
+__device__ __forceinline__ void l1_commit(const TrainLoss &tl, float l1, float *red) {
+  loss_commit(tl, block_sum_to_thread0(l1, red) * tl.inv_n);
+}
+
+// ---- trilinear sample of the 12 channels from a STAGED copy of the grid ([node][12] as three float4) --------------------------------
+// g0 / g1: the two guidance planes; o..: float4 offsets of the cell's four corners; w..: their in-plane weights (corner_weights).
+// slice_sample_n's order.  Load: how a 16-byte read is made.
+struct LoadPlain {
+  static __device__ __forceinline__ float4 ld(const float4 *p) { return *p; }
+};
+// a 16-byte LDS read the compiler may not narrow: where a component of the result is unused it splits the access into ds_read_b96 +
+// ds_read2_b32 (8 + 4 LDS cycles instead of 4: measured as the first cost of the cell-aligned backward, which is bound by the LDS pipeline)
+struct LoadLds16 {
+  static __device__ __forceinline__ float4 ld(const float4 *p) {
+    float4 v = *p;
+    asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
+    return v;
+  }
+};
+template <bool kOut, bool kDz, class Load = LoadPlain>
+__device__ __forceinline__ void trilinear12(const float4 *__restrict__ g0, const float4 *__restrict__ g1, int o00, int o01, int o10, int o11,
+                                            float w00, float w01, float w10, float w11, float fz, float *out12, float *dz12) {
+#pragma unroll
+  for (int q = 0; q < 3; q++) {
+    const float4 a00 = Load::ld(g0 + o00 + q), a01 = Load::ld(g0 + o01 + q), a10 = Load::ld(g0 + o10 + q), a11 = Load::ld(g0 + o11 + q);
+    const float4 b00 = Load::ld(g1 + o00 + q), b01 = Load::ld(g1 + o01 + q), b10 = Load::ld(g1 + o10 + q), b11 = Load::ld(g1 + o11 + q);
+    const float a[4] = {a00.x * w00 + a01.x * w01 + a10.x * w10 + a11.x * w11, a00.y * w00 + a01.y * w01 + a10.y * w10 + a11.y * w11,
+                        a00.z * w00 + a01.z * w01 + a10.z * w10 + a11.z * w11, a00.w * w00 + a01.w * w01 + a10.w * w10 + a11.w * w11};
+    const float b[4] = {b00.x * w00 + b01.x * w01 + b10.x * w10 + b11.x * w11, b00.y * w00 + b01.y * w01 + b10.y * w10 + b11.y * w11,
+                        b00.z * w00 + b01.z * w01 + b10.z * w10 + b11.z * w11, b00.w * w00 + b01.w * w01 + b10.w * w10 + b11.w * w11};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      if (kOut) out12[q * 4 + k] = a[k] * (1.f - fz) + b[k] * fz;
+      if (kDz) dz12[q * 4 + k] = b[k] - a[k];
+    }
+  }
+}
 // ---- cell-aligned kernels (csrc/bilagrid_cells.hip) -------------------------------------------------------------------------
 // A level qualifies when it has ONE grid (n_avg == 1) with gl <= kCellMaxGl planes; its low-resolution pixels are then processed
 // in jobs that lie inside ONE (y, x) cell of the grid.

@@ -34,26 +34,15 @@ struct TileGeom {
   float g_inv_ncols[BDS_MAX_LEVELS];   // 1 / ncols of the group's block
 };
 
-// trilinear sample from the tile's sub-grid copy sub[z][ly][lx][12] (origin node (yn0, xn0)); slice_sample's arithmetic and order
+// trilinear sample from the tile's sub-grid copy sub[z][ly][lx][12] (origin node (yn0, xn0))
 __device__ __forceinline__ void slice_sub(const float *__restrict__ sub, int xn0, int yn0, const Cell &c, float *out12) {
   const int o00 = ((c.y0 - yn0) * kSubNodes + (c.x0 - xn0)) * 3, o01 = ((c.y0 - yn0) * kSubNodes + (c.x1 - xn0)) * 3;
   const int o10 = ((c.y1 - yn0) * kSubNodes + (c.x0 - xn0)) * 3, o11 = ((c.y1 - yn0) * kSubNodes + (c.x1 - xn0)) * 3;
-  const float w00 = (1.f - c.fy) * (1.f - c.fx), w01 = (1.f - c.fy) * c.fx, w10 = c.fy * (1.f - c.fx), w11 = c.fy * c.fx;
-  const float4 *g0 = reinterpret_cast<const float4 *>(sub) + c.z0 * (kSubNodes * kSubNodes * 3);
-  const float4 *g1 = reinterpret_cast<const float4 *>(sub) + c.z1 * (kSubNodes * kSubNodes * 3);
-#pragma unroll
-  for (int q = 0; q < 3; q++) {
-    const float4 a00 = g0[o00 + q], a01 = g0[o01 + q], a10 = g0[o10 + q], a11 = g0[o11 + q];
-    const float4 b00 = g1[o00 + q], b01 = g1[o01 + q], b10 = g1[o10 + q], b11 = g1[o11 + q];
-    const float ax = a00.x * w00 + a01.x * w01 + a10.x * w10 + a11.x * w11, bx = b00.x * w00 + b01.x * w01 + b10.x * w10 + b11.x * w11;
-    const float ay = a00.y * w00 + a01.y * w01 + a10.y * w10 + a11.y * w11, by = b00.y * w00 + b01.y * w01 + b10.y * w10 + b11.y * w11;
-    const float az = a00.z * w00 + a01.z * w01 + a10.z * w10 + a11.z * w11, bz = b00.z * w00 + b01.z * w01 + b10.z * w10 + b11.z * w11;
-    const float aw = a00.w * w00 + a01.w * w01 + a10.w * w10 + a11.w * w11, bw = b00.w * w00 + b01.w * w01 + b10.w * w10 + b11.w * w11;
-    out12[q * 4 + 0] = ax * (1.f - c.fz) + bx * c.fz;
-    out12[q * 4 + 1] = ay * (1.f - c.fz) + by * c.fz;
-    out12[q * 4 + 2] = az * (1.f - c.fz) + bz * c.fz;
-    out12[q * 4 + 3] = aw * (1.f - c.fz) + bw * c.fz;
-  }
+  float w00, w01, w10, w11;
+  corner_weights(c.fx, c.fy, w00, w01, w10, w11);
+  const float4 *sub4 = reinterpret_cast<const float4 *>(sub);
+  trilinear12<true, false>(sub4 + c.z0 * (kSubNodes * kSubNodes * 3), sub4 + c.z1 * (kSubNodes * kSubNodes * 3), o00, o01, o10, o11, w00, w01, w10,
+                           w11, c.fz, out12, nullptr);
 }
 
 // x pass of the up-sampler for one low-res row of the tile's block: out[c] = lo[row][i0][c] (1 - wx) + lo[row][i1][c] wx
@@ -74,11 +63,7 @@ __global__ __launch_bounds__(kBgBlock) void ms_tile_fwd_kernel(MsParams p, TileG
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ float red[kBgBlock / kWave];
   __shared__ int sub_org[BDS_MAX_LEVELS][4];   // per level: xn0, yn0, nodes in x, nodes in y (0 = sample the grid in global memory)
-  if (kTrain && (int)blockIdx.x >= tl.pix_blocks) {   // the TV term of the loss: one grid element per thread
-    const float t = block_sum_to_thread0(tv_train_element(tl.T, (int)blockIdx.x - tl.pix_blocks, tl.v_loss), red);
-    if (threadIdx.x == 0 && t != 0.f) atomicAdd(tl.loss + (size_t)(blockIdx.x & (tl.loss_slots - 1)) * kLossSlotStride, t);
-    return;
-  }
+  if (train_tv_workgroup<kTrain>(tl, red)) return;
   const int tile = xcd_contiguous((int)blockIdx.x, G.tiles_x * G.tiles_y);   // one band of tile rows per XCD
   const int ty_ = tile / G.tiles_x, tx_ = tile - ty_ * G.tiles_x;
   const int Y0 = ty_ * kTileH, X0 = tx_ * kTileW;
@@ -199,26 +184,13 @@ __global__ __launch_bounds__(kBgBlock) void ms_tile_fwd_kernel(MsParams p, TileG
         apply_affine(A, r[q], g[q], b[q]);
       }
     }
-    const float gs = kTrain ? tl.v_loss * tl.inv_n : 0.f;
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       if (ib + q >= p.H) break;
-      const int pix = row_major(ib + q, p.W, j), p3 = times3(pix);
-      out[p3] = r[q]; out[p3 + 1] = g[q]; out[p3 + 2] = b[q];
-      if (p.depth_out) p.depth_out[pix] = p.rgb[(pix << 2) + 3] / fmaxf(p.alpha[pix], 1e-10f);
-      if (kTrain) {   // photometric L1 of the pixel just produced + its gradient (torch: sign(0) = 0)
-        const float d0 = r[q] - tl.target[p3], d1 = g[q] - tl.target[p3 + 1], d2 = b[q] - tl.target[p3 + 2];
-        l1 += fabsf(d0) + fabsf(d1) + fabsf(d2);
-        tl.v_out[p3] = d0 > 0.f ? gs : (d0 < 0.f ? -gs : 0.f);
-        tl.v_out[p3 + 1] = d1 > 0.f ? gs : (d1 < 0.f ? -gs : 0.f);
-        tl.v_out[p3 + 2] = d2 > 0.f ? gs : (d2 < 0.f ? -gs : 0.f);
-      }
+      l1 += emit_pixel<kTrain>(p, tl, out, row_major(ib + q, p.W, j), r[q], g[q], b[q]);
     }
   }
-  if (kTrain) {
-    const float t = block_sum_to_thread0(l1, red);
-    if (threadIdx.x == 0 && t != 0.f) atomicAdd(tl.loss + (size_t)(blockIdx.x & (tl.loss_slots - 1)) * kLossSlotStride, t * tl.inv_n);
-  }
+  if (kTrain) l1_commit(tl, l1, red);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------

@@ -40,12 +40,6 @@ __global__ __launch_bounds__(kProjBlock) void project_fwd_kernel(
   }
 }
 
-__device__ __forceinline__ float wave_sum_shfl(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // kComp: v_comps [C,N] (rasterize_mode "antialiased") adds the compensation's gradient (gs_math.h project_one_vjp_aa)
 template <bool kComp = false>
 __global__ __launch_bounds__(kProjBlock) void project_bwd_kernel(
@@ -83,8 +77,8 @@ __global__ __launch_bounds__(kProjBlock) void project_bwd_kernel(
     if (v_viewmats != nullptr) {  // block reduction of the pose gradient, one atomic set per block
       const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
       float r[12];
-      for (int i = 0; i < 9; i++) r[i] = wave_sum_shfl(pg.v_R[i]);
-      for (int i = 0; i < 3; i++) r[9 + i] = wave_sum_shfl(pg.v_t[i]);
+      for (int i = 0; i < 9; i++) r[i] = wave_sum_all(pg.v_R[i]);
+      for (int i = 0; i < 3; i++) r[9 + i] = wave_sum_all(pg.v_t[i]);
       __syncthreads();
       if (lane == 0)
         for (int i = 0; i < 12; i++) red[wv][i] = r[i];

@@ -1036,60 +1036,44 @@ __global__ __launch_bounds__(kPackBlock) void splat_pack_rgbd_kernel(int64_t n, 
   rec[r * 3 + 1] = make_float4((-0.5f * kLog2e) * cn[2], opacities[g], cl[0], cl[1]);
   rec[r * 3 + 2] = make_float4(cl[2], depths[g], 0.f, __int_as_float(radii ? radii[g] : kUnboundedRadius));
 }
-// expected depth of gsplat's "ED" modes: out = (r, g, b, D / max(alpha, 1e-10))
-__global__ __launch_bounds__(256) void ed_fwd_kernel(int64_t P, const float4 *__restrict__ render, const float *__restrict__ alphas,
-                                                     float4 *__restrict__ out) {
+// expected depth of gsplat's "ED" modes (bilagrid_math.h expected_depth; ed = 0: the composited depth as it is) as one image
+// out [P,4] = (r, g, b, depth), or, kSplit, as TWO arrays out [P,3] and depth [P,1] -- what the reference's trainer splits the render
+// into right away (models/trainers/base.py:409-419 torch.split(renders, [3, 1])): as node outputs of their own they need no slice backward
+template <bool kSplit>
+__global__ __launch_bounds__(256) void ed_fwd_kernel(int64_t P, int ed, const float4 *__restrict__ render, const float *__restrict__ alphas,
+                                                     float *__restrict__ out, float *__restrict__ depth) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= P) return;
   float4 v = render[i];
-  v.w = v.w / fmaxf(alphas[i], 1e-10f);
-  out[i] = v;
+  if (ed) v.w = expected_depth(v.w, alphas[i]);
+  if (kSplit) {
+    out[i * 3] = v.x; out[i * 3 + 1] = v.y; out[i * 3 + 2] = v.z;
+    depth[i] = v.w;
+  } else {
+    reinterpret_cast<float4 *>(out)[i] = v;
+  }
 }
 // its backward, and the widening of a 3-channel ("RGB") image gradient to the compositor's 4 channels: v_render = (v_out.rgb,
-// v_out.d / max(alpha, 1e-10) | 0), v_alphas = v_alphas_in - [alpha >= 1e-10] D v_out.d / max(alpha, 1e-10)^2
+// v_out.d / max(alpha, 1e-10) | 0), v_alphas = v_alphas_in - [alpha >= 1e-10] D v_out.d / max(alpha, 1e-10)^2.  The image gradient is
+// v_rgb [P,ch] with the depth's in channel 3 where ch == 4, or, kSplit, v_rgb [P,3] and v_depth [P]
+template <bool kSplit>
 __global__ __launch_bounds__(256) void ed_bwd_kernel(int64_t P, int ch, int ed, const float4 *__restrict__ render, const float *__restrict__ alphas,
-                                                     const float *__restrict__ v_out, const float *__restrict__ v_alphas_in,
-                                                     float4 *__restrict__ v_render, float *__restrict__ v_alphas) {
+                                                     const float *__restrict__ v_rgb, const float *__restrict__ v_depth,
+                                                     const float *__restrict__ v_alphas_in, float4 *__restrict__ v_render,
+                                                     float *__restrict__ v_alphas) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= P) return;
   float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
   float va = v_alphas_in ? v_alphas_in[i] : 0.f;
-  if (v_out) {
-    v.x = v_out[i * ch]; v.y = v_out[i * ch + 1]; v.z = v_out[i * ch + 2];
-    if (ch == 4) v.w = v_out[i * 4 + 3];
+  if (v_rgb) {
+    v.x = v_rgb[i * ch]; v.y = v_rgb[i * ch + 1]; v.z = v_rgb[i * ch + 2];
+    if (!kSplit && ch == 4) v.w = v_rgb[i * 4 + 3];
   }
+  if (kSplit && v_depth) v.w = v_depth[i];
   if (ed) {
-    const float a = alphas[i], ac = fmaxf(a, 1e-10f), vd = v.w;
-    v.w = vd / ac;
-    if (a >= 1e-10f) va -= render[i].w * vd / (ac * ac);
-  }
-  v_render[i] = v;
-  v_alphas[i] = va;
-}
-// the same with the image handed out as TWO arrays, rgb [P,3] and depth [P,1] -- what the reference's trainer splits the render into
-// right away (models/trainers/base.py:409-419 torch.split(renders, [3, 1])): as node outputs of their own they need no slice backward
-__global__ __launch_bounds__(256) void ed_split_fwd_kernel(int64_t P, int ed, const float4 *__restrict__ render, const float *__restrict__ alphas,
-                                                           float *__restrict__ rgb, float *__restrict__ depth) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= P) return;
-  const float4 v = render[i];
-  rgb[i * 3] = v.x; rgb[i * 3 + 1] = v.y; rgb[i * 3 + 2] = v.z;
-  depth[i] = ed ? v.w / fmaxf(alphas[i], 1e-10f) : v.w;
-}
-__global__ __launch_bounds__(256) void ed_split_bwd_kernel(int64_t P, int ed, const float4 *__restrict__ render, const float *__restrict__ alphas,
-                                                           const float *__restrict__ v_rgb, const float *__restrict__ v_depth,
-                                                           const float *__restrict__ v_alphas_in, float4 *__restrict__ v_render,
-                                                           float *__restrict__ v_alphas) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= P) return;
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  float va = v_alphas_in ? v_alphas_in[i] : 0.f;
-  if (v_rgb) { v.x = v_rgb[i * 3]; v.y = v_rgb[i * 3 + 1]; v.z = v_rgb[i * 3 + 2]; }
-  if (v_depth) v.w = v_depth[i];
-  if (ed) {   // (the arithmetic of ed_bwd_kernel)
-    const float a = alphas[i], ac = fmaxf(a, 1e-10f), vd = v.w;
-    v.w = vd / ac;
-    if (a >= 1e-10f) va -= render[i].w * vd / (ac * ac);
+    const EdGrad g = expected_depth_backward(render[i].w, alphas[i], v.w);
+    v.w = g.v_D;
+    va -= g.alpha_sub;
   }
   v_render[i] = v;
   v_alphas[i] = va;
@@ -1111,8 +1095,8 @@ extern "C" int bds_expected_depth_fwd(int64_t P, const float *render4, const flo
   BDS_REQUIRE(P >= 0);
   if (P == 0) return BDS_OK;
   BDS_REQUIRE(render4 && alphas && out4 && aligned16(render4) && aligned16(out4));
-  hipLaunchKernelGGL(ed_fwd_kernel, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, as_stream(stream), P, reinterpret_cast<const float4 *>(render4),
-                     alphas, reinterpret_cast<float4 *>(out4));
+  hipLaunchKernelGGL(ed_fwd_kernel<false>, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, as_stream(stream), P, 1,
+                     reinterpret_cast<const float4 *>(render4), alphas, out4, static_cast<float *>(nullptr));
   BDS_LAUNCH_CHECK();
   return BDS_OK;
 }
@@ -1122,8 +1106,9 @@ extern "C" int bds_expected_depth_bwd(int64_t P, int channels, int expected_dept
   BDS_REQUIRE(P >= 0 && (channels == 3 || channels == 4) && !(expected_depth && channels != 4));
   if (P == 0) return BDS_OK;
   BDS_REQUIRE(render4 && alphas && v_render4 && v_alphas && aligned16(render4) && aligned16(v_render4));
-  hipLaunchKernelGGL(ed_bwd_kernel, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, as_stream(stream), P, channels, expected_depth,
-                     reinterpret_cast<const float4 *>(render4), alphas, v_out, v_alphas_in, reinterpret_cast<float4 *>(v_render4), v_alphas);
+  hipLaunchKernelGGL(ed_bwd_kernel<false>, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, as_stream(stream), P, channels, expected_depth,
+                     reinterpret_cast<const float4 *>(render4), alphas, v_out, static_cast<const float *>(nullptr), v_alphas_in,
+                     reinterpret_cast<float4 *>(v_render4), v_alphas);
   BDS_LAUNCH_CHECK();
   return BDS_OK;
 }
@@ -1133,7 +1118,7 @@ extern "C" int bds_expected_depth_split_fwd(int64_t P, int expected_depth, const
   BDS_REQUIRE(P >= 0);
   if (P == 0) return BDS_OK;
   BDS_REQUIRE(render4 && alphas && rgb3 && depth1 && aligned16(render4));
-  hipLaunchKernelGGL(ed_split_fwd_kernel, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, as_stream(stream), P, expected_depth,
+  hipLaunchKernelGGL(ed_fwd_kernel<true>, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, as_stream(stream), P, expected_depth,
                      reinterpret_cast<const float4 *>(render4), alphas, rgb3, depth1);
   BDS_LAUNCH_CHECK();
   return BDS_OK;
@@ -1144,7 +1129,7 @@ extern "C" int bds_expected_depth_split_bwd(int64_t P, int expected_depth, const
   BDS_REQUIRE(P >= 0);
   if (P == 0) return BDS_OK;
   BDS_REQUIRE(render4 && alphas && v_render4 && v_alphas && aligned16(render4) && aligned16(v_render4));
-  hipLaunchKernelGGL(ed_split_bwd_kernel, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, as_stream(stream), P, expected_depth,
+  hipLaunchKernelGGL(ed_bwd_kernel<true>, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, as_stream(stream), P, 3, expected_depth,
                      reinterpret_cast<const float4 *>(render4), alphas, v_rgb3, v_depth1, v_alphas_in, reinterpret_cast<float4 *>(v_render4),
                      v_alphas);
   BDS_LAUNCH_CHECK();

@@ -117,3 +117,28 @@ extern "C" void hm_axis_cells(int n, int g, int *i0, float *f, int *x0, int *x1,
     x0[i] = c.x0; x1[i] = c.x1; fx[i] = c.fx;
   }
 }
+
+// the pixel formulas in front of / behind the colour transform (csrc/bilagrid_math.h), one call per pixel
+extern "C" void hm_expected_depth(int n, const float *D, const float *alpha, float *depth) {
+  for (int i = 0; i < n; i++) depth[i] = expected_depth(D[i], alpha[i]);
+}
+
+extern "C" void hm_expected_depth_backward(int n, const float *D, const float *alpha, const float *vd, float *v_D, float *alpha_sub) {
+  for (int i = 0; i < n; i++) {
+    const EdGrad g = expected_depth_backward(D[i], alpha[i], vd[i]);
+    v_D[i] = g.v_D; alpha_sub[i] = g.alpha_sub;
+  }
+}
+
+extern "C" void hm_sky_clamp_backward(int n, const float *v3, const float *colour3, const float *alpha, const float *sky3, float *v_colour3,
+                                      float *v_sky3, float *alpha_add) {
+  for (int i = 0; i < n; i++) {
+    const SkyGrad g = sky_clamp_backward(v3 + i * 3, colour3 + i * 3, alpha[i], sky3 + i * 3);
+    for (int c = 0; c < 3; c++) { v_colour3[i * 3 + c] = g.v[c]; v_sky3[i * 3 + c] = g.v_sky[c]; }
+    alpha_add[i] = g.alpha_add;
+  }
+}
+
+extern "C" void hm_sign_scaled(int n, const float *d, const float *gs, float *out) {
+  for (int i = 0; i < n; i++) out[i] = sign_scaled(d[i], gs[i]);
+}

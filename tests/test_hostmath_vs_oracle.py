@@ -9,6 +9,7 @@ import torch
 
 from oracle import bilagrid_oracle as BO
 from oracle import gs_oracle as G
+from tests import pixel_formulas_ref64 as PF
 from tests.util import fptr, hostmath, make_scene, rel_err
 
 F64 = torch.float64
@@ -245,3 +246,48 @@ def test_block_bound_never_rejects_a_box_that_holds_a_visible_gaussian(hm):
         else:
             n_visible_in_kept += int((radii > 0).any())
     assert n_rejected > 0.45 * n_boxes and n_visible_in_kept > 0.1 * n_boxes, (n_rejected, n_visible_in_kept, n_boxes)
+
+
+def _pixel_formulas(hm, z):
+    """The three formulas on the cases `z`, and the alpha gradient put together from their terms in the kernels' order: the sky's,
+    then the caller's own, then the depth's."""
+    P = len(z["alpha"])
+    f = lambda *s: np.zeros(s, np.float32)
+    depth, v_D, sub, v_colour, v_sky, add = f(P), f(P), f(P), f(P, 3), f(P, 3), f(P)
+    hm.hm_expected_depth(P, fptr(z["D"]), fptr(z["alpha"]), fptr(depth))
+    hm.hm_expected_depth_backward(P, fptr(z["D"]), fptr(z["alpha"]), fptr(z["vd"]), fptr(v_D), fptr(sub))
+    hm.hm_sky_clamp_backward(P, fptr(z["v"]), fptr(z["colour"]), fptr(z["alpha"]), fptr(z["sky"]), fptr(v_colour), fptr(v_sky), fptr(add))
+    return dict(depth=depth, v_D=v_D, v_colour=v_colour, v_sky=v_sky, alpha_sub=sub, alpha_add=add, v_alpha=(add + z["va_in"]) - sub)
+
+
+def test_expected_depth_and_sky_clamp_backward_match_float64_autograd(hm):
+    """csrc/bilagrid_math.h expected_depth / expected_depth_backward / sky_clamp_backward against torch autograd in float64 over
+    D / clamp(alpha, min=1e-10) and clamp(rgb, max=1) + sky * (1 - alpha), on both sides of either clamp's gate (tests/pixel_formulas_ref64.py:
+    the inputs, and the bounds with their derivation)."""
+    z = PF.cases(7 * 4 * 12)
+    assert set(z["alpha"].tolist()) == set(PF.ALPHAS.tolist()) and set(z["colour"].ravel().tolist()) == set(PF.COLOURS.tolist())
+    got = _pixel_formulas(hm, z)
+    PF.check(got, PF.reference(z))
+    # each formula alone: its share of the alpha gradient within the same bound, the depth's share with the gate's pattern
+    none = dict(z, va_in=np.zeros_like(z["va_in"]))
+    PF.check(dict(v_alpha=-got["alpha_sub"]), PF.reference(none, blend=False), alpha_is_gated=True)
+    PF.check(dict(v_alpha=got["alpha_add"]), PF.reference(none, expected_depth=False))
+    below = z["alpha"] < PF.FLOOR
+    assert below.sum() >= 3 * 48 and (~below).sum() >= 4 * 48 and np.all(got["alpha_sub"][below] == 0) and np.all(got["alpha_sub"][~below] != 0)
+    over = z["colour"] > 1
+    assert over.any() and (~over).any() and np.all(got["v_colour"][over] == 0) and np.array_equal(got["v_colour"][~over], z["v"][~over])
+
+
+def test_sign_scaled_is_gs_times_sign(hm):
+    """csrc/bilagrid_math.h sign_scaled(d, gs), the gradient of gs |d|: gs * sign(d) bit for bit, with torch's sign(0) = 0 for d = 0 and
+    d = -0, and 0 for a NaN d (neither d > 0 nor d < 0 holds: what the expression has always given).  The zero is +0 whatever the
+    signs of d and gs."""
+    d = np.array([0.0, -0.0, np.nan, -np.nan, 1.0, -1.0, 1e-45, -1e-45, np.inf, -np.inf, 3.5, -0.25], np.float32)
+    gs = np.array([0.125, -0.125, 3.0e-7, 1.0, -2.5, 0.0], np.float32)
+    dd, gg = (a.ravel().copy() for a in np.meshgrid(d, gs))
+    out = np.full(dd.shape, 7.0, np.float32)
+    hm.hm_sign_scaled(len(dd), fptr(dd), fptr(gg), fptr(out))
+    sign = np.where(np.isnan(dd), np.float32(0), np.sign(dd)).astype(np.float32)
+    ref = np.where(sign > 0, gg, np.where(sign < 0, -gg, np.float32(0))).astype(np.float32)
+    assert np.array_equal(out.view(np.uint32), ref.view(np.uint32))
+    assert np.array_equal(out, gg * sign)     # (== takes -0 for +0: gs * sign(d) has a -0 where exactly one of gs, sign(d) is negative zero)
