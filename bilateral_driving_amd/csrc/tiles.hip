@@ -137,8 +137,8 @@ static int exclusive_scan_u32(const uint32_t *in, uint32_t *out, int64_t n, uint
 // Four forms of one pass, chosen by the host code below:
 //   pairs,     <= 8-bit digit, scanned [digit][workgroup] histogram:  radix_hist_kernel + radix_scatter_lds_kernel
 //   keys only, <= 8-bit digit, the same histogram:                    radix_hist_kernel + radix_scatter_keys_kernel
-//   keys only, 9/10-bit digit, workgroup-major histogram + group rows: radix_hist_wide_kernel + radix_scatter_keys_wide_kernel
-//   pairs,     8-bit digit, workgroup-major + group rows, 1024-entry chunks, no LDS staging: short_hist_kernel + short_scatter_kernel
+//   keys only, 9/10-bit digit, workgroup-major histogram + partial rows: radix_hist_wide_kernel + radix_scatter_keys_wide_kernel
+//   pairs,     8-bit digit, workgroup-major + partial rows, 1024-entry chunks, no LDS staging: short_hist_kernel + short_scatter_kernel
 // The steps they have in common are the device functions that follow; where the bases come from, whether the output is staged through
 // LDS and what else a kernel fuses stay in the kernels.
 constexpr int kSortBlock = 256;
@@ -146,6 +146,7 @@ constexpr int kSortRounds = 16;
 constexpr int kSortChunk = kSortBlock * kSortRounds;  // 4096 entries per workgroup
 constexpr int kSortWaves = kSortBlock / kWave;
 constexpr int kGroupShift = 6;   // workgroup-major histograms: 64 workgroups per group row
+constexpr int kSubShift = 3;     //   and 8 workgroups per sub-group row
 
 // Chunk histogram: h[kBins] (LDS) = digit counts of the kRounds * 256 keys from `base` on.  Holds barriers.
 template <int kBins, int kRounds>
@@ -221,68 +222,85 @@ __device__ __forceinline__ uint32_t rank_round(uint32_t d, bool on, uint32_t *wr
   return pos + rank;
 }
 
-// Bases from a workgroup-major histogram hist[workgroup][bins] and its group rows ghist[group][bins] (the sums of 64 workgroups'
-// rows each), bins = 256 kPer, for the kPer consecutive digits from threadIdx.x * kPer on: their entries in the whole input (total)
-// and in front of workgroup vb (below), from the <= ng group rows and the <= 63 workgroup rows of vb's own group, all L2-resident.
-// kSums independent partial sums over the workgroup rows, so that kSums loads per digit are in flight at a time (a single running sum
-// serialises the L2 latency of every row: that chain was most of short_scatter_kernel's 14 us).  kSums was tuned per caller.
-template <int kPer, int kSums>
-__device__ __forceinline__ void grouped_bases(const uint32_t *__restrict__ hist, const uint32_t *__restrict__ ghist, int vb, int nb,
-                                              uint32_t (&total)[kPer], uint32_t (&below)[kPer]) {
+// Rows of a table read through one buffer descriptor: the table's address sits in scalar registers, a row is a scalar byte offset and
+// the thread's column ONE vector offset shared by every load -- no 64-bit vector add and address pair per row.  `rows` bounds the
+// descriptor; everything but the column is workgroup-uniform.
+struct RowTable {
+  __amdgpu_buffer_rsrc_t rsrc;
+  __device__ __forceinline__ RowTable(const uint32_t *base, int rows, int bins)
+      : rsrc(__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(base), 0, rows * bins * (int)sizeof(uint32_t), 0x00020000)) {}
+  __device__ __forceinline__ uint32_t load(int row_bytes, uint32_t col_bytes) const {
+    return __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)col_bytes, row_bytes, 0);
+  }
+};
+
+// Bases from a workgroup-major histogram hist[workgroup][bins] and its two levels of partial rows: ghist[group][bins], the sums of 64
+// workgroups' rows each, and shist[sub-group][bins], the sums of 8 each; bins = 256 kPer.  For the kPer consecutive digits from
+// threadIdx.x * kPer on: their entries in the whole input (total) and in front of workgroup vb (below) =
+//   the group rows in front of vb's group + the <= 7 sub-group rows of vb's group in front of vb's sub-group + the <= 7 workgroup rows
+//   of vb's sub-group in front of vb                                                                       (all L2-resident).
+// The 14 short loads are issued first and unconditionally -- a row that does not count is replaced by the first of its set, which always
+// does exist, and its value dropped -- so that behind the group rows no workgroup waits for a further dependent round of loads,
+// whatever vb is.  (Before the sub-group rows a workgroup summed up to 63 workgroup rows in batches of 4-8 loads: 8-16 dependent L2
+// round trips in the slowest workgroup of every launch, most of what short_scatter_kernel took.)
+template <int kPer>
+__device__ __forceinline__ void grouped_bases(const uint32_t *__restrict__ hist, const uint32_t *__restrict__ ghist,
+                                              const uint32_t *__restrict__ shist, int vb, int nb, uint32_t (&total)[kPer],
+                                              uint32_t (&below)[kPer]) {
   constexpr int kBins = kSortBlock * kPer;
-  const int ng = (nb + (1 << kGroupShift) - 1) >> kGroupShift, gb = vb >> kGroupShift;
+  constexpr int kSubRows = (1 << (kGroupShift - kSubShift)) - 1, kOwnRows = (1 << kSubShift) - 1;   // 7 and 7
+  const int ng = (nb + (1 << kGroupShift) - 1) >> kGroupShift, gb = vb >> kGroupShift, sb = vb >> kSubShift;
+  const int n_sub = sb - (gb << (kGroupShift - kSubShift)), n_own = vb - (sb << kSubShift);
+  constexpr int kRowBytes = kBins * (int)sizeof(uint32_t);
+  const uint32_t col = threadIdx.x * kPer;
+  const RowTable sp(shist + ((int64_t)gb << (kGroupShift - kSubShift)) * kBins, kSubRows, kBins);
+  const RowTable hp(hist + ((int64_t)sb << kSubShift) * kBins, kOwnRows, kBins);
+  uint32_t cs[kSubRows][kPer], ch[kOwnRows][kPer];
+#pragma unroll
+  for (int j = 0; j < kSubRows; j++)
+#pragma unroll
+    for (int u = 0; u < kPer; u++) cs[j][u] = sp.load((j < n_sub ? j : 0) * kRowBytes, (col + u) * (uint32_t)sizeof(uint32_t));
+#pragma unroll
+  for (int j = 0; j < kOwnRows; j++)
+#pragma unroll
+    for (int u = 0; u < kPer; u++) ch[j][u] = hp.load((j < n_own ? j : 0) * kRowBytes, (col + u) * (uint32_t)sizeof(uint32_t));
 #pragma unroll
   for (int u = 0; u < kPer; u++) { total[u] = 0; below[u] = 0; }
-  const uint32_t *gp = ghist + threadIdx.x * kPer;
   int g = 0;
   for (; g + 4 <= ng; g += 4) {   // (independent loads first, then the sums)
     uint32_t c[4][kPer];
 #pragma unroll
     for (int j = 0; j < 4; j++)
 #pragma unroll
-      for (int u = 0; u < kPer; u++) c[j][u] = gp[(int64_t)(g + j) * kBins + u];
+      for (int u = 0; u < kPer; u++) c[j][u] = (ghist + (int64_t)(g + j) * kBins)[col + u];
 #pragma unroll
     for (int u = 0; u < kPer; u++) {
       total[u] += (c[0][u] + c[1][u]) + (c[2][u] + c[3][u]);
       below[u] += (g < gb ? c[0][u] : 0u) + (g + 1 < gb ? c[1][u] : 0u) + (g + 2 < gb ? c[2][u] : 0u) + (g + 3 < gb ? c[3][u] : 0u);
     }
   }
-  for (; g < ng; g++) {
+  {   // (the <= 3 group rows left: one more round, loaded together)
+    uint32_t c[3][kPer];
 #pragma unroll
-    for (int u = 0; u < kPer; u++) {
-      const uint32_t c = gp[(int64_t)g * kBins + u];
-      total[u] += c;
-      if (g < gb) below[u] += c;
-    }
-  }
-  const uint32_t *hp = hist + ((int64_t)gb << kGroupShift) * kBins + threadIdx.x * kPer;
-  const int nrows = vb - (gb << kGroupShift);
-  uint32_t p[kSums][kPer];
+    for (int j = 0; j < 3; j++)
 #pragma unroll
-  for (int j = 0; j < kSums; j++)
+      for (int u = 0; u < kPer; u++) c[j][u] = (ghist + (int64_t)(g + j < ng ? g + j : 0) * kBins)[col + u];
 #pragma unroll
-    for (int u = 0; u < kPer; u++) p[j][u] = 0;
-  int r = 0;
-  for (; r + kSums <= nrows; r += kSums) {
-    uint32_t a[kSums][kPer];
+    for (int j = 0; j < 3; j++)
 #pragma unroll
-    for (int j = 0; j < kSums; j++)
-#pragma unroll
-      for (int u = 0; u < kPer; u++) a[j][u] = hp[(int64_t)(r + j) * kBins + u];
-#pragma unroll
-    for (int j = 0; j < kSums; j++)
-#pragma unroll
-      for (int u = 0; u < kPer; u++) p[j][u] += a[j][u];
-  }
-  for (; r < nrows; r++) {
-#pragma unroll
-    for (int u = 0; u < kPer; u++) p[0][u] += hp[(int64_t)r * kBins + u];
+      for (int u = 0; u < kPer; u++) {
+        total[u] += g + j < ng ? c[j][u] : 0u;
+        below[u] += g + j < gb ? c[j][u] : 0u;
+      }
   }
 #pragma unroll
   for (int u = 0; u < kPer; u++) {
+    uint32_t s = 0;
 #pragma unroll
-    for (int j = 1; j < kSums; j++) p[0][u] += p[j][u];
-    below[u] += p[0][u];
+    for (int j = 0; j < kSubRows; j++) s += j < n_sub ? cs[j][u] : 0u;
+#pragma unroll
+    for (int j = 0; j < kOwnRows; j++) s += j < n_own ? ch[j][u] : 0u;
+    below[u] += s;
   }
 }
 
@@ -411,9 +429,10 @@ __global__ __launch_bounds__(kSortBlock) void radix_scatter_keys_kernel(
 // With coarse list tiles the whole tile key is 9-10 bits (1080p, 64-px list tiles: 510 lists): ONE stable pass orders the
 // pairs instead of two (a pass over the list costs a histogram, a scan of [bins][workgroups] and a scatter launch).
 // No scan launches either: as in the short sort below, the histogram is stored workgroup-major, every 64 workgroups also add
-// theirs to a group row (zeroed by the emission kernel in front), and a scatter workgroup derives its bases from <= ng group rows +
-// <= 63 workgroup rows (L2-resident) -- two launches per pass instead of four, which matters most where it runs: next to another
-// stream's compositor every launch of this latency-bound stage waits for wave slots (profiles/NOTES.md, round 4).
+// theirs to a group row, every 8 to a sub-group row (both zeroed by the emission kernel in front), and a scatter workgroup derives its
+// bases from <= ng group rows + <= 7 sub-group rows + <= 7 workgroup rows (L2-resident; grouped_bases) -- two launches per pass
+// instead of four, which matters most where it runs: next to another stream's compositor every launch of this latency-bound stage
+// waits for wave slots (profiles/NOTES.md, round 4).
 // (Round 5 ran the kernels of the device-count tile stage phase by phase inside ONE persistent launch with device-wide barriers; it
 //  lost -- every barrier is an L2 write-back + invalidate per workgroup on this multi-XCD part -- and was removed again:
 //  profiles/NOTES.md)
@@ -421,7 +440,8 @@ template <int kBins>
 __global__ __launch_bounds__(kSortBlock) void radix_hist_wide_kernel(const uint32_t *__restrict__ keys, int64_t n_host,
                                                                     const uint64_t *__restrict__ n_dev, int shift, uint32_t mask,
                                                                     uint32_t *__restrict__ hist /*[nblocks][kBins]*/,
-                                                                    uint32_t *__restrict__ ghist /*[ng][kBins], zeroed*/) {
+                                                                    uint32_t *__restrict__ ghist /*[ng][kBins], zeroed*/,
+                                                                    uint32_t *__restrict__ shist /*[nsg][kBins], zeroed*/) {
   __shared__ uint32_t h[kBins];
   const int64_t n = list_length(n_host, n_dev), base = (int64_t)blockIdx.x * kSortChunk;
   if (base >= n) return;   // (rows of surplus workgroups are never read)
@@ -429,15 +449,19 @@ __global__ __launch_bounds__(kSortBlock) void radix_hist_wide_kernel(const uint3
   for (int d = threadIdx.x; d < kBins; d += kSortBlock) {
     const uint32_t c = h[d];
     hist[(int64_t)blockIdx.x * kBins + d] = c;
-    if (c) atomicAdd(&ghist[(int64_t)(blockIdx.x >> kGroupShift) * kBins + d], c);
+    if (c) {
+      atomicAdd(&ghist[(int64_t)(blockIdx.x >> kGroupShift) * kBins + d], c);
+      atomicAdd(&shist[(int64_t)(blockIdx.x >> kSubShift) * kBins + d], c);
+    }
   }
 }
 
 template <int kBins>
 __global__ __launch_bounds__(kSortBlock) void radix_scatter_keys_wide_kernel(
     const uint32_t *__restrict__ keys_in, int64_t n_host, const uint64_t *__restrict__ n_dev, int shift, uint32_t mask, int bits,
-    const uint32_t *__restrict__ hist, const uint32_t *__restrict__ ghist, uint32_t *__restrict__ keys_out,
-    const uint32_t *__restrict__ unpack, uint32_t rank_mask, uint32_t *__restrict__ vals_out, int32_t *__restrict__ offsets_out,
+    const uint32_t *__restrict__ hist, const uint32_t *__restrict__ ghist, const uint32_t *__restrict__ shist,
+    uint32_t *__restrict__ keys_out, const uint32_t *__restrict__ unpack, uint32_t rank_mask, uint32_t *__restrict__ vals_out,
+    int32_t *__restrict__ offsets_out,
     int n_offsets) {
   constexpr int kPer = kBins / kSortBlock;   // digits per thread (consecutive: thread t owns [t * kPer, (t + 1) * kPer))
   const int64_t n = list_length(n_host, n_dev);
@@ -452,6 +476,17 @@ __global__ __launch_bounds__(kSortBlock) void radix_scatter_keys_wide_kernel(
   for (int d = tid; d < kBins; d += kSortBlock) {
 #pragma unroll
     for (int w = 0; w < kSortWaves; w++) wrun[w][d] = 0;
+  }
+  // (the bases first, and parked in LDS -- each thread reads its own slots back below: the rows' 14 kPer loaded words are summed before
+  //  the sixteen keys per thread arrive; held in registers next to them they would cost a resident workgroup)
+  {
+    uint32_t gt[kPer], below[kPer];
+    grouped_bases<kPer>(hist, ghist, shist, vb, (int)((n + kSortChunk - 1) / kSortChunk), gt, below);
+#pragma unroll
+    for (int u = 0; u < kPer; u++) {
+      dstart[tid * kPer + u] = gt[u];
+      gbase[tid * kPer + u] = below[u];
+    }
   }
   __syncthreads();
   const int64_t wbase = bbase + (int64_t)wv * (kSortChunk / kSortWaves);
@@ -468,11 +503,13 @@ __global__ __launch_bounds__(kSortBlock) void radix_scatter_keys_wide_kernel(
       for (int w = 0; w < kSortWaves; w++) tot[u] += wrun[w][d];
       sum += tot[u];
     }
-    uint32_t gt[kPer], below[kPer];
-    grouped_bases<kPer, 4>(hist, ghist, vb, (int)((n + kSortChunk - 1) / kSortChunk), gt, below);
-    uint32_t gsum = 0;
+    uint32_t gt[kPer], below[kPer], gsum = 0;
 #pragma unroll
-    for (int u = 0; u < kPer; u++) gsum += gt[u];
+    for (int u = 0; u < kPer; u++) {
+      gt[u] = dstart[tid * kPer + u];
+      below[u] = gbase[tid * kPer + u];
+      gsum += gt[u];
+    }
     uint32_t all;
     uint32_t dbase = block_excl_scan(gsum, all, lw);   // entries of smaller digits in the whole input
     uint32_t base = block_excl_scan(sum, all, lw);
@@ -501,17 +538,20 @@ __global__ __launch_bounds__(kSortBlock) void radix_scatter_keys_wide_kernel(
 
 constexpr int kWideBits = 10;   // widest digit of the packed tile pass
 
+// partial rows of a workgroup-major histogram of nb workgroup rows: the group rows, then the sub-group rows
+static int64_t partial_rows(int64_t nb) { return cdiv(nb, 1 << kGroupShift) + cdiv(nb, 1 << kSubShift); }
+
 static size_t radix_temp_elems(int64_t n, int max_bins = 256) {
   const int64_t nblocks = cdiv(n > 0 ? n : 1, kSortChunk);
   const size_t h = align_up((size_t)max_bins * nblocks, 4);
-  const size_t group_rows = max_bins > 256 ? (size_t)max_bins * (size_t)cdiv(nblocks, 1 << kGroupShift) : 0;   // wide passes
+  const size_t group_rows = max_bins > 256 ? (size_t)max_bins * (size_t)partial_rows(nblocks) : 0;   // wide passes
   const size_t behind = scan_temp_elems((int64_t)max_bins * nblocks);
   return h + (behind > group_rows ? behind : group_rows);
 }
 
-// uint32 words behind the histogram that the wide pass expects ZERO when it starts (its group rows)
+// uint32 words behind the histogram that the wide pass expects ZERO when it starts (its group and sub-group rows)
 static size_t radix_wide_group_elems(int64_t n, int bits) {
-  return (size_t)(1 << bits) * (size_t)cdiv(cdiv(n > 0 ? n : 1, kSortChunk), 1 << kGroupShift);
+  return (size_t)(1 << bits) * (size_t)partial_rows(cdiv(n > 0 ? n : 1, kSortChunk));
 }
 
 static int radix_pass(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t *vout, int64_t n, int shift,
@@ -543,15 +583,16 @@ static int radix_pass_keys(const uint32_t *kin, uint32_t *kout, int64_t n, int s
   uint32_t *hist = temp;
   uint32_t *stemp = temp + align_up((size_t)(bits > 8 ? (1 << kWideBits) : 256) * nblocks, 4);
   if (bits > 8) {
-    uint32_t *ghist = stemp;   // zeroed by the caller's preceding launch (radix_wide_group_elems words)
+    // zeroed by the caller's preceding launch (radix_wide_group_elems words): the group rows, the sub-group rows behind them
+    uint32_t *ghist = stemp, *shist = stemp + (size_t)(1 << bits) * (size_t)cdiv(nblocks, 1 << kGroupShift);
     if (bits == 9) {
-      hipLaunchKernelGGL((radix_hist_wide_kernel<512>), dim3(nblocks), dim3(kSortBlock), 0, st, kin, n, n_dev, shift, mask, hist, ghist);
+      hipLaunchKernelGGL((radix_hist_wide_kernel<512>), dim3(nblocks), dim3(kSortBlock), 0, st, kin, n, n_dev, shift, mask, hist, ghist, shist);
       hipLaunchKernelGGL((radix_scatter_keys_wide_kernel<512>), dim3(nblocks), dim3(kSortBlock), 0, st, kin, n, n_dev, shift, mask, bits,
-                         hist, ghist, kout, unpack, rank_mask, vout, offsets_out, n_offsets);
+                         hist, ghist, shist, kout, unpack, rank_mask, vout, offsets_out, n_offsets);
     } else {
-      hipLaunchKernelGGL((radix_hist_wide_kernel<1024>), dim3(nblocks), dim3(kSortBlock), 0, st, kin, n, n_dev, shift, mask, hist, ghist);
+      hipLaunchKernelGGL((radix_hist_wide_kernel<1024>), dim3(nblocks), dim3(kSortBlock), 0, st, kin, n, n_dev, shift, mask, hist, ghist, shist);
       hipLaunchKernelGGL((radix_scatter_keys_wide_kernel<1024>), dim3(nblocks), dim3(kSortBlock), 0, st, kin, n, n_dev, shift, mask, bits,
-                         hist, ghist, kout, unpack, rank_mask, vout, offsets_out, n_offsets);
+                         hist, ghist, shist, kout, unpack, rank_mask, vout, offsets_out, n_offsets);
     }
     BDS_LAUNCH_CHECK();
     return BDS_OK;
@@ -571,8 +612,10 @@ static int radix_pass_keys(const uint32_t *kin, uint32_t *kout, int64_t n, int s
 // ------------------------------------------------------------------------------------------
 // The depth sort of the visible entries is latency-bound (a few hundred thousand keys: every launch costs more
 // than the bytes it moves), so the scan of the [digit][workgroup] histogram is folded away: histograms are stored
-// workgroup-major, every 64 workgroups also add theirs to a group row (256 atomics per workgroup), and a scatter
-// workgroup derives its own bases from <= ng group rows + <= 63 workgroup rows (all L2-resident).
+// workgroup-major, every 64 workgroups also add theirs to a group row and every 8 to a sub-group row (2 x 256 atomics
+// per workgroup at most), and a scatter workgroup derives its own bases from <= ng group rows + <= 7 sub-group rows +
+// <= 7 workgroup rows (all L2-resident; the short sets in ONE round of loads: with group rows alone the workgroup with
+// vb % 64 == 63 summed 63 workgroup rows, 8 dependent rounds -- profiles/NOTES.md "Tile stage: two-level histogram rows").
 // Chunks of 1024 pairs (4 rounds per wave): a few hundred thousand keys then spread over > 256 workgroups.
 // (Measured and dropped: accumulating the NEXT digit's histogram inside the scatter, per output chunk, with global atomics -- the
 // upper bytes of fp32 depths take a handful of values, so a whole chunk hits ONE counter: 14 -> 500 us for the third pass.)
@@ -591,21 +634,25 @@ __device__ __forceinline__ int64_t bounded_count(const uint64_t *n_dev, int64_t 
 __global__ __launch_bounds__(kSortBlock) void short_hist_kernel(const uint32_t *__restrict__ keys,
                                                                const uint64_t *__restrict__ n_dev, int64_t n_cap, int shift,
                                                                uint32_t *__restrict__ hist /*[nblocks][256]*/,
-                                                               uint32_t *__restrict__ ghist /*[ng][256], zeroed*/) {
+                                                               uint32_t *__restrict__ ghist /*[ng][256], zeroed*/,
+                                                               uint32_t *__restrict__ shist /*[nsg][256], zeroed*/) {
   __shared__ uint32_t h[256];
   const int64_t n = bounded_count(n_dev, n_cap), base = (int64_t)blockIdx.x * kShortChunk;
   if (base >= n) return;  // the launch is sized for the host-side bound
   chunk_hist<256, kShortRounds>(h, keys, base, n, shift, 255u);
   const uint32_t c = h[threadIdx.x];
   hist[(int64_t)blockIdx.x * 256 + threadIdx.x] = c;
-  if (c) atomicAdd(&ghist[(int64_t)(blockIdx.x >> kGroupShift) * 256 + threadIdx.x], c);
+  if (c) {
+    atomicAdd(&ghist[(int64_t)(blockIdx.x >> kGroupShift) * 256 + threadIdx.x], c);
+    atomicAdd(&shist[(int64_t)(blockIdx.x >> kSubShift) * 256 + threadIdx.x], c);
+  }
 }
 
-// wave-private ranking as in radix_scatter_lds_kernel; bases from the group / workgroup rows; every round's pairs go straight out
+// wave-private ranking as in radix_scatter_lds_kernel; bases from the group / sub-group / workgroup rows; every round's pairs go straight out
 __global__ __launch_bounds__(kSortBlock) void short_scatter_kernel(
     const uint32_t *__restrict__ keys_in, const uint32_t *__restrict__ vals_in, const uint64_t *__restrict__ n_dev, int64_t n_cap,
-    int shift, const uint32_t *__restrict__ hist, const uint32_t *__restrict__ ghist, uint32_t *__restrict__ keys_out,
-    uint32_t *__restrict__ vals_out) {
+    int shift, const uint32_t *__restrict__ hist, const uint32_t *__restrict__ ghist, const uint32_t *__restrict__ shist,
+    uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out) {
   const int64_t n = bounded_count(n_dev, n_cap);
   const int vb = (int)blockIdx.x;
   if ((int64_t)vb * kShortChunk >= n) return;
@@ -616,7 +663,7 @@ __global__ __launch_bounds__(kSortBlock) void short_scatter_kernel(
   for (int w = 0; w < kSortWaves; w++) wrun[w][tid] = 0;
   // digit `tid`: elements of this digit in the whole input, and in front of this workgroup
   uint32_t total[1], below[1];
-  grouped_bases<1, 8>(hist, ghist, vb, (int)((n + kShortChunk - 1) >> kChunkShift), total, below);
+  grouped_bases<1>(hist, ghist, shist, vb, (int)((n + kShortChunk - 1) >> kChunkShift), total, below);
   uint32_t all;
   const uint32_t digit_base = block_excl_scan(total[0], all, lw);   // (contains the barrier that publishes wrun = 0)
   const int64_t wbase = (int64_t)vb * kShortChunk + (int64_t)wv * (kShortChunk / kSortWaves);
@@ -636,10 +683,11 @@ __global__ __launch_bounds__(kSortBlock) void short_scatter_kernel(
   }
 }
 
-// uint32 elements: one workgroup-major histogram + four zero-initialised group tables
+// uint32 elements: one workgroup-major histogram + four zero-initialised tables of partial rows (a pass's group rows, then its
+// sub-group rows)
 static size_t short_sort_elems(int64_t n_bound) {
-  const int64_t nb = cdiv(n_bound > 0 ? n_bound : 1, kShortChunk), ng = cdiv(nb, 1 << kGroupShift);
-  return (size_t)(nb + 4 * ng) * 256;
+  const int64_t nb = cdiv(n_bound > 0 ? n_bound : 1, kShortChunk);
+  return (size_t)(nb + 4 * partial_rows(nb)) * 256;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -703,14 +751,14 @@ __global__ __launch_bounds__(kScanBlock) void visible_compact_kernel(int64_t CN,
                                                                     const uint32_t *__restrict__ tile_sums,
                                                                     uint32_t *__restrict__ keys, uint32_t *__restrict__ vals,
                                                                     uint32_t *__restrict__ hist, uint32_t *__restrict__ ghist,
-                                                                    uint64_t *__restrict__ n_vis_out, uint32_t *__restrict__ asc,
+                                                                    uint32_t *__restrict__ shist, uint64_t *__restrict__ n_vis_out, uint32_t *__restrict__ asc,
                                                                     int compact, int sums_per_tile, int sd) {
   constexpr int kSpan = kCompactSpan;
   __shared__ uint32_t lw[kScanBlock / kWave + 1];
   __shared__ uint32_t h[kSpan][256];
   const int vb = (int)blockIdx.x, nvb = (int)gridDim.x;
-  uint32_t part = 0;
   // (sums_per_tile = 8: the counts were left per 256-Gaussian workgroup by the one-view projection, bds_project_view_fwd with prep_ws)
+  uint32_t part = 0;
   for (int b = threadIdx.x; b < vb * sums_per_tile; b += kScanBlock) part += tile_sums[b];
   uint32_t my_offset;
   block_excl_scan(part, my_offset, lw);   // total of the partial sums = this tile's offset
@@ -758,6 +806,7 @@ __global__ __launch_bounds__(kScanBlock) void visible_compact_kernel(int64_t CN,
     if (c) {
       atomicAdd(&hist[(int64_t)(chunk0 + t) * 256 + threadIdx.x], c);
       atomicAdd(&ghist[(int64_t)((chunk0 + t) >> kGroupShift) * 256 + threadIdx.x], c);
+      atomicAdd(&shist[(int64_t)((chunk0 + t) >> kSubShift) * 256 + threadIdx.x], c);
     }
   }
   if (vb == nvb - 1 && threadIdx.x == 0) *n_vis_out = (uint64_t)my_offset + tot;
@@ -956,7 +1005,7 @@ __global__ __launch_bounds__(kIsectBlock) void isect_emit_rows_kernel(
     const float *__restrict__ opacities, int tile_size, int tile_w, int tile_h, uint32_t *__restrict__ keys,
     uint32_t *__restrict__ vals, int pack_shift, const float4 *__restrict__ rec, uint32_t *__restrict__ zero_words, int n_zero) {
   __shared__ EmitRowsSh sh;
-  // (the group rows of the tile pass that follows: cleared here, by every workgroup of the launch a word each, before anything returns)
+  // (the group and sub-group rows of the tile pass that follows: cleared here, by every workgroup of the launch a word each, before anything returns)
   for (int64_t i = (int64_t)blockIdx.x * kIsectBlock + threadIdx.x; i < n_zero; i += (int64_t)gridDim.x * kIsectBlock) zero_words[i] = 0u;
   isect_emit_rows_block(sh, (int)blockIdx.x, (int64_t)*n_vis_dev, N, sorted_idx, btot, means2d, radii, conics, opacities, tile_size, tile_w,
                         tile_h, keys, vals, pack_shift, rec);
@@ -996,7 +1045,7 @@ struct PrepWs {
   uint32_t *cum;        // [CN] exclusive scan of counts in depth order
   uint32_t *asc;        // [CN] ids cam*N+g of the visible entries in ascending order (compact position -> id)
   uint32_t *temp;       // radix / scan temp
-  uint32_t *tables;     // short path: workgroup-major histogram + 4 group tables
+  uint32_t *tables;     // short path: workgroup-major histogram + 4 tables of partial rows
   float4 *rec;          // [CN][3] per-member records in depth order, written by EVERY counting kernel, read by the row emission
   uint32_t *btot;       // [cdiv(CN,256)] intersections of each 256-member group of the depth order (every counting kernel)
   size_t bytes;
@@ -1159,9 +1208,9 @@ static int prepare_enqueue(int C, int64_t N, const float *means2d, const int32_t
   int rc;
   if (CN <= kShortSortMax && option_get(kOptShortSort)) {
     // 12 launches instead of 27: the whole stage is launch-latency bound at this size
-    const int64_t nb = cdiv(CN, kShortChunk), ng = cdiv(nb, 1 << kGroupShift);
+    const int64_t nb = cdiv(CN, kShortChunk), ng = cdiv(nb, 1 << kGroupShift), npr = partial_rows(nb);
     const unsigned nb_launch = (unsigned)cdiv(nvis_bound > 0 ? nvis_bound : 1, kShortChunk);
-    uint32_t *hist = L.tables, *ghist = L.tables + nb * 256;   // ghist[p] = ghist + p * ng * 256
+    uint32_t *hist = L.tables, *ghist = L.tables + nb * 256;   // pass p: group rows at ghist + p * npr * 256, sub-group rows ng rows on
     const unsigned tiles = (unsigned)cdiv(CN, kScanTile);
     // 1. visible entries -> (depth key, id) pairs in index order + histogram of the first digit
     // (compact & 2: the one-view projection has already left the visible counts -- per 256 Gaussians -- and cleared the tables)
@@ -1169,15 +1218,15 @@ static int prepare_enqueue(int C, int64_t N, const float *means2d, const int32_t
       hipLaunchKernelGGL(visible_reduce_kernel, dim3(tiles), dim3(kScanBlock), 0, st, CN, radii, L.temp, L.tables,
                          (int64_t)short_sort_elems(CN), L.total, tiles_per_gauss);
     hipLaunchKernelGGL(visible_compact_kernel, dim3(tiles), dim3(kScanBlock), 0, st, CN, radii, depths, L.temp, L.ka, L.va, hist,
-                       ghist, n_vis, L.asc, compact & 1, (compact & 2) ? kScanTile / 256 : 1, pl.sd);
+                       ghist, ghist + ng * 256, n_vis, L.asc, compact & 1, (compact & 2) ? kScanTile / 256 : 1, pl.sd);
     BDS_LAUNCH_CHECK();
     // 2. depth order: 4 stable passes of 8 bits; ends in (ka, va)
     uint32_t *kin = L.ka, *vin = L.va, *kout = L.kb, *vout = L.vb;
     for (int p = 0; p < 4; p++) {
-      uint32_t *gh = ghist + (int64_t)p * ng * 256;
-      if (p > 0) hipLaunchKernelGGL(short_hist_kernel, dim3(nb_launch), dim3(kSortBlock), 0, st, kin, n_vis, n_cap, 8 * p, hist, gh);
-      hipLaunchKernelGGL(short_scatter_kernel, dim3(nb_launch), dim3(kSortBlock), 0, st, kin, vin, n_vis, n_cap, 8 * p, hist, gh, kout,
-                         vout);
+      uint32_t *gh = ghist + (int64_t)p * npr * 256, *sh = gh + ng * 256;
+      if (p > 0) hipLaunchKernelGGL(short_hist_kernel, dim3(nb_launch), dim3(kSortBlock), 0, st, kin, n_vis, n_cap, 8 * p, hist, gh, sh);
+      hipLaunchKernelGGL(short_scatter_kernel, dim3(nb_launch), dim3(kSortBlock), 0, st, kin, vin, n_vis, n_cap, 8 * p, hist, gh, sh,
+                         kout, vout);
       uint32_t *t;
       t = kin; kin = kout; kout = t;
       t = vin; vin = vout; vout = t;
@@ -1327,7 +1376,7 @@ extern "C" int bds_isect_build(int C, int64_t N, int64_t M, int64_t n_visible, c
   if (packed) {
     key_shift = rank_bits;
     uint32_t *k_emit = (npass % 2 == 1) ? B.ka : B.kb;   // the last pass lands in B.kb
-    // a wide pass (radix_pass_keys, bits > 8) finds its group rows behind the histogram; the emission clears them on its way
+    // a wide pass (radix_pass_keys, bits > 8) finds its group and sub-group rows behind the histogram; the emission clears them on its way
     const bool wide = bits_per > 8;
     uint32_t *wide_zero = wide ? B.temp + align_up((size_t)(1 << kWideBits) * (size_t)cdiv(M, kSortChunk), 4) : nullptr;
     const int wide_zero_n = wide ? (int)radix_wide_group_elems(M, bits_per) : 0;
