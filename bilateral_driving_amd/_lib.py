@@ -159,6 +159,8 @@ _SIGS = {
     "bds_view_fields": (_i, [_i, _i, _i, _f, _f, _i, _fl, _f, _f] + [_f] * 9 + [_f]),
     "bds_image_resize_aa": (_i, [_i, _i, C.c_double, _f, _f, _f]),
     "bds_masks_resize_nearest": (_i, [_i, _i, _i, C.c_double, _f, _f, _f]),
+    "bds_error_maps_workspace_bytes": (_sz, [_i, _i, _i]),
+    "bds_error_maps": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _f, _i, _f, _sz, _f]),
     "bds_opacity_reset": (_i, [_i64, _f, _fl, _f, _f, _f]),
     "bds_cubemap_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f]),
     "bds_cubemap_bwd": (_i, [_i64, _i, _i, _i, _f, _f, _f, _f, _f]),

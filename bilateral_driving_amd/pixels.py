@@ -27,7 +27,8 @@ to the device in ONE small copy together with ``height`` and ``width``; the ones
 ``frame_idx`` that is a device tensor still selects the frame's rows through torch's own indexing, which may wait for it).  Per call
 ``get_image`` is one launch at ``downscale_factor == 1``, and at most four (fields, image, masks, lidar map) otherwise.
 
-Not covered: the error-map buffer (``update_image_error_maps``, ``propose_training_image``), ``cam.undistort``, file loading."""
+Not covered: ``cam.undistort``, file loading.  The error-map buffer (``update_image_error_maps``, ``propose_training_image``) lives in
+``sampler.py``."""
 from __future__ import annotations
 
 import math
@@ -285,11 +286,14 @@ def _on_device(obj) -> bool:
     return isinstance(t, Tensor) and t.is_cuda
 
 
-def _dispatch(fn, target, name):
-    """``fn`` for an object on the device; for one on the CPU the method that ``target`` had: its own, else the inherited one."""
+def _dispatch(fn, target, name, seam=None):
+    """``fn`` for an object on the device; for one on the CPU the method that ``target`` had: its own, else the inherited one.
+    ``seam``: the installing module's (default: this one's)."""
+    seam = _SEAM if seam is None else seam
+
     def method(self, *args, **kwargs):
         if not _on_device(self):
-            own = _SEAM.former(target, name)
+            own = seam.former(target, name)
             if own is not MISSING:
                 return own(self, *args, **kwargs)
             inherited = getattr(super(target, self), name, None)

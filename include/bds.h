@@ -1169,6 +1169,27 @@ int bds_view_fields(int B, int H, int W, const float *c2w, const float *intrinsi
 int bds_image_resize_aa(int H, int W, double factor, const float *in, float *out, bds_stream_t stream);
 int bds_masks_resize_nearest(int n, int H, int W, double factor, const float *const *in, float *const *out, bds_stream_t stream);
 
+/* The error-driven image sampler's maps (CameraData.update_image_error_maps, datasets/base/pixel_source.py:431-449, and the per-image
+ * means of ScenePixelSource.update_image_error_maps :948-983) of B rendered views [h,w] in one call: pointers + stream, no allocation,
+ * no read-back, two launches (the maps with one partial per workgroup, then the statistics), no atomics: bit-identical run to run.
+ * pred, gt [B,h,w,3] float32, dyn [B,h,w] float32 or NULL (no dynamic opacity).  Per pixel (csrc/error_buffer_math.h):
+ *   e = ((|g0 - c0| + |g1 - c1|) + |g2 - c2|) / 3, c = clamp(p, 0, 1) (render_images' clamp, models/video_utils.py:185-187; gt is not
+ *   clamped), e * 5 where dyn > 0.1f, strictly; float32, every operation rounded on its own; a NaN in p or g gives a NaN e.
+ * slots, img_ids [B] int64 ON THE DEVICE: view b's map goes to maps[slots[b]] (maps [F,h,w]) and its statistics to stats[img_ids[b]]
+ * (stats [num_imgs,3]: mean, min, max of the view's e).  The mean is summed in double in a fixed order, divided by h w and rounded to
+ * float32 once; min and max propagate a NaN.  The slots of one call must differ, and so must the ids.  Rows of maps and stats that no
+ * view names keep their bits; a slot outside [0, F) or an id outside [0, num_imgs) drops that view's map or statistics (nothing is
+ * written out of bounds).  Views whose bases are 16-byte aligned move 16 bytes per access, others 4: the results are the same bits.
+ * ws: bds_error_maps_workspace_bytes(B, h, w) bytes, 16-byte aligned.  0 with nothing done for B = 0; for h w = 0 the named stats rows
+ * become NaN (the mean of nothing) where stats and img_ids are given.  BDS_EINVAL before any launch: a negative extent, F or num_imgs,
+ * B h w above 2^31 - 1 (the size query then answers 0), more than 2^24 - 1 workgroups (one per 1024 pixels of a view, at most 1024 per
+ * view), a NULL pred / gt / slots / img_ids / maps / stats / ws, a misaligned pointer (4 bytes; slots, img_ids 8; ws 16), or a
+ * workspace that is too small. */
+size_t bds_error_maps_workspace_bytes(int B, int h, int w);
+int bds_error_maps(int B, int h, int w, const float *pred, const float *gt, const float *dyn, const int64_t *slots,
+                   const int64_t *img_ids, float *maps, int F, float *stats, int num_imgs, void *ws, size_t ws_bytes,
+                   bds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
