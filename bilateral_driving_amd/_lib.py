@@ -147,7 +147,8 @@ _SIGS = {
     "bds_chamfer_nn": (_i, [_i64, _i64, _f, _f, _i, _f, _f, _f]),
     "bds_knn_workspace_bytes": (_sz, [_i64]),
     "bds_knn_self": (_i, [_i64, _f, _i, _f, _f, _f, _i, C.c_float, C.c_float, _f, _sz, _f]),
-    "bds_lidar_project": (_i, [_i, _i, _i, _i64] + [_f] * 9 + [_f]),
+    "bds_cross_knn": (_i, [_i, _i64, _i64, _f, _f, _f, _f, _i, _i, _f, _f, _f, _i, C.c_float, C.c_float, _f, _f]),
+    "bds_lidar_project":(_i, [_i, _i, _i, _i64] + [_f] * 9 + [_f]),
     "bds_lidar_visible": (_i, [_i64, _f, _i, _f, _f, _f, _f]),
     "bds_lidar_points_in_boxes": (_i, [_i64, _f, _i, _f, _f, _f, _i, _f, _f]),
     "bds_lidar_boxes_workspace_bytes": (_sz, [_i64]),

@@ -48,6 +48,18 @@ BDS_HD float knn_pair(float ax, float ay, float az, float bx, float by, float bz
   return (xx + yy) + zz;
 }
 
+// the L1 twin of knn_pair for the cross search (csrc/knn_cross.hip, norm = 1): (|dx| + |dy|) + |dz|, each sum rounded on its own
+BDS_HD float knn_pair_l1(float ax, float ay, float az, float bx, float by, float bz) {
+#pragma clang fp contract(off)
+  const float dx = ax - bx, dy = ay - by, dz = az - bz;
+  return (fabsf(dx) + fabsf(dy)) + fabsf(dz);
+}
+
+// the cross search's blend epilogue: the inverse of the clamped distance of a neighbour at squared distance d2
+BDS_HD float knn_blend_weight(float d2, float clamp_lo, float clamp_hi) { return 1.0f / fminf(fmaxf(sqrtf(d2), clamp_lo), clamp_hi); }
+
+constexpr int kKnnEmptyRow = 0x7fffffff;      // the row knn_clear leaves in a slot no candidate has taken
+
 BDS_HD bool knn_less(float da, int ia, float db, int ib) { return da < db || (da == db && ia < ib); }
 
 template <int K>
@@ -81,6 +93,27 @@ BDS_HD void knn_insert(KnnBest<K> &b, float d, int i) {
     b.i[s - 1] = up ? i1 : i0;
     b.i[s] = up ? i0 : i1;
   }
+}
+
+// knn_insert's result by shifting, for the long lists of the cross search: entry s takes entry s - 1 where the newcomer goes below
+// that one, the newcomer itself where it goes below entry s only.  Walking down from the last entry, each step reads entry s - 1
+// before anything has overwritten it, so the list is updated in place: two flags live at a time, no second copy of the list.
+// knn_less without the short circuit: three compares and two mask operations, no branch per entry
+BDS_HD bool knn_less_flat(float da, int ia, float db, int ib) { return (da < db) | ((da == db) & (ia < ib)); }
+
+template <int K>
+BDS_HD void knn_insert_shift(KnnBest<K> &b, float d, int i) {
+  bool below = knn_less_flat(d, i, b.d[K - 1], b.i[K - 1]);
+  if (!below) return;
+#pragma unroll
+  for (int s = K - 1; s > 0; s--) {
+    const bool above = knn_less_flat(d, i, b.d[s - 1], b.i[s - 1]);
+    b.d[s] = above ? b.d[s - 1] : (below ? d : b.d[s]);
+    b.i[s] = above ? b.i[s - 1] : (below ? i : b.i[s]);
+    below = above;
+  }
+  b.d[0] = below ? d : b.d[0];
+  b.i[0] = below ? i : b.i[0];
 }
 
 BDS_HD int knn_cell_axis(float p, float lo, float inv, int dim) {

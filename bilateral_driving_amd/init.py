@@ -17,8 +17,9 @@ One deviation: a point is never its own neighbour here (the query is excluded by
 sklearn's can -- among exact duplicates it drops whichever of them the tree returned first.  The distances are the same either way,
 and the reference discards the rows.
 
-Not covered: pytorch3d's ``knn_points`` of the SMPL classes (batched, K = 30 against the template's vertices); K > 8; queries of one
-cloud against another (``geometry.chamfer_distance`` does K = 1)."""
+Not covered here: K > 8 and queries of one cloud against another.  Those are ``p3d.knn_points`` (pytorch3d's ``knn_points`` of the
+SMPL classes: batched, K up to 32, cross-cloud, the query included; brute force) and, for evaluation's K = 1 over large clouds,
+``geometry.chamfer_distance``."""
 from __future__ import annotations
 
 import math

@@ -1041,6 +1041,37 @@ size_t bds_knn_workspace_bytes(int64_t N);
 int bds_knn_self(int64_t N, const float *x, int K, float *dist, int32_t *idx, float *log_scales, int S, float clamp_lo, float clamp_hi,
                  void *ws, size_t ws_bytes, bds_stream_t stream);
 
+/* Exact K nearest rows of p2[b] for every row of p1[b], batched, forward only: pytorch3d.ops.knn_points as the reference calls it --
+ * models/modules.py:1199 (VoxelDeformer._query_weights_smpl: K = 30 of the template's 6890 vertices for each of 16*64*64 voxel
+ * centres per human), models/nodes/smpl.py:186 (update_knn: a batch of clouds against themselves, K = 3, the query included) and
+ * utils/chamfer_distance.py:45-46 (K = 1) -- with the inverse-distance blend of modules.py:1200-1206 as an epilogue.  One launch, no
+ * workspace, no host wait (csrc/knn_cross.hip).  p1 [B,P1,3], p2 [B,P2,3] float32; the entry does NOT check that the coordinates are
+ * finite (pytorch3d does not either): a NaN coordinate makes a NaN value, which never enters a list.
+ *   value   norm 2: the SQUARED distance (dx*dx + dy*dy) + dz*dz from the float32 coordinate differences, every operation rounded on
+ *           its own (no fused multiply-add); norm 1: (|dx| + |dy|) + |dz|.
+ *   order   ascending; candidates are ordered by (value, row of p2), so the row decides ties, the result does not depend on the order
+ *           of evaluation and is bit-identical run to run.  The query is NOT excluded: a cloud against itself finds each point first.
+ *   lengths len1 / len2 [B] int64 on the device or NULL (every cloud full), clamped to 0..P1 / 0..P2 on the device.  Only the first
+ *           len2[b] rows of p2[b] are candidates; rows of p1[b] at or beyond len1[b], and the slots len2[b]..K-1 of every row, hold
+ *           dists = 0 and idx = 0 (pytorch3d's padding).  Every element of every output is written.
+ *   dists [B,P1,K] float32 or NULL, idx [B,P1,K] int64 or NULL.
+ *   blend [B,P1,J] float32 or NULL, together with feat [B,P2,J] (both or neither; norm 2 only; J 1..BDS_KNN_CROSS_MAX_J;
+ *           0 < clamp_lo <= clamp_hi): w_k = 1 / min(max(sqrt(d2_k), clamp_lo), clamp_hi) over the slots that hold a neighbour,
+ *           blend[j] = sum_k (w_k / sum w) * feat[idx_k][j], k ascending; a row without a neighbour gets zeros.  dists and idx may
+ *           then both be NULL.
+ * BDS_KNN_CROSS_QUERY_BLOCK queries of one cloud per workgroup, the candidates staged through LDS in tiles of
+ * BDS_KNN_CROSS_TARGET_TILE records.  B, P1 or P2 equal to 0 is valid: nothing is launched when B * P1 = 0, and everything is padding
+ * when P2 = 0.
+ * BDS_EINVAL before any launch: K outside 1..BDS_KNN_CROSS_MAX_K; norm outside {1, 2}; a negative size, P2 >= 2^31 - 1 or more than
+ * 2^31 - 1 workgroups; a NULL p1 / p2 that has elements; dists, idx and blend all NULL; feat without blend or the converse; a blend
+ * with norm 1, J out of range, P2 * J above 2^29 or a clamp that is not 0 < lo <= hi; a float pointer not aligned to 4 bytes, idx / len1 / len2 to 8. */
+#define BDS_KNN_CROSS_MAX_K 32
+#define BDS_KNN_CROSS_MAX_J 64
+#define BDS_KNN_CROSS_QUERY_BLOCK 256
+#define BDS_KNN_CROSS_TARGET_TILE 512
+int bds_cross_knn(int B, int64_t P1, int64_t P2, const float *p1, const float *p2, const int64_t *len1, const int64_t *len2, int K, int norm,
+                  float *dists, int64_t *idx, const float *feat, int J, float clamp_lo, float clamp_hi, float *blend, bds_stream_t stream);
+
 /* Lidar scene preparation: what DrivingDataset makes of the lidar before step 0, and the sparse depth map's downsampler of every
  * coarse-to-fine step.  points: [N,3] float32, every coordinate FINITE (the entries do not check; a caller must --
  * bds_nonfinite_flags).  Matrices are row-major float32 ON THE DEVICE.  One thread per point (per pixel / output cell where said); the
