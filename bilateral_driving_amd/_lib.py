@@ -41,6 +41,14 @@ class BdsDeformNet(C.Structure):
                 ("rot_b", C.c_void_p), ("scale_w", C.c_void_p), ("scale_b", C.c_void_p)]
 
 
+class BdsVideoPanel(C.Structure):
+    """bds_video_panel"""
+
+    _fields_ = [("src0", C.c_void_p), ("src1", C.c_void_p), ("kind", C.c_int32), ("flags", C.c_int32), ("src_h", C.c_int32),
+                ("src_w", C.c_int32), ("src_row0", C.c_int32), ("dst_y", C.c_int32), ("dst_x", C.c_int32), ("dst_h", C.c_int32),
+                ("dst_w", C.c_int32), ("reserved", C.c_int32)]
+
+
 _SIGS = {
     "bds_abi_version": (C.c_int, []),
     "bds_strerror": (C.c_char_p, [_i]),
@@ -162,6 +170,7 @@ _SIGS = {
     "bds_masks_resize_nearest": (_i, [_i, _i, _i, C.c_double, _f, _f, _f]),
     "bds_error_maps_workspace_bytes": (_sz, [_i, _i, _i]),
     "bds_error_maps": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _f, _i, _f, _sz, _f]),
+    "bds_video_frame": (_i, [_i, C.POINTER(BdsVideoPanel), _i, _i, _f, _f]),
     "bds_opacity_reset": (_i, [_i64, _f, _fl, _f, _f, _f]),
     "bds_cubemap_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f]),
     "bds_cubemap_bwd": (_i, [_i64, _i, _i, _i, _f, _f, _f, _f, _f]),

@@ -36,7 +36,8 @@ in place (not replaced) after a table was built is not noticed.
 Read-backs: one per ``finish()`` (the statistics, [num_imgs,3] float32).  ``add`` reads nothing back when ``cam_infos`` carries
 ``cam_name`` (the reference's always does) or a host ``cam_id``; a ``cam_id`` that only exists on the device is read to pick the camera.
 
-Not included: the multi-GPU split of the sweep, the mp4 writer and ``dataset.layout``, ``render_images`` itself."""
+Not included: the multi-GPU split of the sweep, ``render_images`` itself, the mp4 encoder.  The videos' frames -- ``dataset.layout``,
+the depth colours and the 8-bit quantiser -- are video.py's."""
 from __future__ import annotations
 
 import bisect

@@ -1221,6 +1221,46 @@ int bds_error_maps(int B, int h, int w, const float *pred, const float *gt, cons
                    const int64_t *img_ids, float *maps, int F, float *stats, int num_imgs, void *ws, size_t ws_bytes,
                    bds_stream_t stream);
 
+/* One finished uint8 frame of an evaluation video (save_concatenated_videos, models/video_utils.py:703-768, and save_seperate_videos
+ * :771-857, with the dataset layouts, to8b and depth_visualizer of utils/visualization.py:19-22, 41-341, 412-497): where the reference
+ * colours, tiles, concatenates and quantises every timestep in numpy from host copies of the renders, one launch writes the canvas
+ * [Hc,Wc,3] uint8 from the device tensors.  panels: a HOST array of n_panels rectangles of the canvas, read during the call (passed on
+ * to the kernel by value: no upload, no allocation, nothing the stream outlives).  A panel shows rows [src_row0, src_row0 + dst_h) and
+ * columns [0, dst_w) of its source [src_h,src_w] at (dst_y, dst_x); where panels overlap the LATER one wins, as the reference's
+ * successive assignments do; a pixel in no panel is 0.  Every byte of the canvas is written: no memset precedes the call.  No
+ * atomics, no read-back: bit-identical run to run.  Per pixel (csrc/video_math.h), by kind:
+ *   BDS_VIDEO_RGB             src0 [src_h,src_w,3] float32: (uint8)(255.0f * clamp(x, 0, 1)) per channel, truncated (to8b); a NaN gives 0
+ *   BDS_VIDEO_GRAY            src0 [src_h,src_w] float32, or bytes (bool, uint8) with BDS_VIDEO_SRC0_BYTES: the same, replicated to three
+ *                             channels (the ``*mask*`` keys and gt_sky_masks, :735-740)
+ *   BDS_VIDEO_DEPTH           src0 depth float32, src1 weight float32, bytes with BDS_VIDEO_SRC1_BYTES, or NULL (1): turbo's entry
+ *                             min((int)(s * 256.0f), 255), s = clamp((-logf(d + 1e-6f) - min(lo, hi)) / |hi - lo|, 0, 1) * weight with
+ *                             lo = -log(4 + 1e-6), hi = -log(120 + 1e-6) (depth_visualizer, :741-756); a NaN s is 0, a NaN product black
+ *   BDS_VIDEO_OVER_GREEN      src0 rgb [.,.,3], src1 opacity [.,.] float32: to8b(clamp(rgb, 0, 1) * op + (0, 177, 64) / 255 * (1 - op))
+ *                             (:201-227 behind the clamp of :185-187)
+ *   BDS_VIDEO_LIDAR_ON_IMAGE  src0 pixels [.,.,3], src1 lidar depth map [.,.] float32: the depth's colour with weight 1 where it is
+ *                             > 0, else to8b of the pixel (:265-271)
+ * More than BDS_VIDEO_MAX_PANELS panels: one launch per band of rows that at most that many panels touch.
+ * BDS_OK with nothing done for Hc Wc = 0.  BDS_EINVAL before any launch: a negative count or extent, Hc Wc 3 or a source's
+ * src_h src_w 3 above 2^31 - 1, a NULL or misaligned (4 bytes) canvas, a NULL panels with n_panels > 0, and per panel an unknown kind or
+ * flag, a NULL src0 (src1 where the kind needs it), a float32 source off a 4-byte boundary, a rectangle outside the canvas or source
+ * rows or columns outside the source.  BDS_ECAPACITY: more than BDS_VIDEO_MAX_PANELS panels touch one row. */
+#define BDS_VIDEO_MAX_PANELS 64
+#define BDS_VIDEO_RGB 0
+#define BDS_VIDEO_GRAY 1
+#define BDS_VIDEO_DEPTH 2
+#define BDS_VIDEO_OVER_GREEN 3
+#define BDS_VIDEO_LIDAR_ON_IMAGE 4
+#define BDS_VIDEO_SRC0_BYTES 1
+#define BDS_VIDEO_SRC1_BYTES 2
+typedef struct bds_video_panel {
+  const void *src0, *src1;
+  int32_t kind, flags;
+  int32_t src_h, src_w, src_row0;
+  int32_t dst_y, dst_x, dst_h, dst_w;
+  int32_t reserved; /* 0 */
+} bds_video_panel;
+int bds_video_frame(int n_panels, const bds_video_panel *panels, int Hc, int Wc, uint8_t *canvas, bds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
