@@ -144,6 +144,9 @@ _SIGS = {
     "bds_node_pose_bwd_temp_bytes": (_sz, [_i64, _i]),
     "bds_node_pose_fwd": (_i, [_i64, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_node_pose_bwd": (_i, [_i64, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _f]),
+    "bds_smpl_skin_bwd_temp_bytes": (_sz, [_i, _i]),
+    "bds_smpl_skin_fwd": (_i, [_i, _i] + [_f] * 12 + [_i, _i, _i, _f, _f, _fl, _i, _f, _f, _f, _f]),
+    "bds_smpl_skin_bwd": (_i, [_i, _i] + [_f] * 11 + [_i, _i, _i, _f, _f, _fl, _i] + [_f] * 9 + [_f, _sz, _f]),
     "bds_pvg_temp_bytes": (_sz, [_i64]),
     "bds_pvg_fwd": (_i, [_i64, _i, _i, _fl, _fl, _i, C.c_double] + [_f] * 18 + [_sz, _f]),
     "bds_pvg_bwd": (_i, [_i64, _i64, _i, _i, _fl, _fl, _i, C.c_double] + [_f] * 9 + [_sz] + [_f] * 17),

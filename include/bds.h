@@ -903,6 +903,39 @@ int bds_node_pose_bwd(int64_t N, int F, int I, int cur_frame, const float *means
                       const float *v_world_quats, const float *v_opacities, float *v_means, float *v_quats, float *v_logits,
                       float *v_instances_quats, float *v_instances_trans, void *temp, size_t temp_bytes, bds_stream_t stream);
 
+/* ---- Pose chain and skinning of the SMPL nodes -------------------------------------------------------------------------------------
+ * SMPLNodes.transform_means_and_quats / transform_means (models/nodes/smpl.py:203-341) with SMPLTemplate.forward
+ * (models/human_body.py:158-180), batch_rigid_transform (third_party/smplx/smplx/lbs.py:362-418) and VoxelDeformer.forward
+ * (models/modules.py:1168-1188).  Instance i owns the rows [i V, (i+1) V) of means [I V,3] and quats [I V,4] (raw).  Per instance:
+ * root_quats [I,1,4] and body_quats [I,23,4] (the current frame's raw rows), trans [I,3], present [I] (one byte each),
+ * J_canonical [I,24,3], A0_inv [I,24,4,4]; parents: 24 int32 on the HOST, parents[0] unused, 0 <= parents[j] < j (else BDS_EINVAL,
+ * nothing launched).  The weights: voxel_base and voxel_corr (may be NULL) [I,24,d,h,w] with offset [I,1,3], scale [I,1,1], ratio and
+ * ratio_dim (0..2: the component of the normalised coordinate that ratio multiplies); or, with voxel_base NULL, the fixed W [I,V,24].
+ *   theta = normalise(cat(root, body)); R_j = quaternion_to_matrix(theta_j) (pytorch3d, 2 / |q|^2); the chain of
+ *   batch_rigid_transform with its rel_transforms column, times A0_inv: A [I,24,3,4] (rows 0..2; stored for the backward)
+ *   w = trilinear sample of voxel_base + voxel_corr at (x - offset) / scale (component ratio_dim times ratio), align_corners, border
+ *   T = sum_j w_j A_j; world_means = T.R x + T.t + trans; world_quats = quat_mult(n(matrix_to_quaternion(T.R)), n(quats))
+ *   (pytorch3d's matrix_to_quaternion on the non-orthogonal blend: largest q_abs, / (2 max(q_abs, 0.1)), sign to w >= 0).
+ * An absent instance (present[i] == 0): world_means = trans[i], world_quats = (1,0,0,0), A = 0.  world_quats NULL: the ball form
+ * (means only; quats may be NULL).
+ * bwd: v_means (the direct term and the one through the sampling coordinate; a clamped axis has none), v_quats (NULL iff
+ * v_world_quats is), v_root_quats [I,1,4] / v_body_quats [I,23,4] (to the RAW quaternions), v_trans [I,3], v_voxel_corr [I,24,d,h,w]
+ * (may be NULL; zeroed here, then float atomics: its summation order is unspecified).  An absent instance: v_trans[i] = the sum of its
+ * rows' v_world_means, every other gradient of it zero.  Pose and translation gradients are summed per workgroup and then per
+ * instance in a fixed order in temp (bds_smpl_skin_bwd_temp_bytes(I, V) bytes, 16-byte aligned): deterministic. */
+size_t bds_smpl_skin_bwd_temp_bytes(int I, int V);
+int bds_smpl_skin_fwd(int I, int V, const float *means, const float *quats, const float *root_quats, const float *body_quats,
+                      const float *trans, const uint8_t *present, const float *J_canonical, const float *A0_inv, const int32_t *parents,
+                      const float *voxel_base, const float *voxel_corr, const float *W, int d, int h, int w, const float *offset,
+                      const float *scale, float ratio, int ratio_dim, float *world_means, float *world_quats, float *A,
+                      bds_stream_t stream);
+int bds_smpl_skin_bwd(int I, int V, const float *means, const float *quats, const float *root_quats, const float *body_quats,
+                      const uint8_t *present, const float *J_canonical, const float *A0_inv, const int32_t *parents,
+                      const float *voxel_base, const float *voxel_corr, const float *W, int d, int h, int w, const float *offset,
+                      const float *scale, float ratio, int ratio_dim, const float *A, const float *v_world_means,
+                      const float *v_world_quats, float *v_means, float *v_quats, float *v_root_quats, float *v_body_quats,
+                      float *v_trans, float *v_voxel_corr, void *temp, size_t temp_bytes, bds_stream_t stream);
+
 /* Time transform of the periodic-vibration Gaussians: PeriodicVibrationGaussians.get_gaussians (models/gaussians/pvg.py:374-425) with
  * get_marginal_t (:81), temporal_means (:65-73), temporal_opacities (:75-78) and velocity / rho (:83-88), as three forward launches and
  * one backward launch.  Raw parameters, contiguous float32: means [N,3], velocity [N,3], taus [N], betas [N], logits [N] (the [N,1]
