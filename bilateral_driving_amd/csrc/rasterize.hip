@@ -163,7 +163,8 @@ __global__ __launch_bounds__(kPackShBlock) void splat_pack_sh_kernel(int64_t n_c
     // (the first form: float by float, 48 scalar loads per thread at degree 3 -- 70 us for the 310 k visible rows of the headline
     //  view where the one-array form takes 33).  Now n4 lanes per row as below: piece 0 = band 0 + the first float of `coeffs_rest`,
     //  piece c >= 1 = floats 4c-3 .. 4c of the row's `coeffs_rest`, ONE 16-byte load at 4-byte alignment each (gfx950 runs with
-    //  unaligned vector access enabled; a piece that would run past the row's end -- K = (DEG+1)^2 exactly -- goes float by float)
+    //  unaligned vector access enabled; a piece that would run past the row's end goes float by float -- K = (DEG+1)^2 = 9 only, whose
+    //  27 floats are no multiple of 4: at K = 4 and K = 16 the last piece ends on the row's last float)
     typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
     const int64_t row_rest = (int64_t)(K - 1) * 3;
     const int total = cnt * n4;

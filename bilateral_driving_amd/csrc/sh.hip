@@ -82,10 +82,13 @@ __global__ __launch_bounds__(kShBlock) void sh_fwd_kernel(int64_t n, int K, cons
 // Masked forward (the hot path evaluates SH after projection, only for the ~15 % of Gaussians that are
 // on screen): no LDS staging -- a visible Gaussian reads its own row with 16-byte loads, a culled one
 // touches nothing but its mask byte, so HBM traffic scales with the visible count.
-template <int DEG, bool kVec>
+// vec (16-byte loads: rows on 16-byte boundaries) is a wave-uniform ARGUMENT, not a template parameter: the two memory paths meet
+// in front of ONE copy of the arithmetic.  As two instantiations the compiler was free to contract a*b + c*d (the norm, the bases)
+// into different fused multiply-adds in each, and an array moved by 4 bytes changed the last bit of its colours.
+template <int DEG>
 __global__ __launch_bounds__(kShBlock) void sh_fwd_masked_kernel(int64_t n, int K, const float *__restrict__ dirs,
                                                                 const float *__restrict__ coeffs,
-                                                                const uint8_t *__restrict__ masks, float *__restrict__ out) {
+                                                                const uint8_t *__restrict__ masks, float *__restrict__ out, int vec) {
   constexpr int nb = (DEG + 1) * (DEG + 1);
   const int64_t g = (int64_t)blockIdx.x * kShBlock + threadIdx.x;
   if (g >= n) return;
@@ -97,7 +100,7 @@ __global__ __launch_bounds__(kShBlock) void sh_fwd_masked_kernel(int64_t n, int 
     sh_bases(DEG, x * inorm, y * inorm, z * inorm, B);
     const float *c = coeffs + g * (int64_t)K * 3;
     float cf[nb * 3 + 3];
-    if (kVec) {
+    if (vec) {
       constexpr int n4 = (nb * 3 + 3) / 4;
 #pragma unroll
       for (int i = 0; i < n4; i++) {
@@ -191,13 +194,15 @@ __global__ __launch_bounds__(kShBlock) void sh_bwd_kernel(int64_t n, int K, cons
 // detached), visibility is radii > 0, and the result leaves already packed for the compositor as
 // (clamp(rgb + 0.5, 0, 1), depth)  (vanilla.py:389 + the RGB+ED channel layout of base.py:393-408).
 // sh_rgb keeps the un-clamped value: the backward needs to know where the clamp was active.
-template <int DEG, bool kVec>
-__global__ __launch_bounds__(kShBlock) void sh_view_fwd_kernel(int64_t n, int K, const float *__restrict__ means,
+// (vec: a wave-uniform argument, one copy of the arithmetic behind both memory paths -- see sh_fwd_masked_kernel.  8 waves / SIMD:
+// with both paths in one kernel degree 3 took 66 registers, two over the 64 of the 16-byte form alone; bound to 64, no scratch)
+template <int DEG>
+__global__ __launch_bounds__(kShBlock, 8) void sh_view_fwd_kernel(int64_t n, int K, const float *__restrict__ means,
                                                               const float *__restrict__ cam_pos,
                                                               const float *__restrict__ coeffs,
                                                               const int32_t *__restrict__ radii,
                                                               const float *__restrict__ depths, float *__restrict__ sh_rgb,
-                                                              float4 *__restrict__ colors) {
+                                                              float4 *__restrict__ colors, int vec) {
   constexpr int nb = (DEG + 1) * (DEG + 1);
   const int64_t g = (int64_t)blockIdx.x * kShBlock + threadIdx.x;
   if (g >= n) return;
@@ -209,7 +214,7 @@ __global__ __launch_bounds__(kShBlock) void sh_view_fwd_kernel(int64_t n, int K,
     sh_bases(DEG, x * inorm, y * inorm, z * inorm, B);
     const float *c = coeffs + g * (int64_t)K * 3;
     float cf[nb * 3 + 3];
-    if (kVec) {
+    if (vec) {
       constexpr int n4 = (nb * 3 + 3) / 4;
 #pragma unroll
       for (int i = 0; i < n4; i++) {
@@ -470,10 +475,7 @@ static void launch_fwd(bool full, int grid, size_t lds, hipStream_t st, int64_t 
                        const float *coeffs, const uint8_t *masks, float *out) {
   if (masks != nullptr) {
     const bool vec = ((K * 3) % 4 == 0) && aligned16(coeffs);  // every row starts on a 16-byte boundary
-    if (vec)
-      hipLaunchKernelGGL((sh_fwd_masked_kernel<DEG, true>), dim3(grid), dim3(kShBlock), 0, st, n, K, dirs, coeffs, masks, out);
-    else
-      hipLaunchKernelGGL((sh_fwd_masked_kernel<DEG, false>), dim3(grid), dim3(kShBlock), 0, st, n, K, dirs, coeffs, masks, out);
+    hipLaunchKernelGGL((sh_fwd_masked_kernel<DEG>), dim3(grid), dim3(kShBlock), 0, st, n, K, dirs, coeffs, masks, out, vec ? 1 : 0);
     return;
   }
   if (full)
@@ -533,12 +535,8 @@ extern "C" int bds_sh_bwd(int64_t n, int K, int deg, const float *dirs, const fl
 template <int DEG>
 static void launch_view_fwd(bool vec, int grid, hipStream_t st, int64_t n, int K, const float *means, const float *cam_pos,
                             const float *coeffs, const int32_t *radii, const float *depths, float *sh_rgb, float4 *colors) {
-  if (vec)
-    hipLaunchKernelGGL((sh_view_fwd_kernel<DEG, true>), dim3(grid), dim3(kShBlock), 0, st, n, K, means, cam_pos, coeffs, radii,
-                       depths, sh_rgb, colors);
-  else
-    hipLaunchKernelGGL((sh_view_fwd_kernel<DEG, false>), dim3(grid), dim3(kShBlock), 0, st, n, K, means, cam_pos, coeffs, radii,
-                       depths, sh_rgb, colors);
+  hipLaunchKernelGGL((sh_view_fwd_kernel<DEG>), dim3(grid), dim3(kShBlock), 0, st, n, K, means, cam_pos, coeffs, radii,
+                     depths, sh_rgb, colors, vec ? 1 : 0);
 }
 
 extern "C" int bds_sh_view_fwd(int64_t n, int K, int deg, const float *means, const float *cam_pos, const float *coeffs,

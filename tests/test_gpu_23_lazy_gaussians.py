@@ -42,11 +42,20 @@ def _run(Hn, model, cam, grids, sky, target, retain=False):
     return out, float(loss), grads
 
 
-@pytest.mark.parametrize("step", [10 ** 6, 2500])       # all three SH bands active; two of them (vanilla.py:387)
-def test_installed_sequence_equals_the_eager_mirror(mods, step):
+# K = 16: all three SH bands active; two of them (vanilla.py:387).  K = 4 and K = 9 are the coefficient counts of the reference's other
+# class configurations (sh_degree 1 and 2: the split storage's 16-byte pieces at 4-byte alignment, and its float-by-float path), each
+# at its full degree and one below (the ramp of vanilla.py:387); these run at the size of this file's other tests.
+@pytest.mark.parametrize("K,step", [pytest.param(16, 10 ** 6, id="1000000"), pytest.param(16, 2500, id="2500"),
+                                    pytest.param(4, 10 ** 6, id="K4-deg1"), pytest.param(4, 0, id="K4-deg0"),
+                                    pytest.param(9, 10 ** 6, id="K9-deg2"), pytest.param(9, 1500, id="K9-deg1")])
+def test_installed_sequence_equals_the_eager_mirror(mods, K, step):
     Hn, M = mods
-    cam, p, grids, sky, target = _setup(Hn)
-    model = Hn.VanillaModel(p, step=step)
+    cam, p, grids, sky, target = _setup(Hn) if K == 16 else _setup(Hn, N=8000, W=256, H=192)
+    sh_degree = int(round(K ** 0.5)) - 1
+    assert (sh_degree + 1) ** 2 == K
+    p = dict(p, sh=p["sh"][:, :K].contiguous())
+    model = Hn.VanillaModel(p, sh_degree=sh_degree, step=step)
+    assert model._features_rest.shape[1] == K - 1 and min(step // model.ctrl_cfg.sh_degree_interval, sh_degree) in (sh_degree, sh_degree - 1)
     out_e, loss_e, g_e = _run(Hn, model, cam, grids, sky, target, retain=True)
     absgrad_e = out_e["info"]["means2d"].absgrad.clone()
     grad_e = out_e["info"]["means2d"].grad.clone()
