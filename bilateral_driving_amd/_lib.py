@@ -89,6 +89,8 @@ _SIGS = {
     "bds_sh_view_bwd_list": (_i, [_i64, _f, _f, _i, _i, _f, _f, _f, _i, _f, _f, _f, _f, _i, _f]),
     "bds_splat_pack_sh": (_i, [_i64, _f, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i64, _f, _f]),
     "bds_nonfinite_flags": (_i, [_i, _f, _f, _f, _f, _f, _f]),
+    "bds_scene_pack": (_i, [_i64, _f, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i64, _f, _f]),
+    "bds_scene_sh_bwd": (_i, [_i64, _f, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_project_view_bwd_list": (_i, [_i, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_view_grads_clear_list": (_i, [_i64, _f, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_view_grads_add_list": (_i, [_i64, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),

@@ -466,7 +466,14 @@ def _composite(f: _Front, opac: Tensor, images=None, zero_grad_records: Optional
     tail = zero_tail if zero_tail is not None else (None if zr is None or zr.shape[0] <= n_vis else zr[n_vis:])
     clear = (L.ptr(zr), L.ptr(tail), 0 if tail is None else tail.numel(), L.ptr(tile_order))
     with L.timed("rasterize_fwd"):
-        if f.colors is None:   # SH colours evaluated by the pack (visible Gaussians only); un-clamped values kept in list order
+        if getattr(f, "scene", None) is not None:
+            # several classes in one row range (rendering._RasterizeSceneView): the pack finds every visible row's class in the segment
+            # table -- SH from that class's two parameters at its degree, or the class's activated colours as they are
+            f.sh_rgb, f.sh_by_rank = _empty((max(n_vis, 1), 3), dev), True
+            L.check(lib.bds_scene_pack(n_vis, f.nvis_dev, L.ptr(f.vis_ids), *f.scene.forward_args(), L.ptr(f.means), L.ptr(f.cam_pos),
+                                       _dp(f.means2d), _dp(f.conics), _dp(f.depths), _dp(opac), L.ptr(f.radii), L.ptr(rec), L.ptr(f.sh_rgb),
+                                       *clear, st), "bds_scene_pack")
+        elif f.colors is None:   # SH colours evaluated by the pack (visible Gaussians only); un-clamped values kept in list order
             f.sh_rgb, f.sh_by_rank = _empty((max(n_vis, 1), 3), dev), True
             if f.m_dev is not None and f.cfg.get("row_catchup") is not None:
                 # a row-lazy optimizer (optim.DeferredRowAdam) brings the coefficient rows of THIS view's visible Gaussians up to

@@ -13,10 +13,18 @@ evaluation renders, ``detach_keys``) see ordinary tensors with the reference's v
 
 Kept lazy: ``torch.cat`` of a single placeholder (base.py:365-366 with one class), ``squeeze`` / ``reshape`` / ``view`` / ``flatten`` of
 the element-wise fields (base.py:397 ``gs.opacities.squeeze()``), metadata reads.
+
+A scene graph (Background + node classes: every shipped OmniRe config) concatenates SEVERAL classes per key.  With sources made by
+``marshalling.install(cls, scene=True)`` that concatenation stays lazy as well: ``torch.cat`` of a list that mixes such placeholders
+with the other classes' activated tensors is a ``LazyCat``, which remembers its parts in order.  ``lazy_scene`` recognises five
+``LazyCat`` s with one partition and ``rendering.rasterization`` runs them through ``_RasterizeSceneView`` (raw segments: deferred
+activations and visible-only SH; dense segments: taken as they are); any other use materialises ``torch.cat([materialised parts], 0)``
+-- exactly what the reference computes.  Without the flag (the default) a placeholder next to a second tensor materialises at the
+``torch.cat``, as before.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import torch
 from torch import Tensor
@@ -29,10 +37,11 @@ class RawGaussians:
     """One class's raw parameters for one camera + the reference's expressions for its activated tensors (vanilla.py:383-395)."""
 
     def __init__(self, means: Tensor, quats: Tensor, log_scales: Tensor, logits: Tensor, features_dc: Tensor, features_rest: Tensor,
-                 sh_degree: int, cam_pos: Tensor, step=-1):
+                 sh_degree: int, cam_pos: Tensor, step=-1, scene: bool = False):
         self.means, self.quats, self.log_scales, self.logits = means, quats, log_scales, logits
         self.features_dc, self.features_rest = features_dc, features_rest
         self.sh_degree, self.cam_pos, self.step = int(sh_degree), cam_pos, step
+        self.scene = bool(scene)      # placeholders of this source stay lazy through a concatenation with other classes (LazyCat)
         self._cache: Dict[str, Tensor] = {}
 
     def materialise(self, field: str) -> Tensor:
@@ -108,6 +117,11 @@ class LazyField(torch.Tensor):
         if func is torch.cat and len(args) >= 1 and isinstance(args[0], (list, tuple)) and len(args[0]) == 1 \
                 and isinstance(args[0][0], LazyField) and (args[1] if len(args) > 1 else kwargs.get("dim", 0)) == 0:
             return args[0][0]
+        # concatenation with OTHER classes' tensors (a scene graph), sources made with scene=True only: a LazyCat
+        if func is torch.cat:
+            lazy = _lazy_cat(args, kwargs)
+            if lazy is not None:
+                return lazy
         # pure reshapes of an element-wise field commute with its activation
         if args and isinstance(args[0], LazyField) and args[0]._field in _ELEMENTWISE and func in (
                 torch.Tensor.squeeze, torch.Tensor.reshape, torch.Tensor.view, torch.Tensor.flatten, torch.squeeze, torch.reshape,
@@ -123,8 +137,104 @@ class LazyField(torch.Tensor):
         return func(*_materialised(args), **_materialised(kwargs or {}))
 
 
+_RESHAPES = None
+
+
+def _reshape_funcs():
+    global _RESHAPES
+    if _RESHAPES is None:
+        _RESHAPES = (torch.Tensor.squeeze, torch.Tensor.reshape, torch.Tensor.view, torch.Tensor.flatten, torch.squeeze, torch.reshape,
+                     torch.flatten, torch.Tensor.unsqueeze, torch.unsqueeze)
+    return _RESHAPES
+
+
+MAX_SEGMENTS = 8      # include/bds.h: the scene view's segment table
+
+
+def _cat_args(args, kwargs):
+    """(parts, dim) of a ``torch.cat`` call, or (None, None) for a form the lazy paths do not serve (``out=``, a non-list)."""
+    if len(args) < 1 or not isinstance(args[0], (list, tuple)) or len(args) > 2 or set(kwargs) - {"dim"}:
+        return None, None
+    return args[0], (args[1] if len(args) > 1 else kwargs.get("dim", 0))
+
+
+def _lazy_cat(args, kwargs):
+    """The ``LazyCat`` of ``torch.cat(parts, dim=0)`` (module docstring), or None where the concatenation has to materialise: fewer than
+    two parts, a placeholder whose source was not made for scenes, mixed fields, a part that is no plain float32 tensor of the same
+    device and trailing shape."""
+    parts, dim = _cat_args(args, kwargs)
+    if parts is None or dim != 0 or len(parts) < 2:
+        return None
+    lazies = [p for p in parts if isinstance(p, LazyField)]
+    if not lazies or any(isinstance(p, LazyCat) for p in parts):
+        return None
+    field = lazies[0]._field
+    with torch._C.DisableTorchFunctionSubclass():
+        dev, tail = lazies[0].device, tuple(torch.Tensor.size(lazies[0]))[1:]
+        rows = 0
+        for p in parts:
+            if isinstance(p, LazyField):
+                if p._field != field or not p._src.scene:
+                    return None
+            elif not (type(p) in (torch.Tensor, torch.nn.Parameter) and p.dtype == torch.float32 and p.dim() == len(tail) + 1):
+                return None
+            if p.device != dev or tuple(torch.Tensor.size(p))[1:] != tail:
+                return None
+            rows += torch.Tensor.size(p, 0)
+    return LazyCat(tuple(parts), field, (rows,) + tail)
+
+
+class LazyCat(torch.Tensor):
+    """Placeholder for ``torch.cat([parts], 0)`` of one field over the classes of a scene graph: ``LazyField`` s of scene sources and
+    the other classes' activated tensors, in order.  A wrapper tensor without storage, as ``LazyField``: only metadata is real.  The
+    shape may be a pure reshape of the concatenation's (element-wise fields only); the materialised value is cached."""
+
+    @staticmethod
+    def __new__(cls, parts, field: str, shape):
+        first = next(p for p in parts if isinstance(p, LazyField))
+        r = torch.Tensor._make_wrapper_subclass(cls, tuple(shape), dtype=torch.float32, device=first._src.means.device, requires_grad=False)
+        r._parts, r._field, r._value, r._of = tuple(parts), field, None, None
+        return r
+
+    def materialise(self) -> Tensor:
+        if self._value is None:
+            # (a reshape of another LazyCat shares that one's concatenation: one graph node per field, as the reference has)
+            t = self._of.materialise() if self._of is not None else torch.cat([_materialised(p) for p in self._parts], dim=0)
+            with torch._C.DisableTorchFunctionSubclass():
+                shape = tuple(torch.Tensor.size(self))
+            self._value = t if tuple(t.shape) == shape else t.reshape(shape)
+        return self._value
+
+    def __repr__(self):
+        with torch._C.DisableTorchFunctionSubclass():
+            return f"LazyCat({self._field}, parts={len(self._parts)}, shape={tuple(torch.Tensor.size(self))})"
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        if func in _meta_funcs():
+            with torch._C.DisableTorchFunctionSubclass():
+                return func(*args, **kwargs)
+        if func is torch.cat:      # torch.cat([x], 0) of one LazyCat: itself
+            parts, dim = _cat_args(args, kwargs)
+            if parts is not None and dim == 0 and len(parts) == 1 and isinstance(parts[0], LazyCat):
+                return parts[0]
+        if args and isinstance(args[0], LazyCat) and args[0]._field in _ELEMENTWISE and func in _reshape_funcs():
+            me = args[0]
+            with torch._C.DisableTorchFunctionSubclass():
+                shape = func(torch.empty(tuple(torch.Tensor.size(me)), device="meta"), *args[1:], **kwargs).shape
+            r = LazyCat(me._parts, me._field, shape)
+            r._of = me
+            return r
+        return func(*_materialised(args), **_materialised(kwargs))
+
+    @classmethod
+    def __torch_dispatch__(cls, func, types, args=(), kwargs=None):
+        return func(*_materialised(args), **_materialised(kwargs or {}))
+
+
 def _materialised(x):
-    if isinstance(x, LazyField):
+    if isinstance(x, (LazyField, LazyCat)):
         return x.materialise()
     if isinstance(x, (list, tuple)):
         return type(x)(_materialised(v) for v in x)
@@ -149,3 +259,54 @@ def lazy_source(means: Tensor, quats, scales, opacities, colors) -> Optional[Raw
     if not all(t._src is src for _, t in fields) or not own_means:
         return None
     return src
+
+
+class SceneSegment:
+    """One class of a lazy scene: rows [start, start + n) of the concatenation.  ``src``: the ``RawGaussians`` of a raw segment, else
+    None and ``dense`` = the class's five activated tensors (means, quats, scales, opacities, colors)."""
+
+    def __init__(self, start: int, n: int, src: Optional[RawGaussians], dense=None):
+        self.start, self.n, self.src, self.dense = start, n, src, dense
+
+    @property
+    def raw(self) -> bool:
+        return self.src is not None
+
+
+def lazy_scene(means, quats, scales, opacities, colors) -> Optional[List[SceneSegment]]:
+    """The segments behind five ``LazyCat`` s handed to ``rasterization``, else None: the same partition in all five (number of parts,
+    row counts, order), every part either RAW -- the five placeholders of ONE ``RawGaussians``, the means its own parameter -- or
+    DENSE -- five plain tensors; at most ``MAX_SEGMENTS`` parts, at least one of them raw, every raw source of the same camera."""
+    named = (("_means", means), ("_quats", quats), ("_scales", scales), ("_opacities", opacities), ("_rgbs", colors))
+    if not all(isinstance(t, LazyCat) and t._field == name for name, t in named):
+        return None
+    n_parts = len(means._parts)
+    if n_parts > MAX_SEGMENTS or any(len(t._parts) != n_parts for _, t in named):
+        return None
+    segs, start, cam = [], 0, None
+    with torch._C.DisableTorchFunctionSubclass():
+        for parts in zip(*(t._parts for _, t in named)):
+            rows = [int(torch.Tensor.size(p, 0)) for p in parts]
+            if any(r != rows[0] for r in rows):
+                return None
+            lazy = [isinstance(p, LazyField) for p in parts]
+            if all(lazy):
+                src = parts[0]._src
+                if not all(p._src is src and p._field == name for p, (name, _) in zip(parts, named)):
+                    return None
+                if src.features_rest.dim() != 3 or src.features_rest.shape[1] < 1:
+                    return None
+                c = src.cam_pos
+                if cam is None:
+                    cam = c
+                elif not (c.data_ptr() == cam.data_ptr() and c.shape == cam.shape and c.stride() == cam.stride()):
+                    return None
+                segs.append(SceneSegment(start, rows[0], src))
+            elif not any(lazy):
+                segs.append(SceneSegment(start, rows[0], None, tuple(parts)))
+            else:
+                return None
+            start += rows[0]
+    if not any(s.raw for s in segs):
+        return None
+    return segs

@@ -18,8 +18,11 @@ Where the reference's code lives:
   ``render_gaussians``                      models/trainers/base.py:385-432 (-> ``rasterization``; returns ``results, render_fn, info``)
 
 ``fused_view`` / ``harness.render_view`` are the faster entry for the background
-class alone (SH evaluated inside the view node); this module is the interface-compatible route for the multi-class scene graph,
-where every class hands over already-activated tensors."""
+class alone (SH evaluated inside the view node); this module is the interface-compatible route for the multi-class scene graph.
+There a class either hands over already-activated tensors (the node classes) or, after ``install(cls, scene=True)``, placeholders
+over its raw parameters that stay lazy through ``collect_gaussians``' concatenation (``lazy_gaussians.LazyCat``) and reach
+``rendering._RasterizeSceneView``: deferred activations and SH colours of the visible rows only for that class, the other classes'
+rows as they are."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -126,13 +129,14 @@ def get_gaussians(model, cam: dataclass_camera) -> Dict[str, Tensor]:
     return gs
 
 
-def get_gaussians_lazy(self, cam: dataclass_camera) -> Dict[str, Tensor]:
+def get_gaussians_lazy(self, cam: dataclass_camera, scene: bool = False) -> Dict[str, Tensor]:
     """Drop-in for ``VanillaGaussians.get_gaussians`` (vanilla.py:378-414) that DEFERS the activations: the same dict, its five entries
     placeholders (``lazy_gaussians.LazyField``) over the raw parameters.  ``rasterization`` runs a complete set of them through one
     node -- sigmoid / exp / quaternion normalisation inside the projection kernel, SH colours for the visible Gaussians only, read
     from ``_features_dc`` / ``_features_rest`` where they lie, the NaN / Inf check as one launch whose flag arrives with the list
     counts; every other use of a placeholder materialises it with the reference's own expression (``lazy_gaussians``).  A class
-    without SH bands (``sh_degree == 0``: sigmoid colours) takes the eager mirror ``get_gaussians``."""
+    without SH bands (``sh_degree == 0``: sigmoid colours) takes the eager mirror ``get_gaussians``.  ``scene``: the placeholders also
+    stay lazy when ``collect_gaussians`` concatenates them with other classes' tensors (``lazy_gaussians.LazyCat``)."""
     from .lazy_gaussians import LazyField, RawGaussians
     if self.sh_degree <= 0:
         return get_gaussians(self, cam)
@@ -140,7 +144,7 @@ def get_gaussians_lazy(self, cam: dataclass_camera) -> Dict[str, Tensor]:
         self.filter_mask = torch.ones(self._means.shape[0], dtype=torch.bool, device=self._means.device)   # vanilla.py:379-380 (all ones: kept)
     n = min(self.step // self.ctrl_cfg.sh_degree_interval, self.sh_degree)           # vanilla.py:387
     src = RawGaussians(self._means, self._quats, self._scales, self._opacities, self._features_dc, self._features_rest, n,
-                       cam.camtoworlds.data[..., :3, 3], step=getattr(self, "step", -1))
+                       cam.camtoworlds.data[..., :3, 3], step=getattr(self, "step", -1), scene=scene)
     N = self._means.shape[0]
     return dict(_means=LazyField(src, "_means", (N, 3)), _opacities=LazyField(src, "_opacities", self._opacities.shape),
                 _rgbs=LazyField(src, "_rgbs", (N, 3)), _scales=LazyField(src, "_scales", (N, 3)), _quats=LazyField(src, "_quats", (N, 4)))
@@ -149,11 +153,20 @@ def get_gaussians_lazy(self, cam: dataclass_camera) -> Dict[str, Tensor]:
 _SEAM = Seam()
 
 
-def install(gaussian_class) -> None:
+def get_gaussians_lazy_scene(self, cam: dataclass_camera) -> Dict[str, Tensor]:
+    """``get_gaussians_lazy`` for a class of a scene graph: what ``install(cls, scene=True)`` installs."""
+    return get_gaussians_lazy(self, cam, scene=True)
+
+
+def install(gaussian_class, scene: bool = False) -> None:
     """``install(VanillaGaussians)``: the class's ``get_gaussians`` becomes ``get_gaussians_lazy`` (the reference's file is not
     touched; the same mechanism as assigning ``densify.refinement_after``).  The original stays reachable as
-    ``gaussian_class._bds_reference_get_gaussians``; ``uninstall`` puts it back."""
-    _SEAM.install(gaussian_class, {"get_gaussians": get_gaussians_lazy}, reference="_bds_reference_get_gaussians")
+    ``gaussian_class._bds_reference_get_gaussians``; ``uninstall`` puts it back.  ``scene=True`` (opt-in): the class is one of several
+    in a scene graph, and its placeholders stay lazy through the concatenation with the other classes' tensors -- the scene then
+    renders through ``rendering._RasterizeSceneView``; without it a placeholder next to a second tensor materialises at the
+    ``torch.cat``."""
+    _SEAM.install(gaussian_class, {"get_gaussians": get_gaussians_lazy_scene if scene else get_gaussians_lazy},
+                  reference="_bds_reference_get_gaussians")
 
 
 def uninstall(*gaussian_classes) -> None:

@@ -18,7 +18,7 @@ from torch import Tensor
 import weakref
 
 from . import _lib as L
-from .lazy_gaussians import lazy_source, materialised
+from .lazy_gaussians import lazy_scene, lazy_source, materialised
 
 
 _SPLIT_RENDER = os.environ.get("BDS_API_SPLIT_RENDER", "1") == "1"
@@ -303,6 +303,168 @@ class _RasterizeRawView(torch.autograd.Function):
                 slots.sum(0) if want_pose else None, None, None)
 
 
+class _SceneTable:
+    """The segment table of include/bds.h "the scene view" as the host arrays its two entries take: rows, kinds, K and active degree
+    per segment, and the forward's pointer pair (raw: ``_features_dc`` / ``_features_rest``; dense: the activated colours)."""
+
+    def __init__(self, segs, colors, rests):
+        n = self.n = len(segs)
+        self.rows = (ctypes.c_int64 * n)(*[s["n"] for s in segs])
+        self.kinds = (ctypes.c_int * n)(*[int(s["raw"]) for s in segs])      # BDS_SCENE_DENSE 0 / BDS_SCENE_RAW 1
+        self.Ks = (ctypes.c_int * n)(*[s["K"] for s in segs])
+        self.degs = (ctypes.c_int * n)(*[s["deg"] for s in segs])
+        self._keep = (colors, rests)
+        self.p0, self.p1 = self.pointers(colors, rests)
+
+    def pointers(self, a, b):
+        n = self.n
+        return ((ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in a]),
+                (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in b]))
+
+    def head(self):
+        return self.n, self.rows, self.kinds, self.Ks, self.degs
+
+    def forward_args(self):
+        return (*self.head(), self.p0, self.p1)
+
+
+_RAW_FIELDS = ("means", "quats", "scales", "opacities", "features_dc", "features_rest")
+
+
+class _RasterizeSceneView(torch.autograd.Function):
+    """rasterization() for one camera over SEVERAL Gaussian classes (``lazy_gaussians.lazy_scene``: the reference's scene graph,
+    models/trainers/base.py:355-366, with ``marshalling.install(cls, scene=True)``): the classes' rows lie one behind the other in one
+    row range [0, N).  A RAW segment hands over a class's six raw parameters -- activations inside its own projection launch
+    (bds_project_view_fwd into rows [start, start + n) of the [N] arrays), SH colours by the record pack for its VISIBLE rows only,
+    straight from its two SH parameters at its own degree (bds_scene_pack) -- a DENSE segment a class's five activated tensors, taken
+    as they are (bds_project_fwd into its rows).  The tile stage and the compositors are ``_RasterizeView``'s, on global row ids.
+    Backward: the list-driven projection backward in its ACTIVATED form over all rows, then bds_scene_sh_bwd: SH backward into each raw
+    segment's own gradient arrays and the exp / sigmoid chain of the raw rows.  Every segment's gradients are slices of the dense
+    arrays.  Only the means and quaternions are concatenated (28 bytes per row: the list-driven kernels gather them by global id);
+    no SH coefficient is concatenated, evaluated for or written back to a culled row.  NaN / Inf: one bds_nonfinite_flags launch
+    per raw segment in front of the projection, read with the one wait of the view (dense segments arrive checked by their class).
+    ``tensors``: per segment in order, raw (means, quats, log_scales, logits, features_dc, features_rest), dense (means, quats,
+    scales, opacities, colors)."""
+
+    @staticmethod
+    def forward(ctx, viewmat, Kmat, cfg, *tensors):
+        L.require_gpu(viewmat, Kmat, *tensors)
+        viewmat, Kmat = L.f32c(viewmat), L.f32c(Kmat)
+        lib, st = L.lib(), L.stream()
+        dev = viewmat.device
+        W, H, N, aa, segs = cfg["width"], cfg["height"], cfg["N"], cfg["aa"], cfg["segments"]
+        per, i = [], 0
+        for s in segs:
+            k = 6 if s["raw"] else 5
+            per.append([L.f32c(t) for t in tensors[i:i + k]])
+            i += k
+        means, quats = torch.cat([p[0] for p in per], 0), torch.cat([p[1] for p in per], 0)      # [N,3], [N,4]: global rows
+        scales, opac = torch.empty(N, 3, device=dev), torch.empty(N, device=dev)
+        opac_eff = torch.empty(N, device=dev) if aa else None
+        radii = torch.empty(1, N, device=dev, dtype=torch.int32)
+        means2d, depths, conics = torch.empty(1, N, 2, device=dev), torch.empty(1, N, device=dev), torch.empty(1, N, 3, device=dev)
+        checked = []
+        if cfg["check_finite"]:      # in front of the projection, by the kinds of _RasterizeRawView; one flag word per raw segment
+            words = _finite_words(dev, 8)
+            for s, p in zip(segs, per):
+                if not (s["raw"] and s["n"] > 0):
+                    continue
+                slot = len(checked)
+                ptrs = (ctypes.c_void_p * 6)(*[t.data_ptr() for t in p])
+                cnts = (ctypes.c_int64 * 6)(*[t.numel() for t in p])
+                kinds = (ctypes.c_int * 6)(0, 2 if p[1].data_ptr() % 16 == 0 else 0, 1, 3, 0, 0)
+                L.check(lib.bds_nonfinite_flags(6, ptrs, cnts, kinds, words[0][slot:].data_ptr(), words[1][slot:].data_ptr(), st),
+                        "bds_nonfinite_flags")
+                checked.append((slot, s))
+
+        def at(t, row, width):      # address of global row `row` of a [N, width] array
+            return None if t is None else t.data_ptr() + 4 * row * width
+
+        with L.timed("project_fwd"):
+            for s, p in zip(segs, per):
+                n, r0 = s["n"], s["start"]
+                if n == 0:
+                    continue
+                outs = (at(radii, r0, 1), at(means2d, r0, 2), at(depths, r0, 1), at(conics, r0, 3))
+                if s["raw"]:
+                    L.check(lib.bds_project_view_fwd(L.PROJ_ANTIALIASED if aa else 0, n, L.ptr(p[0]), L.ptr(p[1]), L.ptr(p[2]), L.ptr(p[3]),
+                                                     L.ptr(viewmat), L.ptr(Kmat), W, H, cfg["eps2d"], cfg["near_plane"], cfg["far_plane"],
+                                                     cfg["radius_clip"], at(scales, r0, 3), at(opac, r0, 1), at(opac_eff, r0, 1), *outs,
+                                                     None, None, 0, None, st), "bds_project_view_fwd")
+                else:
+                    scales[r0:r0 + n].copy_(p[2])
+                    opac[r0:r0 + n].copy_(p[3].reshape(n))
+                    L.check(lib.bds_project_fwd(1, n, L.ptr(p[0]), L.ptr(p[1]), L.ptr(p[2]), L.ptr(p[3]) if aa else None, L.ptr(viewmat),
+                                                L.ptr(Kmat), W, H, cfg["eps2d"], cfg["near_plane"], cfg["far_plane"], cfg["radius_clip"],
+                                                *outs, None, at(opac_eff, r0, 1), st), "bds_project_fwd")
+        opac_c = opac_eff if aa else opac      # what the tile stage and the compositor read
+        ls = _lists_begin(means2d, radii, depths, (L.ptr(conics), L.ptr(opac_c)) if cfg["cull"] else None, W, H, _LIST_TILE)
+        images = _image_buffers(W, H, dev)      # (while the two counts travel to the host)
+        _lists_finish(ls)
+        for slot, s in checked:      # (the flag words' copies are older than the event that wait waited for)
+            word = int(words[1][slot])
+            if word:
+                bad = [n for i, n in enumerate(_RAW_FIELDS) if word >> i & 1]
+                raise ValueError(f"NaN / Inf detected in gaussian {', '.join(bad)} at step {s['step']}")
+        f = _Front()
+        f.flatten, f.vis_ids, f.M, f.n_vis, f.m_dev, f.nvis_dev, f.rec_buf = ls.flatten, ls.vis_ids, ls.M, ls.n_vis, ls.m_dev, ls.nvis_dev, ls.rec_buf
+        f.cfg, f.W, f.H, f.list_tile, f.tw, f.th = cfg, W, H, _LIST_TILE, math.ceil(W / TILE_SIZE), math.ceil(H / TILE_SIZE)
+        f.means, f.means2d, f.depths, f.conics, f.radii, f.isect_offsets = means, means2d, depths, conics, radii, ls.isect_offsets
+        f.opac = f.opac_row = opac_c
+        f.colors, f.cam_pos = None, cfg["cam_pos"]
+        f.scene = _SceneTable(segs, [p[4] for p in per], [p[5] if s["raw"] else None for s, p in zip(segs, per)])
+        rec, render, alphas, last_ids = _composite(f, f.opac, images)
+        ctx.save_for_backward(means, quats, scales, opac, viewmat, Kmat, rec, f.vis_ids, ls.ws, f.flatten, f.isect_offsets, render, alphas,
+                              last_ids, f.sh_rgb, f.cam_pos)
+        ctx.cfg, ctx.M = cfg, f.M
+        ctx.shapes = [tuple(tuple(t.shape) for t in p) for p in per]
+        ctx.mark_non_differentiable(radii, depths, conics, opac_c)
+        ctx.set_materialize_grads(False)
+        if cfg.get("split"):       # rgb and depth as two outputs (SplitRender): 4-channel modes only
+            rgb, depth = torch.empty(H, W, 3, device=dev), torch.empty(H, W, 1, device=dev)
+            L.check(lib.bds_expected_depth_split_fwd(H * W, int(cfg["ed"]), L.ptr(render), L.ptr(alphas), L.ptr(rgb), L.ptr(depth), st),
+                    "bds_expected_depth_split_fwd")
+            return rgb, depth, alphas, means2d, radii, depths, conics, opac_c
+        if cfg["ed"]:
+            out = torch.empty_like(render)
+            L.check(lib.bds_expected_depth_fwd(H * W, L.ptr(render), L.ptr(alphas), L.ptr(out), st), "bds_expected_depth_fwd")
+        else:
+            out = render[..., :3] if cfg["channels"] == 3 else render
+        return out, None, alphas, means2d, radii, depths, conics, opac_c
+
+    @staticmethod
+    def backward(ctx, v_out, v_depth, v_alphas, v_means2d_ext, *_):
+        saved = ctx.saved_tensors
+        means, scales, opac, vis_ids, sh_rgb, cam_pos = saved[0], saved[2], saved[3], saved[7], saved[14], saved[15]
+        cfg, want_pose, segs = ctx.cfg, bool(ctx.needs_input_grad[0]), ctx.cfg["segments"]
+        # dense outputs over the global rows: means 3 | quats 4 | activated scales 3 | activated opacities 1 | colours 3 | grad2d 2 | absgrad2d 2
+        outs, v_rec, slots = _view_backward(ctx, saved, v_out, v_depth, v_alphas, v_means2d_ext, want_pose, (3, 4, 3, 1, 3, 2, 2),
+                                            L.PROJ_ACTIVATED)
+        v_means, v_quats, v_scales, v_opac, v_colors = outs[:5]
+        # the raw segments' SH gradients: their own arrays (ONE zero fill), rows of culled Gaussians stay zero
+        sizes = [(s["n"] * 3, s["n"] * (s["K"] - 1) * 3) if s["raw"] else (0, 0) for s in segs]
+        pool = torch.zeros(sum(a + b for a, b in sizes), device=means.device)
+        v_dc, v_rest, o = [], [], 0
+        for (a, b), s in zip(sizes, segs):
+            v_dc.append(pool[o:o + a] if s["raw"] else None)
+            v_rest.append(pool[o + a:o + a + b] if s["raw"] else None)
+            o += a + b
+        table = _SceneTable(segs, v_dc, v_rest)
+        with L.timed("sh_bwd"):
+            L.check(L.lib().bds_scene_sh_bwd(vis_ids.numel(), None, L.ptr(vis_ids), *table.forward_args(), L.ptr(means), L.ptr(cam_pos),
+                                             L.ptr(sh_rgb), L.ptr(v_rec), L.ptr(scales), L.ptr(opac), L.ptr(v_scales), L.ptr(v_opac),
+                                             L.stream()), "bds_scene_sh_bwd")
+        g = ctx.needs_input_grad
+        grads, i = [slots.sum(0) if want_pose else None, None, None], 3
+        for s, shapes, dc, rest in zip(segs, ctx.shapes, v_dc, v_rest):
+            a, b = s["start"], s["start"] + s["n"]
+            seg = [v_means[a:b], v_quats[a:b], v_scales[a:b], v_opac[a:b]] + ([dc, rest] if s["raw"] else [v_colors[a:b]])
+            for t, shape in zip(seg, shapes):
+                grads.append(t.view(shape) if g[i] else None)
+                i += 1
+        return tuple(grads)
+
+
 def _view_backward(ctx, saved, v_out, v_depth, v_alphas, v_means2d_ext, want_pose: bool, widths, flags: int):
     """The backward both one-view nodes share: expected depth -> ``fused_view._composite_backward`` (host-count form, + a loss on
     meta["means2d"]) -> ONE zero fill of the dense outputs, ``widths`` floats per Gaussian (the four parameter gradients first, grad2d |
@@ -337,14 +499,15 @@ def _view_backward(ctx, saved, v_out, v_depth, v_alphas, v_means2d_ext, want_pos
     return outs, v_rec, slots
 
 
-_FINITE_WORDS: Dict[torch.device, tuple] = {}
+_FINITE_WORDS: Dict[tuple, tuple] = {}
 
 
-def _finite_words(dev):
-    """(device word, page-locked word) of bds_nonfinite_flags, one pair per device (a view waits for its counts before the next one)."""
-    w = _FINITE_WORDS.get(dev)
+def _finite_words(dev, n: int = 1):
+    """(device words, page-locked words) of bds_nonfinite_flags, one pair per device (a view waits for its counts before the next one);
+    ``n`` words: one per launch of a view that checks several classes."""
+    w = _FINITE_WORDS.get((dev, n))
     if w is None:
-        w = _FINITE_WORDS[dev] = (torch.zeros(1, device=dev, dtype=torch.int32), torch.zeros(1, dtype=torch.int32).pin_memory())
+        w = _FINITE_WORDS[(dev, n)] = (torch.zeros(n, device=dev, dtype=torch.int32), torch.zeros(n, dtype=torch.int32).pin_memory())
     return w
 
 
@@ -400,7 +563,11 @@ def rasterization(
     src = lazy_source(means, quats, scales, opacities, colors)     # marshalling.install: a class's raw parameters behind placeholders
     raw_ok = (src is not None and _ONE_VIEW_NODE and viewmats.shape[0] == 1 and sh_degree is None and backgrounds is None
               and render_mode in ("RGB", "RGB+ED") and means.shape[0] > 0 and src.features_rest.shape[1] >= 1)
-    if not raw_ok:
+    # several classes, some of them behind placeholders (marshalling.install(cls, scene=True)): under the same conditions, one node
+    scene = None if raw_ok else lazy_scene(means, quats, scales, opacities, colors)
+    scene_ok = (scene is not None and _ONE_VIEW_NODE and viewmats.shape[0] == 1 and sh_degree is None and backgrounds is None
+                and render_mode in ("RGB", "RGB+ED") and means.shape[0] > 0)
+    if not raw_ok and not scene_ok:
         means, quats, scales, opacities, colors = materialised((means, quats, scales, opacities, colors))
     N = means.shape[0]
     C = viewmats.shape[0]
@@ -441,6 +608,25 @@ def rasterization(
         if depth1 is not None:      # the render as a placeholder over the node's two image outputs (SplitRender)
             out = SplitRender(out[None], depth1[None], first=(out, depth1))
         cfg["_means2d_ref"] = weakref.ref(means2d)      # the backward attaches .absgrad (and .grad, when retained) to THIS tensor object
+        return out, alphas, _meta(radii, means2d, depths, conics, opac.detach()[None, :])
+
+    if scene_ok:
+        segs, tensors = [], []
+        for s in scene:
+            if s.raw:
+                r = s.src
+                segs.append(dict(raw=True, start=s.start, n=s.n, K=1 + r.features_rest.shape[1], deg=r.sh_degree, step=r.step))
+                tensors += [r.means, r.quats, r.log_scales, r.logits, r.features_dc, r.features_rest]
+            else:
+                segs.append(dict(raw=False, start=s.start, n=s.n, K=1, deg=0, step=-1))
+                tensors += list(s.dense)
+        first = next(s.src for s in scene if s.raw)
+        cfg = _one_view_cfg(N=N, segments=segs, cam_pos=L.f32c(first.cam_pos.detach().reshape(3)), check_finite=_CHECK_FINITE,
+                           split=_SPLIT_RENDER and render_mode != "RGB")
+        out, depth1, alphas, means2d, radii, depths, conics, opac = _RasterizeSceneView.apply(viewmats[0], Ks[0], cfg, *tensors)
+        if depth1 is not None:
+            out = SplitRender(out[None], depth1[None], first=(out, depth1))
+        cfg["_means2d_ref"] = weakref.ref(means2d)
         return out, alphas, _meta(radii, means2d, depths, conics, opac.detach()[None, :])
 
     if (_ONE_VIEW_NODE and C == 1 and N > 0 and sh_degree is None and colors.shape[-1] == 3 and backgrounds is None

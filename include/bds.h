@@ -496,6 +496,37 @@ int bds_sh_view_bwd_list(int64_t n_list, const uint64_t *n_dev, const int32_t *i
  * 16-byte aligned (NaN / Inf components, or a row whose squared norm is 0 in fp32: 0/0, x/0) | 3 argument of sigmoid (NaN only). */
 int bds_nonfinite_flags(int n_tensors, const float *const *tensors, const int64_t *counts, const int *kinds, uint32_t *flags_dev,
                         uint32_t *flags_pinned, bds_stream_t stream);
+/* ---- the scene view: one camera over several Gaussian classes (csrc/scene_view.hip) -------------------------------------------
+ * models/trainers/base.py:355-366 concatenates every class's get_gaussians per key; the rows of the classes then lie one behind the other
+ * in ONE global row range [0, N), N = sum of seg_rows.  A segment is RAW (a class whose colours are the reference's two SH parameters,
+ * `_features_dc` [n,3] and `_features_rest` [n,K-1,3], evaluated at seg_degrees[i] as models/gaussians/vanilla.py:382-389 does) or
+ * DENSE (a class that hands over post-activation colours [n,3]).  n_seg in [1, 8]; seg_rows / seg_kinds / seg_K / seg_degrees and the
+ * two pointer tables are HOST arrays of n_seg entries (seg_K, seg_degrees and the second pointer are read for raw segments only); a
+ * segment may have zero rows.  The projection, the tile stage and the compositors work on global row ids and serve such a scene as
+ * they are (per-segment launches of bds_project_view_fwd / bds_project_fwd into rows [start, start + n) of one set of [N] arrays in
+ * the column form; bds_project_view_bwd_list with BDS_PROJ_ACTIVATED over all rows); these two entries are the list-driven ends that
+ * depend on a row's class.  n_dev: the device-count form, as bds_splat_pack's: a rank at or beyond the count reads and writes nothing.
+ *   bds_scene_pack   : the splat records of bds_splat_pack_sh (same layout, same clearing arguments) for the visible rows ids[0..n):
+ *       a raw row's colour is clamp(SH(normalise(mean - cam_pos)) + 0.5, 0, 1) from ITS segment's parameters (seg_colors[i] = band 0,
+ *       seg_rest[i] = bands 1..), the un-clamped value kept in sh_rgb [n,3] by rank; a dense row's colour is seg_colors[i][local row]
+ *       as it is (its sh_rgb row is zero).  means [N,3] are global rows; means2d / conics / depths / opacities / radii the [N]
+ *       column-form outputs of the projection.
+ *   bds_scene_sh_bwd : for the raw rows of the list, the SH backward (colour gradient = floats 0-2 of the gradient record of the same
+ *       rank, the clamp applied through sh_rgb) STORED into the whole row of seg_v_dc[i] [n,3] / seg_v_rest[i] [n,K-1,3] (rows of
+ *       culled Gaussians are the caller's: zero-filled), and the activation chain behind bds_project_view_bwd_list's ACTIVATED form,
+ *       in place on the global arrays: v_scales[g] *= scales[g] (d exp), v_opacities[g] *= o (1 - o) (d sigmoid; scales / opacities =
+ *       what bds_project_view_fwd left).  Dense rows are not touched. */
+#define BDS_SCENE_DENSE 0
+#define BDS_SCENE_RAW 1
+int bds_scene_pack(int64_t n, const uint64_t *n_dev, const int32_t *ids, int n_seg, const int64_t *seg_rows, const int *seg_kinds,
+                   const int *seg_K, const int *seg_degrees, const float *const *seg_colors, const float *const *seg_rest,
+                   const float *means, const float *cam_pos, const float *means2d, const float *conics, const float *depths,
+                   const float *opacities, const int32_t *radii, float *records, float *sh_rgb, float *zero_records, float *zero_tail,
+                   int64_t zero_tail_floats, int32_t *schedule, bds_stream_t stream);
+int bds_scene_sh_bwd(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, int n_seg, const int64_t *seg_rows,
+                     const int *seg_kinds, const int *seg_K, const int *seg_degrees, float *const *seg_v_dc, float *const *seg_v_rest,
+                     const float *means, const float *cam_pos, const float *sh_rgb, const float *v_records, const float *scales,
+                     const float *opacities, float *v_scales, float *v_opacities, bds_stream_t stream);
 /* The list-driven projection backward over the visible entries (C = 1; ids, v_records, `accumulate` and row_map as above): the rows of
  * v_means [N,3] v_quats [N,4] v_scales [N,3] v_opacities [N].
  *   flags & BDS_PROJ_ACCUMULATE: ADD to the rows (accumulate = 1 above) instead of storing them.
