@@ -278,6 +278,18 @@ def f32c(t):
     return t.contiguous()
 
 
+def f32c_aligned(t, align: int = 16):
+    """``f32c`` whose result also starts on an ``align``-byte boundary (16; 8 for the arrays read as pairs of floats): for the entries
+    that require it of a caller's array and answer BDS_EINVAL otherwise.  A contiguous row slice ``t[k:]``, the gradient autograd hands
+    a node behind a ``torch.cat``, or a view into a flat buffer is contiguous at 4-byte alignment only; such a tensor is copied (a
+    fresh allocation is aligned), any other is returned itself."""
+    t = f32c(t)
+    if t is not None and t.data_ptr() % align != 0:
+        t = t.clone(memory_format=torch.contiguous_format)
+        assert t.data_ptr() % align == 0
+    return t
+
+
 def stream(device=None):
     return torch.cuda.current_stream(device).cuda_stream
 

@@ -354,6 +354,19 @@ __device__ __forceinline__ uint32_t nonfinite4(uint4 v) {
 template <int kKind>
 __device__ __forceinline__ uint32_t nonfinite_tensor(const uint32_t *q, int64_t n, int64_t gtid) {
   constexpr int64_t kPiece = 4 * kFiniteBlock;
+  if (kKind == 2 && (reinterpret_cast<uintptr_t>(q) & 15u) != 0) {
+    // rows of a [N,4] array start at q + 4 i whatever the base's 16-byte phase (a contiguous row slice, a view into a flat buffer):
+    // one 16-byte access per row at 4-byte alignment (unaligned vector access is on for gfx950 compute), not the head / body / tail split.
+    // On purpose without the aligned form's non-temporal, four-in-flight loads: a rare case, kept to the plainest correct loop
+    typedef uint32_t v4m __attribute__((ext_vector_type(4), aligned(4)));
+    const v4m *qm = reinterpret_cast<const v4m *>(q);
+    uint32_t b = 0;
+    for (int64_t k = gtid; k < n / 4; k += (int64_t)gridDim.x * kFiniteBlock) {
+      const v4m a = qm[k];
+      b |= nonfinite4<2>(make_uint4(a.x, a.y, a.z, a.w));
+    }
+    return b;
+  }
   const int64_t head = min(n, (int64_t)((16 - (reinterpret_cast<uintptr_t>(q) & 15u)) & 15u) / 4);   // floats in front of a 16-byte boundary
   const int64_t n4 = (n - head) / 4;
   const uint4 *q4 = reinterpret_cast<const uint4 *>(q + head);
@@ -598,7 +611,7 @@ extern "C" int bds_project_view_bwd_list(int flags, int64_t n_list, const uint64
 
 // Bit t of *flags_dev is set when tensors[t] (counts[t] floats) holds a NaN or an Inf (vanilla.py:407-412); the word is cleared first.
 // flags_pinned (optional, page-locked): receives a copy behind the launch -- the host reads it after its next wait on the stream.
-// kinds (optional, [n_tensors]): 0 plain | 1 argument of exp | 2 quaternion rows [n/4, 4] (16-byte aligned) | 3 argument of sigmoid:
+// kinds (optional, [n_tensors]): 0 plain | 1 argument of exp | 2 quaternion rows [n/4, 4] (any 4-byte alignment) | 3 argument of sigmoid:
 // the bit then says "the ACTIVATED tensor would hold a NaN / Inf" (vanilla.py:393-395 activations, :407-412 check)
 extern "C" int bds_nonfinite_flags(int n_tensors, const float *const *tensors, const int64_t *counts, const int *kinds,
                                    uint32_t *flags_dev, uint32_t *flags_pinned, bds_stream_t stream) {
@@ -609,7 +622,7 @@ extern "C" int bds_nonfinite_flags(int n_tensors, const float *const *tensors, c
   for (int t = 0; t < n_tensors; t++) {
     A.kind[t] = kinds ? kinds[t] : 0;
     BDS_REQUIRE(A.kind[t] >= 0 && A.kind[t] <= 3);
-    BDS_REQUIRE(A.kind[t] != 2 || (counts[t] % 4 == 0 && (reinterpret_cast<uintptr_t>(tensors[t]) & 15u) == 0));
+    BDS_REQUIRE(A.kind[t] != 2 || counts[t] % 4 == 0);
     BDS_REQUIRE(counts[t] >= 0 && (counts[t] == 0 || tensors[t]) && (reinterpret_cast<uintptr_t>(tensors[t]) & 3u) == 0);
     A.p[t] = reinterpret_cast<const uint32_t *>(tensors[t]);
     A.n[t] = counts[t];

@@ -207,7 +207,8 @@ class _RasterizeToPixels(torch.autograd.Function):
     def forward(ctx, means2d, conics, colors, opacities, backgrounds, width, height, tile_size, isect_offsets, flatten_ids,
                 absgrad):
         L.require_gpu(means2d, conics, colors, opacities, backgrounds)
-        means2d_c, conics, colors, opacities, backgrounds = map(L.f32c, (means2d, conics, colors, opacities, backgrounds))
+        conics, colors, opacities, backgrounds = map(L.f32c, (conics, colors, opacities, backgrounds))
+        means2d_c = L.f32c_aligned(means2d, align=8)      # bds_splat_pack reads a centre as ONE 8-byte load (a view into a flat buffer may start 4 bytes in)
         Cn, N = means2d_c.shape[0], means2d_c.shape[1]
         CH = colors.shape[-1]
         tw, th = math.ceil(width / TILE_SIZE), math.ceil(height / TILE_SIZE)   # compositing tiles; tile_size = the lists' tile

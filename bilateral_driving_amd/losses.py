@@ -19,8 +19,8 @@ class _PhotometricTV(torch.autograd.Function):
     def forward(ctx, rgb: Tensor, target: Tensor, tv_weights: tuple, grid_grads, *grids: Tensor):
         L.require_gpu(rgb, target, *grids)
         lib, st = L.lib(), L.stream()
-        rgb, target = rgb.contiguous(), target.contiguous()
         assert rgb.shape == target.shape and rgb.dtype == torch.float32 and target.dtype == torch.float32
+        rgb, target = L.f32c_aligned(rgb), L.f32c_aligned(target)      # bds_l1_mean_fwd reads 16 bytes at a time: a row slice of an image is copied
         grids = [g.contiguous() for g in grids]
         out = torch.zeros(1, device=rgb.device, dtype=torch.float32)
         L.check(lib.bds_l1_mean_fwd(rgb.numel(), L.ptr(rgb), L.ptr(target), L.ptr(out), st), "bds_l1_mean_fwd")
@@ -85,8 +85,8 @@ def photometric_tv_train(rgb: Tensor, target: Tensor, grids: Sequence[Tensor], t
     that small reduction than right behind this launch)."""
     L.require_gpu(rgb, target, *grids)
     lib, st = L.lib(), L.stream()
-    rgb, target = rgb.contiguous(), target.contiguous()
     assert rgb.shape == target.shape and rgb.dtype == torch.float32 and target.dtype == torch.float32
+    rgb, target = L.f32c_aligned(rgb), L.f32c_aligned(target)      # bds_l1_tv_train: 16-byte aligned a, b (and v_a, allocated here)
     grids = [g.contiguous() for g in grids]
     assert len(grid_grads) == len(grids) and all(a.numel() == g.numel() and a.is_contiguous() for a, g in zip(grid_grads, grids))
     out = loss_slots(rgb.device)

@@ -30,7 +30,7 @@ class _MlpHead(torch.autograd.Function):
         P, F = feats.shape
         assert supported(F, w1.shape[0]) and w1.shape == (HIDDEN, F) and w2.shape == (HIDDEN, HIDDEN) and w3.shape == (12, HIDDEN)
         assert want_out or want_affine
-        feats_c = feats.detach().contiguous().float()
+        feats_c = L.f32c_aligned(feats.detach())      # bds_mlp_head_fwd / _bwd read a pixel's features 16 bytes at a time (rgb float by float)
         rgb_c = None if rgb is None else rgb.detach().contiguous().float()
         assert not want_out or (rgb_c is not None and rgb_c.shape == (P, 3))
         ws = [w.detach().contiguous().float() for w in (w1, w2, w3)]
@@ -53,7 +53,7 @@ class _MlpHead(torch.autograd.Function):
         if v_out is None and v_aff is None:
             return (None,) * 8
         v_out = None if v_out is None else v_out.contiguous().float()
-        v_aff = None if v_aff is None else v_aff.contiguous().float()
+        v_aff = L.f32c_aligned(v_aff)                  # (a gradient that is a view into a flat buffer may start 4 bytes in)
         v_feats = torch.empty(P, F, device=dev) if need[0] else None
         v_rgb = torch.empty(P, 3, device=dev) if (need[1] and v_out is not None) else None
         v_w = [torch.empty_like(w) if need[2 + i] else None for i, w in enumerate((w1, w2, w3))]

@@ -258,7 +258,7 @@ class _RasterizeRawView(torch.autograd.Function):
             ts = (means, quats, log_scales, logits, dc, rest)
             ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
             cnts = (ctypes.c_int64 * len(ts))(*[t.numel() for t in ts])
-            kinds = (ctypes.c_int * len(ts))(0, 2 if quats.data_ptr() % 16 == 0 else 0, 1, 3, 0, 0)
+            kinds = (ctypes.c_int * len(ts))(0, 2, 1, 3, 0, 0)
             L.check(lib.bds_nonfinite_flags(len(ts), ptrs, cnts, kinds, flags[0].data_ptr(), flags[1].data_ptr(), st), "bds_nonfinite_flags")
         f = _view_front(fcfg, means, quats, log_scales, logits.reshape(N), (dc, rest), viewmat, lambda: _image_buffers(W, H, dev))
         if flags is not None and int(flags[1][0]):
@@ -372,7 +372,7 @@ class _RasterizeSceneView(torch.autograd.Function):
                 slot = len(checked)
                 ptrs = (ctypes.c_void_p * 6)(*[t.data_ptr() for t in p])
                 cnts = (ctypes.c_int64 * 6)(*[t.numel() for t in p])
-                kinds = (ctypes.c_int * 6)(0, 2 if p[1].data_ptr() % 16 == 0 else 0, 1, 3, 0, 0)
+                kinds = (ctypes.c_int * 6)(0, 2, 1, 3, 0, 0)
                 L.check(lib.bds_nonfinite_flags(6, ptrs, cnts, kinds, words[0][slot:].data_ptr(), words[1][slot:].data_ptr(), st),
                         "bds_nonfinite_flags")
                 checked.append((slot, s))

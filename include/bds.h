@@ -493,7 +493,9 @@ int bds_sh_view_bwd_list(int64_t n_list, const uint64_t *n_dev, const int32_t *i
  * kinds ([n_tensors], NULL = all 0): with a KIND the bit says "the tensor's ACTIVATED value would hold a NaN / Inf", for raw
  * parameters whose activation runs inside a kernel (vanilla.py:393-395, checked at :407-412 on the activated tensors):
  * 0 plain (NaN, +-Inf) | 1 argument of exp (NaN, +Inf, x >= 88.72284: exp overflows; -Inf is fine) | 2 quaternion rows [n/4, 4],
- * 16-byte aligned (NaN / Inf components, or a row whose squared norm is 0 in fp32: 0/0, x/0) | 3 argument of sigmoid (NaN only). */
+ * at any 4-byte alignment: row i is the four floats at tensors[t] + 4 i whatever the base's 16-byte phase -- a contiguous row slice or
+ * a view into a flat buffer is checked like a fresh allocation (NaN / Inf components, or a row whose squared norm is 0 in fp32: 0/0,
+ * x/0) | 3 argument of sigmoid (NaN only).  Every tensor is 4-byte aligned, counts[t] of a kind-2 tensor a multiple of 4 (BDS_EINVAL). */
 int bds_nonfinite_flags(int n_tensors, const float *const *tensors, const int64_t *counts, const int *kinds, uint32_t *flags_dev,
                         uint32_t *flags_pinned, bds_stream_t stream);
 /* ---- the scene view: one camera over several Gaussian classes (csrc/scene_view.hip) -------------------------------------------

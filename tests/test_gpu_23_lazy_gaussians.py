@@ -161,14 +161,23 @@ def test_nonfinite_flags_sees_every_element(mods):
 def test_nonfinite_kinds_follow_the_activations(mods):
     """bds_nonfinite_flags with kinds: the raw one-view node checks the raw parameters, so the bit has to say what the reference's check of
     the ACTIVATED tensors would (vanilla.py:393-395,407-412): exp of a log-scale >= 88.72284 is Inf (and of -Inf is 0: fine), a
-    zero quaternion normalises to NaN, sigmoid maps +-Inf logits to 0 / 1 (fine) -- each against torch's own activation."""
+    zero quaternion normalises to NaN, sigmoid maps +-Inf logits to 0 / 1 (fine) -- each against torch's own activation.
+    The quaternions at every 4-byte phase of a 16-byte boundary (a fresh allocation, then a contiguous view 1, 2, 3 floats behind
+    one: a row slice, a view into a flat buffer): row i is q + 4 i whatever the phase, with the same expectations."""
+    for q_off in (0, 1, 2, 3):
+        _nonfinite_kinds_case(q_off)
+
+
+def _nonfinite_kinds_case(q_off):
     import ctypes
     from bilateral_driving_amd import _lib as L
+    from tests.placement import placed
     lib = L.lib()
     flag = torch.zeros(1, device="cuda", dtype=torch.int32)
     g = torch.Generator().manual_seed(0)
     ls = (torch.rand(30011, generator=g) * 8 - 6).cuda()
-    q = torch.randn(5001, 4, generator=g).cuda()
+    q = placed(torch.randn(5001, 4, generator=g).cuda(), q_off)
+    assert q.is_contiguous() and q.data_ptr() % 16 == 4 * q_off
     lo = (torch.randn(7003, generator=g) * 3).cuda()
     ts, kinds = [ls, q, lo], (1, 2, 3)
     acts = [torch.exp, lambda t: t / t.norm(dim=-1, keepdim=True), torch.sigmoid]
@@ -188,13 +197,13 @@ def test_nonfinite_kinds_follow_the_activations(mods):
     for t_i, idx, val, want in cases:
         keep = float(ts[t_i].view(-1)[idx])
         ts[t_i].view(-1)[idx] = val
-        assert run() == want, (t_i, idx, val)
+        assert run() == want, (q_off, t_i, idx, val)
         ts[t_i].view(-1)[idx] = keep
     for row, vals, want in ((123, (0.0, 0.0, 0.0, 0.0), 2), (123, (0.0, -0.0, 0.0, 0.0), 2), (123, (0.0, 0.0, 1e-30, 0.0), 2), (123, (0.0, 0.0, 1e-10, 0.0), 0),
                             (5000, (float("inf"), 1.0, 0.0, 0.0), 2), (0, (float("nan"), 1.0, 0.0, 0.0), 2)):
         keep = q[row].clone()
         q[row] = torch.tensor(vals, device="cuda")
-        assert run() == want, (row, vals)
+        assert run() == want, (q_off, row, vals)
         q[row] = keep
     assert run() == 0
 
