@@ -152,6 +152,13 @@ _SIGS = {
     "bds_pvg_temp_bytes": (_sz, [_i64]),
     "bds_pvg_fwd": (_i, [_i64, _i, _i, _fl, _fl, _i, C.c_double] + [_f] * 18 + [_sz, _f]),
     "bds_pvg_bwd": (_i, [_i64, _i64, _i, _i, _fl, _fl, _i, C.c_double] + [_f] * 9 + [_sz] + [_f] * 17),
+    "bds_pvg_mask_temp_bytes": (_sz, [_i64]),
+    "bds_pvg_densify_stats": (_i, [_i64, _i64, _f, _f, _fl, _fl, _f, _i, _f, _i, _i, _f, _f, _f, _f, _f, _sz, _f]),
+    "bds_pvg_refine_plan": (_i, [_i64] + [_f] * 8 + [_fl] * 5 + [_i, _fl] + [_f] * 5 + [_sz, _f]),
+    "bds_pvg_refine_geometry": (_i, [_i64, _i, _i, C.c_double] + [_f] * 16),
+    "bds_pvg_cull_mask": (_i, [_i64, _i64] + [_f] * 5 + [_fl, _fl, _i, _fl, _i, _fl, _f, _f]),
+    "bds_pvg_velocity_reg_fwd": (_i, [_i64, _i64, C.c_double, _f, _f, _i, _f, _f, _f, _f, _f, _sz, _f]),
+    "bds_pvg_velocity_reg_bwd": (_i, [_i64, C.c_double] + [_f] * 7),
     "bds_image_metrics_workspace_bytes": (_sz, [_i, _i]),
     "bds_image_metrics": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _i, _i, _f, _f, _f, _sz, _f]),
     "bds_geometry_metrics_workspace_bytes": (_sz, [_i, _i]),

@@ -103,4 +103,156 @@ BDS_HD float pvg_clamp_grad(float raw, float v) {
   return (x >= 0.0f && x <= 1.0f) ? v : 0.0f;
 }
 
+// ---- density control (PeriodicVibrationGaussians.refinement_after, pvg.py:148-265) ------------------------------------------------
+// Per-row math of csrc/refine.hip's pvg_* kernels and of the host shim tests/hostmath_pvg_refine_shim.hip.  Every function keeps the
+// reference's operations apart (no FMA contraction), as refine_classify does: the decisions compare float32 values.
+
+// what a row's decision is made of; thresholds that the reference forms from Python floats are formed in double and rounded once
+struct PvgRefineCfg {
+  float grad_thresh, t_grad_thresh;   // densify_grad_thresh, densify_t_grad_thresh
+  float size_thresh;                  // densify_size_thresh * scene_scale
+  float t_size_thresh;                // densify_t_size_thresh
+  int split_by_screen;                // step < stop_screen_size_at
+  float split_screen_size;
+  float scene_scale, origin[3];       // gamma (pvg.py:90-98)
+};
+
+struct PvgCullCfg {
+  float cull_alpha;
+  int by_scale;                       // step > reset_alpha_interval
+  float cull_scale;                   // cull_scale_thresh * scene_scale
+  int by_screen;                      // by_scale and step < stop_screen_size_at
+  float cull_screen;
+  float scene_scale, origin[3];
+};
+
+enum PvgKind : unsigned char { kPvgKeepsScale = 1, kPvgKeepsBeta = 2 };   // second plan array: what a split's children do NOT shrink
+
+// gamma (pvg.py:90-98): max(1, |mean - scene_origin| scene_scale - 1) / scene_scale
+BDS_HD float pvg_gamma(const float *mean, const float *origin, float scene_scale) {
+#pragma clang fp contract(off)
+  const float x = mean[0] - origin[0], y = mean[1] - origin[1], z = mean[2] - origin[2];
+  float g = sqrtf(x * x + y * y + z * z) * scene_scale - 1.0f;
+  if (g <= 1.0f) g = 1.0f;            // torch.where(gamma <= 1, 1, gamma): a NaN stays
+  return g / scene_scale;
+}
+
+BDS_HD float pvg_shrink_log(float ls) {
+#pragma clang fp contract(off)
+  return logf(expf(ls) / 1.6f);       // pvg.py:322-323, :335  log(exp(s) / size_fac)
+}
+
+// pvg.py:165-202.  Returns bit 0 split, bit 1 dup; *kind: kPvgKeepsScale when the (shrunk) parent is not over the size threshold
+// (:339-342, evaluated after :323), kPvgKeepsBeta when its time scale is not over densify_t_size_thresh (:347).  The dup mask is
+// evaluated after split_gaussians has shrunk EVERY split parent's scales in place (:323 runs before :195); betas are not shrunk.
+BDS_HD unsigned pvg_refine_decide(const PvgRefineCfg &c, float xys_grad_norm, float t_grad_accum, float vis_count, float max_2Dsize,
+                                  const float *log_scale, float beta, const float *mean, unsigned char *kind) {
+#pragma clang fp contract(off)
+  const bool high_xyz = (xys_grad_norm / vis_count) > c.grad_thresh;
+  const bool high_t = (t_grad_accum / vis_count) > c.t_grad_thresh;
+  const bool high = high_xyz || high_t;
+  const float lmax = fmaxf(fmaxf(log_scale[0], log_scale[1]), log_scale[2]);
+  const float smax = expf(lmax);      // exp is monotone: max_i exp(s_i) = exp(max_i s_i)
+  const float thr = c.size_thresh * pvg_gamma(mean, c.origin, c.scene_scale);
+  const float st = expf(beta);
+  const bool big_t = st > c.t_size_thresh;
+  bool split = (smax > thr) || (big_t && high_t);
+  if (c.split_by_screen) split = split || (max_2Dsize > c.split_screen_size);
+  split = split && high;
+  const float s_post = split ? expf(pvg_shrink_log(lmax)) : smax;
+  const bool small_xyz = s_post <= thr, small_t = st <= c.t_size_thresh;
+  const bool dup = (small_xyz || (small_t && high_t)) && high;
+  *kind = (unsigned char)((small_xyz ? kPvgKeepsScale : 0) | (small_t ? kPvgKeepsBeta : 0));
+  return (split ? 1u : 0u) | (dup ? 2u : 0u);
+}
+
+// rotation of a split sample: R(quat_act(q)) with the F.normalize of quat_to_rotmat (pvg.py:310-311), rows of R
+BDS_HD void pvg_split_rotation(const float *quat, float *R) {
+#pragma clang fp contract(off)
+  float q[4] = {quat[0], quat[1], quat[2], quat[3]};
+  const float n1 = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  for (int i = 0; i < 4; i++) q[i] = q[i] / n1;
+  const float n2 = fmaxf(sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]), 1e-12f);
+  for (int i = 0; i < 4; i++) q[i] = q[i] / n2;
+  const float w = q[0], x = q[1], y = q[2], z = q[3];
+  R[0] = 1.f - 2.f * (y * y + z * z); R[1] = 2.f * (x * y - w * z); R[2] = 2.f * (x * z + w * y);
+  R[3] = 2.f * (x * y + w * z); R[4] = 1.f - 2.f * (x * x + z * z); R[5] = 2.f * (y * z - w * x);
+  R[6] = 2.f * (x * z - w * y); R[7] = 2.f * (y * z + w * x); R[8] = 1.f - 2.f * (x * x + y * y);
+}
+
+// what every child of one split parent shares (pvg.py:298-354): its log-scale and beta, and the parent's shrunk log-scale
+struct PvgSplitRow {
+  float R[9], scale[3];               // rotation; exp(scale BEFORE the shrink)
+  float st, drift;                    // exp(beta); exp(-0.5 exp(beta) / T) of the velocity property (:83-88)
+  float shrunk[3], child_scale[3], child_beta;
+};
+
+BDS_HD void pvg_split_row(const float *quat, const float *log_scale, float beta, float T, unsigned kind, int no_time_split, PvgSplitRow *o) {
+#pragma clang fp contract(off)
+  pvg_split_rotation(quat, o->R);
+  o->st = expf(beta);
+  o->drift = expf(-0.5f * (o->st / T));
+  for (int i = 0; i < 3; i++) {
+    o->scale[i] = expf(log_scale[i]);
+    o->shrunk[i] = pvg_shrink_log(log_scale[i]);
+    // :343-345 log(get_scaling) of the row the shrink has already rewritten
+    o->child_scale[i] = (kind & kPvgKeepsScale) ? logf(expf(o->shrunk[i])) : o->shrunk[i];
+  }
+  o->child_beta = (no_time_split || (kind & kPvgKeepsBeta)) ? logf(o->st) : logf(o->st / 1.6f);
+}
+
+// one child: sample = {n_x, n_y, n_z, z_t} (:305 randn, :332 normal(0, std) = std z_t)
+BDS_HD void pvg_split_child(const PvgSplitRow &r, const float *mean, const float *vel, float tau, const float *sample, float *o_mean,
+                            float *o_tau) {
+#pragma clang fp contract(off)
+  const float v[3] = {r.scale[0] * sample[0], r.scale[1] * sample[1], r.scale[2] * sample[2]};
+  const float samples_t = 0.0f + r.st * sample[3];
+  for (int i = 0; i < 3; i++) {
+    const float nm = (r.R[i * 3] * v[0] + r.R[i * 3 + 1] * v[1] + r.R[i * 3 + 2] * v[2]) + mean[i];
+    o_mean[i] = nm + (vel[i] * r.drift) * samples_t;
+  }
+  *o_tau = samples_t + tau;
+}
+
+// cull_gaussians (pvg.py:267-284) of one row of the NEW set; max_2Dsize = 0 for a child
+BDS_HD bool pvg_cull(const PvgCullCfg &c, float logit, const float *log_scale, const float *mean, float max_2Dsize) {
+#pragma clang fp contract(off)
+  bool cull = pvg_sigmoid(logit) < c.cull_alpha;
+  if (c.by_scale) {
+    const float smax = expf(fmaxf(fmaxf(log_scale[0], log_scale[1]), log_scale[2]));
+    cull = cull || (smax > c.cull_scale * pvg_gamma(mean, c.origin, c.scene_scale));
+    if (c.by_screen) cull = cull || (max_2Dsize > c.cull_screen);
+  }
+  return cull;
+}
+
+// after_train (pvg.py:100-133) of one kept row: the norm of the scaled 2-D gradient
+BDS_HD float pvg_grad_norm(float gx, float gy, float sx, float sy) {
+#pragma clang fp contract(off)
+  const float x = gx * sx, y = gy * sy;
+  return sqrtf(x * x + y * y);
+}
+
+// velocity_reg (pvg.py:430-435): |_velocity exp(-0.5 exp(beta) / T)| of one row
+BDS_HD float pvg_velocity_norm(const float *vel, float beta, float T) {
+  const float w = expf(-0.5f * (expf(beta) / T));
+  const float x = vel[0] * w, y = vel[1] * w, z = vel[2] * w;
+  return sqrtf(x * x + y * y + z * z);
+}
+
+// ... and its gradient times `go`: a zero velocity gets 0 (torch's norm backward), never 0 / 0
+BDS_HD void pvg_velocity_norm_vjp(const float *vel, float beta, float T, float go, float *g_vel, float *g_beta) {
+  const float st = expf(beta), w = expf(-0.5f * (st / T));
+  const float x = vel[0] * w, y = vel[1] * w, z = vel[2] * w;
+  const float n = sqrtf(x * x + y * y + z * z);
+  if (n == 0.0f) {
+    g_vel[0] = g_vel[1] = g_vel[2] = 0.0f;
+    *g_beta = 0.0f;
+    return;
+  }
+  const float s = go * w / n;         // d n / d vel_k = w (vel_k w) / n
+  g_vel[0] = s * x; g_vel[1] = s * y; g_vel[2] = s * z;
+  *g_beta = go * n * (-0.5f / T) * st;   // d n / d beta = n d log(w) / d beta
+}
+
 }  // namespace bds

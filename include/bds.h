@@ -790,6 +790,67 @@ int bds_refine_rows(int64_t N, int width, int samps, const uint8_t *flags, const
  * exp_avg / exp_avg_sq (either may be NULL) are zeroed. */
 int bds_opacity_reset(int64_t N, float *logits, float reset_value, float *exp_avg, float *exp_avg_sq, bds_stream_t stream);
 
+/* ---- Density control of the periodic-vibration Gaussians (models/gaussians/pvg.py) ------------------------------------
+ * PeriodicVibrationGaussians.after_train (:100-133), refinement_after (:148-265) with split_gaussians (:298-354), dup_gaussians
+ * (:356-372), cull_gaussians (:267-284), and the velocity_reg term of compute_reg_loss (:430-435).  scene_origin [3] is read on
+ * the device (gamma, :90-98); thresholds the reference forms from Python floats arrive multiplied in double and rounded once.
+ *
+ * bds_pvg_densify_stats: after_train.  filter_mask [N] u8 (the bool mask get_gaussians leaves behind) with M rows set; row r of
+ * grad2d [M,2] and radii [M] (i32, or f32 when radii_float != 0) is the r-th set row.  The gradient is scaled by (sx, sy) -- 1 for
+ * the gradients the trainer has already scaled (models/trainers/base.py:285-286), width / 2 and height / 2 for raw ones -- and
+ * taus_grad [N] enters by its absolute value.  first != 0 is the initialising call (:114-120): xys_grad_norm and t_grad_accum are
+ * set for every kept row (0 elsewhere), vis_counts = 1 for EVERY row, max_2Dsize from zero; later calls touch only kept rows with
+ * radius > 0.  temp: bds_pvg_mask_temp_bytes(N) bytes (the kept rows' offsets per workgroup).  N < 2^31, M <= N. */
+size_t bds_pvg_mask_temp_bytes(int64_t N);
+int bds_pvg_densify_stats(int64_t N, int64_t M, const uint8_t *filter_mask, const float *grad2d, float sx, float sy, const void *radii,
+                          int radii_float, const float *taus_grad, int last_size, int first, float *xys_grad_norm,
+                          float *t_grad_accum, float *vis_counts, float *max_2Dsize, void *temp, size_t temp_bytes,
+                          bds_stream_t stream);
+
+/* bds_pvg_refine_plan: the densification decisions of :165-202 WITHOUT a cull, in bds_refine_plan's layout -- flags bit 0 split,
+ * bit 1 dup, bit 2 set for every row, bit 3 = split, bit 4 = dup; ranks [N,4] and totals [5] as there (KO = N) -- so that
+ * bds_refine_rows appends the children in the reference's order.  kinds [N] u8: bit 0 = the (shrunk) parent is not over the size
+ * threshold (:339-342, evaluated after the in-place shrink of :323), bit 1 = its time scale is not over t_size_thresh (:347).
+ *   high = xys_grad_norm / vis > grad_thresh | t_grad_accum / vis > t_grad_thresh
+ *   split = (max exp(scale) > size_thresh gamma | exp(beta) > t_size_thresh & high_t | max_2Dsize > split_screen_size) & high
+ *   dup   = (max exp(scale AFTER the shrink of every split row) <= size_thresh gamma | exp(beta) <= t_size_thresh & high_t) & high
+ * size_thresh = densify_size_thresh * scene_scale; split_by_screen: step < stop_screen_size_at (:179).  The host decides
+ * do_densification as :155-159 does (including num_points < densify_until_num_points).  temp: bds_refine_plan_temp_bytes(N). */
+int bds_pvg_refine_plan(int64_t N, const float *xys_grad_norm, const float *t_grad_accum, const float *vis_counts,
+                        const float *max_2Dsize, const float *log_scales, const float *betas, const float *means,
+                        const float *scene_origin, float scene_scale, float grad_thresh, float t_grad_thresh, float size_thresh,
+                        float t_size_thresh, int split_by_screen, float split_screen_size, uint8_t *flags, uint8_t *kinds,
+                        uint32_t *ranks, int64_t *totals, void *temp, size_t temp_bytes, bds_stream_t stream);
+
+/* The four arrays a split changes, for the N + samps n_split + n_dup rows of such a plan: means [N',3], log-scales [N',3],
+ * taus [N'], betas [N'].  samples [samps n_split, 4]: columns 0-2 the randn of :305, column 3 a unit normal z with
+ * samples_t = exp(beta) z (:330-332).  Child: mean + R(q/|q|)(exp(scale before the shrink) n) + velocity exp(-0.5 exp(beta) / T)
+ * samples_t (:313, :337); tau + samples_t (:333); log-scale log(exp(s) / 1.6), through one more exp / log for a kinds bit 0 child
+ * (:343-345); beta log(exp(beta) / 1.6), log(exp(beta)) for a kinds bit 1 child and for every child when no_time_split (:347-353).
+ * Split parents get the shrunk log-scale and keep tau and beta; dup children copy the possibly shrunk parent.  samps >= 1. */
+int bds_pvg_refine_geometry(int64_t N, int samps, int no_time_split, double T, const uint8_t *flags, const uint8_t *kinds,
+                            const uint32_t *ranks, const int64_t *totals, const float *samples, const float *means,
+                            const float *quats, const float *log_scales, const float *velocity, const float *taus, const float *betas,
+                            float *new_means, float *new_log_scales, float *new_taus, float *new_betas, bds_stream_t stream);
+
+/* cull_gaussians (:267-284) on the N NEW rows, of which the first n_old carry max_2Dsize (children enter with 0): mask[g] = 1 when
+ * sigmoid(logit) < cull_alpha_thresh, or (cull_by_scale: step > reset_alpha_interval) max exp(scale) > cull_scale_thresh gamma(mean)
+ * with cull_scale_thresh already times scene_scale, or (additionally cull_by_screen: step < stop_screen_size_at)
+ * max_2Dsize > cull_screen_size.  The mask is the extra_cull of a cull-only bds_refine_plan (cull_alpha_thresh = 0). */
+int bds_pvg_cull_mask(int64_t N, int64_t n_old, const float *logits, const float *log_scales, const float *means,
+                      const float *max_2Dsize, const float *scene_origin, float scene_scale, float cull_alpha_thresh, int cull_by_scale,
+                      float cull_scale_thresh, int cull_by_screen, float cull_screen_size, uint8_t *mask, bds_stream_t stream);
+
+/* velocity_reg (:430-435): out = {sum, count} (double) of |_velocity exp(-0.5 exp(beta) / T)| over the rows kept by filter_mask
+ * whose radius (radii [M], as above) is > 0, summed in a fixed order without float atomics; vis [N] u8 marks those rows.
+ * _bwd: the gradient of sum * scale[0] (scale: one float on the device) towards _velocity [N,3] and _betas [N]; rows outside the
+ * set get zeros, and so does a row whose velocity is zero (torch's norm backward).  temp: bds_pvg_mask_temp_bytes(N). */
+int bds_pvg_velocity_reg_fwd(int64_t N, int64_t M, double T, const uint8_t *filter_mask, const void *radii, int radii_float,
+                             const float *velocity, const float *betas, uint8_t *vis, double *out, void *temp, size_t temp_bytes,
+                             bds_stream_t stream);
+int bds_pvg_velocity_reg_bwd(int64_t N, double T, const uint8_t *vis, const float *scale, const float *velocity, const float *betas,
+                             float *g_velocity, float *g_betas, bds_stream_t stream);
+
 /* Regularisers of the reference's image loss (models/trainers/base.py:566-585, 638-659), one pass each way:
  *   terms[0] opacity entropy       (-p log p).mean(), p = clamp(opacity, 1e-6, 1-1e-6)                       (opacity != NULL)
  *   terms[1] inverse-depth smoothness  kornia.losses.inverse_depth_smoothness_loss(1/(depth+1e-5), pixels)    (depth != NULL;
