@@ -10,6 +10,7 @@
 #pragma once
 #include <math.h>
 #include "gs_math.h"
+#include "refine_math.h"
 
 namespace bds {
 
@@ -105,7 +106,8 @@ BDS_HD float pvg_clamp_grad(float raw, float v) {
 
 // ---- density control (PeriodicVibrationGaussians.refinement_after, pvg.py:148-265) ------------------------------------------------
 // Per-row math of csrc/refine.hip's pvg_* kernels and of the host shim tests/hostmath_pvg_refine_shim.hip.  Every function keeps the
-// reference's operations apart (no FMA contraction), as refine_classify does: the decisions compare float32 values.
+// reference's operations apart (no FMA contraction), as refine_classify does: the decisions compare float32 values.  What a split does
+// in every class -- the 1 / 1.6 shrink, the sample's rotation, R (scale * noise) + mean -- is csrc/refine_math.h.
 
 // what a row's decision is made of; thresholds that the reference forms from Python floats are formed in double and rounded once
 struct PvgRefineCfg {
@@ -137,11 +139,6 @@ BDS_HD float pvg_gamma(const float *mean, const float *origin, float scene_scale
   return g / scene_scale;
 }
 
-BDS_HD float pvg_shrink_log(float ls) {
-#pragma clang fp contract(off)
-  return logf(expf(ls) / 1.6f);       // pvg.py:322-323, :335  log(exp(s) / size_fac)
-}
-
 // pvg.py:165-202.  Returns bit 0 split, bit 1 dup; *kind: kPvgKeepsScale when the (shrunk) parent is not over the size threshold
 // (:339-342, evaluated after :323), kPvgKeepsBeta when its time scale is not over densify_t_size_thresh (:347).  The dup mask is
 // evaluated after split_gaussians has shrunk EVERY split parent's scales in place (:323 runs before :195); betas are not shrunk.
@@ -159,25 +156,11 @@ BDS_HD unsigned pvg_refine_decide(const PvgRefineCfg &c, float xys_grad_norm, fl
   bool split = (smax > thr) || (big_t && high_t);
   if (c.split_by_screen) split = split || (max_2Dsize > c.split_screen_size);
   split = split && high;
-  const float s_post = split ? expf(pvg_shrink_log(lmax)) : smax;
+  const float s_post = split ? expf(refine_shrink_log(lmax)) : smax;
   const bool small_xyz = s_post <= thr, small_t = st <= c.t_size_thresh;
   const bool dup = (small_xyz || (small_t && high_t)) && high;
   *kind = (unsigned char)((small_xyz ? kPvgKeepsScale : 0) | (small_t ? kPvgKeepsBeta : 0));
   return (split ? 1u : 0u) | (dup ? 2u : 0u);
-}
-
-// rotation of a split sample: R(quat_act(q)) with the F.normalize of quat_to_rotmat (pvg.py:310-311), rows of R
-BDS_HD void pvg_split_rotation(const float *quat, float *R) {
-#pragma clang fp contract(off)
-  float q[4] = {quat[0], quat[1], quat[2], quat[3]};
-  const float n1 = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  for (int i = 0; i < 4; i++) q[i] = q[i] / n1;
-  const float n2 = fmaxf(sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]), 1e-12f);
-  for (int i = 0; i < 4; i++) q[i] = q[i] / n2;
-  const float w = q[0], x = q[1], y = q[2], z = q[3];
-  R[0] = 1.f - 2.f * (y * y + z * z); R[1] = 2.f * (x * y - w * z); R[2] = 2.f * (x * z + w * y);
-  R[3] = 2.f * (x * y + w * z); R[4] = 1.f - 2.f * (x * x + z * z); R[5] = 2.f * (y * z - w * x);
-  R[6] = 2.f * (x * z - w * y); R[7] = 2.f * (y * z + w * x); R[8] = 1.f - 2.f * (x * x + y * y);
 }
 
 // what every child of one split parent shares (pvg.py:298-354): its log-scale and beta, and the parent's shrunk log-scale
@@ -189,12 +172,12 @@ struct PvgSplitRow {
 
 BDS_HD void pvg_split_row(const float *quat, const float *log_scale, float beta, float T, unsigned kind, int no_time_split, PvgSplitRow *o) {
 #pragma clang fp contract(off)
-  pvg_split_rotation(quat, o->R);
+  refine_split_rotation(quat, o->R);
   o->st = expf(beta);
   o->drift = expf(-0.5f * (o->st / T));
   for (int i = 0; i < 3; i++) {
     o->scale[i] = expf(log_scale[i]);
-    o->shrunk[i] = pvg_shrink_log(log_scale[i]);
+    o->shrunk[i] = refine_shrink_log(log_scale[i]);
     // :343-345 log(get_scaling) of the row the shrink has already rewritten
     o->child_scale[i] = (kind & kPvgKeepsScale) ? logf(expf(o->shrunk[i])) : o->shrunk[i];
   }
@@ -205,12 +188,10 @@ BDS_HD void pvg_split_row(const float *quat, const float *log_scale, float beta,
 BDS_HD void pvg_split_child(const PvgSplitRow &r, const float *mean, const float *vel, float tau, const float *sample, float *o_mean,
                             float *o_tau) {
 #pragma clang fp contract(off)
-  const float v[3] = {r.scale[0] * sample[0], r.scale[1] * sample[1], r.scale[2] * sample[2]};
   const float samples_t = 0.0f + r.st * sample[3];
-  for (int i = 0; i < 3; i++) {
-    const float nm = (r.R[i * 3] * v[0] + r.R[i * 3 + 1] * v[1] + r.R[i * 3 + 2] * v[2]) + mean[i];
-    o_mean[i] = nm + (vel[i] * r.drift) * samples_t;
-  }
+  float nm[3];
+  refine_split_mean(r.R, r.scale, sample, mean, nm);
+  for (int i = 0; i < 3; i++) o_mean[i] = nm[i] + (vel[i] * r.drift) * samples_t;
   *o_tau = samples_t + tau;
 }
 

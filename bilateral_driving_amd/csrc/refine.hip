@@ -1,7 +1,12 @@
 // Adaptive density control: split / duplicate / cull of one class of Gaussians together with its Adam state, and the periodic
-// opacity reset -- VanillaGaussians.refinement_after (/root/reference/project/models/gaussians/vanilla.py:205-304),
-// split_gaussians (:336-363), dup_gaussians (:365-376), cull_gaussians (:306-334) and the optimiser surgery
-// dup_in_optim / remove_from_optim (models/gaussians/basics.py:162-206).  SURVEY.md 8f rank 2, second slice.
+// opacity reset.  The CORE serves every class: the planned layout below (the flag bits; refine_plan_run = block scan + ranks behind a
+// class's flags kernel; RefineDest = where a row's original and children go), refine_rows_kernel for every array that only moves (the
+// optimiser surgery dup_in_optim / remove_from_optim, models/gaussians/basics.py:162-206, is this kernel on the Adam moments),
+// opacity_reset_kernel, and the per-row math of a split in csrc/refine_math.h.  A class adds its decision and its geometry kernel:
+//   vanilla and the node classes: refine_flags_kernel (split, dup AND cull in one plan) and refine_geometry_kernel --
+//     VanillaGaussians.refinement_after (models/gaussians/vanilla.py:205-304), split_gaussians (:336-363), dup_gaussians (:365-376),
+//     cull_gaussians (:306-334); refine_out_of_bound_kernel is the node classes' box test, compacted by a second, cull-only plan
+//   periodic-vibration: the pvg_* kernels, see their section below (a plan without a cull, then a cull-only plan over the NEW rows)
 //
 // The reference builds the new set in three rounds of boolean-mask indexing + torch.cat per tensor (6 parameters + 12 state
 // tensors, each round a nonzero() with a host sync) and then compacts everything again for the cull.  Here the whole topology
@@ -17,9 +22,10 @@
 //   split child s of g    -> KO + s*KS + rank_keepS[g]        (its noise sample is row s*S + rank_split[g] of `samples`)
 //   dup child of g        -> KO + samps*KS + rank_keepD[g]
 // HBM-bound byte movement: every parameter / state row is read once and written once (+ once per kept child).
-// PINNED by tests/golden/refine_*.npz (the reference's own refinement_after, oracle/gen_golden_refine.py).
+// PINNED by tests/golden/refine_*.npz (the reference's own refinement_after, oracle/gen_golden_refine.py) and pvg_refine_*.npz.
 #include "bds_common.h"
 #include "pvg_math.h"
+#include "refine_math.h"
 #include "scan.h"
 
 namespace bds {
@@ -42,10 +48,19 @@ struct RefineCfg {
   float cull_screen;
 };
 
-__device__ __forceinline__ float shrink_log_scale(float ls) {
-#pragma clang fp contract(off)
-  return logf(expf(ls) / 1.6f);  // vanilla.py:358-359  log(exp(s) / size_fac)
-}
+// Where the rows that input Gaussian g leaves behind go in the planned layout (the table in the file header), and which row of
+// `samples` its s-th split child reads.  Built once the row is known to keep anything: a dropped row reads neither ranks nor totals.
+struct RefineDest {
+  uint4 r;              // exclusive ranks of g: split, keepO, keepS, keepD
+  int64_t S, KO, KS;    // totals: split parents, kept originals, kept split parents
+  int samps;
+  __device__ __forceinline__ RefineDest(int64_t g, int samps_, const uint32_t *__restrict__ ranks, const int64_t *__restrict__ totals)
+      : r(reinterpret_cast<const uint4 *>(ranks)[g]), S(totals[0]), KO(totals[2]), KS(totals[3]), samps(samps_) {}
+  __device__ __forceinline__ int64_t original() const { return (int64_t)r.y; }
+  __device__ __forceinline__ int64_t split_child(int s) const { return KO + (int64_t)s * KS + r.z; }
+  __device__ __forceinline__ int64_t dup_child() const { return KO + (int64_t)samps * KS + r.w; }
+  __device__ __forceinline__ int64_t sample_row(int s) const { return (int64_t)s * S + r.x; }
+};
 
 __device__ __forceinline__ uint8_t refine_classify(int64_t g, const RefineCfg &c, const float *__restrict__ xys_grad_norm,
                                                    const float *__restrict__ vis_counts, const float *__restrict__ max_2Dsize,
@@ -62,7 +77,7 @@ __device__ __forceinline__ uint8_t refine_classify(int64_t g, const RefineCfg &c
     split = smax > c.size_thresh;
     if (c.split_by_screen) split = split || (m2d > c.split_screen_size);
     split = split && high;
-    if (split) s_post = expf(shrink_log_scale(lmax));
+    if (split) s_post = expf(refine_shrink_log(lmax));
     // the dup mask is evaluated AFTER the split (:246-250): a small Gaussian that is large on screen, or one that drops below
     // the size threshold by the 1/1.6 shrink, is split AND duplicated
     dup = (s_post <= c.size_thresh) && high;
@@ -151,38 +166,29 @@ __global__ __launch_bounds__(kRefBlock) void refine_geometry_kernel(int64_t N, i
   if (g >= N) return;
   const uint8_t f = flags[g];
   if (!(f & (kKeepO | kKeepS | kKeepD))) return;
-  const uint4 r = reinterpret_cast<const uint4 *>(ranks)[g];
-  const int64_t S = totals[0], KO = totals[2], KS = totals[3];
+  const RefineDest d(g, samps, ranks, totals);
   const float m[3] = {means[g * 3], means[g * 3 + 1], means[g * 3 + 2]};
   const float ls[3] = {log_scales[g * 3], log_scales[g * 3 + 1], log_scales[g * 3 + 2]};
   float lp[3] = {ls[0], ls[1], ls[2]};
   if (f & kSplit)
-    for (int i = 0; i < 3; i++) lp[i] = shrink_log_scale(ls[i]);  // parent and children alike (vanilla.py:358-359)
+    for (int i = 0; i < 3; i++) lp[i] = refine_shrink_log(ls[i]);  // parent and children alike (vanilla.py:358-359)
   auto put = [&](int64_t dst, const float *mm) {
     for (int i = 0; i < 3; i++) { new_means[dst * 3 + i] = mm[i]; new_log_scales[dst * 3 + i] = lp[i]; }
   };
-  if (f & kKeepO) put((int64_t)r.y, m);
+  if (f & kKeepO) put(d.original(), m);
   if (f & kKeepS) {
     // vanilla.py:343-348: rotate (scale * noise) by the normalised quaternion, add the mean
-    float q[4] = {quats[g * 4], quats[g * 4 + 1], quats[g * 4 + 2], quats[g * 4 + 3]};
-    const float n1 = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    for (int i = 0; i < 4; i++) q[i] = q[i] / n1;                                  // quat_act
-    const float n2 = fmaxf(sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]), 1e-12f);
-    for (int i = 0; i < 4; i++) q[i] = q[i] / n2;                                  // F.normalize inside quat_to_rotmat
-    const float w = q[0], x = q[1], y = q[2], z = q[3];
-    const float R[9] = {1.f - 2.f * (y * y + z * z), 2.f * (x * y - w * z), 2.f * (x * z + w * y),
-                        2.f * (x * y + w * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - w * x),
-                        2.f * (x * z - w * y), 2.f * (y * z + w * x), 1.f - 2.f * (x * x + y * y)};
+    const float q[4] = {quats[g * 4], quats[g * 4 + 1], quats[g * 4 + 2], quats[g * 4 + 3]};
+    float R[9];
+    refine_split_rotation(q, R);
     const float sc[3] = {expf(ls[0]), expf(ls[1]), expf(ls[2])};  // the scale BEFORE the shrink
     for (int s = 0; s < samps; s++) {
-      const float *smp = samples + ((int64_t)s * S + r.x) * 3;
-      const float v[3] = {sc[0] * smp[0], sc[1] * smp[1], sc[2] * smp[2]};
       float nm[3];
-      for (int i = 0; i < 3; i++) nm[i] = (R[i * 3] * v[0] + R[i * 3 + 1] * v[1] + R[i * 3 + 2] * v[2]) + m[i];
-      put(KO + (int64_t)s * KS + r.z, nm);
+      refine_split_mean(R, sc, samples + d.sample_row(s) * 3, m, nm);
+      put(d.split_child(s), nm);
     }
   }
-  if (f & kKeepD) put(KO + (int64_t)samps * KS + r.w, m);
+  if (f & kKeepD) put(d.dup_child(), m);
 }
 
 // any other per-Gaussian array, one thread per element: rows of kept originals move to their new place; the children receive a
@@ -197,14 +203,13 @@ __global__ __launch_bounds__(kRefBlock) void refine_rows_kernel(int64_t N, int w
   const int c = (int)(i - g * width);
   const uint8_t f = flags[g];
   if (!(f & (kKeepO | kKeepS | kKeepD))) return;
-  const uint4 r = reinterpret_cast<const uint4 *>(ranks)[g];
-  const int64_t KO = totals[2], KS = totals[3];
+  const RefineDest d(g, samps, ranks, totals);
   const float v = src[i];
   const float cv = zero_children ? 0.f : v;
-  if (f & kKeepO) dst[(int64_t)r.y * width + c] = v;
+  if (f & kKeepO) dst[d.original() * width + c] = v;
   if (f & kKeepS)
-    for (int s = 0; s < samps; s++) dst[(KO + (int64_t)s * KS + r.z) * width + c] = cv;
-  if (f & kKeepD) dst[(KO + (int64_t)samps * KS + r.w) * width + c] = cv;
+    for (int s = 0; s < samps; s++) dst[d.split_child(s) * width + c] = cv;
+  if (f & kKeepD) dst[d.dup_child() * width + c] = cv;
 }
 
 // nodes/rigid.py:374-383 (get_out_of_bound_mask): |mean| > instances_size[point_id] / 2 in any axis, means in the object frame
@@ -281,8 +286,7 @@ __global__ __launch_bounds__(kRefBlock) void pvg_refine_geometry_kernel(
   if (g >= N) return;
   const uint8_t f = flags[g];
   if (!(f & (kKeepO | kKeepS | kKeepD))) return;
-  const uint4 r = reinterpret_cast<const uint4 *>(ranks)[g];
-  const int64_t S = totals[0], KO = totals[2], KS = totals[3];
+  const RefineDest d(g, samps, ranks, totals);
   const float m[3] = {means[g * 3], means[g * 3 + 1], means[g * 3 + 2]};
   const float ls[3] = {log_scales[g * 3], log_scales[g * 3 + 1], log_scales[g * 3 + 2]};
   const float tau = taus[g], beta = betas[g];
@@ -292,22 +296,22 @@ __global__ __launch_bounds__(kRefBlock) void pvg_refine_geometry_kernel(
     new_betas[dst] = be;
   };
   if (!(f & kSplit)) {                      // untouched: the row and, when duplicated, its copy
-    if (f & kKeepO) put((int64_t)r.y, m, ls, tau, beta);
-    if (f & kKeepD) put(KO + (int64_t)samps * KS + r.w, m, ls, tau, beta);
+    if (f & kKeepO) put(d.original(), m, ls, tau, beta);
+    if (f & kKeepD) put(d.dup_child(), m, ls, tau, beta);
     return;
   }
   const float q[4] = {quats[g * 4], quats[g * 4 + 1], quats[g * 4 + 2], quats[g * 4 + 3]};
   const float vel[3] = {velocity[g * 3], velocity[g * 3 + 1], velocity[g * 3 + 2]};
   PvgSplitRow row;
   pvg_split_row(q, ls, beta, T, kinds[g], no_time_split, &row);
-  if (f & kKeepO) put((int64_t)r.y, m, row.shrunk, tau, beta);      // the parent: shrunk scale, its own tau and beta (:323)
+  if (f & kKeepO) put(d.original(), m, row.shrunk, tau, beta);      // the parent: shrunk scale, its own tau and beta (:323)
   if (f & kKeepS)
     for (int s = 0; s < samps; s++) {
       float nm[3], nt;
-      pvg_split_child(row, m, vel, tau, samples + ((int64_t)s * S + r.x) * 4, nm, &nt);
-      put(KO + (int64_t)s * KS + r.z, nm, row.child_scale, nt, row.child_beta);
+      pvg_split_child(row, m, vel, tau, samples + d.sample_row(s) * 4, nm, &nt);
+      put(d.split_child(s), nm, row.child_scale, nt, row.child_beta);
     }
-  if (f & kKeepD) put(KO + (int64_t)samps * KS + r.w, m, row.shrunk, tau, beta);      // a copy of the shrunk parent (:367)
+  if (f & kKeepD) put(d.dup_child(), m, row.shrunk, tau, beta);      // a copy of the shrunk parent (:367)
 }
 
 // cull_gaussians on the rows AFTER the children were appended: rows >= n_old are children (max_2Dsize 0)
@@ -463,6 +467,28 @@ extern "C" size_t bds_refine_plan_temp_bytes(int64_t N) {
   return (size_t)(cdiv(N, kRefBlock) + 1) * kChan * sizeof(uint32_t);
 }
 
+// What every class's plan has in common: the checks on the plan's own arrays, the empty set (zero totals, nothing launched: no
+// pointer but `totals` is needed) and, behind the class's flags kernel, the block scan and the ranks.  `inputs_ok`: the class's own
+// argument checks; `launch_flags(nb, blk, stream)` starts its flags kernel, which leaves flags [N] and the per-workgroup counts.
+template <class LaunchFlags>
+static int refine_plan_run(int64_t N, bool inputs_ok, uint8_t *flags, uint32_t *ranks, int64_t *totals, void *temp, size_t temp_bytes,
+                           bds_stream_t stream, LaunchFlags launch_flags) {
+  BDS_REQUIRE(N >= 0 && N < ((int64_t)1 << 31) && totals);
+  hipStream_t st = as_stream(stream);
+  if (N == 0) {
+    if (hipMemsetAsync(totals, 0, kChan * sizeof(int64_t), st) != hipSuccess) return BDS_ELAUNCH;
+    return BDS_OK;
+  }
+  BDS_REQUIRE(inputs_ok && flags && ranks && temp && temp_bytes >= bds_refine_plan_temp_bytes(N) && aligned16(ranks));
+  const int64_t nb = cdiv(N, kRefBlock);
+  uint32_t *blk = static_cast<uint32_t *>(temp);
+  launch_flags(nb, blk, st);
+  hipLaunchKernelGGL(refine_blockscan_kernel, dim3(1), dim3(kScanThreads), 0, st, nb, blk, totals);
+  hipLaunchKernelGGL(refine_ranks_kernel, dim3((unsigned)nb), dim3(kRefBlock), 0, st, N, flags, blk, ranks);
+  BDS_LAUNCH_CHECK();
+  return BDS_OK;
+}
+
 extern "C" int bds_refine_plan(int64_t N, const float *xys_grad_norm, const float *vis_counts, const float *max_2Dsize,
                                const float *log_scales, const float *logits, const uint8_t *extra_cull, int do_densify,
                                float grad_thresh,
@@ -470,25 +496,13 @@ extern "C" int bds_refine_plan(int64_t N, const float *xys_grad_norm, const floa
                                float cull_alpha_thresh, int cull_by_scale, float cull_scale_thresh, int cull_by_screen,
                                float cull_screen_size, uint8_t *flags, uint32_t *ranks, int64_t *totals, void *temp,
                                size_t temp_bytes, bds_stream_t stream) {
-  BDS_REQUIRE(N >= 0 && N < ((int64_t)1 << 31) && totals);
-  hipStream_t st = as_stream(stream);
-  if (N == 0) {
-    if (hipMemsetAsync(totals, 0, kChan * sizeof(int64_t), st) != hipSuccess) return BDS_ELAUNCH;
-    return BDS_OK;
-  }
-  BDS_REQUIRE(log_scales && logits && flags && ranks && temp && temp_bytes >= bds_refine_plan_temp_bytes(N));
-  BDS_REQUIRE(!do_densify || (xys_grad_norm && vis_counts));
-  BDS_REQUIRE(aligned16(ranks));
   RefineCfg c{do_densify, grad_thresh, size_thresh, split_by_screen, split_screen_size, do_cull, cull_alpha_thresh,
               cull_by_scale, cull_scale_thresh, cull_by_screen, cull_screen_size};
-  const int64_t nb = cdiv(N, kRefBlock);
-  uint32_t *blk = static_cast<uint32_t *>(temp);
-  hipLaunchKernelGGL(refine_flags_kernel, dim3((unsigned)nb), dim3(kRefBlock), 0, st, N, c, xys_grad_norm, vis_counts, max_2Dsize,
-                     log_scales, logits, extra_cull, flags, blk);
-  hipLaunchKernelGGL(refine_blockscan_kernel, dim3(1), dim3(kScanThreads), 0, st, nb, blk, totals);
-  hipLaunchKernelGGL(refine_ranks_kernel, dim3((unsigned)nb), dim3(kRefBlock), 0, st, N, flags, blk, ranks);
-  BDS_LAUNCH_CHECK();
-  return BDS_OK;
+  const bool inputs = log_scales && logits && (!do_densify || (xys_grad_norm && vis_counts));
+  return refine_plan_run(N, inputs, flags, ranks, totals, temp, temp_bytes, stream, [&](int64_t nb, uint32_t *blk, hipStream_t st) {
+    hipLaunchKernelGGL(refine_flags_kernel, dim3((unsigned)nb), dim3(kRefBlock), 0, st, N, c, xys_grad_norm, vis_counts, max_2Dsize,
+                       log_scales, logits, extra_cull, flags, blk);
+  });
 }
 
 extern "C" int bds_refine_geometry(int64_t N, int samps, const uint8_t *flags, const uint32_t *ranks, const int64_t *totals,
@@ -542,24 +556,13 @@ extern "C" int bds_pvg_refine_plan(int64_t N, const float *xys_grad_norm, const 
                                    float size_thresh, float t_size_thresh, int split_by_screen, float split_screen_size, uint8_t *flags,
                                    uint8_t *kinds, uint32_t *ranks, int64_t *totals, void *temp, size_t temp_bytes,
                                    bds_stream_t stream) {
-  BDS_REQUIRE(N >= 0 && N < ((int64_t)1 << 31) && totals);
-  hipStream_t st = as_stream(stream);
-  if (N == 0) {
-    if (hipMemsetAsync(totals, 0, kChan * sizeof(int64_t), st) != hipSuccess) return BDS_ELAUNCH;
-    return BDS_OK;
-  }
-  BDS_REQUIRE(xys_grad_norm && t_grad_accum && vis_counts && max_2Dsize && log_scales && betas && means && scene_origin);
-  BDS_REQUIRE(flags && kinds && ranks && temp && temp_bytes >= bds_refine_plan_temp_bytes(N) && aligned16(ranks));
-  BDS_REQUIRE(scene_scale > 0.f);
   PvgRefineCfg c{grad_thresh, t_grad_thresh, size_thresh, t_size_thresh, split_by_screen, split_screen_size, scene_scale, {0.f, 0.f, 0.f}};
-  const int64_t nb = cdiv(N, kRefBlock);
-  uint32_t *blk = static_cast<uint32_t *>(temp);
-  hipLaunchKernelGGL(pvg_refine_flags_kernel, dim3((unsigned)nb), dim3(kRefBlock), 0, st, N, c, scene_origin, xys_grad_norm, t_grad_accum,
-                     vis_counts, max_2Dsize, log_scales, betas, means, flags, kinds, blk);
-  hipLaunchKernelGGL(refine_blockscan_kernel, dim3(1), dim3(kScanThreads), 0, st, nb, blk, totals);
-  hipLaunchKernelGGL(refine_ranks_kernel, dim3((unsigned)nb), dim3(kRefBlock), 0, st, N, flags, blk, ranks);
-  BDS_LAUNCH_CHECK();
-  return BDS_OK;
+  const bool inputs = xys_grad_norm && t_grad_accum && vis_counts && max_2Dsize && log_scales && betas && means && scene_origin && kinds &&
+                      scene_scale > 0.f;
+  return refine_plan_run(N, inputs, flags, ranks, totals, temp, temp_bytes, stream, [&](int64_t nb, uint32_t *blk, hipStream_t st) {
+    hipLaunchKernelGGL(pvg_refine_flags_kernel, dim3((unsigned)nb), dim3(kRefBlock), 0, st, N, c, scene_origin, xys_grad_norm, t_grad_accum,
+                       vis_counts, max_2Dsize, log_scales, betas, means, flags, kinds, blk);
+  });
 }
 
 extern "C" int bds_pvg_refine_geometry(int64_t N, int samps, int no_time_split, double T, const uint8_t *flags, const uint8_t *kinds,

@@ -1,5 +1,5 @@
 """Adaptive density control of one class of Gaussians on the device: drop-in for
-``VanillaGaussians.refinement_after`` (/root/reference/project/models/gaussians/vanilla.py:205-304) including the optimiser
+``VanillaGaussians.refinement_after`` (models/gaussians/vanilla.py:205-304) including the optimiser
 surgery of models/gaussians/basics.py:162-206.
 
     from bilateral_driving_amd.densify import refinement_after
@@ -15,10 +15,13 @@ Where the reference runs three rounds of boolean-mask indexing + ``torch.cat`` o
 for the cull (a few hundred launches and a host sync per mask), this plans the topology change once (``bds_refine_plan``: 3
 launches, ONE host read-back of five counts -- the size of the noise tensor has to be known, as in the reference) and writes
 each of the 18 arrays exactly once into its final layout.  The result -- order of the rows included -- is the reference's.
+
+This module is also the CORE of every class's density control (``pvg_densify`` is the second user): a class is a ``RowLayout``
+plus its own decision and geometry kernels; ``schedule``, ``move_rows``, ``compact_rows``, ``reset_opacity``, ``reorder_rows`` are shared.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Callable, Dict, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -26,8 +29,23 @@ from torch.nn import Parameter
 
 from . import _lib as L
 
-_ATTRS = ("_means", "_features_dc", "_features_rest", "_opacities", "_scales", "_quats")
-_GROUPS = ("xyz", "sh_dc", "sh_rest", "opacity", "scaling", "rotation")       # vanilla.py:193-201
+
+class RowLayout(NamedTuple):
+    """What one Gaussian of a class is made of: everything a refinement or a reorder has to move together."""
+    attrs: Tuple[str, ...]              # the nn.Parameters [N, ...]
+    groups: Tuple[str, ...]             # their optimizer groups' names behind ``class_prefix``, in the same order
+    stats: Tuple[str, ...]              # the densification statistics [N] (a refinement consumes them, a reorder moves them)
+    int64_columns: Tuple[str, ...]      # optional int64 columns [N, ...]: moved when the object carries them
+
+
+VANILLA_ROWS = RowLayout(                                                       # vanilla.py:193-201; point_ids: nodes/rigid.py:253,317
+    ("_means", "_features_dc", "_features_rest", "_opacities", "_scales", "_quats"),
+    ("xyz", "sh_dc", "sh_rest", "opacity", "scaling", "rotation"), ("xys_grad_norm", "vis_counts", "max_2Dsize"), ("point_ids",))
+PERIODIC_ROWS = RowLayout(                                                      # pvg.py:135-146
+    VANILLA_ROWS.attrs + ("_velocity", "_taus", "_betas"), VANILLA_ROWS.groups + ("velocity", "life_peak", "life_span"),
+    ("xys_grad_norm", "t_grad_accum", "vis_counts", "max_2Dsize"), ())
+_ATTRS, _GROUPS = VANILLA_ROWS.attrs, VANILLA_ROWS.groups
+_MOMENTS = ("exp_avg", "exp_avg_sq")
 
 
 def _group_of(optimizer, name: str):
@@ -37,6 +55,22 @@ def _group_of(optimizer, name: str):
     return None
 
 
+def schedule(step: int, ctrl, num_train_images: int) -> dict:
+    """The step-dependent switches every class shares, exactly as vanilla.py:212-215, :229, :280, :287, :311, :318 (pvg.py:154-157,
+    :179, :242, :249, :274, :281) form them."""
+    reset = ctrl.reset_alpha_interval
+    past = bool(step % reset > max(num_train_images, ctrl.refine_interval))
+    return dict(do_densify=bool(step < ctrl.stop_split_at and past), do_cull=past, by_screen=bool(step < ctrl.stop_screen_size_at),
+                cull_by_scale=bool(step > reset), do_reset=bool(step % reset == ctrl.refine_interval))
+
+
+def plan_outputs(N: int, dev):
+    """What any class's plan writes: flags [N] u8, ranks [N,4] i32, totals [5] i64, and the scan's scratch bytes."""
+    u8 = lambda *shape: torch.empty(*shape, dtype=torch.uint8, device=dev)
+    return (u8(N), torch.empty(N, 4, dtype=torch.int32, device=dev), torch.empty(5, dtype=torch.int64, device=dev),
+            u8(int(L.lib().bds_refine_plan_temp_bytes(N))))
+
+
 def plan(log_scales: Tensor, logits: Tensor, xys_grad_norm: Optional[Tensor], vis_counts: Optional[Tensor],
          max_2Dsize: Optional[Tensor], *, do_densify: bool, grad_thresh: float, size_thresh: float, split_by_screen: bool,
          split_screen_size: float, do_cull: bool, cull_alpha_thresh: float, cull_by_scale: bool, cull_scale_thresh: float,
@@ -44,12 +78,8 @@ def plan(log_scales: Tensor, logits: Tensor, xys_grad_norm: Optional[Tensor], vi
     """bds_refine_plan: (flags [N] u8, ranks [N,4] i32, totals [5] i64 on the device).  ``extra_cull`` [N] u8: a cull mask over the
     input rows OR-ed into the originals' decision."""
     L.require_gpu(log_scales)
-    N, dev = log_scales.shape[0], log_scales.device
-    flags = torch.empty(N, dtype=torch.uint8, device=dev)
-    ranks = torch.empty(N, 4, dtype=torch.int32, device=dev)
-    totals = torch.empty(5, dtype=torch.int64, device=dev)
-    nb = int(L.lib().bds_refine_plan_temp_bytes(N))
-    temp = torch.empty(nb, dtype=torch.uint8, device=dev)
+    N = log_scales.shape[0]
+    flags, ranks, totals, temp = plan_outputs(N, log_scales.device)
     f32 = lambda t: None if t is None else t.detach().reshape(-1).contiguous().float()
     xs, vc, m2 = f32(xys_grad_norm), f32(vis_counts), f32(max_2Dsize)
     ls, lg = log_scales.detach().contiguous(), logits.detach().reshape(-1).contiguous()
@@ -59,7 +89,7 @@ def plan(log_scales: Tensor, logits: Tensor, xys_grad_norm: Optional[Tensor], vi
                                     float(grad_thresh),
                                     float(size_thresh), int(split_by_screen), float(split_screen_size), int(do_cull),
                                     float(cull_alpha_thresh), int(cull_by_scale), float(cull_scale_thresh), int(cull_by_screen),
-                                    float(cull_screen_size), L.ptr(flags), L.ptr(ranks), L.ptr(totals), L.ptr(temp), nb, L.stream()),
+                                    float(cull_screen_size), L.ptr(flags), L.ptr(ranks), L.ptr(totals), L.ptr(temp), temp.numel(), L.stream()),
             "bds_refine_plan")
     return flags, ranks, totals
 
@@ -84,34 +114,71 @@ def _ctrl_get(ctrl, key: str, default):
     return getattr(ctrl, key, default)
 
 
-def _move_rows(self, optimizer, flags, ranks, totals, samps: int, n_new: int, geometry: Optional[Dict[str, Tensor]]) -> None:
-    """Writes every per-Gaussian array of the class once into the planned layout: the six parameters (``geometry`` holds the two a
-    split changes, already computed), the Adam moments of their groups (children start from zero, basics.py:191-201) and -- node
-    classes -- the ``point_ids`` column (nodes/rigid.py:253,317: int64, moved as two 32-bit words per row)."""
+def _replace_parameter(self, optimizer, attr: str, group_name: str, new: Tensor, move: Callable[[Tensor], Tensor]) -> None:
+    """THE optimiser surgery (basics.py:162-206): ``self.<attr>`` becomes a new ``nn.Parameter`` over ``new``, seated in its named
+    group, and the old parameter's Adam state goes with it, its two moments through ``move`` (one array's rows -> the new rows).
+    ``optimizer`` None or without that group: only the attribute changes."""
+    prm = Parameter(new)
+    setattr(self, attr, prm)
+    group = _group_of(optimizer, self.class_prefix + group_name) if optimizer is not None else None
+    if group is None:
+        return
+    state = optimizer.state.pop(group["params"][0], None)
+    if state:
+        for k in _MOMENTS:
+            if torch.is_tensor(state.get(k)):
+                state[k] = move(state[k])
+        optimizer.state[prm] = state
+    group["params"] = [prm]
+
+
+def move_rows(self, optimizer, layout: RowLayout, flags, ranks, totals, samps: int, n_new: int,
+              geometry: Optional[Dict[str, Tensor]] = None) -> None:
+    """Writes every per-Gaussian array of the class once into the planned layout: the layout's parameters (``geometry`` holds the ones
+    a split changes, already computed), the Adam moments of their groups (children start from zero, basics.py:191-201) and the int64
+    columns the object carries (``point_ids`` of the node classes, nodes/rigid.py:253,317: moved as two 32-bit words per row)."""
     new: Dict[str, Tensor] = dict(geometry or {})
-    for a in _ATTRS:
+    for a in layout.attrs:
         if a not in new:
             new[a] = _rows(getattr(self, a), n_new, samps, flags, ranks, totals, zero_children=False)
-    ids = getattr(self, "point_ids", None)
-    if ids is not None:
+    for name in layout.int64_columns:
+        ids = getattr(self, name, None)
+        if ids is None:
+            continue
         assert ids.dtype == torch.int64 and ids.shape[0] == flags.shape[0]
         L.require_gpu(ids)
         words = ids.contiguous().view(torch.float32).reshape(ids.shape[0], -1)
         moved = _rows(words, n_new, samps, flags, ranks, totals, zero_children=False)
-        self.point_ids = moved.view(torch.int64).reshape((n_new,) + tuple(ids.shape[1:]))
-    for a, gname in zip(_ATTRS, _GROUPS):
-        prm = Parameter(new[a])
-        setattr(self, a, prm)
-        group = _group_of(optimizer, self.class_prefix + gname)
-        if group is None:
-            continue
-        old_p = group["params"][0]
-        state = optimizer.state.pop(old_p, None)                          # basics.py:162-206
-        if state:
-            for k in ("exp_avg", "exp_avg_sq"):
-                state[k] = _rows(state[k], n_new, samps, flags, ranks, totals, zero_children=True)
-            optimizer.state[prm] = state
-        group["params"] = [prm]
+        setattr(self, name, moved.view(torch.int64).reshape((n_new,) + tuple(ids.shape[1:])))
+    for a, gname in zip(layout.attrs, layout.groups):
+        _replace_parameter(self, optimizer, a, gname, new[a], lambda t: _rows(t, n_new, samps, flags, ranks, totals, zero_children=True))
+
+
+def compact_rows(self, optimizer, layout: RowLayout, mask: Tensor) -> int:
+    """Drops the rows whose ``mask`` [N] uint8 entry is set from every array of the class, order kept -> the number of rows left.  One
+    cull-only plan, ONE host read-back (the new size) and, unless nothing is dropped, one ``move_rows``."""
+    n = mask.shape[0]
+    if n == 0:
+        return 0
+    # bds_refine_plan as a bare compaction: nothing densifies and the plan's own cull tests are off, so the mask alone decides.  The
+    # opacity test cannot be switched off, but sigmoid(x) lies in [0, 1] (NaN compares false): no row is below -1, "never"
+    flags, ranks, totals = plan(self._scales, self._opacities, None, None, None, do_densify=False, grad_thresh=0.0, size_thresh=0.0,
+                                split_by_screen=False, split_screen_size=0.0, do_cull=True, cull_alpha_thresh=-1.0, cull_by_scale=False,
+                                cull_scale_thresh=0.0, cull_by_screen=False, cull_screen_size=0.0, extra_cull=mask)
+    n_left = int(totals[2].item())
+    if n_left != n:
+        move_rows(self, optimizer, layout, flags, ranks, totals, 0, n_left)
+    return n_left
+
+
+def reset_opacity(self, optimizer, layout: RowLayout, value: float) -> None:
+    """vanilla.py:286-299 (pvg.py:249-261): opacity = logit(min(sigmoid(opacity), value)), the opacity group's moments back to zero."""
+    prm = self._opacities
+    L.require_gpu(prm)
+    group = _group_of(optimizer, self.class_prefix + layout.groups[layout.attrs.index("_opacities")])
+    state = optimizer.state.get(group["params"][0]) if group is not None else None
+    m, v = (state[k] for k in _MOMENTS) if state else (None, None)
+    L.check(L.lib().bds_opacity_reset(prm.numel(), L.ptr(prm.data), float(value), L.ptr(m), L.ptr(v), L.stream()), "bds_opacity_reset")
 
 
 def spatial_order(means: Tensor, bits: int = 10) -> Tensor:
@@ -133,27 +200,20 @@ def spatial_order(means: Tensor, bits: int = 10) -> Tensor:
 
 
 @torch.no_grad()
-def reorder_rows(self, optimizer, perm: Tensor) -> None:
-    """Row ``i`` of every per-Gaussian array of the class becomes old row ``perm[i]``: the six parameters (new ``nn.Parameter``s in
-    their optimizer groups, as the reference's own densification replaces them: basics.py:162-206), their Adam moments, ``point_ids``
-    of the node classes and the densification statistics -- everything ``refinement_after`` moves.  ``optimizer`` may be None."""
+def reorder_rows(self, optimizer, perm: Tensor, layout: RowLayout = VANILLA_ROWS) -> None:
+    """Row ``i`` of every per-Gaussian array of the class becomes old row ``perm[i]``: the layout's parameters (new ``nn.Parameter``s
+    in their optimizer groups, as the reference's own densification replaces them: basics.py:162-206), their Adam moments, the int64
+    columns (``point_ids`` of the node classes) and the densification statistics -- everything a refinement moves.  ``optimizer`` may
+    be None.  An object that carries parameters of a larger layout than the one given is refused: its rows would be torn apart."""
     N = self._means.shape[0]
     assert perm.shape == (N,) and perm.dtype == torch.int64
-    for a, gname in zip(_ATTRS, _GROUPS):
-        old_p = getattr(self, a)
-        prm = Parameter(old_p.detach().index_select(0, perm))
-        setattr(self, a, prm)
-        group = _group_of(optimizer, self.class_prefix + gname) if optimizer is not None else None
-        if group is None:
-            continue
-        state = optimizer.state.pop(group["params"][0], None)
-        if state:
-            for k in ("exp_avg", "exp_avg_sq"):
-                if torch.is_tensor(state.get(k)) and state[k].shape[:1] == (N,):
-                    state[k] = state[k].index_select(0, perm)
-            optimizer.state[prm] = state
-        group["params"] = [prm]
-    for name in ("point_ids", "xys_grad_norm", "vis_counts", "max_2Dsize"):
+    torn = [a for a in PERIODIC_ROWS.attrs if a not in layout.attrs and isinstance(getattr(self, a, None), Parameter)]
+    if torn:
+        raise ValueError(f"reorder_rows: the layout leaves out {', '.join(torn)} of this class; pass the layout that holds them")
+    move = lambda t: t.index_select(0, perm) if t.shape[:1] == (N,) else t
+    for a, gname in zip(layout.attrs, layout.groups):
+        _replace_parameter(self, optimizer, a, gname, getattr(self, a).detach().index_select(0, perm), move)
+    for name in layout.int64_columns + layout.stats:
         t = getattr(self, name, None)
         if torch.is_tensor(t) and t.shape[:1] == (N,):
             setattr(self, name, t.index_select(0, perm))
@@ -193,10 +253,8 @@ def refinement_after(self, step: int, optimizer: torch.optim.Optimizer, samples:
         return
     if getattr(self, "ball_gaussians", False) or getattr(self, "gaussian_2d", False):
         raise NotImplementedError("ball / 2-D Gaussians are not covered by the fused refinement")
-    reset_interval = ctrl.reset_alpha_interval
-    past = self.step % reset_interval > max(self.num_train_images, ctrl.refine_interval)
-    do_densify = bool(self.step < ctrl.stop_split_at and past)
-    do_cull = bool(past)
+    sch = schedule(self.step, ctrl, self.num_train_images)
+    do_densify, do_cull, by_scale = sch["do_densify"], sch["do_cull"], sch["cull_by_scale"]
     box_cull = bool(do_cull and _ctrl_get(ctrl, "cull_out_of_bound", False))
     if box_cull:
         assert getattr(self, "point_ids", None) is not None and getattr(self, "instances_size", None) is not None, \
@@ -210,13 +268,12 @@ def refinement_after(self, step: int, optimizer: torch.optim.Optimizer, samples:
             L.require_gpu(getattr(self, a))
         N = self._means.shape[0]
         samps = int(ctrl.n_split_samples) if do_densify else 0
-        by_scale = bool(self.step > reset_interval)
         flags, ranks, totals = plan(
             self._scales, self._opacities, self.xys_grad_norm, self.vis_counts, self.max_2Dsize,
             do_densify=do_densify, grad_thresh=ctrl.densify_grad_thresh, size_thresh=ctrl.densify_size_thresh * self.scene_scale,
-            split_by_screen=self.step < ctrl.stop_screen_size_at, split_screen_size=ctrl.split_screen_size, do_cull=do_cull,
+            split_by_screen=sch["by_screen"], split_screen_size=ctrl.split_screen_size, do_cull=do_cull,
             cull_alpha_thresh=ctrl.cull_alpha_thresh, cull_by_scale=by_scale, cull_scale_thresh=ctrl.cull_scale_thresh * self.scene_scale,
-            cull_by_screen=by_scale and self.step < ctrl.stop_screen_size_at, cull_screen_size=ctrl.cull_screen_size)
+            cull_by_screen=by_scale and sch["by_screen"], cull_screen_size=ctrl.cull_screen_size)
         n_split, n_dup, KO, KS, KD = (int(v) for v in totals.tolist())       # the one host sync (the reference: one per mask)
         n_new = KO + samps * KS + KD
         dev = self._means.device
@@ -233,18 +290,10 @@ def refinement_after(self, step: int, optimizer: torch.optim.Optimizer, samples:
             L.check(L.lib().bds_refine_geometry(N, samps, L.ptr(flags), L.ptr(ranks), L.ptr(totals), L.ptr(samples) if do_densify else None,
                                                 L.ptr(means), L.ptr(quats), L.ptr(ls), L.ptr(geometry["_means"]), L.ptr(geometry["_scales"]),
                                                 L.stream()), "bds_refine_geometry")
-        _move_rows(self, optimizer, flags, ranks, totals, samps, n_new, geometry)
+        move_rows(self, optimizer, VANILLA_ROWS, flags, ranks, totals, samps, n_new, geometry)
         n_out = 0
-        if box_cull and n_new:
-            mask = out_of_bound_mask(self._means, self.point_ids, self.instances_size)
-            flags2, ranks2, totals2 = plan(self._scales, self._opacities, None, None, None, do_densify=False, grad_thresh=0.0,
-                                           size_thresh=0.0, split_by_screen=False, split_screen_size=0.0, do_cull=True,
-                                           cull_alpha_thresh=-1.0, cull_by_scale=False, cull_scale_thresh=0.0, cull_by_screen=False,
-                                           cull_screen_size=0.0, extra_cull=mask)
-            kept = int(totals2[2].item())                                    # second (and last) host read-back: the new size
-            n_out = n_new - kept
-            if n_out:
-                _move_rows(self, optimizer, flags2, ranks2, totals2, 0, kept, None)
+        if box_cull and n_new:                                               # second (and last) host read-back: the new size
+            n_out = n_new - compact_rows(self, optimizer, VANILLA_ROWS, out_of_bound_mask(self._means, self.point_ids, self.instances_size))
         if verbose:
             if do_densify:
                 print(f"    Split: {n_split}")
@@ -254,15 +303,7 @@ def refinement_after(self, step: int, optimizer: torch.optim.Optimizer, samples:
             reorder_rows(self, optimizer, spatial_order(self._means))
     if verbose:
         print(f"Class {self.class_prefix} left points: {self._means.shape[0]}")
-    if self.step % reset_interval == ctrl.refine_interval:                    # vanilla.py:286-299
-        prm = self._opacities
-        L.require_gpu(prm)
-        group = _group_of(optimizer, self.class_prefix + "opacity")
-        state = optimizer.state.get(group["params"][0]) if group is not None else None
-        m = state["exp_avg"] if state else None
-        v = state["exp_avg_sq"] if state else None
-        L.check(L.lib().bds_opacity_reset(prm.numel(), L.ptr(prm.data), float(ctrl.reset_alpha_value), L.ptr(m), L.ptr(v), L.stream()),
-                "bds_opacity_reset")
-    self.xys_grad_norm = None
-    self.vis_counts = None
-    self.max_2Dsize = None
+    if sch["do_reset"]:                                                       # vanilla.py:286-299
+        reset_opacity(self, optimizer, VANILLA_ROWS, ctrl.reset_alpha_value)
+    for name in VANILLA_ROWS.stats:
+        setattr(self, name, None)

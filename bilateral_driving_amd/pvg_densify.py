@@ -7,10 +7,11 @@ class's NINE named groups, :135-146) and ``compute_reg_loss`` (:427-436, the ``v
   runs about ten masked-index operations, each with a host wait.
 * ``refinement_after`` plans the densification (``bds_pvg_refine_plan``: the EXISTING flags / ranks / totals layout, no cull), reads
   the counts back once -- the noise tensor's size has to be known -- writes the four arrays a split changes
-  (``bds_pvg_refine_geometry``) and moves the other 23 with ``bds_refine_rows``.  The cull is evaluated on the NEW rows
+  (``bds_pvg_refine_geometry``) and moves the other 23 with ``densify.move_rows``.  The cull is evaluated on the NEW rows
   (``bds_pvg_cull_mask``: every child is judged by gamma of its own mean, so two children of one parent can fare differently) and
-  compacted by a cull-only ``bds_refine_plan`` + ``bds_refine_rows``, with one more read-back.  The two order-preserving compactions
-  leave the reference's rows in the reference's order; on a refinement step every array is therefore written twice.
+  compacted by ``densify.compact_rows`` (``densify`` is the core: this class is ``PERIODIC_ROWS`` plus its three kernels), with one more
+  read-back.  The two order-preserving compactions leave the reference's rows in the reference's order; on a refinement step every
+  array is therefore written twice.
 * ``velocity_reg`` is the bare operator (fixed-order reduction, no float atomics; a zero velocity gets gradient 0, not NaN).
 * ``install(cls)`` / ``uninstall(*classes)`` swap the three methods on the reference's own class, independently of ``pvg.install``;
   both read the ``filter_mask`` either ``get_gaussians`` leaves behind.  CPU tensors keep the class's own methods; the operators
@@ -18,7 +19,8 @@ class's NINE named groups, :135-146) and ``compute_reg_loss`` (:427-436, the ``v
 * ``framework_*``: the reference's sequence as framework ops in the tensors' own dtype and device (tests, and the A side of
   scripts/pvg_refine_time.py).
 
-Not covered: ball / 2-D Gaussians, ``reorder=``, ``dist.refinement_after_synced`` and the lazy one-view path."""
+Not covered: ball / 2-D Gaussians, ``reorder=``, ``dist.refinement_after_synced`` and the lazy one-view path.  ``reorder=`` now needs
+only the wiring: ``densify.reorder_rows(..., PERIODIC_ROWS)`` moves all nine arrays, their moments and the four statistics."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple
@@ -26,25 +28,22 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.nn.functional as F
 from torch import Tensor
-from torch.nn import Parameter
 
 from . import _lib as L
+from . import densify as core
 from ._patch import Seam
-from .densify import _ctrl_get, _group_of, _rows, plan as cull_plan
+from .densify import PERIODIC_ROWS, _ctrl_get
 
-ATTRS = ("_means", "_features_dc", "_features_rest", "_opacities", "_scales", "_quats", "_velocity", "_taus", "_betas")
-GROUPS = ("xyz", "sh_dc", "sh_rest", "opacity", "scaling", "rotation", "velocity", "life_peak", "life_span")      # pvg.py:135-146
-STATS = ("xys_grad_norm", "t_grad_accum", "vis_counts", "max_2Dsize")
+ATTRS, GROUPS, STATS = PERIODIC_ROWS.attrs, PERIODIC_ROWS.groups, PERIODIC_ROWS.stats
 SIZE_FAC = 1.6
 
 
 def schedule(step: int, ctrl, num_train_images: int, num_points: int) -> dict:
-    """The step-dependent switches, exactly as pvg.py:150-159, :179, :242, :249, :274, :281 form them."""
-    reset = ctrl.reset_alpha_interval
-    past = bool(step % reset > max(num_train_images, ctrl.refine_interval))
-    return dict(do_densify=bool(step < ctrl.stop_split_at and past and num_points < ctrl.densify_until_num_points), do_cull=past,
-                by_screen=bool(step < ctrl.stop_screen_size_at), cull_by_scale=bool(step > reset),
-                do_reset=bool(step % reset == ctrl.refine_interval))
+    """The shared switches (``densify.schedule``) with the class's own term: no densification from
+    ``densify_until_num_points`` rows on (pvg.py:158)."""
+    sch = core.schedule(step, ctrl, num_train_images)
+    sch["do_densify"] = bool(sch["do_densify"] and num_points < ctrl.densify_until_num_points)
+    return sch
 
 
 def _mask_u8(mask: Tensor) -> Tensor:
@@ -114,20 +113,16 @@ def refine_plan(xys_grad_norm: Tensor, t_grad_accum: Tensor, vis_counts: Tensor,
     """``bds_pvg_refine_plan``: (flags [N] u8, kinds [N] u8, ranks [N,4] i32, totals [5] i64), the densification decisions without a
     cull.  ``size_thresh``: densify_size_thresh * scene_scale."""
     L.require_gpu(xys_grad_norm, t_grad_accum, vis_counts, max_2Dsize, log_scales, betas, means, scene_origin)
-    N, dev = log_scales.shape[0], log_scales.device
-    flags = torch.empty(N, dtype=torch.uint8, device=dev)
-    kinds = torch.empty(N, dtype=torch.uint8, device=dev)
-    ranks = torch.empty(N, 4, dtype=torch.int32, device=dev)
-    totals = torch.empty(5, dtype=torch.int64, device=dev)
-    nb = int(L.lib().bds_refine_plan_temp_bytes(N))
-    temp = torch.empty(nb, dtype=torch.uint8, device=dev)
+    N = log_scales.shape[0]
+    flags, ranks, totals, temp = core.plan_outputs(N, log_scales.device)
+    kinds = torch.empty_like(flags)
     flat = lambda t: L.f32c(t.detach()).reshape(-1)
     args = [flat(t) for t in (xys_grad_norm, t_grad_accum, vis_counts, max_2Dsize, log_scales, betas, means)]
     assert all(a.numel() == N * w for a, w in zip(args, (1, 1, 1, 1, 3, 1, 3)))
     L.check(L.lib().bds_pvg_refine_plan(N, *[L.ptr(a) for a in args], L.ptr(scene_origin), float(scene_scale), float(grad_thresh),
                                         float(t_grad_thresh), float(size_thresh), float(t_size_thresh), int(split_by_screen),
-                                        float(split_screen_size), L.ptr(flags), L.ptr(kinds), L.ptr(ranks), L.ptr(totals), L.ptr(temp), nb,
-                                        L.stream()), "bds_pvg_refine_plan")
+                                        float(split_screen_size), L.ptr(flags), L.ptr(kinds), L.ptr(ranks), L.ptr(totals), L.ptr(temp),
+                                        temp.numel(), L.stream()), "bds_pvg_refine_plan")
     return flags, kinds, ranks, totals
 
 
@@ -163,27 +158,6 @@ def cull_mask(logits: Tensor, log_scales: Tensor, means: Tensor, max_2Dsize: Opt
                                       float(cull_alpha_thresh), int(cull_by_scale), float(cull_scale_thresh), int(cull_by_screen),
                                       float(cull_screen_size), L.ptr(mask), L.stream()), "bds_pvg_cull_mask")
     return mask
-
-
-def _move_rows(self, optimizer, flags, ranks, totals, samps: int, n_new: int, geometry: Optional[Dict[str, Tensor]]) -> None:
-    """Every per-Gaussian array of the class into the planned layout: the nine parameters (``geometry`` holds the ones already
-    computed) and the Adam moments of their groups; children start from zero moments (basics.py:191-201)."""
-    new: Dict[str, Tensor] = dict(geometry or {})
-    for a in ATTRS:
-        if a not in new:
-            new[a] = _rows(getattr(self, a), n_new, samps, flags, ranks, totals, zero_children=False)
-    for a, gname in zip(ATTRS, GROUPS):
-        prm = Parameter(new[a])
-        setattr(self, a, prm)
-        group = _group_of(optimizer, self.class_prefix + gname)
-        if group is None:
-            continue
-        state = optimizer.state.pop(group["params"][0], None)
-        if state:
-            for k in ("exp_avg", "exp_avg_sq"):
-                state[k] = _rows(state[k], n_new, samps, flags, ranks, totals, zero_children=True)
-            optimizer.state[prm] = state
-        group["params"] = [prm]
 
 
 @torch.no_grad()
@@ -227,7 +201,7 @@ def refinement_after(self, step: int, optimizer: torch.optim.Optimizer, samples:
         if n_new != N:
             geometry = refine_geometry(flags, kinds, ranks, totals, n_new, samps, samples, self._means, self._quats, self._scales,
                                        self._velocity, self._taus, self._betas, float(self.T), bool(_ctrl_get(ctrl, "no_time_split", False)))
-            _move_rows(self, optimizer, flags, ranks, totals, samps, n_new, geometry)
+            core.move_rows(self, optimizer, PERIODIC_ROWS, flags, ranks, totals, samps, n_new, geometry)
     if sch["do_cull"]:
         n_bef = self._means.shape[0]
         n_left = n_bef
@@ -238,27 +212,13 @@ def refinement_after(self, step: int, optimizer: torch.optim.Optimizer, samples:
                              cull_alpha_thresh=ctrl.cull_alpha_thresh, cull_by_scale=sch["cull_by_scale"],
                              cull_scale_thresh=ctrl.cull_scale_thresh * scale, cull_by_screen=by_screen,
                              cull_screen_size=ctrl.cull_screen_size)
-            flags2, ranks2, totals2 = cull_plan(self._scales, self._opacities, None, None, None, do_densify=False, grad_thresh=0.0,
-                                                size_thresh=0.0, split_by_screen=False, split_screen_size=0.0, do_cull=True,
-                                                cull_alpha_thresh=0.0, cull_by_scale=False, cull_scale_thresh=0.0, cull_by_screen=False,
-                                                cull_screen_size=0.0, extra_cull=mask)
-            n_left = int(totals2[2].item())                                   # host read-back 2: the new size
-            if n_left != n_bef:
-                _move_rows(self, optimizer, flags2, ranks2, totals2, 0, n_left, None)
+            n_left = core.compact_rows(self, optimizer, PERIODIC_ROWS, mask)    # host read-back 2: the new size
         print(f"     Cull: {n_bef - n_left}")
     print(f"Class {self.class_prefix} left points: {self._means.shape[0]}")
     if sch["do_reset"]:                                                       # pvg.py:249-261
-        prm = self._opacities
-        group = _group_of(optimizer, self.class_prefix + "opacity")
-        state = optimizer.state.get(group["params"][0]) if group is not None else None
-        m = state["exp_avg"] if state else None
-        v = state["exp_avg_sq"] if state else None
-        L.check(L.lib().bds_opacity_reset(prm.numel(), L.ptr(prm.data), float(ctrl.reset_alpha_value), L.ptr(m), L.ptr(v), L.stream()),
-                "bds_opacity_reset")
-    self.xys_grad_norm = None
-    self.t_grad_accum = None
-    self.vis_counts = None
-    self.max_2Dsize = None
+        core.reset_opacity(self, optimizer, PERIODIC_ROWS, ctrl.reset_alpha_value)
+    for name in STATS:
+        setattr(self, name, None)
 
 
 # ---- velocity_reg ---------------------------------------------------------------------------------------------------------------------

@@ -305,7 +305,7 @@ def test_refinement_with_reorder_leaves_the_same_set_in_spatial_order():
 
 def test_deferred_row_adam_goes_through_a_refinement_bit_equal_to_the_dense_one():
     """optim.DeferredRowAdam keeps the SH rows of unseen Gaussians behind; ``before_refinement()`` brings them up to date, the
-    refinement's optimizer-state surgery (basics.py:162-206 as densify._move_rows does it) moves parameters and moments, the rows'
+    refinement's optimizer-state surgery (basics.py:162-206 as densify.move_rows does it) moves parameters and moments, the rows'
     step words are made again at the new size -- and the run continues.  Same random visibility, same gradients, same refinement:
     the SH parameters and both moments equal the dense FusedAdam's bit for bit before and after the refinement."""
     from bilateral_driving_amd.densify import refinement_after

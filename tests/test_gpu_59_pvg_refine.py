@@ -182,6 +182,75 @@ def test_port_equals_restatement(N, no_time_split, kind, capsys):
             np.testing.assert_allclose(prm.cpu().numpy(), ref, rtol=3e-6, atol=3e-6, err_msg=a)
 
 
+# ---- the core's compaction, with either class's rows ---------------------------------------------------------------------------------
+TRAILING = {"_means": (3,), "_features_dc": (3,), "_features_rest": (8, 3), "_opacities": (1,), "_scales": (3,), "_quats": (4,), "_velocity": (3,),
+            "_taus": (1,), "_betas": (1,)}
+
+
+def byte_mask(kind, N):
+    m = torch.zeros(N, dtype=torch.uint8)
+    if kind == "all":
+        m.fill_(1)
+    elif kind == "last":
+        m[-1] = 1
+    elif kind == "half":
+        m = (torch.rand(N, generator=torch.Generator().manual_seed(7 * N)) < 0.5).to(torch.uint8)
+    return m
+
+
+@pytest.mark.parametrize("kind", ["none", "all", "last", "half"])
+@pytest.mark.parametrize("N", [1, 255, 256, 257, 513])
+@pytest.mark.parametrize("rows", ["periodic", "vanilla_with_point_ids"])
+def test_compact_rows_equals_boolean_mask_indexing(rows, N, kind):
+    """``densify.compact_rows`` (one cull-only plan of 256-wide workgroups, one read-back, one move): every array of the layout, both
+    Adam moments after a real step and ``point_ids`` are bit-equal to indexing with ``~mask``."""
+    from bilateral_driving_amd.densify import PERIODIC_ROWS, VANILLA_ROWS, compact_rows
+    lay = PERIODIC_ROWS if rows == "periodic" else VANILLA_ROWS
+    g = torch.Generator().manual_seed(N)
+    model = types.SimpleNamespace(class_prefix="Background#")
+    groups = []
+    for a, n in zip(lay.attrs, lay.groups):
+        prm = torch.nn.Parameter(torch.randn((N,) + TRAILING[a], generator=g).cuda())
+        setattr(model, a, prm)
+        groups.append({"params": [prm], "lr": 1e-3, "name": model.class_prefix + n})
+    opt = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+    for a in lay.attrs:
+        getattr(model, a).grad = torch.randn((N,) + TRAILING[a], generator=g).cuda()
+    opt.step()
+    if lay.int64_columns:
+        model.point_ids = (torch.arange(N, dtype=torch.int64)[:, None] * 1_000_003 - (1 << 40)).cuda()      # both 32-bit words in use
+    before = {a: getattr(model, a) for a in lay.attrs}
+    old = {a: p.detach().clone() for a, p in before.items()}
+    old_m = {a: opt.state[p]["exp_avg"].clone() for a, p in before.items()}
+    old_v = {a: opt.state[p]["exp_avg_sq"].clone() for a, p in before.items()}
+    assert all(bool(old_m[a].any()) and bool(old_v[a].any()) for a in lay.attrs)
+    old_ids = model.point_ids.clone() if lay.int64_columns else None
+    mask = byte_mask(kind, N).cuda()
+    keep = ~mask.bool()
+    want = int(keep.sum())
+    with poisoned_allocations(True, name=f"compact_rows {rows} N={N} {kind}"):
+        n_left = compact_rows(model, opt, lay, mask)
+        torch.cuda.synchronize()
+    assert n_left == want == getattr(model, lay.attrs[0]).shape[0]
+    for a, n in zip(lay.attrs, lay.groups):
+        prm = getattr(model, a)
+        assert (prm is before[a]) == (want == N), a                          # nothing culled: no parameter is replaced
+        assert isinstance(prm, torch.nn.Parameter) and prm.shape == (want,) + TRAILING[a] and torch.equal(prm.detach(), old[a][keep]), a
+        grp = [gr for gr in opt.param_groups if gr["name"] == model.class_prefix + n][0]
+        assert len(grp["params"]) == 1 and grp["params"][0] is prm
+        st = opt.state[prm]
+        assert st["exp_avg"].shape == prm.shape and st["exp_avg_sq"].shape == prm.shape and float(st["step"]) == 1.0
+        assert torch.equal(st["exp_avg"], old_m[a][keep]) and torch.equal(st["exp_avg_sq"], old_v[a][keep]), a
+    assert len(opt.state) == len(lay.attrs)
+    if lay.int64_columns:
+        assert model.point_ids.dtype == torch.int64 and model.point_ids.shape == (want, 1) and torch.equal(model.point_ids, old_ids[keep])
+    if want:
+        for a in lay.attrs:
+            getattr(model, a).grad = torch.zeros_like(getattr(model, a))
+        opt.step()
+        assert all(float(opt.state[getattr(model, a)]["step"]) == 2.0 for a in lay.attrs)
+
+
 # ---- statistics ----------------------------------------------------------------------------------------------------------------------
 def run_after_train(calls, last_size):
     from bilateral_driving_amd.pvg_densify import after_train

@@ -102,6 +102,42 @@ def test_schedule_regimes():
     assert not RO.schedule(400, ctrl, sc, n)["active"]
 
 
+PVG = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "pvg_refine_step*.npz")))
+
+
+@pytest.mark.parametrize("step", [1300, 3100, 3300, 16300, 20300])
+def test_product_schedule_forms_the_references_switches(step):
+    """``densify.schedule`` and the periodic class's ``pvg_densify.schedule`` against the reference's own expressions, quoted here by
+    line, over the ctrl tables the goldens were recorded with (both classes' shipped values; the periodic ones include a table whose
+    ``densify_until_num_points`` lies below the row count)."""
+    from bilateral_driving_amd import densify, pvg_densify
+
+    class Cfg(dict):
+        __getattr__ = dict.__getitem__
+    tables = [(load(FILES[0])[1], int(load(FILES[0])[0]["num_train_images"]), None)]
+    for f in PVG:
+        z = np.load(f)
+        tables.append(({k[5:]: z[k].item() for k in z.files if k.startswith("ctrl_")}, int(z["num_train_images"]), int(z["N"])))
+    assert len(tables) == 9 and any(c["densify_until_num_points"] < n for c, _, n in tables[1:])
+    seen = set()
+    for ctrl, num_train_images, num_points in tables:
+        c = Cfg(ctrl)
+        reset_interval = c.reset_alpha_interval                                                          # vanilla.py:212, pvg.py:154
+        want = dict(do_densify=step < c.stop_split_at and step % reset_interval > max(num_train_images, c.refine_interval),   # vanilla.py:213-216
+                    by_screen=step < c.stop_screen_size_at,                                              # vanilla.py:229, :318; pvg.py:179, :281
+                    do_cull=step % reset_interval > max(num_train_images, c.refine_interval),            # vanilla.py:280, pvg.py:242
+                    do_reset=step % reset_interval == c.refine_interval,                                 # vanilla.py:287, pvg.py:249
+                    cull_by_scale=step > c.reset_alpha_interval)                                         # vanilla.py:311, pvg.py:274
+        if num_points is None:
+            got = densify.schedule(step, c, num_train_images)
+        else:
+            want["do_densify"] = want["do_densify"] and num_points < c.densify_until_num_points          # pvg.py:155-159
+            got = pvg_densify.schedule(step, c, num_train_images, num_points)
+        assert got == want and all(type(v) is bool for v in got.values()), (step, got, want)
+        seen.add(tuple(sorted(got.items())))
+    assert len(seen) >= (2 if step == 3300 else 1)      # at 3300 the full table switches the densification off
+
+
 def test_product_refinement_has_no_cpu_path():
     """The product (bilateral_driving_amd.densify) must refuse CPU tensors instead of falling back to anything."""
     import types
