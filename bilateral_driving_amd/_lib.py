@@ -149,6 +149,12 @@ _SIGS = {
     "bds_smpl_skin_bwd_temp_bytes": (_sz, [_i, _i]),
     "bds_smpl_skin_fwd": (_i, [_i, _i] + [_f] * 12 + [_i, _i, _i, _f, _f, _fl, _i, _f, _f, _f, _f]),
     "bds_smpl_skin_bwd": (_i, [_i, _i] + [_f] * 11 + [_i, _i, _i, _f, _f, _fl, _i] + [_f] * 9 + [_f, _sz, _f]),
+    "bds_smpl_knn_reg_temp_bytes": (_sz, [_i, _i, _i]),
+    "bds_smpl_knn_reg_fwd": (_i, [_i, _i, _i, _f, _f, _f, _f, _i, _f, _f, _i, _f, _f, _f, _f, _f, _f, _sz, _f]),
+    "bds_smpl_knn_reg_bwd": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _i] + [_f] * 10 + [_f]),
+    "bds_voxel_reg_temp_bytes": (_sz, [_i, _i, _i, _i]),
+    "bds_voxel_reg_fwd": (_i, [_i] * 5 + [_f, _f, _f, _f, _sz, _f]),
+    "bds_voxel_reg_bwd": (_i, [_i] * 5 + [_f, _f, _f, _f, _f]),
     "bds_pvg_temp_bytes": (_sz, [_i64]),
     "bds_pvg_fwd": (_i, [_i64, _i, _i, _fl, _fl, _i, C.c_double] + [_f] * 18 + [_sz, _f]),
     "bds_pvg_bwd": (_i, [_i64, _i64, _i, _i, _fl, _fl, _i, C.c_double] + [_f] * 9 + [_sz] + [_f] * 17),

@@ -1030,6 +1030,48 @@ int bds_smpl_skin_bwd(int I, int V, const float *means, const float *quats, cons
                       const float *v_world_quats, float *v_means, float *v_quats, float *v_root_quats, float *v_body_quats,
                       float *v_trans, float *v_voxel_corr, void *temp, size_t temp_bytes, bds_stream_t stream);
 
+/* ---- The SMPL nodes' every-step regularisers ---------------------------------------------------------------------------------------
+ * knn_reg of SMPLNodes.compute_reg_loss (models/nodes/smpl.py:462-503).  nn_ind [I,V,K] int32: within-instance indices in [0,V) (the
+ * query itself and repeats allowed; the caller validates them -- an index outside the range reads row 0), 2 <= K <= 32; present [I]
+ * (one byte each: instances_fv[cur_frame]).  Five attribute groups, each pointer may be NULL (a frozen group: term 0, no gradient):
+ * features_dc [I V,3], features_rest [I V,c_rest] (c_rest 9, 24 or 45), opacities [I V,1] (raw; sigmoid inside), scales [I V,s_dim]
+ * (raw; exp inside; s_dim 1 or 3), quats [I V,4] (raw).
+ *   terms[g] = mean over (present instance, point, channel of g) of the unbiased std over the K gathered values of that channel
+ * (:472, :480, :487, :495, :502; two passes: the mean as v_0 + sum(v_k - v_0) / K, then the squared deviations), in the order dc,
+ * rest, opacity, scales, quats; 0 with no instance present.  One launch over (row, channel) of the live groups (mean and
+ * rstd = 1 / ((K-1) std), 0 where std == 0, stored per (row, channel) of the `channels` live ones: [I V, channels] each, kept for
+ * the backward) and a one-workgroup finish that sums the workgroups' rows of temp (bds_smpl_knn_reg_temp_bytes bytes) in a fixed
+ * order and leaves norm[5] = 1 / (present V C_g), formed on the device.
+ * bwd: ONE launch in gather form.  rev_offsets [I,V+1] / rev_edges [I,V K] (int32): the (point K + slot) pairs that list each row,
+ * ascending; row r of group g receives v_terms[g] norm[g] sum_edges (a_r - mean_p) rstd_p, times the activation's derivative
+ * (gradients to the RAW parameters), summed in list order: no atomics, bit-identical run to run.  Rows of absent instances and rows
+ * nobody lists are written zeros.  v_<group> NULL exactly where <group> is. */
+size_t bds_smpl_knn_reg_temp_bytes(int I, int V, int channels);
+int bds_smpl_knn_reg_fwd(int I, int V, int K, const int32_t *nn_ind, const uint8_t *present, const float *features_dc,
+                         const float *features_rest, int c_rest, const float *opacities, const float *scales, int s_dim,
+                         const float *quats, float *terms, float *norm, float *mean, float *rstd, void *temp, size_t temp_bytes,
+                         bds_stream_t stream);
+int bds_smpl_knn_reg_bwd(int I, int V, int K, const int32_t *rev_offsets, const int32_t *rev_edges, const uint8_t *present,
+                         const float *features_dc, const float *features_rest, int c_rest, const float *opacities, const float *scales,
+                         int s_dim, const float *quats, const float *mean, const float *rstd, const float *norm, const float *v_terms,
+                         float *v_features_dc, float *v_features_rest, float *v_opacities, float *v_scales, float *v_quats,
+                         bds_stream_t stream);
+
+/* voxel_deformer_reg of SMPLNodes.compute_reg_loss (models/nodes/smpl.py:448-459): VoxelDeformer.get_tv and get_mag
+ * (models/modules.py:1139-1166) of one field [I,J,D,H,W], 1 <= J <= 64, D, H, W >= 2 (else BDS_EINVAL: the reference's mean over an
+ * empty slice is NaN).
+ *   terms[0] = (mean|x[d+1] - x| + mean|x[h+1] - x| + mean|x[w+1] - x|) / 3, each mean over its own count (:1148-1151)
+ *   terms[1] = mean over [I,D,H,W] of the 2-norm over J (:1166)
+ * One pass, a thread per voxel walking J; rnorm [I,D,H,W] = 1 / norm (0 for the zero vector) is kept for the backward; the
+ * workgroups' rows of temp (bds_voxel_reg_temp_bytes bytes) are summed in a fixed order by a one-workgroup finish.
+ * bwd: one pass in gather form, v_field[e] = v_terms[0] / 3 (the signs of e's up to six differences over their counts; sign(0) = 0)
+ * + v_terms[1] x rnorm / (I D H W): every element written, no atomics, bit-identical run to run. */
+size_t bds_voxel_reg_temp_bytes(int I, int D, int H, int W);
+int bds_voxel_reg_fwd(int I, int J, int D, int H, int W, const float *field, float *terms, float *rnorm, void *temp, size_t temp_bytes,
+                      bds_stream_t stream);
+int bds_voxel_reg_bwd(int I, int J, int D, int H, int W, const float *field, const float *rnorm, const float *v_terms, float *v_field,
+                      bds_stream_t stream);
+
 /* Time transform of the periodic-vibration Gaussians: PeriodicVibrationGaussians.get_gaussians (models/gaussians/pvg.py:374-425) with
  * get_marginal_t (:81), temporal_means (:65-73), temporal_opacities (:75-78) and velocity / rho (:83-88), as three forward launches and
  * one backward launch.  Raw parameters, contiguous float32: means [N,3], velocity [N,3], taus [N], betas [N], logits [N] (the [N,1]
