@@ -92,7 +92,9 @@ _SIGS = {
     "bds_scene_pack": (_i, [_i64, _f, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i64, _f, _f]),
     "bds_scene_sh_bwd": (_i, [_i64, _f, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_project_view_bwd_list": (_i, [_i, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "bds_project_view_bwd_list_touched": (_i, [_i, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _fl, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_view_grads_clear_list": (_i, [_i64, _f, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "bds_view_grads_clear_list_touched": (_i, [_i64, _f, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_view_grads_add_list": (_i, [_i64, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
     "bds_isect_counts_offset": (_sz, [_i]),
     "bds_rasterize_schedule_ints": (_i64, [_i, _i, _i]),
@@ -242,6 +244,8 @@ def lib():
 
 SPLAT_RECORD_FLOATS, GRAD_RECORD_FLOATS, POSE_GRAD_SLOTS = 12, 16, 64
 PROJ_ACCUMULATE, PROJ_ACTIVATED, PROJ_ANTIALIASED = 1, 2, 4      # include/bds.h bds_project_view_fwd / _bwd_list flags
+PROJ_SKIP_UNTOUCHED = 8                                          # bds_project_view_bwd_list_touched only
+SH_ACCUMULATE, SH_SKIP_UNTOUCHED = 1, 2                          # bds_sh_view_bwd_list `accumulate`
 OPT_DEBUG = 3          # profiling only: ablation mask
 OPT_SCHED_BINS = 8     # device-count compositor: 1 [default] = the forward's waves bin the backward's schedule, 0 = a sort launch (include/bds.h)
 OPT_CELLS = 7          # bilateral transform, bit mask [default 3]: 1 = cell-aligned kernels, 2 = one-pass pyramid forward, 0 = general kernels (include/bds.h)

@@ -267,7 +267,7 @@ __global__ __launch_bounds__(kProjBlock) void project_view_bwd_list_kernel(
     const float *__restrict__ K, int W, int H, float eps2d, const float4 *__restrict__ v_rec, float *__restrict__ v_means,
     float *__restrict__ v_quats, float *__restrict__ v_log_scales, float *__restrict__ v_logits, float *__restrict__ v_viewmat_slots,
     float *__restrict__ grad2d, float *__restrict__ absgrad2d, const int32_t *__restrict__ row_map, float *__restrict__ v_colors = nullptr,
-    const GradLayout gl = GradLayout{3, 4, 3, 1}) {
+    const GradLayout gl = GradLayout{3, 4, 3, 1}, int skip = 0, uint8_t *__restrict__ touched = nullptr) {
   __shared__ float red[kProjBlock / kWave][12];
   const int64_t n_list = list_length(n_cap, n_dev);
   if ((int64_t)blockIdx.x * kProjBlock >= n_list) return;   // (whole workgroup: nothing to add to the pose slots either)
@@ -275,9 +275,25 @@ __global__ __launch_bounds__(kProjBlock) void project_view_bwd_list_kernel(
   ProjGrad pg;
   for (int i = 0; i < 9; i++) pg.v_R[i] = 0.f;
   for (int i = 0; i < 3; i++) pg.v_t[i] = 0.f;
+  // A rank whose record floats 0-11 are all +-0 belongs to a Gaussian no pixel blended (~87 % of a view's list at 2 M Gaussians).  Its
+  // VJP is a sum of products with those zeros: every gradient it yields is +-0.  `touched` [n_list] (nullable) receives 1 / 0 per rank:
+  // "the record was non-zero"; with `skip` (BDS_PROJ_SKIP_UNTOUCHED) such a rank issues none of its gathers, runs no VJP, stores
+  // nothing and adds zeros to the pose reduce (whose t != 0 test drops an all-zero workgroup's atomics).  Adding +-0 is a no-op, so
+  // an accumulated row differs from the dense form at most in the sign of a zero; a STORED row is left as it was -- the caller
+  // guarantees it is zero (bds.h).  With non-finite parameters the dense form leaves 0 x Inf = NaN in such a row, this one zero (the
+  // reference rejects such parameters upstream, vanilla.py:407-412).
+  bool live = false;
+  float4 r0, r1, r2;
+  int64_t g = 0;
   if (r < n_list) {
-    const int64_t g = ids[r];
-    const float4 r0 = v_rec[r * 4], r1 = v_rec[r * 4 + 1], r2 = v_rec[r * 4 + 2];
+    g = ids[r];
+    r0 = v_rec[r * 4]; r1 = v_rec[r * 4 + 1]; r2 = v_rec[r * 4 + 2];
+    const bool nz = r0.x != 0.f || r0.y != 0.f || r0.z != 0.f || r0.w != 0.f || r1.x != 0.f || r1.y != 0.f || r1.z != 0.f || r1.w != 0.f ||
+                    r2.x != 0.f || r2.y != 0.f || r2.z != 0.f || r2.w != 0.f;
+    if (touched) touched[r] = nz ? 1 : 0;
+    live = nz || !skip;
+  }
+  if (live) {
     // every gather that depends on g is issued here, in front of the arithmetic -- including, in accumulate mode, the eleven old
     // gradient values: read next to the stores that update them, each would wait out a full memory latency behind the previous
     // store (the compiler may not move a load of an array above a store to it)
@@ -574,15 +590,18 @@ extern "C" int bds_gaussian_block_bounds(int64_t N, const float *means, const fl
 }
 
 // The list-driven one-view backward (include/bds.h): BDS_PROJ_ACCUMULATE selects kAcc, BDS_PROJ_ACTIVATED !kRaw, BDS_PROJ_ANTIALIASED
-// kAA, v_viewmat_slots kPose; n_dev (nullable) the device-count form.
-extern "C" int bds_project_view_bwd_list(int flags, int64_t n_list, const uint64_t *n_dev, const int32_t *ids, const float *means,
-                                         const float *quats, const float *scales, const float *opacities, const float *viewmat,
-                                         const float *K, int W, int H, float eps2d, const float *v_records, float *v_means, float *v_quats,
-                                         float *v_scales, float *v_opacities, float *v_colors, float *v_viewmat_slots, float *grad2d,
-                                         float *absgrad2d, const int32_t *row_map, bds_stream_t stream) {
+// kAA, v_viewmat_slots kPose; n_dev (nullable) the device-count form.  BDS_PROJ_SKIP_UNTOUCHED and `touched` are runtime arguments of
+// the same kernels (project_view_bwd_list_kernel).
+extern "C" int bds_project_view_bwd_list_touched(int flags, int64_t n_list, const uint64_t *n_dev, const int32_t *ids, const float *means,
+                                                 const float *quats, const float *scales, const float *opacities, const float *viewmat,
+                                                 const float *K, int W, int H, float eps2d, const float *v_records, float *v_means,
+                                                 float *v_quats, float *v_scales, float *v_opacities, float *v_colors,
+                                                 float *v_viewmat_slots, float *grad2d, float *absgrad2d, const int32_t *row_map,
+                                                 uint8_t *touched, bds_stream_t stream) {
   BDS_REQUIRE(n_list >= 0 && W > 0 && H > 0);
-  BDS_REQUIRE((flags & ~(BDS_PROJ_ACCUMULATE | BDS_PROJ_ACTIVATED | BDS_PROJ_ANTIALIASED)) == 0);
+  BDS_REQUIRE((flags & ~(BDS_PROJ_ACCUMULATE | BDS_PROJ_ACTIVATED | BDS_PROJ_ANTIALIASED | BDS_PROJ_SKIP_UNTOUCHED)) == 0);
   const bool acc = flags & BDS_PROJ_ACCUMULATE, activated = flags & BDS_PROJ_ACTIVATED, aa = flags & BDS_PROJ_ANTIALIASED;
+  const int skip = (flags & BDS_PROJ_SKIP_UNTOUCHED) ? 1 : 0;
   BDS_REQUIRE(!activated || (!acc && row_map == nullptr));
   // (v_viewmat_slots is ADDED to: the caller zero-fills it -- a memset node of 4 KB between two kernels costs ~15 us of idle GPU)
   if (n_list == 0) return BDS_OK;
@@ -596,7 +615,7 @@ extern "C" int bds_project_view_bwd_list(int flags, int64_t n_list, const uint64
 #define BDS_LIST(A, P, R, AA)                                                                                                         \
   hipLaunchKernelGGL((project_view_bwd_list_kernel<A, P, R, AA>), grid, block, 0, as_stream(stream), n_list, n_dev, ids, means, quats, \
                      scales, opacities, viewmat, K, W, H, eps2d, v4, v_means, v_quats, v_scales, v_opacities, v_viewmat_slots, grad2d, \
-                     absgrad2d, row_map, v_colors, gl)
+                     absgrad2d, row_map, v_colors, gl, skip, touched)
 #define BDS_LIST_P(A, R, AA) do { if (v_viewmat_slots) BDS_LIST(A, true, R, AA); else BDS_LIST(A, false, R, AA); } while (0)
 #define BDS_LIST_AA(A, R) do { if (aa) BDS_LIST_P(A, R, true); else BDS_LIST_P(A, R, false); } while (0)
   if (activated) BDS_LIST_AA(false, false);
@@ -607,6 +626,17 @@ extern "C" int bds_project_view_bwd_list(int flags, int64_t n_list, const uint64
 #undef BDS_LIST
   BDS_LAUNCH_CHECK();
   return BDS_OK;
+}
+
+extern "C" int bds_project_view_bwd_list(int flags, int64_t n_list, const uint64_t *n_dev, const int32_t *ids, const float *means,
+                                         const float *quats, const float *scales, const float *opacities, const float *viewmat,
+                                         const float *K, int W, int H, float eps2d, const float *v_records, float *v_means, float *v_quats,
+                                         float *v_scales, float *v_opacities, float *v_colors, float *v_viewmat_slots, float *grad2d,
+                                         float *absgrad2d, const int32_t *row_map, bds_stream_t stream) {
+  BDS_REQUIRE((flags & BDS_PROJ_SKIP_UNTOUCHED) == 0);   // (the dense entry: every listed row is written)
+  return bds_project_view_bwd_list_touched(flags, n_list, n_dev, ids, means, quats, scales, opacities, viewmat, K, W, H, eps2d, v_records,
+                                           v_means, v_quats, v_scales, v_opacities, v_colors, v_viewmat_slots, grad2d, absgrad2d, row_map,
+                                           nullptr, stream);
 }
 
 // Bit t of *flags_dev is set when tensors[t] (counts[t] floats) holds a NaN or an Inf (vanilla.py:407-412); the word is cleared first.

@@ -246,6 +246,12 @@ __global__ __launch_bounds__(kShBlock, 8) void sh_view_fwd_kernel(int64_t n, int
 // and writes each as whole 16-byte pieces, 12 lanes per 192-byte row.  kAcc = false stores the rows (every other row of v_coeffs is
 // the caller's business: zero-filled, or kept zero by bds_view_grads_clear_list), kAcc = true adds to them (several views summed
 // into one buffer before one exchange).
+// skip != 0 (BDS_SH_SKIP_UNTOUCHED): a row whose three colour-gradient floats are all +-0 behind the clamp mask -- a Gaussian no pixel
+// blended; ~87 % of a view's list at 2 M Gaussians, and with the rows in spatial order 3 of 4 workgroups hold nothing else -- is
+// neither read nor written, and a workgroup with no live row returns before it gathers, stages or writes anything.  Adding +-0 is a no-op, so in accumulate mode the row differs from
+// the dense form at most in the sign of a zero; in store mode the caller guarantees that the destination rows ARE zero (fresh zero
+// tensors, an arena kept zero row-wise).  With non-finite means the dense form leaves 0 x Inf = NaN in such a row, this one zero (the
+// reference rejects such parameters upstream, vanilla.py:407-412).
 template <int DEG, bool kVec, bool kAcc>
 __global__ __launch_bounds__(kShBlock) void sh_view_bwd_list_kernel(int64_t n_cap, const uint64_t *__restrict__ n_dev,
                                                                    const int32_t *__restrict__ ids, int K,
@@ -254,9 +260,9 @@ __global__ __launch_bounds__(kShBlock) void sh_view_bwd_list_kernel(int64_t n_ca
                                                                    const float *__restrict__ sh_rgb,
                                                                    const float4 *__restrict__ v_rec, float *__restrict__ v_coeffs,
                                                                    const int32_t *__restrict__ row_map, int sh_rgb_by_rank,
-                                                                   float *__restrict__ v_rest) {
+                                                                   float *__restrict__ v_rest, int skip) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  __shared__ int32_t s_g[kShBlock];   // destination row of each staged entry
+  __shared__ int32_t s_g[kShBlock];   // destination row of each staged entry (-1: a skipped row)
   constexpr int nb = (DEG + 1) * (DEG + 1);
   const int row = K * 3;
   const int ldr = row + 1;
@@ -265,26 +271,39 @@ __global__ __launch_bounds__(kShBlock) void sh_view_bwd_list_kernel(int64_t n_ca
   if (r0 >= n_list) return;
   const int cnt = (int)min((int64_t)kShBlock, n_list - r0);
   const int tid = threadIdx.x;
+  int64_t g = -1;
+  float vo[3] = {0.f, 0.f, 0.f}, m[3] = {0.f, 0.f, 0.f};
+  bool live = false;
   if (tid < cnt) {
-    const int64_t g = ids[r0 + tid];
-    s_g[tid] = row_map ? row_map[g] : (int32_t)g;
+    g = ids[r0 + tid];
     const float4 v = v_rec[(r0 + tid) * (BDS_GRAD_RECORD_FLOATS / 4)];
-    float vo[3] = {v.x, v.y, v.z};
+    vo[0] = v.x; vo[1] = v.y; vo[2] = v.z;
+    live = !skip || vo[0] != 0.f || vo[1] != 0.f || vo[2] != 0.f;
+    if (live) {   // (both gathers of a row in flight together, in front of the vote)
+      m[0] = means[g * 3]; m[1] = means[g * 3 + 1]; m[2] = means[g * 3 + 2];
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-      const float x = sh_rgb[(sh_rgb_by_rank ? r0 + tid : g) * 3 + k] + 0.5f;   // [N,3] by Gaussian, or [n_list,3] in list order
-      if (!(x >= 0.f && x <= 1.f)) vo[k] = 0.f;   // torch.clamp passes the gradient on the closed interval
+      for (int k = 0; k < 3; k++) {
+        const float x = sh_rgb[(sh_rgb_by_rank ? r0 + tid : g) * 3 + k] + 0.5f;   // [N,3] by Gaussian, or [n_list,3] in list order
+        if (!(x >= 0.f && x <= 1.f)) vo[k] = 0.f;   // torch.clamp passes the gradient on the closed interval
+      }
+      live = !skip || vo[0] != 0.f || vo[1] != 0.f || vo[2] != 0.f;
     }
-    const float x = means[g * 3] - cam_pos[0], y = means[g * 3 + 1] - cam_pos[1], z = means[g * 3 + 2] - cam_pos[2];
-    const float inorm = 1.0f / sqrtf(x * x + y * y + z * z);
-    float B[16];
-    sh_bases(DEG, x * inorm, y * inorm, z * inorm, B);
-    float *c = lds + tid * ldr;
+  }
+  if (skip && !__syncthreads_or(live)) return;   // (the vote is the only barrier an untouched workgroup meets)
+  if (tid < cnt) {
+    s_g[tid] = !live ? -1 : row_map ? row_map[g] : (int32_t)g;
+    if (live) {
+      const float x = m[0] - cam_pos[0], y = m[1] - cam_pos[1], z = m[2] - cam_pos[2];
+      const float inorm = 1.0f / sqrtf(x * x + y * y + z * z);
+      float B[16];
+      sh_bases(DEG, x * inorm, y * inorm, z * inorm, B);
+      float *c = lds + tid * ldr;
 #pragma unroll
-    for (int k = 0; k < 16; k++) {
-      if (k < K) {
-        const float b = k < nb ? B[k < nb ? k : 0] : 0.f;
-        c[k * 3] = b * vo[0]; c[k * 3 + 1] = b * vo[1]; c[k * 3 + 2] = b * vo[2];
+      for (int k = 0; k < 16; k++) {
+        if (k < K) {
+          const float b = k < nb ? B[k < nb ? k : 0] : 0.f;
+          c[k * 3] = b * vo[0]; c[k * 3 + 1] = b * vo[1]; c[k * 3 + 2] = b * vo[2];
+        }
       }
     }
   }
@@ -303,9 +322,11 @@ __global__ __launch_bounds__(kShBlock) void sh_view_bwd_list_kernel(int64_t n_ca
         dst[u] = nullptr;
         if (e < total) {
           const int r = e / q4, cc = (e - r * q4) * 4;
-          const float *sp = lds + r * ldr + cc;
-          dst[u] = reinterpret_cast<float4 *>(v_coeffs + (int64_t)s_g[r] * row + cc);
-          o[u] = make_float4(sp[0], sp[1], sp[2], sp[3]);
+          if (s_g[r] >= 0) {
+            const float *sp = lds + r * ldr + cc;
+            dst[u] = reinterpret_cast<float4 *>(v_coeffs + (int64_t)s_g[r] * row + cc);
+            o[u] = make_float4(sp[0], sp[1], sp[2], sp[3]);
+          }
         }
       }
       if (kAcc) {
@@ -328,6 +349,7 @@ __global__ __launch_bounds__(kShBlock) void sh_view_bwd_list_kernel(int64_t n_ca
       const int r = e / q4, c = e - r * q4;
       const float *sp = lds + r * ldr + c * 4;
       const int64_t g = s_g[r];
+      if (g < 0) continue;
       float *rest = v_rest + g * (row - 3);
       if (c == 0) {
         float *dc = v_coeffs + g * 3;
@@ -344,6 +366,7 @@ __global__ __launch_bounds__(kShBlock) void sh_view_bwd_list_kernel(int64_t n_ca
   } else {
     for (int e = tid; e < cnt * row; e += kShBlock) {
       const int r = e / row, cc = e - r * row;
+      if (s_g[r] < 0) continue;
       // split storage (v_rest != null): band 0 -> v_coeffs [N,3], bands 1.. -> v_rest [N,K-1,3]
       float *dst = v_rest == nullptr ? v_coeffs + (int64_t)s_g[r] * row + cc
                    : (cc < 3 ? v_coeffs + (int64_t)s_g[r] * 3 + cc : v_rest + (int64_t)s_g[r] * (row - 3) + (cc - 3));
@@ -353,14 +376,19 @@ __global__ __launch_bounds__(kShBlock) void sh_view_bwd_list_kernel(int64_t n_ca
 }
 
 // zero the rows ids[0..n_list) of the five per-Gaussian gradient arrays (row-wise clear of a persistent buffer: the rows a
-// previous view wrote); v_sh rows leave as whole 16-byte pieces, 12 lanes per 192-byte row
+// previous view wrote); v_sh rows leave as whole 16-byte pieces, 12 lanes per 192-byte row.
+// touched (nullable, [n_list] bytes by rank: what the skipping projection backward of the same list left): only ranks with a non-zero
+// byte are cleared.  The invariant this keeps -- every gradient row is zero behind the begin stage: a row is written only where its
+// gradient record was non-zero (the SH rows: where the colour part of it was), the mask says 1 exactly there, and exactly those ranks
+// are cleared in front of the next frame.
 template <bool kVec>
 __global__ __launch_bounds__(kShBlock) void view_grads_clear_list_kernel(int64_t n_cap, const uint64_t *__restrict__ n_dev,
                                                                         const int32_t *__restrict__ ids, int K,
                                                                         float *__restrict__ v_means, float *__restrict__ v_quats,
                                                                         float *__restrict__ v_log_scales, float *__restrict__ v_logits,
                                                                         float *__restrict__ v_sh, float2 *__restrict__ grad2d,
-                                                                        float2 *__restrict__ absgrad2d, const GradLayout gl) {
+                                                                        float2 *__restrict__ absgrad2d, const GradLayout gl,
+                                                                        const uint8_t *__restrict__ touched) {
   __shared__ int32_t s_g[kShBlock];
   const int64_t n_list = list_length(n_cap, n_dev);
   const int64_t r0 = (int64_t)blockIdx.x * kShBlock;
@@ -368,7 +396,7 @@ __global__ __launch_bounds__(kShBlock) void view_grads_clear_list_kernel(int64_t
   const int cnt = (int)min((int64_t)kShBlock, n_list - r0);
   const int tid = threadIdx.x;
   if (tid < cnt) {
-    const int64_t g = ids[r0 + tid];
+    const int64_t g = (touched && !touched[r0 + tid]) ? -1 : (int64_t)ids[r0 + tid];   // (an untouched rank: treated as padding)
     s_g[tid] = (int32_t)g;
     if (g >= 0) {   // negative ids: padding of a fixed-capacity list
       if (v_means) {   // (null: only the screen-space arrays -- the parameter gradients are cleared by their consumer, bds_adam_step with `consume`)
@@ -562,20 +590,24 @@ template <int DEG>
 static void launch_view_bwd_list(bool vec, bool acc, int grid, size_t lds, hipStream_t st, int64_t n_list, const uint64_t *n_dev,
                                  const int32_t *ids, int K,
                                  const float *means, const float *cam_pos, const float *sh_rgb, const float4 *v_rec, float *v_coeffs,
-                                 const int32_t *row_map, int by_rank, float *v_rest) {
+                                 const int32_t *row_map, int by_rank, float *v_rest, int skip) {
 #define BDS_LIST(V, A)                                                                                                           \
   hipLaunchKernelGGL((sh_view_bwd_list_kernel<DEG, V, A>), dim3(grid), dim3(kShBlock), lds, st, n_list, n_dev, ids, K, means, cam_pos, \
-                     sh_rgb, v_rec, v_coeffs, row_map, by_rank, v_rest)
+                     sh_rgb, v_rec, v_coeffs, row_map, by_rank, v_rest, skip)
   if (vec) { if (acc) BDS_LIST(true, true); else BDS_LIST(true, false); }
   else     { if (acc) BDS_LIST(false, true); else BDS_LIST(false, false); }
 #undef BDS_LIST
 }
 
 // v_coeffs_rest != NULL: the split storage (v_coeffs = band 0 [N,3], v_coeffs_rest = bands 1.. [N,K-1,3]; ignored for K = 1)
+// accumulate: BDS_SH_ACCUMULATE | BDS_SH_SKIP_UNTOUCHED (include/bds.h)
 extern "C" int bds_sh_view_bwd_list(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, int K, int deg, const float *means,
                                     const float *cam_pos, const float *sh_rgb, int sh_rgb_by_rank, const float *v_records, float *v_coeffs,
                                     float *v_coeffs_rest, const int32_t *row_map, int accumulate, bds_stream_t stream) {
   BDS_REQUIRE(n_list >= 0 && deg >= 0 && deg <= 3 && K >= (deg + 1) * (deg + 1) && K <= 16);
+  BDS_REQUIRE((accumulate & ~(BDS_SH_ACCUMULATE | BDS_SH_SKIP_UNTOUCHED)) == 0);
+  const bool acc = accumulate & BDS_SH_ACCUMULATE;
+  const int skip = (accumulate & BDS_SH_SKIP_UNTOUCHED) ? 1 : 0;
   BDS_REQUIRE(!(v_coeffs_rest && row_map));   // (the split storage holds dense parameter gradients: no exchange-buffer rows)
   if (n_list == 0) return BDS_OK;
   BDS_REQUIRE(ids && means && cam_pos && sh_rgb && v_records && v_coeffs && aligned16(v_records));
@@ -586,18 +618,18 @@ extern "C" int bds_sh_view_bwd_list(int64_t n_list, const uint64_t *n_dev, const
   hipStream_t st = as_stream(stream);
   const float4 *v4 = reinterpret_cast<const float4 *>(v_records);
   switch (deg) {
-    case 0: launch_view_bwd_list<0>(vec, accumulate != 0, grid, lds, st, n_list, n_dev, ids, K, means, cam_pos, sh_rgb, v4, v_coeffs, row_map, sh_rgb_by_rank, v_rest); break;
-    case 1: launch_view_bwd_list<1>(vec, accumulate != 0, grid, lds, st, n_list, n_dev, ids, K, means, cam_pos, sh_rgb, v4, v_coeffs, row_map, sh_rgb_by_rank, v_rest); break;
-    case 2: launch_view_bwd_list<2>(vec, accumulate != 0, grid, lds, st, n_list, n_dev, ids, K, means, cam_pos, sh_rgb, v4, v_coeffs, row_map, sh_rgb_by_rank, v_rest); break;
-    default: launch_view_bwd_list<3>(vec, accumulate != 0, grid, lds, st, n_list, n_dev, ids, K, means, cam_pos, sh_rgb, v4, v_coeffs, row_map, sh_rgb_by_rank, v_rest); break;
+    case 0: launch_view_bwd_list<0>(vec, acc, grid, lds, st, n_list, n_dev, ids, K, means, cam_pos, sh_rgb, v4, v_coeffs, row_map, sh_rgb_by_rank, v_rest, skip); break;
+    case 1: launch_view_bwd_list<1>(vec, acc, grid, lds, st, n_list, n_dev, ids, K, means, cam_pos, sh_rgb, v4, v_coeffs, row_map, sh_rgb_by_rank, v_rest, skip); break;
+    case 2: launch_view_bwd_list<2>(vec, acc, grid, lds, st, n_list, n_dev, ids, K, means, cam_pos, sh_rgb, v4, v_coeffs, row_map, sh_rgb_by_rank, v_rest, skip); break;
+    default: launch_view_bwd_list<3>(vec, acc, grid, lds, st, n_list, n_dev, ids, K, means, cam_pos, sh_rgb, v4, v_coeffs, row_map, sh_rgb_by_rank, v_rest, skip); break;
   }
   BDS_LAUNCH_CHECK();
   return BDS_OK;
 }
 
-extern "C" int bds_view_grads_clear_list(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, int K, float *v_means, float *v_quats,
-                                         float *v_log_scales, float *v_logits, float *v_sh, float *grad2d, float *absgrad2d,
-                                         bds_stream_t stream) {
+extern "C" int bds_view_grads_clear_list_touched(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, int K, float *v_means,
+                                                 float *v_quats, float *v_log_scales, float *v_logits, float *v_sh, float *grad2d,
+                                                 float *absgrad2d, const uint8_t *touched, bds_stream_t stream) {
   BDS_REQUIRE(n_list >= 0 && K >= 1 && K <= 16);
   if (n_list == 0) return BDS_OK;
   const bool params = v_means || v_quats || v_log_scales || v_logits || v_sh;    // all five, or none (then the screen-space arrays only)
@@ -609,12 +641,19 @@ extern "C" int bds_view_grads_clear_list(int64_t n_list, const uint64_t *n_dev, 
   BDS_REQUIRE(gl.sm != 16 || aligned16(v_means));
   if (((K * 3) % 4 == 0) && aligned16(v_sh))
     hipLaunchKernelGGL((view_grads_clear_list_kernel<true>), grid, block, 0, as_stream(stream), n_list, n_dev, ids, K, v_means, v_quats,
-                       v_log_scales, v_logits, v_sh, g2, a2, gl);
+                       v_log_scales, v_logits, v_sh, g2, a2, gl, touched);
   else
     hipLaunchKernelGGL((view_grads_clear_list_kernel<false>), grid, block, 0, as_stream(stream), n_list, n_dev, ids, K, v_means, v_quats,
-                       v_log_scales, v_logits, v_sh, g2, a2, gl);
+                       v_log_scales, v_logits, v_sh, g2, a2, gl, touched);
   BDS_LAUNCH_CHECK();
   return BDS_OK;
+}
+
+extern "C" int bds_view_grads_clear_list(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, int K, float *v_means, float *v_quats,
+                                         float *v_log_scales, float *v_logits, float *v_sh, float *grad2d, float *absgrad2d,
+                                         bds_stream_t stream) {
+  return bds_view_grads_clear_list_touched(n_list, n_dev, ids, K, v_means, v_quats, v_log_scales, v_logits, v_sh, grad2d, absgrad2d, nullptr,
+                                           stream);
 }
 
 extern "C" int bds_view_grads_add_list(int64_t n_list, const int32_t *ids, int K, const float *s_means, const float *s_quats,

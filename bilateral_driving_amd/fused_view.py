@@ -536,17 +536,26 @@ def _composite_backward(cfg: dict, saved, vis_ids: Tensor, M: int, list_tile: in
 
 
 def _project_backward(cfg: dict, flags: int, nvis_dev, vis_ids: Tensor, inputs, v_rec: Tensor, outs, g2d: Tensor, ag2d: Optional[Tensor],
-                      v_colors=None, slots=None, row_map=None, grad_always: bool = False) -> None:
+                      v_colors=None, slots=None, row_map=None, grad_always: bool = False, touched: Optional[Tensor] = None) -> None:
     """Gradient records -> parameter gradients, list-driven over the visible Gaussians.  ``inputs``: the saved (means, quats, scales,
     opacities, viewmat, K); ``outs``: their four gradients, dense arrays or columns of the gradients' [N,16] row block; ``g2d`` /
     ``ag2d`` [N,2]: the dense screen-space gradient and its absolute sum (None: not wanted); ``v_colors``: the colour gradient of the
     ACTIVATED form; ``slots``: camera-pose gradient slots; ``row_map``: a gradient sink's row table.  The tensor the caller holds as
     means2d (cfg["_means2d_ref"]; trainers/base.py:280-297 read .absgrad / .grad) then gets ``.absgrad`` where there is one, and
-    ``.grad`` when it retains it -- with ``grad_always``, in any case."""
+    ``.grad`` when it retains it -- with ``grad_always``, in any case.  ``touched`` [>= n list entries] u8: the skipping form
+    (include/bds.h UNTOUCHED ROWS) -- ranks with an all-zero record write nothing, the mask says which ranks did; the caller
+    guarantees that the rows stored into are zero."""
     with L.timed("project_bwd"):   # (antialiased: record channel 11 is the gradient of opacity * comp)
-        L.check(L.lib().bds_project_view_bwd_list(flags, vis_ids.numel(), nvis_dev, L.ptr(vis_ids), *map(L.ptr, inputs), cfg["width"],
-                                                  cfg["height"], cfg["eps2d"], L.ptr(v_rec), *map(_dp, outs), L.ptr(v_colors), L.ptr(slots),
-                                                  L.ptr(g2d), L.ptr(ag2d), L.ptr(row_map), L.stream()), "bds_project_view_bwd_list")
+        if touched is not None:
+            assert touched.dtype == torch.uint8 and touched.is_contiguous() and touched.numel() >= vis_ids.numel()
+            L.check(L.lib().bds_project_view_bwd_list_touched(
+                flags | L.PROJ_SKIP_UNTOUCHED, vis_ids.numel(), nvis_dev, L.ptr(vis_ids), *map(L.ptr, inputs), cfg["width"], cfg["height"],
+                cfg["eps2d"], L.ptr(v_rec), *map(_dp, outs), L.ptr(v_colors), L.ptr(slots), L.ptr(g2d), L.ptr(ag2d), L.ptr(row_map),
+                L.ptr(touched), L.stream()), "bds_project_view_bwd_list_touched")
+        else:
+            L.check(L.lib().bds_project_view_bwd_list(flags, vis_ids.numel(), nvis_dev, L.ptr(vis_ids), *map(L.ptr, inputs), cfg["width"],
+                                                      cfg["height"], cfg["eps2d"], L.ptr(v_rec), *map(_dp, outs), L.ptr(v_colors), L.ptr(slots),
+                                                      L.ptr(g2d), L.ptr(ag2d), L.ptr(row_map), L.stream()), "bds_project_view_bwd_list")
     carrier = cfg["_means2d_ref"]() if cfg.get("_means2d_ref") is not None else None
     if carrier is not None:
         if ag2d is not None:
@@ -794,11 +803,16 @@ class _FusedView(torch.autograd.Function):
                 t.zero_()
             return t.view(t.shape)  # a fresh tensor object (no other owner): autograd adopts it as .grad without cloning
 
+        # untouched rows (include/bds.h): with the caller's per-view mask, a rank no pixel blended moves nothing.  Every row stored into
+        # is zero here -- a fresh zero tensor, or an arena / g2d buffer the caller clears row-wise by this mask.  Not with a sink: its
+        # compact exchange buffers are reduced as they are.
+        touched = cfg.get("touched_buf") if sink is None else None
         v_sh = out_like("sh", sh)
         with L.timed("sh_bwd"):
+            sh_mode = (L.SH_ACCUMULATE if rows == 2 else 0) | (L.SH_SKIP_UNTOUCHED if touched is not None else 0)
             L.check(lib.bds_sh_view_bwd_list(n_vis, None if dev_counts is None else dev_counts[1], L.ptr(vis_ids), K, cfg["sh_degree"],
                                              L.ptr(means), L.ptr(cam_pos), L.ptr(sh_rgb), int(ctx.sh_by_rank),
-                                             L.ptr(v_rec), L.ptr(v_sh), None, L.ptr(row_map), int(rows == 2), st), "bds_sh_view_bwd_list")
+                                             L.ptr(v_rec), L.ptr(v_sh), None, L.ptr(row_map), sh_mode, st), "bds_sh_view_bwd_list")
         v_means, v_quats = out_like("means", means), out_like("quats", quats)
         v_ls, v_logits = out_like("log_scales", log_scales), out_like("opacity_logits", opac)
         v_vm_slots = None      # camera-pose gradient (base.py:328-329,399): the slots behind the records, or the caller's tail buffer
@@ -807,7 +821,8 @@ class _FusedView(torch.autograd.Function):
         flags = (L.PROJ_ACCUMULATE if rows == 2 else 0) | (L.PROJ_ANTIALIASED if cfg.get("antialiased") else 0)
         _project_backward(cfg, flags, None if dev_counts is None else dev_counts[1], vis_ids,
                           (means, quats, scales, opac, viewmat.contiguous(), cfg["K"].contiguous()), v_rec,
-                          (v_means, v_quats, v_ls, v_logits), g2d=g2d[0], ag2d=g2d[1], slots=v_vm_slots, row_map=row_map, grad_always=True)
+                          (v_means, v_quats, v_ls, v_logits), g2d=g2d[0], ag2d=g2d[1], slots=v_vm_slots, row_map=row_map, grad_always=True,
+                          touched=touched)
         # (defer_pose_sum: the caller sums the slots of all its views in one launch -- graph_view, once per frame)
         v_viewmat = None if (v_vm_slots is None or cfg.get("defer_pose_sum")) else v_vm_slots.sum(0)
         if grids_in_place:
@@ -974,6 +989,9 @@ def train_view(params: Dict[str, Tensor], viewmat: Tensor, K: Tensor, width: int
     list_tile, caps = kwargs.pop("list_tile", None), kwargs.pop("caps", None)
     prep_ws, two_phase = kwargs.pop("prep_ws", None), bool(kwargs.pop("two_phase", False))
     g2d_buf = kwargs.pop("g2d_buf", None)    # persistent [2,N,2] screen-space gradient arrays whose stale rows the caller clears
+    # persistent [>= list capacity] u8 mask by rank, written by the projection backward: the Gaussian half skips the ranks no pixel blended
+    # (include/bds.h UNTOUCHED ROWS); the caller clears the gradient rows and g2d_buf by it (bds_view_grads_clear_list_touched)
+    touched_buf = kwargs.pop("touched_buf", None)
     tail_buf, defer_pose_sum = kwargs.pop("tail_buf", None), bool(kwargs.pop("defer_pose_sum", False))
     lazy_loss = bool(kwargs.pop("lazy_loss", False))    # leave the loss value as out["loss_slots"] (losses.slots_value sums it on demand)
     defer_epilogue = bool(kwargs.pop("defer_epilogue", True))   # (see _DEFER_EPILOGUE)
@@ -991,7 +1009,7 @@ def train_view(params: Dict[str, Tensor], viewmat: Tensor, K: Tensor, width: int
                sh_degree=int(opts["sh_degree"]), near_plane=float(opts["near_plane"]), far_plane=float(opts["far_plane"]),
                radius_clip=float(opts["radius_clip"]), eps2d=float(opts["eps2d"]), tile_cull=bool(opts["tile_cull"]),
                grad_arena=grad_arena, grad_sink=grad_sink, img_idx=None if img_idx is None else int(img_idx), arena_rows=arena_rows,
-               list_tile=int(LIST_TILE if list_tile is None else list_tile), caps=caps, prep_ws=prep_ws, g2d_buf=g2d_buf, tail_buf=tail_buf,
+               list_tile=int(LIST_TILE if list_tile is None else list_tile), caps=caps, prep_ws=prep_ws, g2d_buf=g2d_buf, touched_buf=touched_buf, tail_buf=tail_buf,
                defer_epilogue=defer_epilogue, split_len=split_len, split_cap=split_cap, block_bounds=block_bounds,
                front_bufs=front_bufs, defer_pose_sum=defer_pose_sum, row_catchup=row_catchup, antialiased=bool(opts["antialiased"]))
     gs = [g if g.dim() == 5 else g[None] for g in grids]

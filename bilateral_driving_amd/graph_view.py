@@ -145,6 +145,10 @@ class FrameGraph(FrameCapacities):
         # per view: d(loss)/d(means2d) and its absolute sum, [2, N, 2], dense for the densification statistics (info["means2d"].grad /
         # .absgrad); the projection backward stores the visible rows, the begin stage clears the rows of the previous visit
         self.g2d = [torch.zeros(2, self.N, 2, device=self.dev, dtype=torch.float32) for _ in range(self.V)] if self.fx is None else None
+        # per view, by RANK of its visible-id list: 1 where the view's last backward had a non-zero gradient record (include/bds.h
+        # UNTOUCHED ROWS).  The Gaussian half writes only those ranks' rows, the begin stage clears only those.  The invariant: every
+        # gradient row (parameters and g2d) is zero behind the begin stage.  All ones = "clear every listed rank": where a capture starts
+        self.touched = [torch.ones(max(self.N, 1), device=self.dev, dtype=torch.uint8) for _ in range(self.V)] if self.fx is None else None
         # all views' camera-pose gradient slots (+ loss accumulators) in ONE tensor: the slots are summed once per frame, not per view
         self._tail_rows = L.POSE_GRAD_SLOTS + L.LOSS_SLOTS * L.LOSS_SLOT_STRIDE // L.GRAD_RECORD_FLOATS
         self._tails = torch.zeros(self.V, self._tail_rows, L.GRAD_RECORD_FLOATS, device=self.dev, dtype=torch.float32)
@@ -180,7 +184,7 @@ class FrameGraph(FrameCapacities):
                 arena = dict(self.arena, **{f"grid{i}": g for i, g in enumerate(self.sel_grads[v])})
                 kw.update(tv_grids=self.grids, tv_grid_grads=grid_grads)
                 grid_grads = self.sel_grads[v]
-            kw.update(grid_grads=grid_grads, grad_arena=arena, arena_rows=1 if v == 0 else 2, g2d_buf=self.g2d[v])
+            kw.update(grid_grads=grid_grads, grad_arena=arena, arena_rows=1 if v == 0 else 2, g2d_buf=self.g2d[v], touched_buf=self.touched[v])
             if self._defer_pose:
                 kw.update(tail_buf=self._tails[v], defer_pose_sum=True)
         return kw
@@ -228,8 +232,10 @@ class FrameGraph(FrameCapacities):
             g2 = self.g2d[v]      # (the view's persistent screen-space gradient arrays: the same rows, no dense fill per view)
             row_clear = self.clear_grads and self._frame_fx is None   # (per-frame exchange: step() clears the flat buffer densely)
             pa = [a[k].data_ptr() if row_clear else None for k in ("means", "quats", "log_scales", "opacity_logits", "sh")]
-            L.check(lib.bds_view_grads_clear_list(self.caps[v].nvis_cap, ws.data_ptr() + self._nvis_off, L.ptr(ids), self.K, *pa,
-                                                  L.ptr(g2[0]), L.ptr(g2[1]), st), "bds_view_grads_clear_list")
+            # (only the ranks the view's last backward wrote: its mask; all ones right after a capture started)
+            L.check(lib.bds_view_grads_clear_list_touched(self.caps[v].nvis_cap, ws.data_ptr() + self._nvis_off, L.ptr(ids), self.K, *pa,
+                                                          L.ptr(g2[0]), L.ptr(g2[1]), L.ptr(self.touched[v]), st),
+                    "bds_view_grads_clear_list_touched")
         if self._tail.numel() and tail and self.clear_grads and self._frame_fx is None:
             self._tail.zero_()
 
@@ -262,6 +268,8 @@ class FrameGraph(FrameCapacities):
         torch.cuda.synchronize()
         for fb in self.front_bufs or ():     # (a capture starts from "unknown": whatever ran since the last one, the state does not rely on it)
             fb.reset()
+        for m in self.touched or ():         # (likewise: the warm-up frame's begin stage clears every listed rank, as a dense list clear)
+            m.fill_(1)
         if self.fx is not None:
             self.fx.static_setup(self._unions)
         self._point_grads_at_flat()

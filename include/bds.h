@@ -429,6 +429,7 @@ int bds_gaussian_block_bounds(int64_t N, const float *means, const float *log_sc
 #define BDS_PROJ_ACCUMULATE 1
 #define BDS_PROJ_ACTIVATED 2
 #define BDS_PROJ_ANTIALIASED 4
+#define BDS_PROJ_SKIP_UNTOUCHED 8   /* bds_project_view_bwd_list_touched only (see there) */
 /* The one-view forward (C = 1): scales [N] = exp(log_scales), opacities [N] = sigmoid(logits), and the projection's outputs.
  *   flags & BDS_PROJ_ANTIALIASED: rasterize_mode "antialiased" (models/trainers/base.py:406, :824) -- the opacity the tile stage and the
  *       compositor read is the EFFECTIVE one, sigmoid(logit) * comp: slot 7 of the [N,8] row form, else opac_eff [N] (required in the
@@ -482,7 +483,28 @@ int bds_sh_view_fwd(int64_t N, int K, int degrees_to_use, const float *means, co
  * [n_list,3] in list order (bds_splat_pack_sh).
  * v_coeffs_rest (NULL: v_coeffs is [N,K,3]): the split storage of bds_splat_pack_sh -- v_coeffs [N,3], v_coeffs_rest [N,K-1,3]
  * (visible rows stored or added to; ignored for K = 1).  Dense arrays only: not together with row_map.
- * n_dev (NULL: n_list is the count): the device-count form, as bds_project_view_bwd_list's. */
+ * n_dev (NULL: n_list is the count): the device-count form, as bds_project_view_bwd_list's.
+ * accumulate: 0 / BDS_SH_ACCUMULATE as above, optionally | BDS_SH_SKIP_UNTOUCHED -- see UNTOUCHED ROWS below. */
+#define BDS_SH_ACCUMULATE 1
+#define BDS_SH_SKIP_UNTOUCHED 2
+/* UNTOUCHED ROWS.  A view lists every visible Gaussian, but its pixels saturate after some tens of blends: most listed Gaussians lie
+ * behind everything, no pixel blends them, and their gradient record stays at the exact zeros the record pack wrote (~87 % of the
+ * ranks of a 2 M-Gaussian 1080p view; with the rows in spatial order 3 of 4 workgroups of 256 ranks hold nothing else).  Every
+ * gradient of such a rank is +-0.  The skipping forms leave its rows alone:
+ *   bds_sh_view_bwd_list with BDS_SH_SKIP_UNTOUCHED: a row whose colour gradient (record floats 0-2, behind the clamp mask) is all +-0
+ *       is neither read nor written;
+ *   bds_project_view_bwd_list_touched with BDS_PROJ_SKIP_UNTOUCHED: a rank whose record floats 0-11 are all +-0 reads no parameter,
+ *       runs no VJP, stores nothing (parameter gradients, grad2d / absgrad2d, v_colors) and adds nothing to the pose slots.  With or
+ *       without the flag, `touched` [n_list] bytes (may be NULL) receives per rank 1 = "floats 0-11 not all +-0", else 0;
+ *   bds_view_grads_clear_list_touched: clears only the listed ranks whose `touched` byte is non-zero (NULL: every listed rank).
+ * Adding +-0 is a no-op: accumulating, a skipped row differs from the dense form at most in the SIGN OF A ZERO.  Storing, the skipped
+ * row keeps what it held, so skipping is allowed only where the destination rows are known to be zero: fresh zero tensors, an arena
+ * the caller keeps zero, buffers cleared row-wise with the mask -- the invariant of graph_view.FrameGraph: every gradient row is zero
+ * behind the begin stage; a row is written only where its record was non-zero; the mask (a caller-owned persistent buffer: the records
+ * themselves do not outlive the frame) says 1 exactly there; exactly those ranks are cleared by the next begin stage.  A colour
+ * gradient is part of floats 0-11, so the SH rows written are a subset of the mask.
+ * NON-FINITE PARAMETERS: the dense forms compute 0 x Inf = NaN for an untouched row, the skipping forms leave it zero (the reference
+ * rejects such parameters upstream, models/gaussians/vanilla.py:407-412; bds_nonfinite_flags). */
 int bds_sh_view_bwd_list(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, int K, int degrees_to_use, const float *means,
                          const float *cam_pos, const float *sh_rgb, int sh_rgb_by_rank, const float *v_records, float *v_coeffs,
                          float *v_coeffs_rest, const int32_t *row_map, int accumulate, bds_stream_t stream);
@@ -553,6 +575,12 @@ int bds_project_view_bwd_list(int flags, int64_t n_list, const uint64_t *n_dev, 
                               int W, int H, float eps2d, const float *v_records, float *v_means, float *v_quats, float *v_scales,
                               float *v_opacities, float *v_colors, float *v_viewmat_slots, float *grad2d, float *absgrad2d,
                               const int32_t *row_map, bds_stream_t stream);
+/* The same with the untouched-rows mask (UNTOUCHED ROWS above): flags may add BDS_PROJ_SKIP_UNTOUCHED; touched [n_list] u8, may be NULL. */
+int bds_project_view_bwd_list_touched(int flags, int64_t n_list, const uint64_t *n_dev, const int32_t *ids, const float *means,
+                                      const float *quats, const float *scales, const float *opacities, const float *viewmat,
+                                      const float *K, int W, int H, float eps2d, const float *v_records, float *v_means, float *v_quats,
+                                      float *v_scales, float *v_opacities, float *v_colors, float *v_viewmat_slots, float *grad2d,
+                                      float *absgrad2d, const int32_t *row_map, uint8_t *touched, bds_stream_t stream);
 /* Zero the rows ids[0..n_list) of the five per-Gaussian gradient arrays (v_sh is [N,K,3]); n_dev (NULL: n_list is the count): the
  * device-count form, as above.
  * grad2d / absgrad2d [N,2], optional: the same rows of a view's PERSISTENT screen-space gradient arrays are cleared as well -- the
@@ -562,6 +590,10 @@ int bds_project_view_bwd_list(int flags, int64_t n_list, const uint64_t *n_dev, 
  * takes them with a host count as well.) */
 int bds_view_grads_clear_list(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, int K, float *v_means, float *v_quats,
                               float *v_log_scales, float *v_logits, float *v_sh, float *grad2d, float *absgrad2d, bds_stream_t stream);
+/* touched [n_list] u8 by rank (NULL: as above): only the ranks with a non-zero byte are cleared (UNTOUCHED ROWS above). */
+int bds_view_grads_clear_list_touched(int64_t n_list, const uint64_t *n_dev, const int32_t *ids, int K, float *v_means, float *v_quats,
+                                      float *v_log_scales, float *v_logits, float *v_sh, float *grad2d, float *absgrad2d,
+                                      const uint8_t *touched, bds_stream_t stream);
 /* v_*[ids[s]] += s_*[s]: compact rows (s_means [n_list,3] s_quats [n_list,4] s_log_scales [n_list,3] s_logits [n_list]
  * s_sh [n_list,K,3], e.g. a reduced exchange buffer) added to the dense arrays; entries with ids[s] < 0 are skipped. */
 int bds_view_grads_add_list(int64_t n_list, const int32_t *ids, int K, const float *s_means, const float *s_quats,
