@@ -3,6 +3,7 @@
 // (SURVEY.md 8f rank 1).  One streaming pass each way instead of the ~8 framework kernels of
 // (a - b).abs().mean() and its autograd graph; HBM-bound (8 B/element forward, 12 B/element backward).
 #include "bds_common.h"
+#include "image_loss_math.h"
 
 namespace bds {
 
@@ -381,6 +382,94 @@ __global__ __launch_bounds__(kLossBlock) void reg_loss_bwd_kernel(RegLossArgs a,
   }
 }
 
+// ---- the whole image loss in one pass each way (csrc/image_loss_math.h: the six terms, per pixel) -----------------------------------
+// BasicTrainer.compute_losses, models/trainers/base.py:518-585 and :638-652, at every option of models/losses.py:33-178.  HBM-bound: the
+// forward reads 48 B a pixel (rgb, pixels, opacity, sky, depth, lidar, egocar, dyn_opacity; the smoothness term's neighbours come from
+// the cache), the backward those and writes 20 B (v_rgb, v_opacity, v_depth, each ONCE: the sum of the terms that reach it).  Whether a
+// term is on is a kernel argument: uniform branches.  No floating-point atomics: each forward workgroup writes its row of kIlSums sums
+// (the two counts as integers), a one-workgroup finish adds the rows in a fixed order, keeps the finished row for the backward and forms
+// the six weighted terms: bit-identical run to run.
+constexpr int kIlBlock = 256, kIlMaxBlocks = 2048;   // the forward strides a grid of at most 2048 x 256 threads: the finish reads <= 2048 rows
+
+__global__ __launch_bounds__(kIlBlock) void image_loss_fwd_kernel(ImageLossArgs a, float *__restrict__ partials) {
+  __shared__ float red[kIlBlock / kWave][kIlSums];
+  float s[kIlFloatSums] = {};
+  int n[2] = {0, 0};
+  const int64_t P = (int64_t)a.H * a.W;
+  for (int64_t i = (int64_t)blockIdx.x * kIlBlock + threadIdx.x; i < P; i += (int64_t)gridDim.x * kIlBlock)
+    image_loss_pixel_fwd(a, (int)i, s, &n[0], &n[1]);
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+#pragma unroll
+  for (int k = 0; k < kIlFloatSums; k++) {
+    const float t = wave_sum_all(s[k]);
+    if (lane == 0) red[wave][k] = t;
+  }
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    int t = n[k];
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) t += __shfl_xor(t, o);
+    if (lane == 0) red[wave][kIlFloatSums + k] = __int_as_float(t);
+  }
+  __syncthreads();
+  if (threadIdx.x < kIlSums) {
+    const int k = threadIdx.x;
+    float out;
+    if (k < kIlFloatSums) {
+      out = red[0][k];
+#pragma unroll
+      for (int w = 1; w < kIlBlock / kWave; w++) out += red[w][k];
+    } else {
+      int t = 0;
+#pragma unroll
+      for (int w = 0; w < kIlBlock / kWave; w++) t += __float_as_int(red[w][k]);
+      out = __int_as_float(t);
+    }
+    partials[(int64_t)blockIdx.x * kIlSums + k] = out;
+  }
+}
+
+// one workgroup of kIlSums waves: wave k adds column k of the rows (lanes stride the rows with four sums each, then the butterfly)
+__global__ __launch_bounds__(kIlSums *kWave) void image_loss_finish_kernel(ImageLossArgs a, const float *__restrict__ partials, int blocks,
+                                                                          float *__restrict__ sums, float *__restrict__ terms) {
+  __shared__ float tot[kIlSums];
+  const int lane = threadIdx.x & (kWave - 1), k = threadIdx.x / kWave;
+  float total;
+  if (k < kIlFloatSums) {
+    float s[4] = {};
+    for (int b = lane; b < blocks; b += 4 * kWave) {
+#pragma unroll
+      for (int u = 0; u < 4; u++)
+        if (b + u * kWave < blocks) s[u] += partials[(int64_t)(b + u * kWave) * kIlSums + k];
+    }
+    total = wave_sum_all((s[0] + s[1]) + (s[2] + s[3]));
+  } else {
+    int64_t t = 0;
+    for (int b = lane; b < blocks; b += kWave) t += __float_as_int(partials[(int64_t)b * kIlSums + k]);
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) t += __shfl_xor(t, o);
+    total = (float)t;
+  }
+  if (lane == 0) {
+    tot[k] = total;
+    sums[k] = total;
+  }
+  __syncthreads();
+  if (threadIdx.x < kIlTerms) {
+    float t[kIlTerms];
+    image_loss_terms(a, tot, t);
+    terms[threadIdx.x] = t[threadIdx.x];
+  }
+}
+
+__global__ __launch_bounds__(kIlBlock) void image_loss_bwd_kernel(ImageLossArgs a, const float *__restrict__ sums,
+                                                                 const float *__restrict__ v_terms, float *__restrict__ v_rgb,
+                                                                 float *__restrict__ v_opacity, float *__restrict__ v_depth) {
+  const int64_t i = (int64_t)blockIdx.x * kIlBlock + threadIdx.x;
+  if (i >= (int64_t)a.H * a.W) return;
+  image_loss_pixel_bwd(a, image_loss_scales(a, sums, v_terms), (int)i, v_rgb, v_opacity, v_depth);
+}
+
 }  // namespace bds
 
 using namespace bds;
@@ -540,6 +629,74 @@ extern "C" int bds_reg_loss_bwd(int H, int W, const float *opacity, const float 
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(reg_loss_bwd_kernel, dim3((unsigned)blocks), dim3(kLossBlock), 0, as_stream(stream), a, sums, v_terms,
                      v_opacity, v_depth, v_rgb);
+  BDS_LAUNCH_CHECK();
+  return BDS_OK;
+}
+
+static int64_t image_loss_blocks(int H, int W) {
+  const int64_t b = cdiv((int64_t)H * W, kIlBlock);
+  return b < kIlMaxBlocks ? b : kIlMaxBlocks;
+}
+
+static int image_loss_args(ImageLossArgs &a, int H, int W, const float *rgb, const float *pixels, const float *opacity, const float *depth,
+                           const float *sky_masks, const float *lidar, const float *egocar, const float *dyn_opacity, int mask_kind,
+                           double safe_limit, int depth_type, int depth_normalize, int depth_inverse, float max_depth, int depth_reduction,
+                           int entropy, int smoothness, float dyn_threshold, const float *weights) {
+  BDS_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W <= INT32_MAX && rgb && pixels && weights);
+  BDS_REQUIRE(mask_kind >= kIlMaskOff && mask_kind <= kIlMaskSafeBce && (sky_masks != nullptr) == (mask_kind != kIlMaskOff));
+  BDS_REQUIRE(mask_kind == kIlMaskOff || opacity);
+  BDS_REQUIRE(mask_kind != kIlMaskSafeBce || (safe_limit > 0.0 && safe_limit < 1.0));
+  BDS_REQUIRE(depth_type >= kIlDepthL1 && depth_type <= kIlDepthSmoothL1 && depth_reduction >= kIlMeanOnHit && depth_reduction <= kIlSum);
+  BDS_REQUIRE(lidar == nullptr || (depth && max_depth > 0.f));
+  BDS_REQUIRE((!entropy || opacity) && (!smoothness || depth));
+  a.rgb = rgb; a.pixels = pixels; a.opacity = opacity; a.depth = depth; a.sky = sky_masks; a.lidar = lidar; a.egocar = egocar;
+  a.dyn_opacity = dyn_opacity;
+  a.H = H; a.W = W; a.mask_kind = mask_kind;
+  const double ln_limit = mask_kind == kIlMaskSafeBce ? log(safe_limit) : 0.0, limit = exp(ln_limit);   // SafeBCE: np.log, then np.exp of it
+  a.ln_limit = (float)ln_limit; a.limit = (float)limit; a.one_minus_limit = (float)(1.0 - limit);
+  a.depth_type = depth_type; a.normalize = depth_normalize ? 1 : 0; a.inverse = depth_inverse ? 1 : 0; a.reduction = depth_reduction;
+  a.max_depth = max_depth; a.entropy = entropy ? 1 : 0; a.smoothness = smoothness ? 1 : 0; a.dyn_threshold = dyn_threshold;
+  for (int k = 0; k < kIlTerms; k++) a.w[k] = weights[k];
+  return BDS_OK;
+}
+
+extern "C" size_t bds_image_loss_temp_bytes(int H, int W) {
+  if (H < 1 || W < 1) return 0;
+  return sizeof(float) * kIlSums * (size_t)image_loss_blocks(H, W);
+}
+
+extern "C" int bds_image_loss_fwd(int H, int W, const float *rgb, const float *pixels, const float *opacity, const float *depth,
+                                  const float *sky_masks, const float *lidar, const float *egocar, const float *dyn_opacity, int mask_kind,
+                                  double safe_limit, int depth_type, int depth_normalize, int depth_inverse, float max_depth,
+                                  int depth_reduction, int entropy, int smoothness, float dyn_threshold, const float *weights, float *terms,
+                                  float *sums, void *temp, size_t temp_bytes, bds_stream_t stream) {
+  ImageLossArgs a;
+  int rc = image_loss_args(a, H, W, rgb, pixels, opacity, depth, sky_masks, lidar, egocar, dyn_opacity, mask_kind, safe_limit, depth_type,
+                           depth_normalize, depth_inverse, max_depth, depth_reduction, entropy, smoothness, dyn_threshold, weights);
+  if (rc != BDS_OK) return rc;
+  BDS_REQUIRE(terms && sums && temp && temp_bytes >= bds_image_loss_temp_bytes(H, W));
+  const int blocks = (int)image_loss_blocks(H, W);
+  hipLaunchKernelGGL(image_loss_fwd_kernel, dim3((unsigned)blocks), dim3(kIlBlock), 0, as_stream(stream), a, static_cast<float *>(temp));
+  hipLaunchKernelGGL(image_loss_finish_kernel, dim3(1), dim3(kIlSums * kWave), 0, as_stream(stream), a, static_cast<const float *>(temp),
+                     blocks, sums, terms);
+  BDS_LAUNCH_CHECK();
+  return BDS_OK;
+}
+
+extern "C" int bds_image_loss_bwd(int H, int W, const float *rgb, const float *pixels, const float *opacity, const float *depth,
+                                  const float *sky_masks, const float *lidar, const float *egocar, const float *dyn_opacity, int mask_kind,
+                                  double safe_limit, int depth_type, int depth_normalize, int depth_inverse, float max_depth,
+                                  int depth_reduction, int entropy, int smoothness, float dyn_threshold, const float *weights,
+                                  const float *sums, const float *v_terms, float *v_rgb, float *v_opacity, float *v_depth,
+                                  bds_stream_t stream) {
+  ImageLossArgs a;
+  int rc = image_loss_args(a, H, W, rgb, pixels, opacity, depth, sky_masks, lidar, egocar, dyn_opacity, mask_kind, safe_limit, depth_type,
+                           depth_normalize, depth_inverse, max_depth, depth_reduction, entropy, smoothness, dyn_threshold, weights);
+  if (rc != BDS_OK) return rc;
+  BDS_REQUIRE(sums && v_terms);
+  if (!v_rgb && !v_opacity && !v_depth) return BDS_OK;
+  hipLaunchKernelGGL(image_loss_bwd_kernel, dim3((unsigned)cdiv((int64_t)H * W, kIlBlock)), dim3(kIlBlock), 0, as_stream(stream), a, sums,
+                     v_terms, v_rgb, v_opacity, v_depth);
   BDS_LAUNCH_CHECK();
   return BDS_OK;
 }

@@ -898,6 +898,37 @@ int bds_reg_loss_bwd(int H, int W, const float *opacity, const float *depth, con
                      const float *dyn_opacity, const float *egocar, float dyn_threshold, const float *sums, const float *v_terms,
                      float *v_opacity, float *v_depth, float *v_rgb, bds_stream_t stream);
 
+/* ---- The whole image loss of BasicTrainer.compute_losses in one pass each way ---------------------------------------------------------
+ * models/trainers/base.py:518-585 and :638-652 at every option of models/losses.py:33-178 (csrc/image_loss_math.h).  rgb, pixels
+ * [H*W,3]; opacity, depth, sky_masks, lidar, egocar, dyn_opacity [H*W], 4-byte aligned.  valid = 1 - egocar (NULL: 1).  weights [6] are
+ * HOST floats; terms [6] (device) come out weighted:
+ *   terms[0] rgb L1 (:533-540)                 w0 mean |pixels*valid - rgb*valid| over 3 H W
+ *   terms[1] sky opacity (:536-550)            mask_kind 0 off (sky_masks NULL), 1 torch's binary_cross_entropy (losses.py:81-83), 2
+ *            SafeBCE with safe_limit in (0,1) (losses.py:33-79: its own backward, a gradient where the forward clipped, none where the
+ *            re-clipped x equals y); x = opacity*valid, y = (1 - sky_masks)*valid, mean over H W
+ *   terms[2] lidar depth (:552-565)            on where lidar != NULL.  DepthLoss (losses.py:91-178): hit = (lidar > 0)*valid, over
+ *            {0.01 < lidar*hit < max_depth, depth*hit > 1e-4}; depth_normalize: clamp(d / max_depth, 1e-6, 1); depth_inverse: 1 / d;
+ *            depth_type 0 l1, 1 l2, 2 smooth_l1 (beta 1); depth_reduction 0 mean_on_hit (NaN over an empty set, as torch's empty
+ *            mean), 1 mean_on_hw, 2 sum
+ *   terms[3] opacity entropy (:568-573)        on where entropy != 0: mean of -p log p, p = clamp(opacity, 1e-6, 1 - 1e-6)
+ *   terms[4] inverse-depth smoothness (:576-585)  on where smoothness != 0: as bds_reg_loss_fwd's terms[1] (kornia: PARITY UNPINNED)
+ *   terms[5] dynamic-region L1 (:638-652)      on where dyn_opacity != NULL: over {dyn_opacity > dyn_threshold, valid != 0}; 0 when empty
+ * A term that is off is 0.  No atomics: the forward's workgroups write rows of sums into temp (bds_image_loss_temp_bytes bytes), a
+ * one-workgroup finish adds them in a fixed order into sums [9] (kept for the backward: seven numerators, the depth and the dynamic
+ * count) and forms the terms; bit-identical run to run.  The backward writes (not accumulates) each given output once: v_rgb [H*W,3] =
+ * terms 0 + 5, v_opacity [H*W] = terms 1 + 3, v_depth [H*W] = terms 2 + 4, scaled by v_terms [6] (device); any of them may be NULL. */
+size_t bds_image_loss_temp_bytes(int H, int W);
+int bds_image_loss_fwd(int H, int W, const float *rgb, const float *pixels, const float *opacity, const float *depth,
+                       const float *sky_masks, const float *lidar, const float *egocar, const float *dyn_opacity, int mask_kind,
+                       double safe_limit, int depth_type, int depth_normalize, int depth_inverse, float max_depth, int depth_reduction,
+                       int entropy, int smoothness, float dyn_threshold, const float *weights, float *terms, float *sums, void *temp,
+                       size_t temp_bytes, bds_stream_t stream);
+int bds_image_loss_bwd(int H, int W, const float *rgb, const float *pixels, const float *opacity, const float *depth,
+                       const float *sky_masks, const float *lidar, const float *egocar, const float *dyn_opacity, int mask_kind,
+                       double safe_limit, int depth_type, int depth_normalize, int depth_inverse, float max_depth, int depth_reduction,
+                       int entropy, int smoothness, float dyn_threshold, const float *weights, const float *sums, const float *v_terms,
+                       float *v_rgb, float *v_opacity, float *v_depth, bds_stream_t stream);
+
 /* ---- Cube-map sky (the ROCm replacement of nvdiffrast's cube texture) -----------------------------
  * EnvLight.forward (models/modules.py:176-211): out[i] = bilinear cube-map lookup of tex [6,res,res,channels] along
  * dirs[i] @ rot^T (rot: 9 floats on the device, row-major, NULL = identity; the reference's to_opengl, :189,196) --
