@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BDS_LIB") or os.path.join(_HERE, "libbds.so")    # (BDS_LIB: an A/B variant built by build.py --variant)
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _lock = threading.Lock()
 _lib = None
@@ -120,10 +120,6 @@ _SIGS = {
     "bds_ssim_workspace_bytes": (_sz, [_i, _i, _i]),
     "bds_ssim_fwd": (_i, [_i, _i, _i, _f, _f, _f, _f, _sz, _f]),
     "bds_ssim_bwd": (_i, [_i, _i, _i, _f, _f, _f, _sz, _f, _f, _f]),
-    "bds_pixel_loss_fwd": (_i, [_i64, _f, _f, _f, _f, _f, _f, _f, _fl, _fl, _fl, _i, _fl, _f, _f, _f]),
-    "bds_pixel_loss_bwd": (_i, [_i64, _f, _f, _f, _f, _f, _f, _f, _fl, _fl, _fl, _i, _fl, _f, _f, _f, _f, _f, _f]),
-    "bds_reg_loss_fwd": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _fl, _f, _f, _f]),
-    "bds_reg_loss_bwd": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _fl, _f, _f, _f, _f, _f, _f]),
     "bds_image_loss_temp_bytes": (_sz, [_i, _i]),
     "bds_image_loss_fwd": (_i, [_i, _i] + [_f] * 8 + [_i, C.c_double, _i, _i, _i, _fl, _i, _i, _i, _fl, C.POINTER(C.c_float), _f, _f, _f, _sz, _f]),
     "bds_image_loss_bwd": (_i, [_i, _i] + [_f] * 8 + [_i, C.c_double, _i, _i, _i, _fl, _i, _i, _i, _fl, C.POINTER(C.c_float)] + [_f] * 6),

@@ -8,10 +8,16 @@
 //                                    {gt > 0.01, gt < max_depth, pred > 1e-4}: optional clamp(d / max_depth, 1e-6, 1), optional 1 / d, then
 //                                    l1 / l2 / smooth_l1 (beta 1); mean over the set, over P, or the sum
 //   3 opacity entropy (:568-573)     p = clamp(opacity, 1e-6, 1 - 1e-6); -p log p, mean over P
-//   4 inverse-depth smoothness (:576-585)  kornia's inverse_depth_smoothness_loss of 1 / (depth + 1e-5) and pixels, restated from its
-//                                    published definition (an external package: parity unpinned, as the note above reg_loss_fwd_kernel says)
-//   5 dynamic-region L1 (:638-652)   |pixels*valid - rgb*valid| over {dyn_opacity > threshold, valid != 0}, mean over 3 x their count
+//   4 inverse-depth smoothness (:576-585)  kornia.losses.inverse_depth_smoothness_loss -- an external package, PARITY UNPINNED, restated from
+//                                    its published definition: id = 1 / (depth + 1e-5); mean |(id[x] - id[x+1]) * exp(-mean_c |img[x] -
+//                                    img[x+1]|)| over (H, W-1) + the same along y over (H-1, W); the reference repeats id to three equal
+//                                    channels (:575-582), which leaves the mean unchanged
+//   5 dynamic-region L1 (:638-652)   |pixels*valid - rgb*valid| over {dyn_opacity > threshold (detached), valid != 0}, mean over 3 x their
+//                                    count
 // A torch.clamp passes the gradient on its closed range; |t| has derivative sign(t) with sign(0) = 0.
+// losses.pixel_loss is terms 0-2 as the trainer's defaults build them (:230-250: binary_cross_entropy, DepthLoss(normalize=False,
+// use_inverse_depth=False, reduction="mean_on_hit")), PINNED by tests/golden/pixel_loss_*.npz (generated with the reference's own
+// functions); losses.reg_losses is terms 3-5 unweighted (:566-585, 638-659).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -1,8 +1,12 @@
 """Image loss of the training step on the path's outputs (reference:
 models/trainers/base.py:518-565 + models/losses.py, affine TV :590-594 + models/modules.py:445,466-472):
 ``photometric_tv_loss`` (L1 + per-level TV as ONE node accumulating into one device scalar -- the benchmark's loss),
-``pixel_loss`` (rgb L1 + sky-mask BCE + lidar depth in one pass each way), ``ssim`` / ``ssim_loss``, and ``image_terms``: all six image
-terms of ``compute_losses`` at every option of models/losses.py as one node, with ``install`` / ``uninstall`` of that method."""
+``ssim`` / ``ssim_loss``, and ``image_terms``: all six image terms of ``compute_losses`` at every option of models/losses.py as one node,
+with ``install`` / ``uninstall`` of that method.
+
+There is ONE node for the per-pixel terms (``_ImageLoss``, over ``bds_image_loss_fwd`` / ``_bwd``).  ``pixel_loss`` (rgb L1 + sky-mask BCE +
+lidar depth, the first three terms at the trainer's default options) and ``reg_losses`` (opacity entropy + inverse-depth smoothness +
+dynamic-region L1, the last three, unweighted) are its two older option sets, kept as names: each is one call of ``image_terms``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -158,101 +162,6 @@ def ssim_loss(pred: Tensor, target: Tensor) -> Tensor:
     return 1.0 - ssim(pred, target)
 
 
-class _PixelLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, rgb, opacity, depth, pixels, sky_masks, lidar, egocar, w, depth_l2, max_depth):
-        L.require_gpu(rgb, pixels)
-        lib, st = L.lib(), L.stream()
-        f = lambda t: None if t is None else t.contiguous().to(torch.float32)
-        rgb, opacity, depth, pixels, sky_masks, lidar, egocar = (f(t) for t in (rgb, opacity, depth, pixels, sky_masks, lidar, egocar))
-        P = rgb.numel() // 3
-        assert rgb.shape[-1] == 3 and pixels.shape == rgb.shape
-        for t in (opacity, depth, sky_masks, lidar, egocar):
-            assert t is None or t.numel() == P, "per-pixel inputs must have H*W elements"
-        use_mask = opacity is not None and sky_masks is not None and w[1] != 0.0
-        use_depth = depth is not None and lidar is not None and w[2] != 0.0
-        sums = torch.empty(4, device=rgb.device, dtype=torch.float32)
-        terms = torch.empty(3, device=rgb.device, dtype=torch.float32)
-        L.check(lib.bds_pixel_loss_fwd(P, L.ptr(rgb), L.ptr(pixels), L.ptr(opacity) if use_mask else None,
-                                       L.ptr(sky_masks) if use_mask else None, L.ptr(depth) if use_depth else None,
-                                       L.ptr(lidar) if use_depth else None, L.ptr(egocar), w[0], w[1], w[2], int(depth_l2), max_depth,
-                                       L.ptr(sums), L.ptr(terms), st), "bds_pixel_loss_fwd")
-        ctx.save_for_backward(rgb, opacity, depth, pixels, sky_masks, lidar, egocar, sums)
-        ctx.cfg = (tuple(w), int(depth_l2), float(max_depth), use_mask, use_depth)
-        return terms
-
-    @staticmethod
-    def backward(ctx, v_terms):
-        rgb, opacity, depth, pixels, sky_masks, lidar, egocar, sums = ctx.saved_tensors
-        w, depth_l2, max_depth, use_mask, use_depth = ctx.cfg
-        P = rgb.numel() // 3
-        v_terms = v_terms.contiguous().to(torch.float32)
-        v_rgb = torch.empty_like(rgb)
-        v_op = torch.empty_like(opacity) if (opacity is not None and ctx.needs_input_grad[1]) else None
-        v_dp = torch.empty_like(depth) if (depth is not None and ctx.needs_input_grad[2]) else None
-        L.check(L.lib().bds_pixel_loss_bwd(P, L.ptr(rgb), L.ptr(pixels), L.ptr(opacity) if use_mask else None,
-                                           L.ptr(sky_masks) if use_mask else None, L.ptr(depth) if use_depth else None,
-                                           L.ptr(lidar) if use_depth else None, L.ptr(egocar), w[0], w[1], w[2], depth_l2, max_depth,
-                                           L.ptr(sums), L.ptr(v_terms), L.ptr(v_rgb), L.ptr(v_op), L.ptr(v_dp), L.stream()),
-                "bds_pixel_loss_bwd")
-        return v_rgb, v_op, v_dp, None, None, None, None, None, None, None
-
-
-def pixel_loss(rgb: Tensor, opacity: Tensor, depth: Tensor, pixels: Tensor, sky_masks: Tensor, lidar_depth: Tensor,
-               egocar_masks: Tensor = None, w_rgb: float = 0.8, w_mask: float = 0.05, w_depth: float = 0.01,
-               depth_loss_type: str = "l1", max_depth: float = 80.0) -> Tensor:
-    """The per-pixel terms of ``BasicTrainer.compute_losses`` (models/trainers/base.py:518-565) in one pass each way:
-    returns the three WEIGHTED terms ``[rgb_loss, sky_loss_opacity, depth_loss]`` (sum them for the total; they are what
-    the trainer logs).  rgb / pixels [H,W,3]; opacity, depth [H,W,1] or [H,W]; sky_masks, lidar_depth, egocar_masks [H,W].
-    Pass ``opacity=None`` / ``depth=None`` to drop a term."""
-    if depth_loss_type not in ("l1", "l2"):
-        raise NotImplementedError(f"Unknown loss type: {depth_loss_type}")   # DepthLoss (models/losses.py:150) also has smooth_l1
-    return _PixelLoss.apply(rgb, opacity, depth, pixels, sky_masks, lidar_depth, egocar_masks,
-                            (float(w_rgb), float(w_mask), float(w_depth)), depth_loss_type == "l2", float(max_depth))
-
-
-class _RegLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, opacity, depth, rgb, pixels, dyn_opacity, egocar, dyn_threshold):
-        L.require_gpu(pixels, opacity, depth, rgb)
-        f = lambda t: None if t is None else t.contiguous().to(torch.float32)
-        opacity, depth, rgb, pixels, dyn_opacity, egocar = (f(t) for t in (opacity, depth, rgb, pixels, dyn_opacity, egocar))
-        H, W = pixels.shape[0], pixels.shape[1]
-        for t in (opacity, depth, dyn_opacity, egocar):
-            assert t is None or t.numel() == H * W, "per-pixel inputs must have H*W elements"
-        dev = pixels.device
-        sums, terms = torch.empty(5, device=dev, dtype=torch.float32), torch.empty(3, device=dev, dtype=torch.float32)
-        L.check(L.lib().bds_reg_loss_fwd(H, W, L.ptr(opacity), L.ptr(depth), L.ptr(pixels), L.ptr(rgb), L.ptr(dyn_opacity), L.ptr(egocar),
-                                         dyn_threshold, L.ptr(sums), L.ptr(terms), L.stream()), "bds_reg_loss_fwd")
-        ctx.save_for_backward(opacity, depth, rgb, pixels, dyn_opacity, egocar, sums)
-        ctx.dyn_threshold = dyn_threshold
-        return terms
-
-    @staticmethod
-    def backward(ctx, v_terms):
-        opacity, depth, rgb, pixels, dyn_opacity, egocar, sums = ctx.saved_tensors
-        H, W = pixels.shape[0], pixels.shape[1]
-        v_terms = v_terms.contiguous().to(torch.float32)
-        v_op = torch.empty_like(opacity) if (opacity is not None and ctx.needs_input_grad[0]) else None
-        v_dp = torch.empty_like(depth) if (depth is not None and ctx.needs_input_grad[1]) else None
-        v_rgb = torch.empty_like(rgb) if (rgb is not None and dyn_opacity is not None and ctx.needs_input_grad[2]) else None
-        L.check(L.lib().bds_reg_loss_bwd(H, W, L.ptr(opacity), L.ptr(depth), L.ptr(pixels), L.ptr(rgb), L.ptr(dyn_opacity), L.ptr(egocar),
-                                         ctx.dyn_threshold, L.ptr(sums), L.ptr(v_terms), L.ptr(v_op), L.ptr(v_dp), L.ptr(v_rgb), L.stream()),
-                "bds_reg_loss_bwd")
-        return v_op, v_dp, v_rgb, None, None, None, None
-
-
-def reg_losses(pixels: Tensor, opacity: Tensor = None, depth: Tensor = None, rgb: Tensor = None, dyn_opacity: Tensor = None,
-               egocar_masks: Tensor = None, dyn_threshold: float = 0.2) -> Tensor:
-    """The regularisers of ``BasicTrainer.compute_losses`` (models/trainers/base.py:566-585, 638-659) in one pass each way; returns the
-    three UNWEIGHTED terms ``[opacity_entropy, inverse_depth_smoothness, dynamic_region_l1]`` (the trainer multiplies them by
-    ``losses.opacity_entropy.w`` / ``losses.inverse_depth_smoothness.w`` / ``losses.dynamic_region.w``).  pixels / rgb [H,W,3];
-    opacity, depth, dyn_opacity (``outputs["Dynamic_opacity"]``, treated as data like the reference's ``.data``) [H,W,1] or [H,W].
-    Pass ``None`` to drop a term (it is then 0).  The dynamic-region term is 0 when no pixel qualifies (the reference adds none)."""
-    return _RegLoss.apply(opacity, depth, rgb, pixels, None if dyn_opacity is None else dyn_opacity.detach(), egocar_masks,
-                          float(dyn_threshold))
-
-
 # ---- the whole image loss under compute_losses --------------------------------------------------------------------------------------
 IMAGE_TERMS = ("rgb_loss", "sky_loss_opacity", "depth_loss", "opacity_entropy_loss", "inverse_depth_smoothness_loss", "vehicle_region_rgb_loss")
 _MASK_KINDS = {"bce": 1, "safe_bce": 2}
@@ -290,8 +199,8 @@ class _ImageLoss(torch.autograd.Function):
         H, W = rgb.shape[0], rgb.shape[1]
         v_terms = L.f32c(v_terms)
         v_rgb = torch.empty_like(rgb) if ctx.needs_input_grad[0] else None
-        v_op = torch.empty_like(opacity) if (ctx.needs_input_grad[1] and (mask_kind or entropy)) else None
-        v_dp = torch.empty_like(depth) if (ctx.needs_input_grad[2] and (lidar is not None or smoothness)) else None
+        v_op = torch.empty_like(opacity) if (opacity is not None and ctx.needs_input_grad[1]) else None   # (all of its terms off: zeros)
+        v_dp = torch.empty_like(depth) if (depth is not None and ctx.needs_input_grad[2]) else None
         images = (H, W, L.ptr(rgb), L.ptr(pixels), L.ptr(opacity), L.ptr(depth), L.ptr(sky_masks), L.ptr(lidar), L.ptr(egocar), L.ptr(dyn_opacity))
         options = (mask_kind, safe_limit, depth_type, normalize, inverse, max_depth, reduction, entropy, smoothness, dyn_threshold,
                    (C.c_float * 6)(*weights))
@@ -333,6 +242,36 @@ def image_terms(rgb: Tensor, pixels: Tensor, opacity: Tensor = None, depth: Tens
            float(dyn_threshold), tuple(float(w) for w in weights))
     return _ImageLoss.apply(rgb, opacity, depth, pixels, sky_masks, lidar_depth, egocar_masks, None if dyn_opacity is None else dyn_opacity.detach(),
                             cfg)
+
+
+def pixel_loss(rgb: Tensor, opacity: Tensor, depth: Tensor, pixels: Tensor, sky_masks: Tensor, lidar_depth: Tensor,
+               egocar_masks: Tensor = None, w_rgb: float = 0.8, w_mask: float = 0.05, w_depth: float = 0.01,
+               depth_loss_type: str = "l1", max_depth: float = 80.0) -> Tensor:
+    """The per-pixel terms of ``BasicTrainer.compute_losses`` (models/trainers/base.py:518-565) in one pass each way:
+    returns the three WEIGHTED terms ``[rgb_loss, sky_loss_opacity, depth_loss]`` (sum them for the total; they are what
+    the trainer logs).  rgb / pixels [H,W,3]; opacity, depth [H,W,1] or [H,W]; sky_masks, lidar_depth, egocar_masks [H,W].
+    Pass ``opacity=None`` / ``depth=None`` to drop a term."""
+    if depth_loss_type not in ("l1", "l2"):
+        raise NotImplementedError(f"Unknown loss type: {depth_loss_type}")   # DepthLoss (models/losses.py:150) also has smooth_l1
+    if rgb.dim() != 3:                                                        # any shape ending in 3: no term here looks at a neighbour
+        rgb, pixels = rgb.reshape(1, -1, 3), pixels.reshape(1, -1, 3)
+    use_mask = opacity is not None and sky_masks is not None and w_mask != 0.0
+    use_depth = depth is not None and lidar_depth is not None and w_depth != 0.0
+    return image_terms(rgb, pixels, opacity, depth, sky_masks if use_mask else None, lidar_depth if use_depth else None, egocar_masks,
+                       weights=(w_rgb, w_mask, w_depth, 0.0, 0.0, 0.0), depth_loss_type=depth_loss_type, max_depth=max_depth)[:3]
+
+
+def reg_losses(pixels: Tensor, opacity: Tensor = None, depth: Tensor = None, rgb: Tensor = None, dyn_opacity: Tensor = None,
+               egocar_masks: Tensor = None, dyn_threshold: float = 0.2) -> Tensor:
+    """The regularisers of ``BasicTrainer.compute_losses`` (models/trainers/base.py:566-585, 638-659) in one pass each way; returns the
+    three UNWEIGHTED terms ``[opacity_entropy, inverse_depth_smoothness, dynamic_region_l1]`` (the trainer multiplies them by
+    ``losses.opacity_entropy.w`` / ``losses.inverse_depth_smoothness.w`` / ``losses.dynamic_region.w``).  pixels / rgb [H,W,3];
+    opacity, depth, dyn_opacity (``outputs["Dynamic_opacity"]``, treated as data like the reference's ``.data``) [H,W,1] or [H,W].
+    Pass ``None`` to drop a term (it is then 0).  The dynamic-region term is 0 when no pixel qualifies (the reference adds none)."""
+    if dyn_opacity is None:      # the rgb term has weight 0 and no other term reads rgb: it may be absent, and it gets no gradient
+        rgb = pixels.detach()
+    return image_terms(rgb, pixels, opacity, depth, egocar_masks=egocar_masks, dyn_opacity=dyn_opacity, weights=(0.0, 0.0, 0.0, 1.0, 1.0, 1.0),
+                       entropy=opacity is not None, smoothness=depth is not None, dyn_threshold=dyn_threshold)[3:]
 
 
 def _affine_loss(self, affine_reg, outputs, image_infos, valid):

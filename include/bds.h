@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define BDS_ABI_VERSION 6   /* 3: the projection's entries folded into four (bds_project_fwd, bds_project_view_fwd and
+#define BDS_ABI_VERSION 7  /* 3: the projection's entries folded into four (bds_project_fwd, bds_project_view_fwd and
                                bds_project_view_bwd_list changed signatures)
                                4: the view path's host-count / device-count / split-storage twins folded into one entry each
                                (bds_splat_pack, bds_splat_pack_sh, bds_rasterize_fwd / _bwd, bds_sh_view_bwd_list, bds_view_grads_clear_list)
@@ -34,7 +34,9 @@ extern "C" {
                                entry each (bds_bilagrid_ms_fwd, bds_bilagrid_ms_bwd, bds_adam_step, bds_nonfinite_flags changed
                                signatures; bds_bilagrid_ms_ed_fwd, _ms_ed_train_fwd, _ms_ed_bwd, _ms_ed_bwd_deferred,
                                bds_adam_step_consume, bds_adam_step_rows, bds_nonfinite_flags_kinds and the unused
-                               bds_bilagrid_tv_fwd / _bwd are gone; bds_bilagrid_ms_ed_bwd_deferrable is bds_bilagrid_ms_bwd_deferrable) */
+                               bds_bilagrid_tv_fwd / _bwd are gone; bds_bilagrid_ms_ed_bwd_deferrable is bds_bilagrid_ms_bwd_deferrable)
+                               7: bds_pixel_loss_fwd / _bwd and bds_reg_loss_fwd / _bwd are gone: bds_image_loss_fwd / _bwd compute their
+                               terms as two of its option sets */
 
 #define BDS_OK 0
 #define BDS_EINVAL (-1)      /* null / misaligned pointer, bad shape or unsupported parameter */
@@ -693,22 +695,6 @@ int bds_ssim_fwd(int H, int W, int CH, const float *target, const float *pred, f
 int bds_ssim_bwd(int H, int W, int CH, const float *target, const float *pred, const void *ws, size_t ws_bytes,
                  const float *v_ssim, float *v_pred, bds_stream_t stream);
 
-/* Per-pixel terms of the reference's image loss in one pass each way (models/trainers/base.py:518-565; loss functions
- * :230-250 = models/losses.py binary_cross_entropy and DepthLoss(normalize=False, use_inverse_depth=False)):
- *   terms[0] = w_rgb   * mean |pixels*valid - rgb*valid|                          rgb, pixels [P,3]
- *   terms[1] = w_mask  * mean BCE(opacity*valid, (1 - sky_masks)*valid)           opacity, sky_masks [P] (both or neither)
- *   terms[2] = w_depth * mean over valid lidar returns of |.| (or (.)^2 if depth_l2) of depth*hit - lidar*hit,
- *              hit = (lidar > 0)*valid, valid returns: 0.01 < gt < max_depth, pred > 1e-4   depth, lidar [P] (both or neither)
- * valid = 1 - egocar [P] (NULL: 1).  sums [4] is scratch that the backward reads (three numerators + the depth count);
- * v_terms [3] are the upstream gradients of the three terms (device); v_opacity / v_depth may be NULL. */
-int bds_pixel_loss_fwd(int64_t P, const float *rgb, const float *pixels, const float *opacity, const float *sky_masks,
-                       const float *depth, const float *lidar, const float *egocar, float w_rgb, float w_mask, float w_depth,
-                       int depth_l2, float max_depth, float *sums, float *terms, bds_stream_t stream);
-int bds_pixel_loss_bwd(int64_t P, const float *rgb, const float *pixels, const float *opacity, const float *sky_masks,
-                       const float *depth, const float *lidar, const float *egocar, float w_rgb, float w_mask, float w_depth,
-                       int depth_l2, float max_depth, const float *sums, const float *v_terms, float *v_rgb, float *v_opacity,
-                       float *v_depth, bds_stream_t stream);
-
 /* ---- Adam step on one parameter tensor (first slice) --------------------------------------
  * torch.optim.Adam as the reference trainer configures it (models/trainers/base.py:201-222: per-group lr / eps /
  * weight_decay, betas (0.9, 0.999), amsgrad off), one streaming pass, in place on param / exp_avg / exp_avg_sq.
@@ -883,21 +869,6 @@ int bds_pvg_velocity_reg_fwd(int64_t N, int64_t M, double T, const uint8_t *filt
 int bds_pvg_velocity_reg_bwd(int64_t N, double T, const uint8_t *vis, const float *scale, const float *velocity, const float *betas,
                              float *g_velocity, float *g_betas, bds_stream_t stream);
 
-/* Regularisers of the reference's image loss (models/trainers/base.py:566-585, 638-659), one pass each way:
- *   terms[0] opacity entropy       (-p log p).mean(), p = clamp(opacity, 1e-6, 1-1e-6)                       (opacity != NULL)
- *   terms[1] inverse-depth smoothness  kornia.losses.inverse_depth_smoothness_loss(1/(depth+1e-5), pixels)    (depth != NULL;
- *            kornia is an external package absent here: restated from its published definition, PARITY UNPINNED)
- *   terms[2] dynamic-region L1     |pixels*valid - rgb*valid| averaged over {dyn_opacity > dyn_threshold and valid} (dyn_opacity != NULL;
- *            0 when the mask is empty, where the reference adds no term)
- * opacity / depth / dyn_opacity / egocar [H*W], pixels / rgb [H*W,3]; sums [5] and terms [3] on the device.  The backward writes
- * (not accumulates) v_opacity / v_depth [H*W], v_rgb [H*W,3] (each may be NULL) for the UNWEIGHTED terms scaled by v_terms [3]. */
-int bds_reg_loss_fwd(int H, int W, const float *opacity, const float *depth, const float *pixels, const float *rgb,
-                     const float *dyn_opacity, const float *egocar, float dyn_threshold, float *sums, float *terms,
-                     bds_stream_t stream);
-int bds_reg_loss_bwd(int H, int W, const float *opacity, const float *depth, const float *pixels, const float *rgb,
-                     const float *dyn_opacity, const float *egocar, float dyn_threshold, const float *sums, const float *v_terms,
-                     float *v_opacity, float *v_depth, float *v_rgb, bds_stream_t stream);
-
 /* ---- The whole image loss of BasicTrainer.compute_losses in one pass each way ---------------------------------------------------------
  * models/trainers/base.py:518-585 and :638-652 at every option of models/losses.py:33-178 (csrc/image_loss_math.h).  rgb, pixels
  * [H*W,3]; opacity, depth, sky_masks, lidar, egocar, dyn_opacity [H*W], 4-byte aligned.  valid = 1 - egocar (NULL: 1).  weights [6] are
@@ -911,7 +882,8 @@ int bds_reg_loss_bwd(int H, int W, const float *opacity, const float *depth, con
  *            depth_type 0 l1, 1 l2, 2 smooth_l1 (beta 1); depth_reduction 0 mean_on_hit (NaN over an empty set, as torch's empty
  *            mean), 1 mean_on_hw, 2 sum
  *   terms[3] opacity entropy (:568-573)        on where entropy != 0: mean of -p log p, p = clamp(opacity, 1e-6, 1 - 1e-6)
- *   terms[4] inverse-depth smoothness (:576-585)  on where smoothness != 0: as bds_reg_loss_fwd's terms[1] (kornia: PARITY UNPINNED)
+ *   terms[4] inverse-depth smoothness (:576-585)  on where smoothness != 0: kornia.losses.inverse_depth_smoothness_loss(1 / (depth + 1e-5),
+ *            pixels); kornia is an external package absent here: restated from its published definition, PARITY UNPINNED
  *   terms[5] dynamic-region L1 (:638-652)      on where dyn_opacity != NULL: over {dyn_opacity > dyn_threshold, valid != 0}; 0 when empty
  * A term that is off is 0.  No atomics: the forward's workgroups write rows of sums into temp (bds_image_loss_temp_bytes bytes), a
  * one-workgroup finish adds them in a fixed order into sums [9] (kept for the backward: seven numerators, the depth and the dynamic

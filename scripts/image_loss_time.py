@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Time of the image loss of one 1920 x 1080 view, forward + backward, in three forms on the same inputs in one process:
   (a) framework   the reference's expressions as framework ops (tests/image_loss_ref64.framework_terms)
-  (b) two_nodes   losses.pixel_loss + losses.reg_losses, the fused nodes before image_terms
+  (b) two_nodes   losses.pixel_loss + losses.reg_losses: the same kernels as (c) called as two nodes, each with the other's terms off (the
+                  two names are option sets of image_terms; before that fold they had kernels of their own, which the 0.198 ms of
+                  profiles/image_loss_time.json is of)
   (c) image_terms the one node
 with the option set all three can form (bce, l1 depth without normalize / inverse, every regulariser, an egocar mask).  Median of
 device events over --iters runs after --warmup, in the rounds c b a c b a c (A / B / A: every b and a lies between two rounds of c).

@@ -24,7 +24,7 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(bds_[a-z0-9_]+)\s*\(", header())))
 
 
-def test_header_and_library_symbols_match_abi_6(libpath):
+def test_header_and_library_symbols_match_abi_7(libpath):
     names = _declared_symbols()
     assert len(names) >= 19
     h = ctypes.CDLL(libpath)
@@ -37,7 +37,7 @@ def test_header_and_library_symbols_match_abi_6(libpath):
     assert not exported - set(names), f"exported by libbds.so but not declared in include/bds.h: {sorted(exported - set(names))}"
     h.bds_abi_version.restype = ctypes.c_int
     from bilateral_driving_amd import _lib as _L
-    assert h.bds_abi_version() == _L.ABI_VERSION == 6
+    assert h.bds_abi_version() == _L.ABI_VERSION == 7
     h.bds_strerror.restype = ctypes.c_char_p
     assert b"workspace" in h.bds_strerror(-2)
 

@@ -206,7 +206,7 @@ def test_entries_resolve_with_the_declared_signatures():
                          ("BDS_GEOMETRY_TARGET_TILE", geometry.TARGET_TILE)):
         assert f"#define {macro} {value}\n" in hdr, macro
     assert sorted(geometry.ROW_SLOTS.values()) == list(range(geometry.ROW))
-    assert lib.bds_abi_version() == L.ABI_VERSION == 6 and "#define BDS_ABI_VERSION 6 " in hdr
+    assert lib.bds_abi_version() == L.ABI_VERSION == 7 and "#define BDS_ABI_VERSION 7 " in hdr
 
 
 def test_entries_reject_bad_arguments_without_a_gpu():

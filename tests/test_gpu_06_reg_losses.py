@@ -48,3 +48,78 @@ def test_reg_losses_match_oracle(H, W, ego, terms):
         assert float((got.cpu().double() - ref).norm() / ref.norm()) < 2e-5, k
     if use_op:
         assert float(c["op"].grad[0, 0, 0]) == 0.0 and float(c["op"].grad[-1, -1, 0]) == 0.0
+
+
+# ---- the edges of the two names over the one node (losses.image_terms), on poisoned memory (tests/poison.py) -------------------------------
+def _pixel_inputs(H, W):
+    g = torch.Generator().manual_seed(H * 100 + W)
+    t = dict(rgb=torch.rand(H, W, 3, generator=g), pixels=torch.rand(H, W, 3, generator=g), opacity=torch.rand(H, W, 1, generator=g) * 0.98 + 0.01,
+             depth=torch.rand(H, W, 1, generator=g) * 40 + 0.5, sky=(torch.rand(H, W, generator=g) > 0.7).float(),
+             lidar=torch.rand(H, W, generator=g) * 60 + 1.0)
+    return {k: v.cuda() for k, v in t.items()}
+
+
+@pytest.mark.parametrize("H,W", [(1, 1), (3, 5)])
+def test_pixel_loss_with_zero_weights_gives_zero_terms_and_zero_gradients(H, W):
+    """opacity and depth given and requiring grad, w_mask = w_depth = 0: terms 1 and 2 exactly 0, both gradients zero tensors, not None."""
+    from bilateral_driving_amd.losses import pixel_loss
+    from tests import poison
+    t = _pixel_inputs(H, W)
+    rgb, op, dp = (t[k].clone().requires_grad_(True) for k in ("rgb", "opacity", "depth"))
+    with poison.poisoned_allocations(True, name=f"pixel_loss zero weights {H}x{W}"):
+        terms = pixel_loss(rgb, op, dp, t["pixels"], t["sky"], t["lidar"], None, 0.8, 0.0, 0.0)
+        terms.sum().backward()
+        torch.cuda.synchronize()
+    assert terms.shape == (3,) and float(terms[0]) > 0 and float(terms[1]) == 0.0 and float(terms[2]) == 0.0
+    for v in (op, dp):
+        assert v.grad is not None and v.grad.shape == v.shape and not bool(poison.holds_poison(v.grad).any())
+        assert bool((v.grad == 0).all())
+    assert float(rgb.grad.abs().max()) > 0
+
+
+@pytest.mark.parametrize("H,W", [(1, 1), (3, 5)])
+def test_pixel_loss_on_flat_inputs_equals_the_image_call_bit_for_bit(H, W):
+    from bilateral_driving_amd.losses import pixel_loss
+    from tests import poison
+    t = _pixel_inputs(H, W)
+    ego = (torch.arange(H * W).reshape(H, W) % 4 == 3).float().cuda()
+
+    def run(flat):
+        shape = (lambda v: v.reshape(-1, 3) if v.shape[-1] == 3 and v.dim() == 3 else v.reshape(-1)) if flat else (lambda v: v)
+        rgb, op, dp = (shape(t[k]).clone().requires_grad_(True) for k in ("rgb", "opacity", "depth"))
+        terms = pixel_loss(rgb, op, dp, shape(t["pixels"]), shape(t["sky"]), shape(t["lidar"]), shape(ego), 0.8, 0.05, 0.01, "l2")
+        terms.sum().backward()
+        torch.cuda.synchronize()
+        assert rgb.grad.shape == rgb.shape and op.grad.shape == op.shape and dp.grad.shape == dp.shape
+        return [terms.detach()] + [v.grad.reshape(-1) for v in (rgb, op, dp)]
+    image = run(False)
+    with poison.poisoned_allocations(True, name=f"pixel_loss flat {H}x{W}"):
+        flat = run(True)
+    for a, b in zip(image, flat):
+        assert not bool(poison.holds_poison(b).any()) and torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+@pytest.mark.parametrize("H,W", [(1, 1), (3, 5)])
+def test_reg_losses_without_rgb_and_dyn_opacity_matches_the_oracle_entropy(H, W):
+    from bilateral_driving_amd import losses as Ls
+    from tests import poison
+    g = torch.Generator().manual_seed(H * 131 + W)
+    pix, op = torch.rand(H, W, 3, generator=g), torch.rand(H, W, 1, generator=g) * 0.98 + 0.01
+    o64 = op.double().requires_grad_(True)
+    t_ref = LO.reg_losses(pix.double(), o64)
+    t_ref.sum().backward()
+    c = op.cuda().requires_grad_(True)
+    with poison.poisoned_allocations(True, name=f"reg_losses no rgb {H}x{W}"):
+        t = Ls.reg_losses(pix.cuda(), c, rgb=None, dyn_opacity=None)
+        t.sum().backward()
+        torch.cuda.synchronize()
+    assert torch.allclose(t.cpu().double(), t_ref.detach(), rtol=2e-5, atol=1e-7), (t, t_ref)
+    assert float(t[1]) == 0.0 and float(t[2]) == 0.0
+    assert float((c.grad.cpu().double() - o64.grad).norm() / o64.grad.norm()) < 2e-5
+
+
+def test_pixel_loss_still_refuses_smooth_l1():
+    from bilateral_driving_amd.losses import pixel_loss
+    t = _pixel_inputs(1, 1)
+    with pytest.raises(NotImplementedError, match="Unknown loss type: smooth_l1"):
+        pixel_loss(t["rgb"], t["opacity"], t["depth"], t["pixels"], t["sky"], t["lidar"], depth_loss_type="smooth_l1")

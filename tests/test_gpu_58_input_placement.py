@@ -25,7 +25,8 @@ What reads each placed input, with what load, and what happens at 4-byte alignme
   fused view sh                                sh_view_fwd / pack         float4 / scalar            host and Python pick scalar (sh.hip:548, fused_view.py:273)
   L1 rgb, target                               loss.hip, bilagrid.hip     float4                     the wrapper copies
   train_view target                            bilagrid_ms.h              scalar (16-byte required)  Python takes the one-launch loss (fused_view.py:1004)
-  ssim, pixel_loss, reg_losses maps            loss.hip                   scalar                     same form
+  ssim maps                                    loss.hip                   scalar                     same form
+  pixel_loss, reg_losses, image_terms maps     image_loss_math.h          scalar                     same form (one kernel set)
   bilagrid rgb, alpha, sky, v_out              bilagrid_ms.h              scalar                     same form
   slice xy, rgb, v_out (three forms)           bilagrid.hip               scalar                     same form
   head feats, v_aff                            mlp_head.hip               float4                     the wrapper copies

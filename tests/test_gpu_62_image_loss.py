@@ -1,6 +1,6 @@
 """The fused image loss on the MI355X (the image-loss section of csrc/loss.hip through bilateral_driving_amd/losses.py ``image_terms``)
 against the float64 restatement (tests/image_loss_ref64.py), the reference-generated golden (scripts/gen_golden_image_loss.py) and the
-existing ``pixel_loss`` + ``reg_losses``, on poisoned, recycled memory with guard bands (tests/poison.py), with every input and the
+same kernels called as two nodes (``pixel_loss`` + ``reg_losses``), on poisoned, recycled memory with guard bands (tests/poison.py), with every input and the
 incoming gradient at 4-byte phases (tests/placement.py), twice for the bit-equality the op claims; and the installed
 ``compute_losses`` on a stand-in with BasicTrainer's attribute layout.
 
@@ -12,7 +12,8 @@ gradient under the egocar mask) is held exactly, a NaN one (an empty mean) by Na
 workgroups of 256 threads (R.FWD_GRID = 524 288 pixels a sweep): the 725 x 725 case is more than one sweep.
 
 Measured on the MI355X: over the cases the worst error is 2.2e-7 (a depth gradient) against bounds of 8e-7 and more; the old option set
-is 1.3e-7 from float64 (``pixel_loss`` + ``reg_losses``: 1.7e-7; 9.5e-8 between the two).  Under the installed ``compute_losses`` the
+is 1.3e-7 from float64 (``pixel_loss`` + ``reg_losses``, the same kernels as two nodes: 1.3e-7; 5.7e-9 between the two, the rgb gradient's
+two products against one).  Under the installed ``compute_losses`` the
 rgb gradient also carries SSIM's node: 3.7e-7 .. 1.35e-6 against the framework's own 2.6e-7 .. 5.2e-7 (bounds 1.1e-6 .. 1.64e-6)."""
 import os
 
@@ -140,7 +141,9 @@ def test_exact_cases_on_the_device(S):
 
 
 def test_the_old_option_set_equals_pixel_loss_plus_reg_losses(S):
-    """Not bit-equal (the summation order differs by design): both within the bound of float64, so within twice the bound of each other."""
+    """One node against the same kernels called as two nodes (``pixel_loss`` and ``reg_losses`` are option sets of ``image_terms``).  Not
+    bit-equal: the one node's rgb gradient is one product with the sum of the rgb and the dynamic-region factors, the two nodes' is two
+    products that autograd adds.  Both within the bound of float64, so within twice the bound of each other."""
     H, W, seed = 37, 53, 90
     d = R.make(H, W, seed)
     o = R.options(mask="bce", depth=("l1", False, False))
@@ -156,6 +159,7 @@ def test_the_old_option_set_equals_pixel_loss_plus_reg_losses(S):
     e, e_prev, between = R.errors(got, ref), R.errors(prev, ref), R.errors(got, prev)
     print(f"\nimage_terms vs float64 {max(e.values()):.3e}, pixel_loss + reg_losses vs float64 {max(e_prev.values()):.3e}, between {max(between.values()):.3e}")
     assert R.within(e, b)
+    assert R.within(e_prev, b), {k: (e_prev[k], b[k]) for k in b if e_prev[k] > b[k]}
     assert all(between[k] <= 2 * b[k] for k in b), {k: (between[k], 2 * b[k]) for k in b if between[k] > 2 * b[k]}
 
 

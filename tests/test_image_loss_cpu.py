@@ -97,14 +97,14 @@ def shim():
     return h
 
 
-def shim_run(h, d, o, v6=R.V6):
+def shim_run(h, d, o, v6=R.V6, w6=R.W6):
     """The host shim on inputs ``d`` under options ``o`` -> (terms, grads) in ``R.run``'s layout (a gradient no term reaches: zeros)."""
     a = {k: np.ascontiguousarray(v.numpy(), np.float32) for k, v in d.items()}
     H, W = a["sky"].shape
     p = lambda k, on=True: a[k].ctypes.data if on else None
     need_o, need_d = o["mask"] is not None or o["entropy"], o["depth"] is not None or o["smoothness"]
     t, n, i = o["depth"] or ("l1", False, False)
-    w, v = np.array(R.W6, np.float32), np.array(v6, np.float32)
+    w, v = np.array(w6, np.float32), np.array(v6, np.float32)
     head = (H, W, p("rgb"), p("pixels"), p("opacity", need_o), p("depth", need_d), p("sky", o["mask"] is not None), p("lidar", o["depth"] is not None),
             p("ego", o["ego"]), p("dyn", o["dyn"]), KINDS[o["mask"]], o["limit"], TYPES[t], int(n), int(i), o["max_depth"], REDUCTIONS[o["reduction"]],
             int(o["entropy"]), int(o["smoothness"]), o["threshold"], w.ctypes.data)
@@ -207,6 +207,109 @@ def test_one_row_has_a_nan_smoothness_term_and_a_finite_gradient(shim):
     assert R.err(g["depth"], g64["depth"]) <= R.FLOOR
 
 
+# ---- the two older option sets: losses.pixel_loss and losses.reg_losses ---------------------------------------------------------------
+# The math under those two names is this file's math at two option sets.  Held here, without a GPU, to the oracle the GPU tests of the two
+# names use (oracle/loss_oracle.py, float64) at THEIR bounds: pixel_loss 3e-6 of max(1, |term|) and 3e-6 of a gradient's largest entry
+# (tests/test_gpu_00_bilagrid_parity.py test_pixel_loss_matches_reference_goldens), reg_losses rtol 2e-5 / atol 1e-7 on the terms and 2e-5 of
+# a gradient's norm (tests/test_gpu_29_losses_random_sweep.py).  Inputs as tests/test_gpu_47_poisoned_memory.py _pixel_loss_case and
+# tests/test_gpu_06_reg_losses.py build them.
+OLD_SET_SHAPES = [(1, 1), (1, 37), (3, 5), (37, 53)]
+
+
+def _pixel_set(shim, d, w, depth_type, use_mask, use_depth, use_ego):
+    o = R.options(mask="bce" if use_mask else None, depth=(depth_type, False, False) if use_depth else None, entropy=False, smoothness=False,
+                  dyn=False, ego=use_ego)
+    terms, g = shim_run(shim, d, o, v6=(1.0, 1.0, 1.0, 0.0, 0.0, 0.0), w6=(*w, 0.0, 0.0, 0.0))
+    assert not terms[3:].any()
+    return terms[:3], g
+
+
+def _pixel_set_check(terms, g, want, on, tag):
+    for i, k in enumerate(("rgb_loss", "sky_loss", "depth_loss")):
+        w_ = float(want[k]) if on[i] else 0.0
+        assert abs(float(terms[i]) - w_) <= 3e-6 * max(1.0, abs(w_)), (tag, k, float(terms[i]), w_)
+    for i, (k, name) in enumerate((("rgb", "v_rgb"), ("opacity", "v_opacity"), ("depth", "v_depth"))):
+        if not on[i]:
+            assert not g[k].any(), (tag, k)
+            continue
+        ref = np.asarray(want[name], np.float64)
+        assert np.abs(g[k].astype(np.float64) - ref).max() / max(np.abs(ref).max(), 1e-30) <= 3e-6, (tag, k)
+
+
+@pytest.mark.parametrize("H,W", OLD_SET_SHAPES)
+def test_host_math_at_the_pixel_loss_option_set_matches_the_loss_oracle(shim, H, W):
+    from oracle import loss_oracle as LO
+    g = torch.Generator().manual_seed(H * 100 + W)
+    t = dict(rgb=torch.rand(H, W, 3, generator=g), pixels=torch.rand(H, W, 3, generator=g), opacity=torch.rand(H, W, 1, generator=g) * 0.98 + 0.01,
+             depth=torch.rand(H, W, 1, generator=g) * 40 + 0.5, sky=(torch.rand(H, W, generator=g) > 0.7).float(),
+             lidar=torch.rand(H, W, generator=g) * 60 * (torch.rand(H, W, generator=g) > 0.3).float(), ego=(torch.rand(H, W, generator=g) > 0.8).float())
+    t["lidar"].reshape(-1)[0] = 12.0            # (at least one lidar hit: the depth term divides by their count)
+    t["ego"].reshape(-1)[0] = 0.0
+    t["dyn"] = torch.zeros(H, W, 1)
+    d64 = {k: v.double() for k, v in t.items()}
+    w = (0.8, 0.05, 0.01)
+    for depth_type in ("l1", "l2"):
+        for um, ud, ue in ((True, True, True), (False, True, True), (True, False, True), (True, True, False)):
+            want = LO.pixel_loss(d64["rgb"], d64["pixels"], d64["opacity"], d64["sky"], d64["depth"], d64["lidar"], d64["ego"] if ue else None, w=w,
+                                 depth_l2=depth_type == "l2")
+            terms, grads = _pixel_set(shim, t, w, depth_type, um, ud, ue)
+            _pixel_set_check(terms, grads, {k: v.numpy() for k, v in want.items()}, (True, um, ud), (depth_type, um, ud, ue))
+
+
+def test_host_math_at_the_pixel_loss_option_set_matches_the_reference_goldens(shim):
+    import glob
+    files = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "pixel_loss_*f32.npz")))
+    assert len(files) >= 3
+    for f in files:
+        z = np.load(f)
+        ego = bool(z["egocar"].size)
+        d = {k: torch.from_numpy(z[s]) for k, s in (("rgb", "rgb"), ("pixels", "pixels"), ("opacity", "opacity"), ("depth", "depth"), ("sky", "sky_masks"),
+                                                    ("lidar", "lidar"))}
+        d["ego"] = torch.from_numpy(z["egocar"]).float() if ego else torch.zeros_like(d["sky"])
+        d["dyn"] = torch.zeros_like(d["opacity"])
+        terms, grads = _pixel_set(shim, d, [float(v) for v in z["w"]], "l2" if int(z["depth_l2"]) else "l1", True, True, ego)
+        _pixel_set_check(terms, grads, z, (True, True, True), os.path.basename(f))
+
+
+@pytest.mark.parametrize("H,W", OLD_SET_SHAPES)
+def test_host_math_at_the_reg_losses_option_set_matches_the_loss_oracle(shim, H, W):
+    import itertools
+    from oracle import loss_oracle as LO
+    g = torch.Generator().manual_seed(H * 131 + W)
+    pix = torch.rand(H, W, 3, generator=g)
+    rgb = torch.rand(H, W, 3, generator=g) * 1.1
+    op = torch.rand(H, W, 1, generator=g)
+    if H * W > 1:
+        op[0, 0, 0], op[-1, -1, 0] = 0.0, 1.0             # outside the clamp interval: zero gradient
+    dep = torch.rand(H, W, 1, generator=g) * 30 + 0.2
+    dyn = torch.rand(H, W, 1, generator=g)
+    dyn.reshape(-1)[0] = 0.9                              # (at least one pixel above the threshold)
+    ego = (torch.rand(H, W, generator=g) > 0.8).float()
+    ego.reshape(-1)[0] = 0.0
+    wt = (0.7, 1.3, 0.4)
+    d = dict(rgb=rgb, pixels=pix, opacity=op, depth=dep, dyn=dyn, ego=ego, sky=torch.zeros(H, W), lidar=torch.zeros(H, W))
+    for use_op, use_dyn, use_dep, use_ego in itertools.product((False, True), repeat=4):
+        if not (use_op or use_dyn or use_dep) or (use_dep and (H == 1 or W == 1)):
+            continue
+        tag = (use_op, use_dyn, use_dep, use_ego)
+        o64 = {k: v.double().requires_grad_(True) for k, v in dict(op=op, dep=dep, rgb=rgb).items()}
+        t_ref = LO.reg_losses(pix.double(), o64["op"] if use_op else None, o64["dep"] if use_dep else None, o64["rgb"],
+                              dyn.double() if use_dyn else None, ego.double() if use_ego else None)
+        (t_ref * torch.tensor(wt, dtype=torch.float64)).sum().backward()
+        o = R.options(mask=None, depth=None, entropy=use_op, smoothness=use_dep, dyn=use_dyn, ego=use_ego)
+        terms, grads = shim_run(shim, d, o, v6=(0.0, 0.0, 0.0, *wt), w6=(0.0, 0.0, 0.0, 1.0, 1.0, 1.0))
+        assert not terms[:3].any(), tag
+        assert torch.allclose(torch.from_numpy(terms[3:]).double(), t_ref.detach(), rtol=2e-5, atol=1e-7), (tag, terms, t_ref)
+        for k, name in (("op", "opacity"), ("dep", "depth"), ("rgb", "rgb")):
+            want, got = o64[k].grad, torch.from_numpy(grads[name]).double()
+            if want is None or float(want.abs().max()) == 0.0:
+                assert float(got.abs().max()) == 0.0, (tag, k)
+                continue
+            assert float((got - want).norm() / want.norm()) < 2e-5, (tag, k)
+        if use_op and H * W > 1:
+            assert grads["opacity"][0, 0, 0] == 0.0 and grads["opacity"][-1, -1, 0] == 0.0
+
+
 # ---- argument validation, options, the seam -----------------------------------------------------------------------------------------------
 def test_entries_reject_bad_arguments_without_a_gpu():
     lib, p = L.lib(), 1 << 20      # never dereferenced: every case fails its argument check first
@@ -238,7 +341,7 @@ def test_entries_reject_bad_arguments_without_a_gpu():
 
 
 def test_abi_version_and_signatures():
-    assert L.lib().bds_abi_version() == 6
+    assert L.lib().bds_abi_version() == 7
     decl = {k: v for k, v in declared_signatures().items() if k.startswith("bds_image_loss")}
     assert sorted(decl) == ["bds_image_loss_bwd", "bds_image_loss_fwd", "bds_image_loss_temp_bytes"]
     for name, (ret, args) in decl.items():

@@ -299,7 +299,7 @@ def test_entries_resolve_with_the_declared_signatures():
         assert f"#define {macro} {value}\n" in hdr, macro
     assert (R.QUERY_BLOCK, R.TARGET_TILE, R.RING_MAX) == (init.QUERY_BLOCK, init.TARGET_TILE, init.RING_MAX)
     assert init.MAX_POINTS <= 2 ** 31 - 1
-    assert lib.bds_abi_version() == L.ABI_VERSION == 6 and "#define BDS_ABI_VERSION 6 " in hdr
+    assert lib.bds_abi_version() == L.ABI_VERSION == 7 and "#define BDS_ABI_VERSION 7 " in hdr
 
 
 def test_entries_reject_bad_arguments_without_a_gpu():

@@ -306,7 +306,7 @@ def test_entries_resolve_with_the_declared_signatures():
         assert f"#define {macro} {value}\n" in hdr, macro
     assert lidar.MAX_ROWS == 2 ** 31 - 1 - 256
     assert (lidar.RIGID_NODES, lidar.SMPL_NODES, lidar.DEFORMABLE_NODES) == (R.RIGID, R.SMPL, R.DEFORMABLE)
-    assert lib.bds_abi_version() == L.ABI_VERSION == 6 and "#define BDS_ABI_VERSION 6 " in hdr
+    assert lib.bds_abi_version() == L.ABI_VERSION == 7 and "#define BDS_ABI_VERSION 7 " in hdr
     full = open(os.path.join(ROOT, "include", "bds.h")).read()      # each entry cites the reference lines it serves
     for cite in ("driving_dataset.py:644-727", ":576-603", ":341-354", ":521-536", "pixel_source.py:77-92"):
         assert cite in full, cite

@@ -112,7 +112,7 @@ def test_entries_resolve_with_the_declared_signatures():
         assert getattr(lib, name).argtypes == args, name
     assert "BDS_IMAGE_METRICS_ROW 14" in hdr
     from bilateral_driving_amd import metrics
-    assert metrics.ROW == 14 and lib.bds_abi_version() == L.ABI_VERSION == 6
+    assert metrics.ROW == 14 and lib.bds_abi_version() == L.ABI_VERSION == 7
 
 
 def test_entries_reject_bad_arguments_without_a_gpu():
