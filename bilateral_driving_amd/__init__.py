@@ -2,7 +2,7 @@
 ones listed here are also reachable as attributes of the package, imported on first use."""
 import importlib
 
-__all__ = ["metrics", "geometry", "init", "lidar", "pseudo_lidar", "pixels", "sampler", "video"]
+__all__ = ["metrics", "geometry", "init", "lidar", "pseudo_lidar", "pixels", "sampler", "video", "undistort"]
 
 
 def __getattr__(name):

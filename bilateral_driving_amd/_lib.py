@@ -190,6 +190,7 @@ _SIGS = {
     "bds_error_maps_workspace_bytes": (_sz, [_i, _i, _i]),
     "bds_error_maps": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _f, _i, _f, _sz, _f]),
     "bds_video_frame": (_i, [_i, C.POINTER(BdsVideoPanel), _i, _i, _f, _f]),
+    "bds_undistort": (_i, [_i, _i, _i, _i, _f, _f, _i, _f, _f]),
     "bds_opacity_reset": (_i, [_i64, _f, _fl, _f, _f, _f]),
     "bds_cubemap_fwd": (_i, [_i64, _i, _i, _f, _f, _f, _f, _f]),
     "bds_cubemap_bwd": (_i, [_i64, _i, _i, _i, _f, _f, _f, _f, _f]),

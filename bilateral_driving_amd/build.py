@@ -15,7 +15,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbds.so")
-SOURCES = ["api.hip", "sh.hip", "project.hip", "tiles.hip", "rasterize.hip", "bilagrid.hip", "bilagrid_cells.hip", "bilagrid_tile.hip", "loss.hip", "optim.hip", "refine.hip", "envlight.hip", "colorcorrect.hip", "mlp_head.hip", "exchange.hip", "deform.hip", "nodes.hip", "smpl.hip", "smpl_reg.hip", "pvg.hip", "metrics.hip", "geometry.hip", "knn.hip", "knn_cross.hip", "lidar.hip", "pseudo_lidar.hip", "pixels.hip", "error_buffer.hip", "video.hip", "scene_view.hip"]
+SOURCES = ["api.hip", "sh.hip", "project.hip", "tiles.hip", "rasterize.hip", "bilagrid.hip", "bilagrid_cells.hip", "bilagrid_tile.hip", "loss.hip", "optim.hip", "refine.hip", "envlight.hip", "colorcorrect.hip", "mlp_head.hip", "exchange.hip", "deform.hip", "nodes.hip", "smpl.hip", "smpl_reg.hip", "pvg.hip", "metrics.hip", "geometry.hip", "knn.hip", "knn_cross.hip", "lidar.hip", "pseudo_lidar.hip", "pixels.hip", "error_buffer.hip", "video.hip", "scene_view.hip", "undistort.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-ffp-contract=fast-honor-pragmas", "-Wall", "-Wno-unused-function"]
 # per-file additions.  bilagrid.hip: the SLP vectoriser pairs fp32 operations into v_pk_* instructions, which issue at half rate on

@@ -33,7 +33,10 @@ Read-backs: the error flag of the finiteness check (every entry point), the emit
 ``get_init_objects``) and, in ``get_init_objects`` alone, the per-instance counts that it returns as Python ints.  Everything else is
 enqueued on the current stream without a host wait.
 
-Not covered: ``cam.undistort`` (needs OpenCV: NotImplementedError), ``get_init_smpl_objects``, dataset file loading, novel-view
+``cam.undistort``: ``project_lidar_pts_on_images`` here refuses it (NotImplementedError); ``undistort.project_lidar_pts_on_images``
+runs the same sequence with the optimal new camera matrix and is what ``undistort.install`` sets after ``lidar.install``.
+
+Not covered: ``get_init_smpl_objects``, dataset file loading, novel-view
 trajectories, ``seg_dynamic_instances_in_lidar_frame``."""
 from __future__ import annotations
 
@@ -278,10 +281,17 @@ def project_lidar_pts_on_images(dataset, delete_out_of_view_points: bool = True)
     """driving_dataset.py:644-727: every camera receives its sparse depth maps (``cam.load_depth`` of [F,H,W] float32), the lidar
     source its ``visible_masks`` and ``colors``; with ``delete_out_of_view_points`` the invisible points are then deleted.  One launch
     sequence per camera on the current stream.  Read-back: the error flag."""
+    if any(getattr(cam, "undistort", False) for cam in dataset.pixel_source.camera_data.values()):
+        raise NotImplementedError("cam.undistort needs getOptimalNewCameraMatrix: undistort.project_lidar_pts_on_images serves it "
+                                  "(undistort.install, after lidar.install)")
+    _project_on_images(dataset, delete_out_of_view_points, camera_matrices)
+
+
+@torch.no_grad()
+def _project_on_images(dataset, delete_out_of_view_points: bool, matrices) -> None:
+    """``project_lidar_pts_on_images`` with ``matrices(cam)`` -> [F,4,4] forming a camera's lidar-to-image matrices."""
     ls, ps = dataset.lidar_source, dataset.pixel_source
     cams = list(ps.camera_data.values())
-    if any(getattr(cam, "undistort", False) for cam in cams):
-        raise NotImplementedError("cam.undistort needs OpenCV's getOptimalNewCameraMatrix, which this build does not have")
     dev = _device(dataset)
     cloud = _lidar_cloud(ls, dev)
     uniq = ls.unique_normalized_timestamps.to(dev)
@@ -293,7 +303,7 @@ def project_lidar_pts_on_images(dataset, delete_out_of_view_points: bool = True)
         F = len(cam)
         closest = torch.argmin(torch.abs(uniq[None, :] - ps.normalized_time[:F].to(dev)[:, None]), dim=1)      # find_closest_timestep
         ranges = torch.stack([offsets[closest], offsets[closest + 1]], dim=1)
-        depth = project_points(x, camera_matrices(cam), ranges, cam.WIDTH, cam.HEIGHT, cam.images[:F].to(dev), visible, colors, _checked=True)[0]
+        depth = project_points(x, matrices(cam), ranges, cam.WIDTH, cam.HEIGHT, cam.images[:F].to(dev), visible, colors, _checked=True)[0]
         cam.load_depth(depth)
     vis = torch.empty_like(visible)
     vis[perm] = visible

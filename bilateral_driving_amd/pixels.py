@@ -27,8 +27,8 @@ to the device in ONE small copy together with ``height`` and ``width``; the ones
 ``frame_idx`` that is a device tensor still selects the frame's rows through torch's own indexing, which may wait for it).  Per call
 ``get_image`` is one launch at ``downscale_factor == 1``, and at most four (fields, image, masks, lidar map) otherwise.
 
-Not covered: ``cam.undistort``, file loading.  The error-map buffer (``update_image_error_maps``, ``propose_training_image``) lives in
-``sampler.py``."""
+``cam.undistort`` and the loaders that fill ``images`` and the masks live in ``undistort.py`` (``undistort.install``).  The error-map
+buffer (``update_image_error_maps``, ``propose_training_image``) lives in ``sampler.py``."""
 from __future__ import annotations
 
 import math

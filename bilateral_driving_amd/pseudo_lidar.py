@@ -30,7 +30,8 @@ Read-backs: none in ``depth_to_lidar`` / ``cloud_to_lidar`` (``split=True``: the
 arrays and so read their result back.  The small per-call tables (16 floats per camera, 12 doubles) are formed on the host and
 uploaded.  ValueError for a non-finite matrix, intrinsic or cloud coordinate; BdsError for a CPU tensor.
 
-Not covered: ``save_ply``, ``pto_rec_map``, ``gen_sparse_points_all``, the radar and box scripts, distortion."""
+Not covered: ``save_ply``, ``pto_rec_map``, ``gen_sparse_points_all``, the radar and box scripts.  Lens distortion: the
+depth maps are renders of undistorted cameras (``undistort`` prepares their images and the lidar projection), so the pinhole model here holds."""
 from __future__ import annotations
 
 import math

@@ -1465,6 +1465,32 @@ typedef struct bds_video_panel {
 } bds_video_panel;
 int bds_video_frame(int n_panels, const bds_video_panel *panels, int Hc, int Wc, uint8_t *canvas, bds_stream_t stream);
 
+/* Lens undistortion of F frames [H,W,C] of bytes (C = 1 or 3) in one call: what cv2.undistort does frame by frame on the host in
+ * CameraData.load_images, load_egocar_mask, load_dynamic_masks and load_sky_masks.  Pointers + stream, no allocation, no read-back,
+ * one launch (one per 65535 frames), no atomics: bit-identical run to run.  OpenCV is not installed where this is built: the
+ * algorithm (csrc/undistort_math.h) restates OpenCV 4.x's published one, PARITY UNPINNED.
+ *   cams [F,18] doubles ON THE DEVICE, 8-byte aligned, per frame: fx, fy, u0, v0 of the camera matrix | k1, k2, p1, p2, k3 | the nine
+ *   entries of inverse(new camera matrix), row-major, formed by the caller in double (the new matrix is the camera matrix itself in
+ *   cv2.undistort's default form).
+ *   Per output pixel (row i, column j), in double, every operation rounded on its own: (_x, _y, _w) = ir (j, i, 1); x = _x / _w,
+ *   y = _y / _w; r2 = x x + y y; kr = 1 + ((k3 r2 + k2) r2 + k1) r2; xd = x kr + p1 (2 x y) + p2 (r2 + 2 x x); yd = y kr +
+ *   p1 (r2 + 2 y y) + p2 (2 x y); u = fx xd + u0, v = fy yd + v0.  iu = rint(32 u), iv = rint(32 v), half to even, saturated to
+ *   int32; sx = iu >> 5, ax = iu & 31, sy = iv >> 5, ay = iv & 31 (floor and rest); the four 15-bit weights (32 - ay)(32 - ax) 32,
+ *   (32 - ay) ax 32, ay (32 - ax) 32, ay ax 32 of the taps (sy, sx), (sy, sx + 1), (sy + 1, sx), (sy + 1, sx + 1); per channel
+ *   (sum of tap x weight + 16384) >> 15 in integers.  The border is a constant 0: a tap outside the image contributes 0, and the
+ *   pixel is 0 when sx >= W, sx + 1 < 0, sy >= H or sy + 1 < 0.  Deviations from OpenCV: the image is one stripe (OpenCV shifts v0 per
+ *   stripe of rows), and a coordinate beyond +-32767 px counts as outside (OpenCV's 16-bit map wraps there).
+ *   out_kind: BDS_UNDISTORT_UINT8 -- out [F,H,W,C] bytes; BDS_UNDISTORT_UNIT -- float32, value / 255 (the image stack's ``/ 255``);
+ *   BDS_UNDISTORT_MASK -- float32, value > 0 ? 1 : 0 (the masks' ``> 0`` then ``.float()``).  Every element of out is written.
+ * All indexing is 64-bit.  BDS_EINVAL before any launch: a NULL pointer, F, H or W below 1, H or W above 32767, C other than 1 or 3,
+ * an unknown out_kind, cams off an 8-byte or a float32 out off a 4-byte boundary. */
+#define BDS_UNDISTORT_UINT8 0
+#define BDS_UNDISTORT_UNIT 1
+#define BDS_UNDISTORT_MASK 2
+/* datasets/base/pixel_source.py:249-256,273-278,296-303,319-326,342-349,366-373 (cv2.undistort) */
+int bds_undistort(int F, int H, int W, int C, const uint8_t *src /*[F,H,W,C]*/, const double *cams /*[F,18]*/,
+                  int out_kind, void *out, bds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
